@@ -9,11 +9,16 @@ detections copied to pinned host memory) on N MI355X GPUs, one process per GPU.
 
 Images are independent (per-image NMS, eval-mode BN), so ranks shard the batch with no
 data-path collective: weak scaling, value = all ranks' images / max-over-ranks time.
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (the
+wall time of one timed step) and the configuration.  A plain run does only that: set up, warm
+up, time --steps steps, write the last timed step's detections if --dump-outputs DIR is given
+(DIR/dets.npy, labels.npy, count.npy) and print the line.  With --full the line also holds
   roofline     fp32 MFMA: algorithmic conv FLOPs / HIP-event time of the conv launches
                measured inside the timed region, against the 157.3 TFLOP/s fp32 matrix peak
+  output_check images 0-1 of the timed step against a batch-2 plan, bit for bit
   cpu_baseline the CPU oracle (plain torch CPU restatement of the reference) timed on this
-               box's host cores on a bounded sample (rank 0, N=1 only)
+               box's host cores on a bounded sample (rank 0, N=1 only), and
+               output_check_oracle: image 0's pred maps against that oracle
   train_step   the bf16 batch-64/GPU training step (BASELINE.json configs[2]) measured by
                tools/train_bench.py in a child process per rank, data-parallel over RCCL when N > 1
 """
@@ -475,11 +480,18 @@ def main():
     ap.add_argument('--size', type=int, default=608)
     ap.add_argument('--model', default='yolov4l', choices=sorted(MODELS))
     ap.add_argument('--candidates', type=float, default=2000.0, help='target NMS candidates per image')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: per-conv HIP events in the timed '
+                         'region (roofline), the batch-2 output check, the CPU baseline with the oracle check, the train step')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write the detections of the last timed step to DIR/{dets,labels,count}.npy (float32; rows past '
+                         'an image\'s count are 0 in dets and -1 in labels)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-output-check', action='store_true',
                     help='skip the batch-2 plan of the output check (profiling runs: every profiled conv launch is then a '
                          'launch of the timed configuration, so rocprofv3 averages are per-step averages)')
-    ap.add_argument('--layers', default='', help='write a per-conv timing table (JSON) to this path')
+    ap.add_argument('--layers', default='', help='write a per-conv timing table (JSON) to this path (instruments the '
+                                                 'conv launches as --full does)')
     ap.add_argument('--autotune', action='store_true',
                     help='re-decide the conv tile of every layer by timing the candidates on this box (default: the static '
                          'choice of pick_tile, which measures the same images/s; see DESIGN.md 2.3)')
@@ -498,8 +510,8 @@ def main():
                     help='run the step as this many part-batch plans on as many HIP streams (default 1; 2: every conv launch has a '
                          'compute phase that leaves HBM idle and a memory phase that leaves the matrix pipe idle, and one '
                          'persistent workgroup per CU keeps all CUs in the same phase; two independent half-batch plans fill each '
-                         'other\'s phases and kernel boundaries.  Measured (profiles/r06_two_stream_probe.txt, r06_ab_streams.txt): fp32 +0.9-2.2 %, '
-                         'configs[3] -1 to +8 %, bf16 0, and the batch-16 launches fill the chip worse (dominant tile 0.79 -> 0.71 of its '
+                         'other\'s phases and kernel boundaries.  Measured (profiles/r06_two_stream_probe.txt, r06_ab_streams.txt): fp32 +0.9-2.2 %%, '
+                         'configs[3] -1 to +8 %%, bf16 0, and the batch-16 launches fill the chip worse (dominant tile 0.79 -> 0.71 of its '
                          'roof) -- not the default')
     ap.add_argument('--event-every', type=int, default=10,
                     help='bracket the conv launches with HIP events in every n-th timed step.  The two event records around a '
@@ -507,6 +519,8 @@ def main():
                          'instrumented 0.5 %% of the fp32 rate, 3 %% of the bf16 rate and 1.5 %% of configs[3]\'s '
                          '(profiles/r06_ab_events.txt)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher (it never touches the GPU) and the N
@@ -634,13 +648,14 @@ def main():
             if NS > 1:
                 step_done[i].record(streams_[i])
 
-    # per-conv HIP events: with one stream, every n-th step INSIDE the timed region is instrumented; with several streams
-    # (and under --graph) instrumented steps run after it -- a launch bracketed while the other stream's kernels share the chip
-    # would time the mixture, not the kernel
-    events_inside = NS == 1 and not args.graph
+    # per-conv HIP events (--full, --layers): with one stream, every n-th step INSIDE the timed region is instrumented; with
+    # several streams (and under --graph) instrumented steps run after it -- a launch bracketed while the other stream's kernels
+    # share the chip would time the mixture, not the kernel.  A plain run brackets nothing.
+    instrument = args.full or bool(args.layers)
+    events_inside = instrument and NS == 1 and not args.graph
     n_instr = (args.steps + max(args.event_every, 1) - 1) // max(args.event_every, 1) + 2
     ev_pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-               for _ in range(n_instr * len(conv_ops))]
+               for _ in range(n_instr * len(conv_ops) if instrument else 0)]
     for _ in range(args.warmup):
         step()
     # no garbage collection inside the timed region: an instrumented step allocates ~230 event objects, and a
@@ -668,13 +683,130 @@ def main():
     else:
         per_rank = [mine]
     gc.enable()
-    if not events_inside:                               # per-conv events: instrumented steps outside the timed region
+    torch.cuda.synchronize()
+    assert int(host_count.min()) >= 0, 'an image took the split NMS path; lower --candidates'
+    if args.dump_outputs:                               # the last timed step's detections, before any further step
+        dump_outputs(args.dump_outputs, host_dets, host_labels, host_count, '' if world == 1 else f'_rank{rank}')
+    if instrument and not events_inside:                # per-conv events: instrumented steps outside the timed region
         for _ in range(max(2, args.steps // max(args.event_every, 1))):
             step(events)
         torch.cuda.synchronize()
-    assert int(host_count.min()) >= 0, 'an image took the split NMS path; lower --candidates'
 
     # ---- roofline of the dominant kernel (the fused MFMA conv), from the timed region ------
+    roofline = per_layer = None
+    if instrument:
+        roofline, per_layer = roofline_block(args, events, events_inside, conv_ops, h16, nb, NS, elapsed)
+    if args.layers and rank == 0:
+        rows = []
+        for op, tsum, n, tile in per_layer.values():
+            i = op.info
+            rows.append(dict(name=op.name, Cin=i['Cin'], Cout=i['Cout'], k=i['k'], stride=i['stride'], H=i['H'],
+                             W=i['W'], tile=tile, us=round(tsum / n * 1e6, 1),
+                             tflops=round(op.flops / (tsum / n) / 1e12, 1), gflop=round(op.flops / 1e9, 2),
+                             mbytes=round(op.bytes / 1e6, 2), residual=i['launch']['res'] is not None))
+        with open(args.layers, 'w') as f:
+            json.dump(rows, f, indent=1)
+
+    # the timed batch's output is the real thing: image 0 (and 1) of the batch-N step must equal, bit for bit, what a
+    # batch-2 plan computes for the same two images (per-image NMS, eval-mode BN, every conv tile walks K in the same
+    # order -- the wide-tile 3x3 kernel's 16x16x32 MFMAs included: tests/test_gpu_h16.py::test_wide3x3_matches_generic_bitwise)
+    # -- a wrong fast path (cached outputs, skipped images) cannot pass this
+    torch.cuda.synchronize()
+    check_failed = None
+    output_check = None
+    if args.full and args.batch >= 2 and not args.no_output_check:
+        small = det.compile(2, args.size, args.size, device=dev, rescale=True,
+                            dtype={'f32': torch.float32, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype])
+        pin_note = '' if h16 else pin_check_plan(plan, small)
+        if pin_note:
+            print('bench.py: output check' + pin_note[2:], file=sys.stderr)
+        small.run(img[:2])
+        torch.cuda.synchronize()
+        for n in range(2):
+            k = int(host_count[n])
+            if int(small.post['count'][n]) != k:
+                check_failed = f'image {n}: batch-{args.batch} step kept {k} detections, batch-2 plan {int(small.post["count"][n])}'
+            elif not (torch.equal(small.post['dets'][n, :k].cpu(), host_dets[n, :k]) and
+                      torch.equal(small.post['labels'][n, :k].cpu().to(torch.int32), host_labels[n, :k])):
+                check_failed = f'image {n} of the batch-{args.batch} step differs from the batch-2 plan'
+        del small
+        output_check = f'images 0-1 of the timed batch-{args.batch} step == a batch-2 plan on the same images (bit-exact; ' \
+                       f'{int(host_count[0])} + {int(host_count[1])} detections)' + pin_note
+        if check_failed:
+            output_check = 'FAILED: ' + check_failed
+    # image 0's pred maps of the TIMED plan, kept for the oracle leg below (the CPU oracle runs on this box anyway for
+    # cpu_baseline): the batch-2 comparison above goes through the same library, so a library that is wrong in a
+    # self-consistent way would pass it; the oracle is independent of the library
+    pred0 = [v.buf.tensor.view(v.N, v.H, v.W, v.C)[0].permute(2, 0, 1).float().cpu() for v in plan.pred_views] \
+        if args.full and getattr(plan, 'pred_views', None) and rank == 0 else None
+    dets0 = (int(host_count[0]), host_dets[0].clone(), host_labels[0].clone())
+
+    # the inference numbers are final here: leave the group, free the plan, then let a child measure the train step
+    D.finalize()
+    train = None
+    if args.full and not args.no_train:
+        del plan, plans, conv_ops, events, per_layer, post
+        det._engines.clear()
+        torch.cuda.empty_cache()
+        train = train_step_leg(args, rank, local_rank, world)
+
+    if rank == 0:
+        total_images = args.batch * world * args.steps
+        out = dict(
+            metric=f'images/sec (inference) {"YOLOv3" if MODELS[args.model].get("v3") else "YOLOv4"} {args.size}x{args.size}', value=round(total_images / elapsed, 2),
+            unit='images/sec', n_gpus=world, steps=args.steps, warmup=args.warmup,
+            ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling='weak',
+            vs_baseline=vs_published(args, total_images / elapsed), dtype=args.dtype, data='synthetic',
+            config=dict(workload=(f'{args.model} (Darknet-53 + YOLOV3Neck + YOLOV3Head, 80 classes) '
+                                  if MODELS[args.model].get('v3') else
+                                  f'{args.model} (DarknetCSP {MODELS[args.model]["scale"]} + '
+                                  f'{MODELS[args.model].get("neck", "YOLOV4Neck")} + YOLOCSPHead, 80 classes) ') +
+                                 f'{args.size}x{args.size} {dict(f32="fp32", f16="fp16", bf16="bf16")[args.dtype]} inference, batch {args.batch}/GPU: image -> '
+                                 'fused conv path -> decode -> per-class NMS -> detections on host ' +
+                                 ('[one hipGraph replay per step] ' if args.graph else '') +
+                                 (f'[the step runs as {NS} batch-{nb} plans on {NS} HIP streams, joined at every step] ' if NS > 1 else '') +
+                                 ('(BASELINE.json configs[1])' if (args.model, args.size, args.batch, args.dtype) == ('yolov4l', 608, 32, 'f32')
+                                  else '(not the headline configuration)'),
+                        global_batch=args.batch * world, per_gpu_batch=args.batch, input=f'{args.size}x{args.size}',
+                        weights='random init (seed 0), BN statistics fitted on the batch, head bias set for '
+                                f'~{ncand:.0f} NMS candidates/image', parallelism=f'replicated weights, batch '
+                                f'sharded over {world} rank(s), no collective'),
+            full=args.full, ranks=per_rank)
+        if roofline is not None:
+            out['roofline'] = roofline
+        if args.full:
+            out.update(output_check=output_check, train_step=train)
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(det, args.size)
+                if pred0 is not None and not MODELS[args.model].get('v3'):
+                    ok, msg = oracle_check(det, img[:1].cpu(), pred0, dets0, args.dtype)
+                    out['output_check_oracle'] = ('' if ok else 'FAILED: ') + msg
+                    check_failed = check_failed or (None if ok else msg)
+            else:
+                out['cpu_baseline'] = None
+        print(json.dumps(out), flush=True)
+        if check_failed:            # the metric line is out; a wrong result still fails the run
+            sys.exit(3)
+
+
+def dump_outputs(path, host_dets, host_labels, host_count, suffix=''):
+    """What a caller of the timed path receives for the batch, as float32 arrays: dets (N, max_per_img, 5: x1 y1 x2 y2
+    score), labels (N, max_per_img) and count (N).  Rows at and past an image's count are 0 in dets and -1 in labels:
+    the NMS kernel leaves them unspecified.  7.2 KB per image."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    count = host_count.numpy().astype(np.int64).reshape(-1)
+    valid = np.arange(host_dets.shape[1])[None, :] < count[:, None]
+    dets = np.where(valid[:, :, None], host_dets.numpy(), 0).astype(np.float32)
+    labels = np.where(valid, host_labels.numpy(), -1).astype(np.float32)
+    for name, a in (('dets', dets), ('labels', labels), ('count', count.astype(np.float32))):
+        np.save(os.path.join(path, f'{name}{suffix}.npy'), a)
+
+
+def roofline_block(args, events, events_inside, conv_ops, h16, nb, NS, elapsed):
+    """The roofline of the dominant conv tile class from the HIP events of the instrumented steps, and the per-layer sums
+    behind --layers."""
+    import mmdet_yolov4_amd as pkg
     per_tile = {}
     per_layer = {}
 
@@ -742,94 +874,7 @@ def main():
         roofline.update(bound='hbm', achieved=round(dbytes / dtime / 1e9, 1), peak=PEAK_HBM_GBPS, unit='GB/s',
                         frac=round(dbytes / dtime / 1e9 / PEAK_HBM_GBPS, 4),
                         mfma_tflops=round(dflops / dtime / 1e12, 2), mfma_frac=round(dflops / dtime / 1e12 / peak, 4))
-    if args.layers and rank == 0:
-        rows = []
-        for op, tsum, n, tile in per_layer.values():
-            i = op.info
-            rows.append(dict(name=op.name, Cin=i['Cin'], Cout=i['Cout'], k=i['k'], stride=i['stride'], H=i['H'],
-                             W=i['W'], tile=tile, us=round(tsum / n * 1e6, 1),
-                             tflops=round(op.flops / (tsum / n) / 1e12, 1), gflop=round(op.flops / 1e9, 2),
-                             mbytes=round(op.bytes / 1e6, 2), residual=i['launch']['res'] is not None))
-        with open(args.layers, 'w') as f:
-            json.dump(rows, f, indent=1)
-
-    # the timed batch's output is the real thing: image 0 (and 1) of the batch-N step must equal, bit for bit, what a
-    # batch-2 plan computes for the same two images (per-image NMS, eval-mode BN, every conv tile walks K in the same
-    # order -- the wide-tile 3x3 kernel's 16x16x32 MFMAs included: tests/test_gpu_h16.py::test_wide3x3_matches_generic_bitwise)
-    # -- a wrong fast path (cached outputs, skipped images) cannot pass this
-    torch.cuda.synchronize()
-    check_failed = None
-    if args.batch >= 2 and not args.no_output_check:
-        small = det.compile(2, args.size, args.size, device=dev, rescale=True,
-                            dtype={'f32': torch.float32, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.dtype])
-        pin_note = '' if h16 else pin_check_plan(plan, small)
-        if pin_note:
-            print('bench.py: output check' + pin_note[2:], file=sys.stderr)
-        small.run(img[:2])
-        torch.cuda.synchronize()
-        for n in range(2):
-            k = int(host_count[n])
-            if int(small.post['count'][n]) != k:
-                check_failed = f'image {n}: batch-{args.batch} step kept {k} detections, batch-2 plan {int(small.post["count"][n])}'
-            elif not (torch.equal(small.post['dets'][n, :k].cpu(), host_dets[n, :k]) and
-                      torch.equal(small.post['labels'][n, :k].cpu().to(torch.int32), host_labels[n, :k])):
-                check_failed = f'image {n} of the batch-{args.batch} step differs from the batch-2 plan'
-        del small
-        output_check = f'images 0-1 of the timed batch-{args.batch} step == a batch-2 plan on the same images (bit-exact; ' \
-                       f'{int(host_count[0])} + {int(host_count[1])} detections)' + pin_note
-        if check_failed:
-            output_check = 'FAILED: ' + check_failed
-    else:
-        output_check = None
-    # image 0's pred maps of the TIMED plan, kept for the oracle leg below (the CPU oracle runs on this box anyway for
-    # cpu_baseline): the batch-2 comparison above goes through the same library, so a library that is wrong in a
-    # self-consistent way would pass it; the oracle is independent of the library
-    pred0 = [v.buf.tensor.view(v.N, v.H, v.W, v.C)[0].permute(2, 0, 1).float().cpu() for v in plan.pred_views] \
-        if getattr(plan, 'pred_views', None) and rank == 0 else None
-    dets0 = (int(host_count[0]), host_dets[0].clone(), host_labels[0].clone())
-
-    # the inference numbers are final here: leave the group, free the plan, then let a child measure the train step
-    D.finalize()
-    train = None
-    if not args.no_train:
-        del plan, plans, conv_ops, events, per_layer, post
-        det._engines.clear()
-        torch.cuda.empty_cache()
-        train = train_step_leg(args, rank, local_rank, world)
-
-    if rank == 0:
-        total_images = args.batch * world * args.steps
-        out = dict(
-            metric=f'images/sec (inference) {"YOLOv3" if MODELS[args.model].get("v3") else "YOLOv4"} {args.size}x{args.size}', value=round(total_images / elapsed, 2),
-            unit='images/sec', n_gpus=world, steps=args.steps, warmup=args.warmup,
-            ms_per_step=round(elapsed / args.steps * 1e3, 3), higher_is_better=True, scaling='weak',
-            vs_baseline=vs_published(args, total_images / elapsed), dtype=args.dtype, data='synthetic',
-            config=dict(workload=(f'{args.model} (Darknet-53 + YOLOV3Neck + YOLOV3Head, 80 classes) '
-                                  if MODELS[args.model].get('v3') else
-                                  f'{args.model} (DarknetCSP {MODELS[args.model]["scale"]} + '
-                                  f'{MODELS[args.model].get("neck", "YOLOV4Neck")} + YOLOCSPHead, 80 classes) ') +
-                                 f'{args.size}x{args.size} {dict(f32="fp32", f16="fp16", bf16="bf16")[args.dtype]} inference, batch {args.batch}/GPU: image -> '
-                                 'fused conv path -> decode -> per-class NMS -> detections on host ' +
-                                 ('[one hipGraph replay per step] ' if args.graph else '') +
-                                 (f'[the step runs as {NS} batch-{nb} plans on {NS} HIP streams, joined at every step] ' if NS > 1 else '') +
-                                 ('(BASELINE.json configs[1])' if (args.model, args.size, args.batch, args.dtype) == ('yolov4l', 608, 32, 'f32')
-                                  else '(not the headline configuration)'),
-                        global_batch=args.batch * world, per_gpu_batch=args.batch, input=f'{args.size}x{args.size}',
-                        weights='random init (seed 0), BN statistics fitted on the batch, head bias set for '
-                                f'~{ncand:.0f} NMS candidates/image', parallelism=f'replicated weights, batch '
-                                f'sharded over {world} rank(s), no collective'),
-            roofline=roofline, output_check=output_check, train_step=train, ranks=per_rank)
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(det, args.size)
-            if pred0 is not None and not MODELS[args.model].get('v3'):
-                ok, msg = oracle_check(det, img[:1].cpu(), pred0, dets0, args.dtype)
-                out['output_check_oracle'] = ('' if ok else 'FAILED: ') + msg
-                check_failed = check_failed or (None if ok else msg)
-        else:
-            out['cpu_baseline'] = None
-        print(json.dumps(out), flush=True)
-        if check_failed:            # the metric line is out; a wrong result still fails the run
-            sys.exit(3)
+    return roofline, per_layer
 
 
 if __name__ == '__main__':

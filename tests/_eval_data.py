@@ -42,3 +42,13 @@ def random_problem(rng, nd, ng, degenerate=False):
         d[-1, 2:] = d[-1, :2]
         g[-1, 2:] = g[-1, :2]
     return d, g, rng.random(ng) < 0.3, rng.random(ng) < 0.3
+
+
+OPS_THRS = np.array([0.1, 0.3, 0.5, 0.75, 0.9], np.float32)
+
+
+def random_problems(count=150):
+    """The seeded problems of tests/golden/eval_ops.npz (tests/golden/make_golden_eval.py ops)."""
+    rng = np.random.default_rng(3)
+    for it in range(count):
+        yield random_problem(rng, int(rng.integers(1, 40)), int(rng.integers(1, 14)), it % 4 == 0)

@@ -40,6 +40,19 @@ def arch_from(npz):
     return stages, reps, chans
 
 
+def assert_yolo_encode_matches(got, g):
+    """YOLOBBoxCoder.encode of tiny_v3.npz's coder boxes against the reference's values: the centre targets bit for bit.
+    The size targets are torch.log of IEEE-exact ratios, and torch's float log differs in the last bit between host CPUs
+    (its vector kernel follows the CPU), so they must equal torch.log of those ratios on this host bit for bit and the
+    reference's values within one unit in the last place."""
+    want, b, gt = g['coder/encode_s32'], g['coder/bboxes'], g['coder/encode_gt']
+    np.testing.assert_array_equal(got[:, :2], want[:, :2])
+    for j in (0, 1):
+        ratio = np.maximum((gt[:, 2 + j] - gt[:, j]) / (b[:, 2 + j] - b[:, j]), np.float32(1e-6))
+        np.testing.assert_array_equal(got[:, 2 + j], torch.log(torch.from_numpy(ratio)).numpy())
+    np.testing.assert_array_max_ulp(got[:, 2:], want[:, 2:], maxulp=1)
+
+
 @pytest.fixture(scope='session')
 def gpu_device():
     if not torch.cuda.is_available():

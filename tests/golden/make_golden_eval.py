@@ -1,13 +1,15 @@
 """Generate tests/golden/eval.npz: outputs of the REFERENCE's evaluation path on a synthetic dataset.
 
-Run in the build container only:   python tests/golden/make_golden_eval.py
+Run in the build container only:   python tests/golden/make_golden_eval.py [ops]
   * ``iou_coco`` / ``match_coco``: the reference's Cython sources compiled where they lie by
     oracle/build_ref.py (cython + gcc -> oracle/_ref/), called directly on seeded problems;
   * ``eval_map_flexible``: mmdet/core/evaluation/mean_ap_flexible.py imported from /root/reference, bound
     to those compiled ops, configured as datasets/coco.py:469-495 ('fast-bbox': ten IoU thresholds,
     S/M/L scale breakdown).  mmcv (absent) is represented by a Registry/build_from_cfg/progress stand-in
     with no arithmetic; ``np.bool`` (removed from numpy 2) is aliased to ``bool`` for the import.
-The fixture is data only.
+``ops`` writes only tests/golden/eval_ops.npz: the compiled ops on the seeded random problems of
+tests/test_oracle_eval_golden.py::test_ops_against_compiled_reference (inputs and outputs).
+The fixtures are data only.
 """
 import os
 import sys
@@ -19,8 +21,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 
 import _ref_import as R  # noqa: E402
+from _eval_data import OPS_THRS, random_problems  # noqa: E402
 from oracle import build_ref  # noqa: E402
 
 
@@ -152,5 +156,28 @@ def main():
     print(path, os.path.getsize(path), {k: float(v) for k, v in report.items()})
 
 
+def make_ops():
+    """iou_coco / match_coco of the compiled reference on random_problems(): every 2nd problem matches a tied IoU
+    matrix (rounded to eighths) instead of the exact one."""
+    iou_ref, match_ref = build_ref.load_eval()
+    out = dict(thrs=OPS_THRS)
+    n = 0
+    for it, (d, g, crowd, ign) in enumerate(random_problems()):
+        iou = iou_ref(d, g, crowd)
+        out[f'p{it}/det'], out[f'p{it}/gt'], out[f'p{it}/crowd'], out[f'p{it}/ignore'] = d, g, crowd, ign
+        out[f'p{it}/iou'] = iou
+        if it % 2:
+            iou = (np.round(iou * 8) / 8).astype(np.float32)
+        out[f'p{it}/match'] = match_ref(iou, OPS_THRS, ign, crowd)
+        n += 1
+    out['n'] = np.int64(n)
+    path = os.path.join(HERE, 'eval_ops.npz')
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), n)
+
+
 if __name__ == '__main__':
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == 'ops':
+        make_ops()
+    else:
+        main()

@@ -204,7 +204,7 @@ def test_yolov3_registry_names_and_checkpoint_layout(golden):
     """YOLOv3 row (8f-3): the reference's registry names build, and the state-dict keys / order / shapes of
     Darknet + YOLOV3Neck + YOLOV3Head equal the reference's (fixture from its own modules)."""
     import mmdet_yolov4_amd as pkg
-    from conftest import state_dict_from
+    from conftest import assert_yolo_encode_matches, state_dict_from
     for reg, name in ((pkg.registry.BACKBONES, 'Darknet'), (pkg.registry.NECKS, 'YOLOV3Neck'),
                       (pkg.registry.HEADS, 'YOLOV3Head'), (pkg.registry.DETECTORS, 'YOLOV3'),
                       (pkg.registry.BBOX_CODERS, 'YOLOBBoxCoder')):
@@ -234,7 +234,7 @@ def test_yolov3_registry_names_and_checkpoint_layout(golden):
     coder = pkg.YOLOBBoxCoder()
     b, p_ = torch.from_numpy(g['coder/bboxes']), torch.from_numpy(g['coder/pred'])
     np.testing.assert_array_equal(coder.decode(b, p_, 32).numpy(), g['coder/decode_s32'])
-    np.testing.assert_array_equal(coder.encode(b, torch.from_numpy(g['coder/encode_gt']), 32).numpy(), g['coder/encode_s32'])
+    assert_yolo_encode_matches(coder.encode(b, torch.from_numpy(g['coder/encode_gt']), 32).numpy(), g)
 
 
 def test_coco_test_annotation():

@@ -369,6 +369,25 @@ def test_bench_launcher_kill_does_not_mask_the_failing_rank(tmp_path, capfd, mon
     assert rc == 124
 
 
+def test_bench_dump_outputs_writes_the_valid_detections(tmp_path):
+    """--dump-outputs: float32 arrays of what the timed path hands its caller; rows past an image's count are masked."""
+    import torch
+    import numpy as np
+    import bench
+    dets = torch.arange(2 * 4 * 5, dtype=torch.float32).view(2, 4, 5)
+    labels = torch.tensor([[3, 7, 9, 9], [1, 9, 9, 9]], dtype=torch.int32)
+    count = torch.tensor([2, 1], dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / 'out'), dets, labels, count)
+    d, l, c = (np.load(tmp_path / 'out' / f'{n}.npy') for n in ('dets', 'labels', 'count'))
+    assert d.dtype == l.dtype == c.dtype == np.float32 and d.shape == (2, 4, 5) and l.shape == (2, 4)
+    assert np.array_equal(c, [2, 1])
+    assert np.array_equal(d[0, :2], dets[0, :2].numpy()) and np.array_equal(d[1, :1], dets[1, :1].numpy())
+    assert not d[0, 2:].any() and not d[1, 1:].any()
+    assert np.array_equal(l, [[3, 7, -1, -1], [1, -1, -1, -1]])
+    bench.dump_outputs(str(tmp_path / 'out'), dets, labels, count, '_rank1')
+    assert (tmp_path / 'out' / 'dets_rank1.npy').exists()
+
+
 def test_bench_main_self_launches_only_without_a_launcher(monkeypatch):
     import bench
     called = {}

@@ -1,10 +1,10 @@
 """Evaluation row, CPU: the oracle restatement of iou_coco / match_coco / eval_map_flexible
 against tests/golden/eval.npz (outputs of the reference's compiled Cython ops and of its
-mean_ap_flexible.py) and, when oracle/_ref holds them, against the compiled ops on random problems."""
+mean_ap_flexible.py) and tests/golden/eval_ops.npz (the compiled ops on seeded random problems), and, when oracle/_ref
+holds them, those stored outputs against the compiled ops."""
 import numpy as np
-import pytest
 
-from _eval_data import REPORT, SCALES, THRS10, dataset, random_problem, result_table
+from _eval_data import OPS_THRS, REPORT, SCALES, THRS10, dataset, result_table
 from oracle import build_ref
 from oracle import eval_oracle as E
 
@@ -45,17 +45,21 @@ def test_shared_tp_quirk(golden):
     assert own[0][1]['mAP'] == 1.0 and z['quirk/mAP'][0] == 0.5
 
 
-def test_ops_against_compiled_reference():
+def test_ops_against_compiled_reference(golden):
+    """150 seeded random problems: the oracle against the compiled reference ops' outputs stored in
+    tests/golden/eval_ops.npz, and those stored outputs against the compiled ops themselves where oracle/_ref holds them."""
+    z = golden('eval_ops')
     fns = build_ref.load_eval()
-    if fns is None:
-        pytest.skip('oracle/_ref holds no compiled eval ops and /root/reference is absent')
-    iou_ref, match_ref = fns
-    rng = np.random.default_rng(3)
-    thrs = np.array([0.1, 0.3, 0.5, 0.75, 0.9], np.float32)
-    for it in range(150):
-        d, g, crowd, ign = random_problem(rng, int(rng.integers(1, 40)), int(rng.integers(1, 14)), it % 4 == 0)
-        iou = iou_ref(d, g, crowd)
+    thrs = z['thrs']
+    assert np.array_equal(thrs, OPS_THRS) and int(z['n']) == 150
+    for it in range(int(z['n'])):
+        d, g, crowd, ign = (z[f'p{it}/{n}'] for n in ('det', 'gt', 'crowd', 'ignore'))
+        iou = z[f'p{it}/iou']
         assert np.array_equal(E.iou_coco(d, g, crowd), iou)
+        if fns is not None:
+            assert np.array_equal(fns[0](d, g, crowd), iou)
         if it % 2:
             iou = (np.round(iou * 8) / 8).astype(np.float32)
-        assert np.array_equal(E.match_coco(iou, thrs, ign, crowd), match_ref(iou, thrs, ign, crowd))
+        assert np.array_equal(E.match_coco(iou, thrs, ign, crowd), z[f'p{it}/match'])
+        if fns is not None:
+            assert np.array_equal(fns[1](iou, thrs, ign, crowd), z[f'p{it}/match'])

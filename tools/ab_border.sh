@@ -13,5 +13,5 @@ done; done
 for i in 1 2 3; do
 for v in product sel; do
 unset YV4_LIB_PATH; [ $v = sel ] && export YV4_LIB_PATH=$L/libyv4_w3f_sel.so
-echo -n "headline $v: "; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac roofline.all_convs_frac output_check
+echo -n "headline $v: "; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac roofline.all_convs_frac output_check
 done; done

@@ -17,5 +17,5 @@ done; done
 for i in 1 2 3; do
 for v in product $VARS; do
 if [ $v = product ]; then unset YV4_LIB_PATH; else export YV4_LIB_PATH=$L/libyv4_w3f_$v.so; fi
-echo -n "headline $v: "; python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac roofline.all_convs_frac output_check
+echo -n "headline $v: "; python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac roofline.all_convs_frac output_check
 done; done

@@ -9,7 +9,7 @@ source "$(dirname "$0")/_measure_lib.sh"
 for ab in ${ABLATIONS:-0 2}; do
   for cfg in "--dtype bf16" "--model yolov4s --size 416 --batch 256 --dtype f16"; do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/abl_dec/$ab; rm -rf "$OUT"; mkdir -p "$OUT"
-  YV4_DEC_ABLATE=$ab rocprofv3 --kernel-trace --output-format csv -d "$OUT" -- python3 bench.py $cfg --steps 6 --warmup 2 --no-cpu-baseline --no-train --no-output-check > "$OUT/log.txt" 2>&1 < /dev/null
+  YV4_DEC_ABLATE=$ab rocprofv3 --kernel-trace --output-format csv -d "$OUT" -- python3 bench.py --full $cfg --steps 6 --warmup 2 --no-cpu-baseline --no-train --no-output-check > "$OUT/log.txt" 2>&1 < /dev/null
   f=$(find "$OUT" -name '*kernel_trace.csv' | head -1)
   if [ -n "$f" ]; then python3 - "$f" "YV4_DEC_ABLATE=$ab $cfg" <<'PY'
 import csv,sys

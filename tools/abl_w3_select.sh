@@ -18,6 +18,6 @@ for i in 1 2; do
 for v in product sel; do
 unset YV4_LIB_PATH
 [ $v = sel ] && export YV4_LIB_PATH=$L/lib_var/libyv4_w3_sel.so
-echo -n "bf16 inference $v: "; python bench.py --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac output_check
-echo -n "configs[3] $v: "; python bench.py --model yolov4s --size 416 --batch 256 --dtype f16 --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac output_check
+echo -n "bf16 inference $v: "; python bench.py --full --dtype bf16 --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac output_check
+echo -n "configs[3] $v: "; python bench.py --full --model yolov4s --size 416 --batch 256 --dtype f16 --steps 20 --warmup 5 --no-cpu-baseline --no-train 2>/dev/null | python tools/last_json.py roofline.frac output_check
 done; done

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Print selected fields of the last JSON line on stdin (bench.py / train_bench.py output): value, ms_per_step and the
-given dotted paths.  usage: python bench.py ... | python tools/last_json.py [roofline.frac ...]"""
+given dotted paths.  usage: python bench.py --full ... | python tools/last_json.py [roofline.frac ...]"""
 import json
 import sys
 

@@ -17,12 +17,12 @@ COMMON="--steps 10 --warmup 2 --no-cpu-baseline --no-train --no-output-check"
 prof_bench () {   # name, bench arguments...
   local name="$1"; shift
   rm -rf "$OUT/$name"; mkdir -p "$OUT/$name"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name/trace" -- python3 bench.py $COMMON "$@" > "$OUT/$name/trace.log" 2>&1 < /dev/null
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name/trace" -- python3 bench.py --full $COMMON "$@" > "$OUT/$name/trace.log" 2>&1 < /dev/null
   grep '^{"metric"' "$OUT/$name/trace.log" | tail -1 > "$OUT/$name/bench_profiled.json"
   echo "$name: trace done"
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$name/pmc_fetch" -- python3 bench.py $COMMON "$@" > "$OUT/$name/pmc_fetch.log" 2>&1 < /dev/null
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$name/pmc_fetch" -- python3 bench.py --full $COMMON "$@" > "$OUT/$name/pmc_fetch.log" 2>&1 < /dev/null
   grep '^{"metric"' "$OUT/$name/pmc_fetch.log" | tail -1 > "$OUT/$name/bench_pmc.json"
-  rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/$name/pmc_write" -- python3 bench.py $COMMON "$@" > "$OUT/$name/pmc_write.log" 2>&1 < /dev/null
+  rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/$name/pmc_write" -- python3 bench.py --full $COMMON "$@" > "$OUT/$name/pmc_write.log" 2>&1 < /dev/null
   echo "$name: pmc done"
 }
 

@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define YV4_ABI_VERSION 7
+#define YV4_ABI_VERSION 8
 
 /* error codes */
 #define YV4_OK 0
@@ -650,6 +650,59 @@ typedef struct yv4_loss_desc {
 } yv4_loss_desc;
 int yv4_yolo_loss_fwd(const yv4_loss_desc* d, void* stream);
 int yv4_yolo_loss_bwd(const yv4_loss_desc* d, const float* grad_out, void* stream);
+
+/* ---- YOLOV3Head training loss, forward and backward (ABI 8) ------------------------------------------
+ * Replaces GridAssigner.assign (core/bbox/assigners/grid_assigner.py:73-156), responsible_flags + grid_anchors
+ * (core/anchor/anchor_generator.py:667-727), BboxOverlaps2D (core/bbox/iou_calculators/iou2d_calculator.py),
+ * YOLOBBoxCoder.encode (core/bbox/coder/yolo_bbox_coder.py:26-60), PseudoSampler and loss / loss_single /
+ * get_targets / _get_targets_single (models/dense_heads/yolo_head.py:396-586) for ALL levels and images of a batch:
+ * forward = assignment + the four loss sums per level, backward = one pass that writes the whole gradient of every
+ * level's prediction map.  Nothing returns to the host in between.
+ *   pred:  fp32 logits (N, A*(5+C), H, W) read through the element strides sn, sc, sh, sw (NCHW and channels-last
+ *          maps without a copy), channel a*(5+C) + j; dpred (backward) is written with the same strides.
+ *   gt (G,4) fp32 x1 y1 x2 y2, gt_label (G) int64, gt_img (G) int64 NON-DECREASING: the batch's ground truths
+ *          concatenated image by image.
+ *   Anchors of an image: all levels concatenated in level order, (y*W + x)*A + a inside a level.
+ *   Negatives: max IoU over the image's ground truths in (neg_lo, neg_hi] -- neg_iou_thr = t is (-1, t] (IoUs are
+ *   >= 0), the tuple form (lo, hi) is (lo, hi]; with no ground truth every anchor is negative.  Threshold positives,
+ *   per-gt claims (gt_max_assign_all), one-hot smoothing (smoother) and the coder's eps (eps, eps_hi = fp32 of
+ *   1 - eps) as the reference; iou_eps is BboxOverlaps2D's union clamp.  A ground truth whose centre cell lies off a
+ *   level's map has no responsible cell at that level (the reference raises or wraps its index there).
+ * Losses per level [cls | conf | xy | wh] = loss_weight[k] * sum, divided by the element count where
+ *   reduce_mean[k] (weight_reduce_loss with reduction='mean'), written to `losses` (L*4 float, device) by the
+ *   forward.  yv4_yolov3_loss_bwd: grad_out (L,4) float (device) = upstream gradients of those.
+ * work buffers (device): img_off N+1, gt_cell L*G, gt_max G, gt_arg G int32; assigned N*(anchors per image) int32 --
+ *   after the forward it holds assigned_gt_inds of every anchor (-1 / 0 / k, k-1 indexing the image's ground truths);
+ *   the backward reads it, so it must survive until then; sums 2*L*4 doubles (the second half: the deterministic
+ *   mode's lo words). */
+#define YV4_V3_LOSS_MAX_LEVELS 5
+typedef struct yv4_v3_loss_level {
+  const float* pred;
+  float* dpred;            /* backward: gradient of pred, same strides */
+  int64_t sn, sc, sh, sw;  /* element strides of pred (and dpred) */
+  int32_t H, W, stride, reserved;
+  float base_anchors[8][4];
+} yv4_v3_loss_level;
+typedef struct yv4_v3_loss_desc {
+  yv4_v3_loss_level levels[YV4_V3_LOSS_MAX_LEVELS];
+  int32_t num_levels, N, A, num_classes, G, gt_max_assign_all;
+  const float* gt;
+  const int64_t* gt_label;
+  const int64_t* gt_img;
+  float pos_iou_thr, neg_lo, neg_hi, min_pos_iou;
+  float eps, eps_hi, iou_eps, smoother;
+  float loss_weight[4];    /* cls, conf, xy, wh */
+  int32_t reduce_mean[4];  /* 0: reduction='sum', 1: reduction='mean' */
+  int32_t* img_off;
+  int32_t* gt_cell;
+  int32_t* gt_max;
+  int32_t* gt_arg;
+  int32_t* assigned;
+  double* sums;
+  float* losses;
+} yv4_v3_loss_desc;
+int yv4_yolov3_loss_fwd(const yv4_v3_loss_desc* d, void* stream);
+int yv4_yolov3_loss_bwd(const yv4_v3_loss_desc* d, const float* grad_out, void* stream);
 
 /* ---- test-time input pipeline (Resize keep_ratio -> Pad -> Normalize -> ImageToTensor of
  * configs/yolov4/yolov4l_coco_mosaic.py:70-84) for one 8-bit HWC image: bilinear resize with OpenCV's 8-bit

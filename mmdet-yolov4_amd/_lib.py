@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get('YV4_LIB_PATH') or os.path.join(LIB_DIR, 'libyv4_hip.s
 CSRC_DIR = os.path.join(_HERE, 'csrc')
 
 # ---- constants mirrored from include/yv4.h -------------------------------------
-ABI_VERSION = 7
+ABI_VERSION = 8
 STATS_REPLICAS = 64        # YV4_STATS_REPLICAS
 GRAD_PREPARE_MAX_WG = 2048  # YV4_GRAD_PREPARE_MAX_WG
 F32, F16, BF16, F64 = 0, 1, 2, 3
@@ -68,6 +68,27 @@ class LossDesc(C.Structure):
                 ('w_cls', C.c_float), ('w_conf', C.c_float), ('w_bbox', C.c_float),
                 ('slot_anchor', C.c_void_p), ('winner', C.c_void_p), ('npos', C.c_void_p), ('conf_t', C.c_void_p),
                 ('gpos', C.c_void_p), ('sums', C.c_void_p), ('losses', C.c_void_p)]
+
+
+class V3LossLevel(C.Structure):
+    """``yv4_v3_loss_level`` (ABI 8)."""
+    _fields_ = [('pred', C.c_void_p), ('dpred', C.c_void_p),
+                ('sn', C.c_int64), ('sc', C.c_int64), ('sh', C.c_int64), ('sw', C.c_int64),
+                ('H', C.c_int32), ('W', C.c_int32), ('stride', C.c_int32), ('reserved', C.c_int32),
+                ('base_anchors', (C.c_float * 4) * 8)]
+
+
+class V3LossDesc(C.Structure):
+    """``yv4_v3_loss_desc`` (ABI 8)."""
+    _fields_ = [('levels', V3LossLevel * 5),
+                ('num_levels', C.c_int32), ('N', C.c_int32), ('A', C.c_int32), ('num_classes', C.c_int32),
+                ('G', C.c_int32), ('gt_max_assign_all', C.c_int32),
+                ('gt', C.c_void_p), ('gt_label', C.c_void_p), ('gt_img', C.c_void_p),
+                ('pos_iou_thr', C.c_float), ('neg_lo', C.c_float), ('neg_hi', C.c_float), ('min_pos_iou', C.c_float),
+                ('eps', C.c_float), ('eps_hi', C.c_float), ('iou_eps', C.c_float), ('smoother', C.c_float),
+                ('loss_weight', C.c_float * 4), ('reduce_mean', C.c_int32 * 4),
+                ('img_off', C.c_void_p), ('gt_cell', C.c_void_p), ('gt_max', C.c_void_p), ('gt_arg', C.c_void_p),
+                ('assigned', C.c_void_p), ('sums', C.c_void_p), ('losses', C.c_void_p)]
 
 
 class AugImage(C.Structure):
@@ -170,6 +191,8 @@ SIGNATURES = {
     'yv4_pack_weights_multi': (C.c_int, [_vp, _i, _i, _vp]),
     'yv4_yolo_loss_fwd': (C.c_int, [C.POINTER(LossDesc), _vp]),
     'yv4_yolo_loss_bwd': (C.c_int, [C.POINTER(LossDesc), _vp, _vp]),
+    'yv4_yolov3_loss_fwd': (C.c_int, [C.POINTER(V3LossDesc), _vp]),
+    'yv4_yolov3_loss_bwd': (C.c_int, [C.POINTER(V3LossDesc), _vp, _vp]),
     'yv4_mosaic_augment_u8': (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     'yv4_augment_boxes': (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _d, _d, _f, _f, _vp, _vp, _vp, _vp]),
     'yv4_letterbox_u8': (C.c_int, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _i, _i, _i, _vp]),
@@ -180,6 +203,10 @@ SIGNATURES = {
     'yv4_loss_scale_update': (C.c_int, [_vp, _vp, _f, _f, _i, _vp]),
     'yv4_ema_update': (C.c_int, [_vp, _vp, _i64, _f, _vp]),
 }
+
+#: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
+#: runs (YV4_LIB_ABI_ANY=1); has_v3_loss() tells the YOLOv3 head whether its fused loss is there
+ABI8_SYMBOLS = frozenset(('yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'))
 
 _lock = threading.Lock()
 _lib = None
@@ -211,21 +238,30 @@ def lib():
                 'Run `python -c "import __graft_entry__ as g; g.build()"` (or '
                 f'`make -C {CSRC_DIR}`). There is no CPU fallback for this path.')
         handle = C.CDLL(LIB_PATH)
+        handle.yv4_abi_version.restype = C.c_int
+        handle.yv4_abi_version.argtypes = []
+        got = handle.yv4_abi_version()
         for name, (res, args) in SIGNATURES.items():
+            if name in ABI8_SYMBOLS and got < 8:
+                continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
             fn.restype = res
             fn.argtypes = args
-        got = handle.yv4_abi_version()
         if got != ABI_VERSION and not (os.environ.get('YV4_LIB_PATH') and os.environ.get('YV4_LIB_ABI_ANY') == '1'
                                        and got == ABI_VERSION - 1):
-            # (YV4_LIB_ABI_ANY=1 with YV4_LIB_PATH: same-box A/B against the previous ABI's build -- ABI 7 only APPENDED
-            # yv4_conv_desc.flags, which an ABI-6 library never reads)
+            # (YV4_LIB_ABI_ANY=1 with YV4_LIB_PATH: same-box A/B against the previous ABI's build -- ABI 8 only APPENDED
+            # the YOLOv3 loss entry points, which are left unbound for an ABI-7 library: see ABI8_SYMBOLS)
             raise RuntimeError(f'libyv4_hip.so ABI {got} != binding ABI {ABI_VERSION}; rebuild')
         form = os.environ.get('YV4_NMS_IOU_FORM', '').lower()
         if form in ('mul', '1', 'product', 'cuda'):
             handle.yv4_nms_set_iou_form(NMS_IOU_MUL)      # mmcv's CUDA-kernel predicate instead of its CPU kernel's
         _lib = handle
     return _lib
+
+
+def has_v3_loss():
+    """The loaded library exports ``yv4_yolov3_loss_fwd`` / ``_bwd`` (ABI >= 8)."""
+    return lib().yv4_abi_version() >= 8
 
 
 class Yv4Error(RuntimeError):

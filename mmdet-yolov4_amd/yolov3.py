@@ -14,9 +14,12 @@ Everything reuses the YOLOv4 machinery: ``Conv`` (mmcv ConvModule layout) with t
 of the fused conv kernel, the residual add in the conv epilogue, nearest-upsample + concat as channel-
 offset stores, and decode + per-class NMS in two launches (``yv4_decode_filter_v3``: v3 box decode,
 per-LEVEL top-k by objectness, ``conf_thr``, ``score_factors``).  Training of the v3 head (GridAssigner +
-MSE / BCE losses, ``yolo_head.py:393-560``) runs on the HIP training kernels for the convs / BN and
-torch tensor ops for the target assignment and the loss, like the YOLOv4 head's.
+MSE / BCE losses, ``yolo_head.py:393-560``) runs on the HIP training kernels for the convs / BN; target
+assignment and loss run on ``yv4_yolov3_loss_fwd`` / ``_bwd`` (``YoloV3LossFunction``) for the configurations
+``_fused_loss_ok`` admits, and on torch tensor ops otherwise.
 """
+import ctypes as C
+import os
 import warnings
 
 import torch
@@ -24,7 +27,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.modules.batchnorm import _BatchNorm
 
+from . import _lib
 from . import assigners as _assigners  # noqa: F401  (registers GridAssigner / PseudoSampler)
+from . import losses as _losses
 from . import ops
 from . import train_ops as T
 from .bricks import HipModule
@@ -33,7 +38,7 @@ from .plan import Plan
 from .registry import (BACKBONES, BBOX_CODERS, DETECTORS, HEADS, NECKS, ConfigDict, build_anchor_generator,
                        build_assigner, build_bbox_coder, build_loss, build_sampler)
 from .single_stage import SingleStageDetector
-from .yolocsp_head import collect_results, set_scale_factors
+from .yolocsp_head import _upload, collect_results, set_scale_factors
 
 _NORM = dict(type='BN', requires_grad=True)
 _ACT = dict(type='LeakyReLU', negative_slope=0.1)
@@ -269,9 +274,105 @@ class YOLOBBoxCoder:
         return torch.stack((xp - wp / 2, yp - hp / 2, xp + wp / 2, yp + hp / 2), dim=-1)
 
 
+class YoloV3LossFunction(torch.autograd.Function):
+    """All levels' ``loss_single`` + ``get_targets`` (GridAssigner, PseudoSampler, YOLOBBoxCoder.encode) of
+    ``YOLOV3Head`` on ``yv4_yolov3_loss_fwd`` / ``yv4_yolov3_loss_bwd``.  Returns the (num_levels, 4) fp32 matrix
+    [loss_cls | loss_conf | loss_xy | loss_wh] and, not differentiable, the (N, anchors per image) int32
+    ``assigned_gt_inds`` of the batch.  The backward writes each level's whole map gradient once, with the map's
+    strides.  Nothing is read back by the host in either direction.  ``scratch``: None, or a dict that receives the
+    forward's work buffers (``sums``: the raw (2, L, 4) sum words -- doubles, or [hi | lo] fixed-point words under
+    ``set_deterministic(True)``; ``assigned``)."""
+
+    @staticmethod
+    def forward(ctx, head, gt, gt_label, gt_img, scratch, *maps):
+        L = len(maps)
+        dev = maps[0].device
+        A = head.num_anchors
+        N = maps[0].shape[0]
+        G = int(gt.shape[0])
+        asg = head.assigner
+        d = _lib.V3LossDesc()
+        d.num_levels, d.N, d.A, d.num_classes, d.G = L, N, A, head.num_classes, G
+        d.gt_max_assign_all = 1 if asg.gt_max_assign_all else 0
+        TA = 0
+        for l, p in enumerate(maps):
+            _, _, H, W = p.shape
+            lv = d.levels[l]
+            lv.pred = p.data_ptr()
+            lv.sn, lv.sc, lv.sh, lv.sw = p.stride()
+            lv.H, lv.W, lv.stride = H, W, int(head.featmap_strides[l])
+            ba = head.anchor_generator.base_anchors[l].float().cpu()
+            for k in range(A):
+                for c in range(4):
+                    lv.base_anchors[k][c] = float(ba[k, c])
+            TA += H * W * A
+        i32 = dict(dtype=torch.int32, device=dev)
+        img_off = torch.empty(N + 1, **i32)
+        gt_cell = torch.empty(max(L * G, 1), **i32)
+        gt_max = torch.empty(max(G, 1), **i32)
+        gt_arg = torch.empty(max(G, 1), **i32)
+        assigned = torch.empty(N, TA, **i32)
+        sums = torch.empty(2, L, 4, dtype=torch.float64, device=dev)
+        out = torch.empty(L, 4, dtype=torch.float32, device=dev)
+        gt = gt.detach().float().contiguous()
+        gt_label = gt_label.long().contiguous()
+        gt_img = gt_img.long().contiguous()
+        d.gt, d.gt_label, d.gt_img = gt.data_ptr(), gt_label.data_ptr(), gt_img.data_ptr()
+        d.pos_iou_thr, d.min_pos_iou = float(asg.pos_iou_thr), float(asg.min_pos_iou)
+        if isinstance(asg.neg_iou_thr, float):
+            d.neg_lo, d.neg_hi = -1.0, float(asg.neg_iou_thr)      # [0, t]: IoUs are never negative
+        else:
+            d.neg_lo, d.neg_hi = float(asg.neg_iou_thr[0]), float(asg.neg_iou_thr[1])
+        eps = head.bbox_coder.eps
+        d.eps, d.eps_hi = float(eps), float(torch.tensor(1 - eps, dtype=torch.float32))
+        d.iou_eps = 1e-6                                             # BboxOverlaps2D's union clamp
+        d.smoother = float(head.one_hot_smoother)
+        terms = (head.loss_cls, head.loss_conf, head.loss_xy, head.loss_wh)
+        for k, t in enumerate(terms):
+            d.loss_weight[k] = float(t.loss_weight)
+            d.reduce_mean[k] = 1 if t.reduction == 'mean' else 0
+        d.img_off, d.gt_cell, d.gt_max, d.gt_arg = (t.data_ptr() for t in (img_off, gt_cell, gt_max, gt_arg))
+        d.assigned, d.sums, d.losses = assigned.data_ptr(), sums.data_ptr(), out.data_ptr()
+        _lib.check(_lib.lib().yv4_yolov3_loss_fwd(C.byref(d), ops.stream_ptr()), 'yv4_yolov3_loss_fwd')
+        if scratch is not None:
+            scratch.update(sums=sums, assigned=assigned)
+        ctx.desc = d
+        ctx.keep = (maps, gt, gt_label, gt_img, img_off, gt_cell, gt_max, gt_arg, assigned, sums)
+        ctx.mark_non_differentiable(assigned)
+        return out, assigned
+
+    @staticmethod
+    def backward(ctx, gout, _gassigned):
+        d = ctx.desc
+        maps = ctx.keep[0]
+        gout = gout.float().contiguous()
+        grads = [torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=p.device) for p in maps]
+        for l, g in enumerate(grads):
+            d.levels[l].dpred = g.data_ptr()
+        _lib.check(_lib.lib().yv4_yolov3_loss_bwd(C.byref(d), gout.data_ptr(), ops.stream_ptr()), 'yv4_yolov3_loss_bwd')
+        return (None, None, None, None, None) + tuple(grads)
+
+
+def v3_fused_loss(head, pred_maps, gt_bboxes, gt_labels, scratch=None):
+    """``YoloV3LossFunction`` on a batch given as the head's ``loss`` takes it: returns ((L, 4) losses,
+    (N, anchors per image) int32 assigned_gt_inds).  The ground truths are concatenated and uploaded once.
+    ``scratch``: see ``YoloV3LossFunction``."""
+    device = pred_maps[0].device
+    sizes = [int(g.shape[0]) for g in gt_bboxes]
+    gt = torch.cat([g.reshape(-1, 4) for g in gt_bboxes], dim=0).to(device)
+    labels = torch.cat([l_.reshape(-1) for l_ in gt_labels], dim=0).to(device)
+    img = _upload(torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes, dtype=torch.long)), device)
+    maps = []
+    for p in pred_maps:
+        if 0 in p.stride():                  # an expanded view: the gradient needs distinct elements
+            p = p.contiguous()
+        maps.append(p)
+    return YoloV3LossFunction.apply(head, gt, labels, img, scratch, *maps)
+
+
 @HEADS.register_module()
 class YOLOV3Head(HipModule):
-    """yolo_head.py:20-391 (layers, forward, get_bboxes).  ``loss`` / training targets are not built."""
+    """yolo_head.py:20-586 (layers, forward, get_bboxes, loss and training targets)."""
 
     def __init__(self, num_classes, in_channels, out_channels=(1024, 512, 256),
                  anchor_generator=dict(type='YOLOAnchorGenerator',
@@ -403,6 +504,11 @@ class YOLOV3Head(HipModule):
     def loss(self, pred_maps, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
         num_imgs = len(img_metas)
         pred_maps = [p.float() for p in pred_maps]
+        if self._fused_loss_ok(pred_maps):
+            out, _ = v3_fused_loss(self, pred_maps, gt_bboxes, gt_labels)
+            cols = out.unbind(1)
+            return dict(loss_cls=list(cols[0].unbind(0)), loss_conf=list(cols[1].unbind(0)),
+                        loss_xy=list(cols[2].unbind(0)), loss_wh=list(cols[3].unbind(0)))
         device = pred_maps[0].device
         featmap_sizes = [pred_maps[i].shape[-2:] for i in range(self.num_levels)]
         multi_level_anchors = self.anchor_generator.grid_anchors(featmap_sizes, device)
@@ -413,6 +519,35 @@ class YOLOV3Head(HipModule):
         res = [self.loss_single(p, t, n) for p, t, n in zip(pred_maps, target_maps_list, neg_maps_list)]
         losses_cls, losses_conf, losses_xy, losses_wh = (list(x) for x in zip(*res))
         return dict(loss_cls=losses_cls, loss_conf=losses_conf, loss_xy=losses_xy, loss_wh=losses_wh)
+
+    def _fused_loss_ok(self, pred_maps):
+        """The fused kernels cover what the recipes use: CUDA fp32 maps of A*(5+C) channels, GridAssigner +
+        PseudoSampler, sigmoid CrossEntropyLoss without class weights for cls / conf / xy and MSELoss for wh, each
+        with reduction 'sum' or 'mean', at most 5 levels of at most 8 anchors.  Anything else takes the tensor-op path
+        below (on the GPU as well).  YV4_FUSED_LOSS=0 forces that path (A/B, tests), as for the YOLOv4 head."""
+        if os.environ.get('YV4_FUSED_LOSS', '1') == '0':
+            return False
+        if not self.train_cfg or len(pred_maps) != self.num_levels or self.num_levels > 5 or self.num_anchors > 8:
+            return False
+        if len(set(self.anchor_generator.num_base_anchors)) != 1 or self.num_classes < 1:
+            return False
+        for p in pred_maps:
+            if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float32 and p.dim() == 4
+                    and p.shape[1] == self.num_anchors * self.num_attrib and p.shape[0] == pred_maps[0].shape[0]):
+                return False
+        if type(getattr(self, 'assigner', None)) is not _assigners.GridAssigner:
+            return False
+        if type(getattr(self, 'sampler', None)) is not _assigners.PseudoSampler:
+            return False
+        neg = self.assigner.neg_iou_thr
+        if not (isinstance(neg, float) or (isinstance(neg, (tuple, list)) and len(neg) == 2)):
+            return False
+        for t in (self.loss_cls, self.loss_conf, self.loss_xy):
+            if type(t) is not _losses.CrossEntropyLoss or t.class_weight is not None or t.reduction not in ('sum', 'mean'):
+                return False
+        if type(self.loss_wh) is not _losses.MSELoss or self.loss_wh.reduction not in ('sum', 'mean'):
+            return False
+        return _lib.has_v3_loss()
 
     def loss_single(self, pred_map, target_map, neg_map):
         num_imgs = len(pred_map)

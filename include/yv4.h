@@ -57,6 +57,9 @@ extern "C" {
 #define YV4_F16 1
 #define YV4_BF16 2
 #define YV4_F64 3
+/* element type of the fp8 inference plans' activations and weights (OCP e4m3fn, max 448; the fp8 entry points below
+ * take it where the other entry points take YV4_F16 / YV4_BF16; the standalone activation op has no fp8 form) */
+#define YV4_F8E4M3 3
 
 /* activations of the fused conv epilogue (Mish everywhere in v4/v5,
  * LeakyReLU(slope) in the v3 path, Swish when a config overrides act_cfg) */
@@ -793,6 +796,33 @@ int yv4_augment_boxes(const yv4_aug_image* imgs, int N, int out_size, const floa
                       const int32_t* tile, const int64_t* seg, int cap, double min_area, double min_visibility,
                       float min_size, float max_aspect_ratio, float* out_boxes, int32_t* out_labels,
                       int32_t* out_count, void* stream);
+
+/* ---- FP8 (OCP e4m3fn) inference (csrc/conv_f8.hip) ------------------------------------------------------------------
+ * A code is e4m3(clamp(v * inv_s, -448, 448)), rounded to nearest even; NaN is never produced.  Activations carry one fp32
+ * scale s per buffer (inv_s = 1/s computed by the caller), weights one per output channel.
+ *
+ * Fused conv with e4m3 operands and fp32 accumulation (v_mfma_scale_f32_32x32x64_f8f6f4, unit block scales).  x and w
+ * are e4m3 codes: x an NHWC view, w (Cout, KH*KW*Cin) in (kh, kw, ci) order.  The dequantization is the caller's
+ * business: scale1 = s1 * sw[co] * sx (folded in double, rounded to fp32).  Epilogue:
+ *   v = act1(acc * scale1 + shift1);  v += residual * r_scale (e4m3 view);  v = act2(v * scale2 + shift2) (optional);
+ *   y = out_dtype == YV4_F8E4M3 ? e4m3(clamp(v * y_inv_scale, +-448)) : v (fp32).
+ * Cin and the input view's cstride / coff must be multiples of 16 (YV4_E_UNSUPPORTED otherwise); output and residual
+ * views may sit at any channel offset.  desc->tile: YV4_TILE_AUTO or one of YV4_F8TILE_*. */
+#define YV4_F8TILE_128x128 1
+#define YV4_F8TILE_128x64 2
+#define YV4_F8TILE_64x64 3
+int yv4_conv_bn_act_fwd_f8(const yv4_conv_desc* d, int out_dtype, const void* x, const void* w, const float* scale1,
+                           const float* shift1, const float* scale2, const float* shift2, const void* residual,
+                           float r_scale, float y_inv_scale, void* y, void* stream);
+/* The tile YV4_TILE_AUTO resolves to for this descriptor. */
+int yv4_conv_f8_pick_tile(const yv4_conv_desc* d);
+/* x: an NHWC view of dtype YV4_F32 / YV4_F16 / YV4_BF16 -> y: an e4m3 view of the same shape, y = e4m3(clamp(x *
+ * inv_scale, +-448)).  C, strides and offsets must be multiples of 4. */
+int yv4_quantize_f8(const void* x, int dtype, int N, int H, int W, int C, int x_cstride, int x_coff, void* y,
+                    int y_cstride, int y_coff, float inv_scale, void* stream);
+/* SPP on e4m3 codes: as yv4_spp_pool_fwd_h16 (channels [coff, coff+C) -> mp5 / mp9 / mp13 into the next three C-channel
+ * slots of the same buffer), codes compared in sign-magnitude order: the max is exact.  C, cstride, coff % 4 == 0. */
+int yv4_spp_pool_fwd_f8(void* buf, int N, int H, int W, int C, int cstride, int coff, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,8 @@ ABI_VERSION = 8
 STATS_REPLICAS = 64        # YV4_STATS_REPLICAS
 GRAD_PREPARE_MAX_WG = 2048  # YV4_GRAD_PREPARE_MAX_WG
 F32, F16, BF16, F64 = 0, 1, 2, 3
+F8E4M3 = 3                 # YV4_F8E4M3: the fp8 entry points' element code (the standalone op's F64 elsewhere)
+F8TILE_128x128, F8TILE_128x64, F8TILE_64x64 = 1, 2, 3
 ACT_NONE, ACT_MISH, ACT_LEAKY, ACT_SWISH = 0, 1, 2, 3
 NMS_IOU_DIV, NMS_IOU_MUL = 0, 1
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4
@@ -202,11 +204,18 @@ SIGNATURES = {
     'yv4_sgd_step': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _vp, _vp]),
     'yv4_loss_scale_update': (C.c_int, [_vp, _vp, _f, _f, _i, _vp]),
     'yv4_ema_update': (C.c_int, [_vp, _vp, _i64, _f, _vp]),
+    'yv4_conv_bn_act_fwd_f8': (C.c_int, [C.POINTER(ConvDesc), _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp]),
+    'yv4_conv_f8_pick_tile': (C.c_int, [C.POINTER(ConvDesc)]),
+    'yv4_quantize_f8': (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp]),
+    'yv4_spp_pool_fwd_f8': (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
 #: runs (YV4_LIB_ABI_ANY=1); has_v3_loss() tells the YOLOv3 head whether its fused loss is there
 ABI8_SYMBOLS = frozenset(('yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'))
+#: the fp8 inference entry points (additive within ABI 8): bound when the library exports them, so that an ABI-8 build
+#: from before them still loads for A/B runs; has_fp8() tells the plan whether they are there
+FP8_SYMBOLS = frozenset(('yv4_conv_bn_act_fwd_f8', 'yv4_conv_f8_pick_tile', 'yv4_quantize_f8', 'yv4_spp_pool_fwd_f8'))
 
 _lock = threading.Lock()
 _lib = None
@@ -244,6 +253,8 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             if name in ABI8_SYMBOLS and got < 8:
                 continue
+            if name in FP8_SYMBOLS and not hasattr(handle, name):
+                continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
             fn.restype = res
             fn.argtypes = args
@@ -262,6 +273,12 @@ def lib():
 def has_v3_loss():
     """The loaded library exports ``yv4_yolov3_loss_fwd`` / ``_bwd`` (ABI >= 8)."""
     return lib().yv4_abi_version() >= 8
+
+
+def has_fp8():
+    """The loaded library exports the fp8 (e4m3) inference entry points."""
+    h = lib()
+    return all(hasattr(h, n) for n in FP8_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

@@ -89,3 +89,24 @@ def calibrate_bn(plan, *inputs):
         L.update(saved)
         op.fn(stream)
     torch.cuda.synchronize()
+
+
+@torch.no_grad()
+def calibrate_fp8(detector, imgs):
+    """Activation amax for the fp8 plans: build the bf16 plan of the same network, run it once on ``imgs`` (NCHW fp32
+    on the device) and record amax|x| of every buffer, keyed by the buffer's emit-order key (the same in every input
+    geometry, so one calibration serves any batch and size).  An fp8 plan takes the max over each of its scale groups
+    and sets s = amax / 448.  Stored on the detector (``fp8_amax``, ``fp8_version``); on a randomly initialised
+    detector run it after the BatchNorm calibration."""
+    assert imgs.is_cuda and imgs.dtype == torch.float32 and imgs.dim() == 4
+    N, _, H, W = imgs.shape
+    plan = detector.build_plan(N, H, W, imgs.device, True, torch.bfloat16)
+    for b in plan.bufs:
+        if b.tensor is not None:
+            b.tensor.zero_()          # channels no producer writes must not count
+    plan.run(imgs)
+    torch.cuda.synchronize()
+    amax = {b.key: float(b.tensor.float().abs().max()) for b in plan.bufs if b.tensor is not None and b.numel}
+    detector.fp8_amax = amax
+    detector.fp8_version = getattr(detector, 'fp8_version', 0) + 1
+    return amax

@@ -27,11 +27,13 @@ class Buf:
     """One NHWC allocation: (N, H, W, C) with C elements per pixel (fp32, or fp16 / bf16 in a
     16-bit plan)."""
 
-    def __init__(self, N, H, W, C_, name='', dtype=torch.float32):
+    def __init__(self, N, H, W, C_, name='', dtype=torch.float32, key=None):
         self.N, self.H, self.W, self.C = int(N), int(H), int(W), int(C_)
         self.name = name
         self.dtype = dtype
         self.tensor = None
+        self.key = key or name      # fp8 plans: '<emit index>:<name>', the calibration key (same in every geometry)
+        self.group = self           # fp8 plans: union-find parent; one activation scale per group (resample edges)
 
     @property
     def numel(self):
@@ -112,19 +114,63 @@ def pack_conv_weight(weight, cin_pad=None, align=4):
     return w.reshape(Cout, KH * KW * cp).contiguous(), cp
 
 
+def quantize_weight_f8(wp):
+    """Packed fp32 weight (Cout, K) -> (e4m3 codes (Cout, K), fp32 per-output-channel scales sw): sw[co] =
+    amax|w[co]| / 448 (1 where the row is all zeros), codes = e4m3(clamp(w * (1 / sw), +-448)) rounded to nearest even."""
+    wp = wp.detach().float().cpu()
+    amax = wp.abs().amax(dim=1)
+    sw = torch.where(amax > 0, amax / F8_MAX, torch.ones_like(amax))
+    inv = 1.0 / sw
+    return (wp * inv[:, None]).clamp(-F8_MAX, F8_MAX).to(F8), sw
+
+
+def fold_s1_f8(s1, sw, sx):
+    """The dequantization folded into the stage-1 affine: s1' = float(double(s1) * double(sw[co]) * double(sx))."""
+    return (s1.detach().double().cpu() * sw.double().cpu() * float(sx)).float()
+
+
+def f8_scale(amax):
+    """Activation scale from a calibrated amax: s = amax / 448 in fp32 (1 when amax is 0)."""
+    a = torch.tensor(float(amax), dtype=torch.float32)
+    return float(a / F8_MAX) if float(a) > 0 else 1.0
+
+
+def f8_inv(s):
+    """inv_s: the fp32 value 1 / s."""
+    return float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(s, dtype=torch.float32))
+
+
 _DCODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # YV4_F32 / YV4_F16 / YV4_BF16
+F8 = torch.float8_e4m3fn
+F8_MAX = 448.0
 _PLAN_NT = os.environ.get('YV4_PLAN_NT', '0') == '1'                 # non-temporal output stores in 16-bit plans (ABI 7): opt-in
+
+
+def _esize(dtype):
+    return torch.empty(0, dtype=dtype).element_size()
 
 
 class Plan:
     """``dtype``: torch.float32 (the parity dtype) or torch.float16 / torch.bfloat16: activations and
     weights are stored in that type, convs accumulate in fp32 (``yv4_conv_bn_act_fwd_h16``), folded BN
-    scale/shift and the pred maps handed to decode stay fp32."""
+    scale/shift and the pred maps handed to decode stay fp32.  torch.float8_e4m3fn: e4m3 activations and
+    weights with calibrated scales (``yv4_conv_bn_act_fwd_f8``) behind a bf16 stem; ``self.dtype`` is then
+    the stem's 16-bit type and ``self.plan_dtype`` the requested one."""
 
-    def __init__(self, device, dtype=torch.float32):
+    def __init__(self, device, dtype=torch.float32, fp8_amax=None):
         self.device = torch.device(device)
-        if dtype not in _DCODE:
-            raise ValueError(f'Plan dtype must be float32, float16 or bfloat16 (got {dtype})')
+        if dtype not in _DCODE and dtype != F8:
+            raise ValueError(f'Plan dtype must be float32, float16, bfloat16 or float8_e4m3fn (got {dtype})')
+        # fp8 plans: activations and weights in e4m3 with fp32 scales (``fp8_amax``: calibrated amax per buffer key,
+        # calibrate.calibrate_fp8); the image-facing stem -- the convs that read the image and the conv that reads the
+        # 3x3 stem's output -- stays on the bf16 kernels, and one quantize op converts what the first fp8 conv reads
+        self.f8 = dtype == F8
+        self.plan_dtype = dtype
+        self.fp8_amax = dict(fp8_amax) if fp8_amax is not None else None
+        if self.f8:
+            dtype = torch.bfloat16
+        self.buf_dtype = F8 if self.f8 else dtype
+        self._quantized = {}  # fp8 plans: 16-bit Buf -> its e4m3 twin (made once by the quantize op)
         self.dtype = dtype
         self.h16 = dtype != torch.float32
         self.dcode = _DCODE[dtype]
@@ -140,9 +186,67 @@ class Plan:
 
     # ---- buffers -----------------------------------------------------------------
     def new_buf(self, N, H, W, C_, name='', dtype=None):
-        b = Buf(N, H, W, C_, name or f'b{len(self.bufs)}', dtype or self.dtype)
+        nkeys = getattr(self, '_nkeys', 0)
+        self._nkeys = nkeys + 1
+        name = name or f'b{len(self.bufs)}'
+        b = Buf(N, H, W, C_, name, dtype or self.buf_dtype, key=f'{nkeys}:{name}')
         self.bufs.append(b)
         return View(b, 0, C_)
+
+    # ---- fp8 scale groups ------------------------------------------------------------
+    @staticmethod
+    def scale_group(buf):
+        """The representative Buf of buf's scale group (union-find root)."""
+        while buf.group is not buf:
+            buf.group = buf.group.group
+            buf = buf.group
+        return buf
+
+    def _union(self, a, b):
+        ra, rb = self.scale_group(a), self.scale_group(b)
+        if ra is not rb:
+            ia, ib = self.bufs.index(ra), self.bufs.index(rb)
+            if ia < ib:
+                rb.group = ra
+            else:
+                ra.group = rb
+
+    def buf_scale(self, buf):
+        """fp8 plans: the fp32 activation scale of buf's group, s = max amax over the group / 448."""
+        if self.fp8_amax is None:
+            raise RuntimeError('fp8 plan has no calibration (calibrate.calibrate_fp8)')
+        root = self.scale_group(buf)
+        amax = None
+        for b in self.bufs:
+            if self.scale_group(b) is root and b.key in self.fp8_amax:
+                amax = max(amax or 0.0, float(self.fp8_amax[b.key]))
+        if amax is None:
+            raise RuntimeError(f'fp8 calibration has no amax for buffer {buf.key}')
+        return f8_scale(amax)
+
+    def _as_f8(self, view, name):
+        """An e4m3 view of the same channels: the view itself, or the quantize op's twin of its 16-bit buffer (one
+        conversion per buffer, same calibration key)."""
+        if view.buf.dtype == F8:
+            return view
+        b = view.buf
+        q = self._quantized.get(b)
+        if q is None:
+            assert b.dtype in (torch.bfloat16, torch.float16, torch.float32), b.dtype
+            assert b.C % 4 == 0, f'{name}: quantize needs a 4-channel aligned buffer ({b.C} channels)'
+            q = Buf(b.N, b.H, b.W, b.C, b.name + '_f8', F8, key=b.key)
+            self.bufs.append(q)
+            self._union(b, q)
+            self._quantized[b] = q
+            L = dict(src=b, dst=q, inv=None)
+            code = _DCODE[b.dtype]
+
+            def fn(stream, L=L, b=b, q=q, code=code):
+                check(_lib.lib().yv4_quantize_f8(b.ptr(), code, b.N, b.H, b.W, b.C, b.C, 0, q.ptr(), q.C, 0,
+                                                 L['inv'], stream), 'yv4_quantize_f8')
+            self.ops.append(Op('quantize', f'{b.name}_to_f8', fn, nbytes=(_esize(b.dtype) + 1.0) * b.numel,
+                               info=dict(launch=L)))
+        return View(q, view.coff, view.C)
 
     def _dev(self, t):
         t = t.to(self.device).contiguous()
@@ -158,6 +262,7 @@ class Plan:
         al = 8 if h16 else 4
         cp = (C_ + al - 1) // al * al if pad4 else C_
         v = self.new_buf(N, H, W, cp, name, dtype=dtype)
+        v.buf.stem16 = self.f8           # fp8 plans: a conv reading the image stays 16-bit
         slot = {'view': v, 'C': C_, 'src': None}
         self.inputs.append(slot)
         if h16:
@@ -180,6 +285,9 @@ class Plan:
         stage 2 of the epilogue were folded from (used by calibrate.py only).
         out_f32: in a 16-bit plan, store this conv's output in fp32 (pred maps feeding decode)."""
         Cout, Cin, KH, KW = weight.shape
+        if self.f8 and not (x.buf.dtype == torch.float32 or getattr(x.buf, 'stem16', False)):
+            return self._conv_f8(x, weight, s1, t1, act1, stride, pad, residual, s2, t2, act2, out, name, tile, bn1, bn2,
+                                 out_f32)
         stem32 = self.h16 and x.buf.dtype == torch.float32      # fp32 image -> fp32 stem kernel -> 16-bit output
         if stem32:
             assert (Cin, KH, KW, stride) == (3, 3, 3, 1) and pad in (None, 1) and Cout <= 64 and residual is None \
@@ -199,8 +307,11 @@ class Plan:
         Ho = (x.H + 2 * pad - KH) // stride + 1
         Wo = (x.W + 2 * pad - KW) // stride + 1
         if out is None:
-            out = self.new_buf(x.N, Ho, Wo, Cout, name, dtype=torch.float32 if out_f32 else None)
+            out = self.new_buf(x.N, Ho, Wo, Cout, name, dtype=torch.float32 if out_f32 else self.dtype)
+            if self.f8 and stem32:
+                out.buf.stem16 = True    # the conv after the 3x3 stem (the stride-2 conv of the stem pair) stays 16-bit
         assert (out.N, out.H, out.W, out.C) == (x.N, Ho, Wo, Cout), f'{name}: output view mismatch {out} vs {(x.N, Ho, Wo, Cout)}'
+        assert out.buf.dtype != F8, f'{name}: a 16-bit stem conv of an fp8 plan writes a 16-bit buffer'
         out_code = _DCODE[out.buf.dtype]
         if self.h16 and out_code != 0:
             assert out.coff % 8 == 0 and out.cstride % 8 == 0, f'{name}: 16-bit output view must be 8-channel aligned ({out})'
@@ -298,11 +409,86 @@ class Plan:
                                 N=x.N, desc=d, launch=L, out=out, bn1=bn1, bn2=bn2, stem32=stem32)))
         return out
 
+    def _conv_f8(self, x, weight, s1, t1, act1, stride, pad, residual, s2, t2, act2, out, name, tile, bn1, bn2, out_f32):
+        """fp8 conv launch (yv4_conv_bn_act_fwd_f8).  The activation scales are resolved at finalize() (a later
+        resample may still join a buffer's scale group); the launch record keeps the unfolded s1, the e4m3 weight
+        codes and their per-channel scales ``sw``, and receives the folded ``s1f``, ``r_scale`` and ``y_inv`` there."""
+        Cout, Cin, KH, KW = weight.shape
+        x = self._as_f8(x, name)
+        if residual is not None:
+            residual = self._as_f8(residual, name)
+        assert Cin % 16 == 0 and x.C == Cin, f'{name}: fp8 convs need Cin % 16 == 0 and a dense input view ({x}, Cin {Cin})'
+        assert x.coff % 16 == 0 and x.cstride % 16 == 0, f'{name}: fp8 input views must be 16-channel aligned ({x})'
+        wp, _ = pack_conv_weight(weight, align=16)
+        wq, sw = quantize_weight_f8(wp)
+        if pad is None:
+            pad = KH // 2
+        Ho = (x.H + 2 * pad - KH) // stride + 1
+        Wo = (x.W + 2 * pad - KW) // stride + 1
+        if out is None:
+            out = self.new_buf(x.N, Ho, Wo, Cout, name, dtype=torch.float32 if out_f32 else F8)
+        assert (out.N, out.H, out.W, out.C) == (x.N, Ho, Wo, Cout), f'{name}: output view mismatch {out} vs {(x.N, Ho, Wo, Cout)}'
+        assert out.buf.dtype in (F8, torch.float32), f'{name}: an fp8 conv stores e4m3 or fp32, not {out.buf.dtype}'
+        out_code = _lib.F8E4M3 if out.buf.dtype == F8 else _lib.F32
+        if residual is not None:
+            assert (residual.N, residual.H, residual.W, residual.C) == (x.N, Ho, Wo, Cout), f'{name}: residual mismatch'
+        d = ConvDesc()
+        d.N, d.H, d.W, d.Cin = x.N, x.H, x.W, Cin
+        d.Ho, d.Wo, d.Cout = Ho, Wo, Cout
+        d.KH, d.KW, d.stride, d.pad = KH, KW, stride, pad
+        d.x_cstride, d.x_coff = x.cstride, x.coff
+        d.y_cstride, d.y_coff = out.cstride, out.coff
+        d.r_cstride, d.r_coff = (residual.cstride, residual.coff) if residual is not None else (0, 0)
+        d.act1, d.slope1 = act1
+        d.act2, d.slope2 = act2 if s2 is not None else (0, 0.0)
+        d.tile = tile
+        L = dict(d=d, x=x.buf, y=out.buf, res=residual.buf if residual is not None else None,
+                 w=self._dev(wq), sw=sw, s1=s1.detach().float().cpu().clone(), s1f=None, t1=self._dev(t1.float()),
+                 s2=self._dev(s2.float()) if s2 is not None else None,
+                 t2=self._dev(t2.float()) if s2 is not None else None, r_scale=1.0, y_inv=1.0)
+        self.params.append(d)
+
+        def fn(stream, L=L, out_code=out_code):
+            check(_lib.lib().yv4_conv_bn_act_fwd_f8(
+                C.byref(L['d']), out_code, L['x'].ptr(), L['w'].data_ptr(), L['s1f'].data_ptr(), L['t1'].data_ptr(),
+                L['s2'].data_ptr() if L['s2'] is not None else None, L['t2'].data_ptr() if L['t2'] is not None else None,
+                L['res'].ptr() if L['res'] is not None else None, L['r_scale'], L['y_inv'], L['y'].ptr(), stream),
+                'yv4_conv_bn_act_fwd_f8')
+        M = x.N * Ho * Wo
+        flops = 2.0 * M * Cout * KH * KW * Cin
+        nbytes = 1.0 * (x.N * x.H * x.W * Cin + Cout * KH * KW * Cin) + (4.0 if out_code == _lib.F32 else 1.0) * M * Cout
+        if residual is not None:
+            nbytes += 1.0 * M * Cout
+        self.ops.append(Op('conv', name, fn, flops, nbytes,
+                           dict(Cin=Cin, Cout=Cout, k=KH, stride=stride, H=x.H, W=x.W, Ho=Ho, Wo=Wo, N=x.N, desc=d,
+                                launch=L, out=out, x=x, residual=residual, bn1=bn1, bn2=bn2, stem32=False, f8=True)))
+        return out
+
+    def _resolve_f8(self):
+        """Fold the calibrated activation scales into every fp8 launch record (s1', inv_s of the output, the
+        residual's scale) and into the quantize ops."""
+        for op in self.ops:
+            L = op.info.get('launch') if op.info else None
+            if op.kind == 'quantize':
+                L['inv'] = f8_inv(self.buf_scale(L['dst']))
+            elif op.kind == 'conv' and op.info.get('f8'):
+                sx = self.buf_scale(L['x'])
+                L['sx'] = sx
+                L['s1f'] = self._dev(fold_s1_f8(L['s1'], L['sw'], sx))
+                L['r_scale'] = self.buf_scale(L['res']) if L['res'] is not None else 1.0
+                L['y_inv'] = f8_inv(self.buf_scale(L['y'])) if L['y'].dtype == F8 else 1.0
+
     def spp(self, cat_view, C_, name='spp'):
         """cat_view: view of 4*C_ channels whose first C_ are filled; fills the other 3*C_."""
         assert cat_view.C == 4 * C_
         b = cat_view.buf
 
+        if b.dtype == F8:
+            def fn(stream, b=b, v=cat_view, C_=C_):
+                check(_lib.lib().yv4_spp_pool_fwd_f8(b.ptr(), v.N, v.H, v.W, C_, v.cstride, v.coff, stream),
+                      'yv4_spp_pool_fwd_f8')
+            self.ops.append(Op('spp', name, fn, nbytes=4.0 * cat_view.N * cat_view.H * cat_view.W * C_))
+            return cat_view
         if self.h16:
             def fn(stream, b=b, v=cat_view, C_=C_):
                 check(_lib.lib().yv4_spp_pool_fwd_h16(b.ptr(), v.N, v.H, v.W, C_, v.cstride, v.coff, self.dcode,
@@ -316,9 +502,16 @@ class Plan:
 
     def resample(self, src, dst, name='resample'):
         """Nearest resample src -> dst (same N and C; dst's H/W are the target size)."""
+        if dst.buf.dtype == F8:
+            src = self._as_f8(src, name)
         assert src.N == dst.N and src.C == dst.C and src.buf.dtype == dst.buf.dtype
-        # a 16-bit view with C % 8 == 0 is byte-identical to an fp32 view with C/2 channels
-        k = 2 if src.buf.dtype != torch.float32 else 1
+        # a 16-bit view with C % 8 == 0 is byte-identical to an fp32 view with C/2 channels, an e4m3 view with C % 4 == 0
+        # to one with C/4; an fp8 copy needs one scale on both ends: src joins dst's scale group
+        k = 4 if src.buf.dtype == F8 else 2 if src.buf.dtype != torch.float32 else 1
+        if k == 4:
+            assert all(v % 4 == 0 for v in (src.C, src.cstride, src.coff, dst.cstride, dst.coff)), \
+                f'{name}: fp8 resample needs 4-channel aligned views'
+            self._union(src.buf, dst.buf)
         if k == 2:
             assert all(v % 8 == 0 for v in (src.C, src.cstride, src.coff, dst.cstride, dst.coff)), \
                 f'{name}: 16-bit resample needs 8-channel aligned views'
@@ -334,6 +527,7 @@ class Plan:
     def add_output_nchw(self, view, name='out'):
         """Materialise a view as a fresh NCHW tensor on every run; returns the slot index."""
         slot = {'view': view, 'dst': None}
+        assert view.buf.dtype != F8, f'{name}: fp8 views have no NCHW output op'
 
         if view.buf.dtype != torch.float32:
             def fn(stream, slot=slot, v=view, code=_DCODE[view.buf.dtype]):
@@ -501,6 +695,8 @@ class Plan:
 
     def finalize(self):
         self._fuse_stem_down()
+        if self.f8:
+            self._resolve_f8()
         for b in self.bufs:
             if getattr(b, 'unused', False):
                 continue
@@ -530,11 +726,15 @@ class Plan:
             d = op.info['desc']
             if op.info.get('stem32'):
                 continue
-            auto = (_lib.lib().yv4_conv_h16_pick_tile if self.h16 else _lib.lib().yv4_conv_pick_tile)(C.byref(d))
-            if auto not in cands:          # stem / generic path: nothing to choose from
+            if op.info.get('f8'):
+                auto, lcands = _lib.lib().yv4_conv_f8_pick_tile(C.byref(d)), (1, 2, 3)     # YV4_F8TILE_*
+            else:
+                auto = (_lib.lib().yv4_conv_h16_pick_tile if self.h16 else _lib.lib().yv4_conv_pick_tile)(C.byref(d))
+                lcands = cands
+            if auto not in lcands:          # stem / generic path: nothing to choose from
                 continue
             best, best_t = auto, None
-            for t in cands:
+            for t in lcands:
                 d.tile = t
                 try:
                     op.fn(stream)          # warm-up + applicability check
@@ -559,7 +759,7 @@ class Plan:
         return sum(o.flops for o in self.ops)
 
     def activation_bytes(self):
-        return sum(b.numel * (4 if b.dtype == torch.float32 else 2) for b in self.bufs)
+        return sum(b.numel * _esize(b.dtype) for b in self.bufs)
 
     def _launch_all(self, stream):
         for op in self.ops:

@@ -71,24 +71,17 @@ class SingleStageDetector(HipModule):
         graph=True records the launch list into a hipGraph (one replay per call; the
         reference's batch-1 protocol is otherwise bound by ~124 host launches);
         autotune=True times the candidate conv tiles per layer first; dtype: torch.float32 (default,
-        the parity dtype), torch.float16 or torch.bfloat16 (``wrap_fp16_model`` sets the default)."""
+        the parity dtype), torch.float16 or torch.bfloat16 (``wrap_fp16_model`` sets the default), or
+        torch.float8_e4m3fn (needs ``calibrate.calibrate_fp8`` first)."""
         dtype = dtype or getattr(self, 'compute_dtype', torch.float32)
-        key = (batch, height, width, str(device), bool(rescale), bool(graph), self._param_version(), dtype)
+        fp8 = dtype == torch.float8_e4m3fn
+        if fp8 and getattr(self, 'fp8_amax', None) is None:
+            raise RuntimeError('an fp8 plan needs activation scales: run calibrate.calibrate_fp8(detector, imgs) first')
+        key = (batch, height, width, str(device), bool(rescale), bool(graph), self._param_version(), dtype,
+               getattr(self, 'fp8_version', 0) if fp8 else 0)
         eng = plan_cache_get(self._engines, key)
         if eng is None:
-            plan = Plan(device, dtype)
-            # 16-bit plans keep the image fp32 when the backbone starts with the 3x3 stem (its own
-            # fp32 kernel, 16-bit output); otherwise the image is converted like any other tensor
-            conv0 = next((m for m in self.backbone.modules() if isinstance(m, torch.nn.Conv2d)), None)
-            stem32 = (plan.h16 and isinstance(conv0, torch.nn.Conv2d) and conv0.kernel_size == (3, 3)
-                      and conv0.stride == (1, 1) and conv0.padding == (1, 1) and conv0.in_channels == 3
-                      and conv0.out_channels <= 64 and conv0.out_channels % 8 == 0)
-            x = plan.add_input_nchw(batch, 3, height, width, name='img', dtype=torch.float32 if stem32 else None)
-            plan.hint_single_consumer(x)             # the image feeds the backbone's first conv and nothing else
-            preds = self.emit(plan, x)
-            self.bbox_head.emit_postprocess(plan, preds, rescale=rescale)
-            plan.pred_views = preds
-            plan.finalize()
+            plan = self.build_plan(batch, height, width, device, rescale, dtype)
             if autotune and torch.device(device).type == 'cuda':
                 plan.inputs[0]['src'] = torch.zeros((batch, 3, height, width), dtype=torch.float32, device=device)
                 plan._launch_all(__import__('ctypes').c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -98,6 +91,22 @@ class SingleStageDetector(HipModule):
             eng = plan
             plan_cache_put(self._engines, key, eng, 6)
         return eng
+
+    def build_plan(self, batch, height, width, device, rescale, dtype):
+        """The finalized (not captured) end-to-end plan of ``compile``."""
+        plan = Plan(device, dtype, fp8_amax=getattr(self, 'fp8_amax', None) if dtype == torch.float8_e4m3fn else None)
+        # 16-bit plans keep the image fp32 when the backbone starts with the 3x3 stem (its own
+        # fp32 kernel, 16-bit output); otherwise the image is converted like any other tensor
+        conv0 = next((m for m in self.backbone.modules() if isinstance(m, torch.nn.Conv2d)), None)
+        stem32 = (plan.h16 and isinstance(conv0, torch.nn.Conv2d) and conv0.kernel_size == (3, 3)
+                  and conv0.stride == (1, 1) and conv0.padding == (1, 1) and conv0.in_channels == 3
+                  and conv0.out_channels <= 64 and conv0.out_channels % 8 == 0)
+        x = plan.add_input_nchw(batch, 3, height, width, name='img', dtype=torch.float32 if stem32 else None)
+        plan.hint_single_consumer(x)             # the image feeds the backbone's first conv and nothing else
+        preds = self.emit(plan, x)
+        self.bbox_head.emit_postprocess(plan, preds, rescale=rescale)
+        plan.pred_views = preds
+        return plan.finalize()
 
     # ---- reference API ------------------------------------------------------------------------
     def extract_feat(self, img):

@@ -824,6 +824,57 @@ int yv4_quantize_f8(const void* x, int dtype, int N, int H, int W, int C, int x_
  * slots of the same buffer), codes compared in sign-magnitude order: the max is exact.  C, cstride, coff % 4 == 0. */
 int yv4_spp_pool_fwd_f8(void* buf, int N, int H, int W, int C, int cstride, int coff, void* stream);
 
+/* ---- test-time augmentation of YOLOV3Head (csrc/tta.hip, csrc/preprocess.hip) -------------------------------------
+ * Flip codes of MultiScaleFlipAug's flip_direction (datasets/pipelines/test_time_aug.py; bit 0 mirrors x, bit 1 y). */
+#define YV4_FLIP_NONE 0
+#define YV4_FLIP_HORIZONTAL 1
+#define YV4_FLIP_VERTICAL 2
+#define YV4_FLIP_DIAGONAL 3
+/* Largest number of augmentations one yv4_tta_merge call takes. */
+#define YV4_TTA_MAX_AUGS 16
+
+/* yv4_letterbox_u8 followed by RandomFlip of the RESIZED (new_h x new_w) image (transforms.py RandomFlip with
+ * mmcv.imflip, between Resize and Normalize / Pad in configs/yolo/yolov3_d53_*): a permutation of the unflipped
+ * output's resized region, bit for bit; the pad region is unchanged.  flip: YV4_FLIP_*. */
+int yv4_letterbox_u8_flip(const uint8_t* src, int src_h, int src_w, int src_pitch, float* dst, int Hp, int Wp,
+                          int64_t plane_stride, int new_h, int new_w, const float* mean3, const float* std3,
+                          int to_rgb, int pad_val, int pad_before_normalize, int flip, void* stream);
+
+/* Slot tables of YOLOV3Head.get_bboxes(with_nms=False) (yolo_head.py:254-311): per image, the levels' boxes in the
+ * reference's concatenation order.  A level of n_l = H_l*W_l*A boxes contributes k_l = nms_pre slots when
+ * 0 < nms_pre < n_l (conf.topk(nms_pre), sorted: descending objectness, ties to the lower anchor index), else n_l
+ * slots in anchor order.  slots (N, S) int32, S = sum_l k_l: slots[n*S + s] = anchor index within the image (what
+ * yv4_decode_filter_v3's boxes / conf / cls rows are indexed by).  conf: (N, total_anchors) objectness from
+ * yv4_decode_filter_v3; level_anchors: num_levels HOST values n_l; topk_keys: (N*num_levels) admission keys of
+ * yv4_conf_topk_levels (required when some level is cut, else may be NULL).  Levels with k_l <= 8192 sort in LDS;
+ * larger ones use the library's radix sort in `work` (yv4_topk_slots_work bytes, 0 when none is needed). */
+size_t yv4_topk_slots_work(int num_levels, const int32_t* level_anchors, int nms_pre);
+int yv4_topk_slots(const float* conf, int N, int64_t total_anchors, int num_levels, const int32_t* level_anchors,
+                   int nms_pre, const uint64_t* topk_keys, void* work, int32_t* slots, int64_t S, void* stream);
+
+/* One augmentation of yv4_tta_merge: image n of the batch reads boxes + n*total*4, conf + n*total,
+ * cls + n*total*num_classes (yv4_decode_filter_v3 with scale_factor NULL) and slots + n*S (yv4_topk_slots). */
+typedef struct yv4_tta_aug {
+  const float* boxes;
+  const float* conf;
+  const float* cls;
+  const int32_t* slots;
+  int64_t total;
+  int32_t S;
+  int32_t flip;         /* YV4_FLIP_* */
+} yv4_tta_aug;
+
+/* Merge of BBoxTestMixin.aug_test_bboxes (dense_test_mixins.py:38-100) up to multiclass_nms, for N images at once.
+ * Merged slot m of image n = (augmentation a, slot s) in augmentation order, m = sum_{a'<a} S_a' + s.  Per slot:
+ * bbox_mapping_back (core/bbox/transforms.py:5-55): bbox_flip over that augmentation's img_shape, then / scale_factor
+ * (fp32, in that order) -> boxes_out[n][m]; per class c with cls > score_thr the key
+ * (~order(cls * conf) << 32 | (m*num_classes + c)) is appended to keys[n*key_cap ...] and the mapped box folded into
+ * max_coord[n] -- the buffers yv4_nms_images / yv4_nms_split take with fused_classes = num_classes and
+ * boxes_per_image = S_total.  meta: device (num_augs, N, 6) fp32 rows img_h, img_w, scale_factor[4].
+ * counts / max_coord must be reset by yv4_decode_reset first.  augs: num_augs HOST descriptors. */
+int yv4_tta_merge(const yv4_tta_aug* augs, int num_augs, int N, int num_classes, float score_thr, const float* meta,
+                  float* boxes_out, uint64_t* keys, int64_t key_cap, int32_t* counts, float* max_coord, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,9 @@ F8E4M3 = 3                 # YV4_F8E4M3: the fp8 entry points' element code (the
 F8TILE_128x128, F8TILE_128x64, F8TILE_64x64 = 1, 2, 3
 ACT_NONE, ACT_MISH, ACT_LEAKY, ACT_SWISH = 0, 1, 2, 3
 NMS_IOU_DIV, NMS_IOU_MUL = 0, 1
+FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL, FLIP_DIAGONAL = 0, 1, 2, 3     # YV4_FLIP_*
+FLIP_CODES = {'horizontal': FLIP_HORIZONTAL, 'vertical': FLIP_VERTICAL, 'diagonal': FLIP_DIAGONAL}
+TTA_MAX_AUGS = 16          # YV4_TTA_MAX_AUGS
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4
 TILE_DMA_64x64, TILE_DMA_128x64, TILE_DMA_128x128, TILE_STEM, TILE_WS_1x1 = 5, 6, 7, 8, 9
 HTILE_NAMES = {1: 'h16_128x128', 2: 'h16_128x64', 3: 'h16_64x64', 4: 'h16_pp3x3', 5: 'h16_w3x3', 6: 'h16_ws_1x1', 7: 'h16_s3x3', 8: 'h16_wide'}
@@ -51,6 +54,12 @@ class LevelDesc(C.Structure):
     """``yv4_level_desc``."""
     _fields_ = [('pred', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32),
                 ('stride', C.c_int32), ('base_anchors', (C.c_float * 4) * 8)]
+
+
+class TtaAug(C.Structure):
+    """``yv4_tta_aug``."""
+    _fields_ = [('boxes', C.c_void_p), ('conf', C.c_void_p), ('cls', C.c_void_p), ('slots', C.c_void_p),
+                ('total', C.c_int64), ('S', C.c_int32), ('flip', C.c_int32)]
 
 
 class LossLevel(C.Structure):
@@ -208,6 +217,10 @@ SIGNATURES = {
     'yv4_conv_f8_pick_tile': (C.c_int, [C.POINTER(ConvDesc)]),
     'yv4_quantize_f8': (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp]),
     'yv4_spp_pool_fwd_f8': (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'yv4_letterbox_u8_flip': (C.c_int, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'yv4_topk_slots_work': (_sz, [_i, _vp, _i]),
+    'yv4_topk_slots': (C.c_int, [_vp, _i, _i64, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
+    'yv4_tta_merge': (C.c_int, [C.POINTER(TtaAug), _i, _i, _i, _f, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -216,6 +229,8 @@ ABI8_SYMBOLS = frozenset(('yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'))
 #: the fp8 inference entry points (additive within ABI 8): bound when the library exports them, so that an ABI-8 build
 #: from before them still loads for A/B runs; has_fp8() tells the plan whether they are there
 FP8_SYMBOLS = frozenset(('yv4_conv_bn_act_fwd_f8', 'yv4_conv_f8_pick_tile', 'yv4_quantize_f8', 'yv4_spp_pool_fwd_f8'))
+#: the YOLOv3 test-time augmentation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_tta()
+TTA_SYMBOLS = frozenset(('yv4_letterbox_u8_flip', 'yv4_topk_slots_work', 'yv4_topk_slots', 'yv4_tta_merge'))
 
 _lock = threading.Lock()
 _lib = None
@@ -253,7 +268,7 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             if name in ABI8_SYMBOLS and got < 8:
                 continue
-            if name in FP8_SYMBOLS and not hasattr(handle, name):
+            if (name in FP8_SYMBOLS or name in TTA_SYMBOLS) and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
             fn.restype = res
@@ -279,6 +294,12 @@ def has_fp8():
     """The loaded library exports the fp8 (e4m3) inference entry points."""
     h = lib()
     return all(hasattr(h, n) for n in FP8_SYMBOLS)
+
+
+def has_tta():
+    """The loaded library exports the YOLOv3 test-time augmentation entry points."""
+    h = lib()
+    return all(hasattr(h, n) for n in TTA_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

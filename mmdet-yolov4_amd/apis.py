@@ -28,13 +28,16 @@ def inference_detector(model, imgs, test_pipeline=None):
     pipe = test_pipeline if callable(test_pipeline) else FusedTestPipeline.from_config(test_pipeline, device=device)
     batch, metas = pipe(list(imgs))
     with torch.no_grad():
-        results = model.simple_test(batch, metas, rescale=True)
+        if isinstance(batch, list):      # test-time augmentation: one batch per augmentation (N images each)
+            results = model.aug_test(batch, metas, rescale=True)
+        else:
+            results = model.simple_test(batch, metas, rescale=True)
     return results if is_batch else results[0]
 
 
 def _unwrap(field):
-    """A test-time batch carries one entry per augmentation (``img=[tensor]``, ``img_metas=[[meta, ...]]``); the path
-    has one (``BaseDetector.forward_test`` -> ``simple_test``, mmdet/models/detectors/base.py:128-166)."""
+    """A test-time batch carries one entry per augmentation (``img=[tensor]``, ``img_metas=[[meta, ...]]``); with one
+    augmentation the path is ``BaseDetector.forward_test`` -> ``simple_test`` (mmdet/models/detectors/base.py:128-166)."""
     if isinstance(field, (list, tuple)) and len(field) == 1 and isinstance(field[0], (list, tuple, torch.Tensor)):
         return field[0]
     return field
@@ -49,7 +52,13 @@ def single_gpu_test(model, data_loader):
     results = []
     with torch.no_grad():
         for data in data_loader:
-            img, metas = _unwrap(data['img']), _unwrap(data['img_metas'])
+            img, metas = data['img'], data['img_metas']
+            if isinstance(img, (list, tuple)) and len(img) > 1:
+                # test-time augmentation: BaseDetector.forward_test -> aug_test (detectors/base.py:147-153)
+                results.extend(model.forward_test([t.to(device, non_blocking=True) for t in img], list(metas),
+                                                  rescale=True))
+                continue
+            img, metas = _unwrap(img), _unwrap(metas)
             results.extend(model.simple_test(img.to(device, non_blocking=True), metas, rescale=True))
     return results
 

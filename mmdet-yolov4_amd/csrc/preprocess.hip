@@ -21,6 +21,7 @@ struct PreArgs {
   double inv_sx, inv_sy;                        // source / destination size ratios (OpenCV: scale_x = 1. / inv_scale_x)
   float mean[3], stdinv[3];
   int to_rgb, pad_val, pad_first;               // pad_first: Pad precedes Normalize (the pad value is normalised too)
+  int flip;                                     // YV4_FLIP_*: bit 0 mirrors x, bit 1 mirrors y of the resized image
 };
 
 // OpenCV resize, INTER_LINEAR, 8-bit: sample position and 11-bit coefficients of one axis
@@ -43,9 +44,13 @@ __global__ __launch_bounds__(256) void letterbox_u8_kernel(PreArgs p) {
   int v[3] = {p.pad_val, p.pad_val, p.pad_val};
   const bool inside = x < p.nw && y < p.nh;
   if (inside) {
+    // RandomFlip after Resize (configs/yolo/yolov3_d53_mstrain-608_273e_coco.py test pipeline): the flip permutes the
+    // resized image, so the pixel at (y, x) is the resized pixel at the mirrored position -- a gather index only
+    const int xs = (p.flip & 1) ? p.nw - 1 - x : x;
+    const int ys = (p.flip & 2) ? p.nh - 1 - y : y;
     int x0, x1, ax0, ax1, y0, y1, ay0, ay1;
-    lin_coef(x, p.inv_sx, p.sw, x0, x1, ax0, ax1);
-    lin_coef(y, p.inv_sy, p.sh, y0, y1, ay0, ay1);
+    lin_coef(xs, p.inv_sx, p.sw, x0, x1, ax0, ax1);
+    lin_coef(ys, p.inv_sy, p.sh, y0, y1, ay0, ay1);
     const uint8_t* r0 = p.src + (size_t)y0 * p.s_pitch;
     const uint8_t* r1 = p.src + (size_t)y1 * p.s_pitch;
 #pragma unroll
@@ -71,13 +76,14 @@ __global__ __launch_bounds__(256) void letterbox_u8_kernel(PreArgs p) {
 
 using namespace yv4;
 
-extern "C" int yv4_letterbox_u8(const uint8_t* src, int src_h, int src_w, int src_pitch, float* dst, int Hp, int Wp,
-                                int64_t plane_stride, int new_h, int new_w, const float* mean3, const float* std3,
-                                int to_rgb, int pad_val, int pad_before_normalize, void* stream) {
+static int letterbox_impl(const uint8_t* src, int src_h, int src_w, int src_pitch, float* dst, int Hp, int Wp,
+                          int64_t plane_stride, int new_h, int new_w, const float* mean3, const float* std3,
+                          int to_rgb, int pad_val, int pad_before_normalize, int flip, void* stream) {
   YV4_REQUIRE(src && dst && mean3 && std3, "letterbox: null pointer");
   YV4_REQUIRE(src_h > 0 && src_w > 0 && src_pitch >= 3 * src_w && Hp > 0 && Wp > 0 && plane_stride >= (int64_t)Hp * Wp,
               "letterbox: bad geometry");
   YV4_REQUIRE(new_h > 0 && new_w > 0 && new_h <= Hp && new_w <= Wp, "letterbox: the resized image exceeds the padded one");
+  YV4_REQUIRE(flip >= YV4_FLIP_NONE && flip <= YV4_FLIP_DIAGONAL, "letterbox: bad flip direction %d", flip);
   YV4_REQUIRE(pad_val >= 0 && pad_val <= 255, "letterbox: pad value must be an 8-bit value");
   PreArgs a;
   a.src = src; a.sh = src_h; a.sw = src_w; a.s_pitch = src_pitch;
@@ -90,8 +96,24 @@ extern "C" int yv4_letterbox_u8(const uint8_t* src, int src_h, int src_w, int sr
     a.stdinv[c] = (float)(1.0 / (double)std3[c]);
   }
   a.to_rgb = to_rgb ? 1 : 0; a.pad_val = pad_val; a.pad_first = pad_before_normalize ? 1 : 0;
+  a.flip = flip;
   hipLaunchKernelGGL(letterbox_u8_kernel, dim3((unsigned)((Wp + 63) / 64), (unsigned)((Hp + 3) / 4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
   YV4_CHECK_LAUNCH("letterbox_u8");
   return YV4_OK;
+}
+
+extern "C" int yv4_letterbox_u8(const uint8_t* src, int src_h, int src_w, int src_pitch, float* dst, int Hp, int Wp,
+                                int64_t plane_stride, int new_h, int new_w, const float* mean3, const float* std3,
+                                int to_rgb, int pad_val, int pad_before_normalize, void* stream) {
+  return letterbox_impl(src, src_h, src_w, src_pitch, dst, Hp, Wp, plane_stride, new_h, new_w, mean3, std3, to_rgb,
+                        pad_val, pad_before_normalize, YV4_FLIP_NONE, stream);
+}
+
+extern "C" int yv4_letterbox_u8_flip(const uint8_t* src, int src_h, int src_w, int src_pitch, float* dst, int Hp,
+                                     int Wp, int64_t plane_stride, int new_h, int new_w, const float* mean3,
+                                     const float* std3, int to_rgb, int pad_val, int pad_before_normalize, int flip,
+                                     void* stream) {
+  return letterbox_impl(src, src_h, src_w, src_pitch, dst, Hp, Wp, plane_stride, new_h, new_w, mean3, std3, to_rgb,
+                        pad_val, pad_before_normalize, flip, stream);
 }

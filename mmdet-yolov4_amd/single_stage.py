@@ -95,18 +95,77 @@ class SingleStageDetector(HipModule):
     def build_plan(self, batch, height, width, device, rescale, dtype):
         """The finalized (not captured) end-to-end plan of ``compile``."""
         plan = Plan(device, dtype, fp8_amax=getattr(self, 'fp8_amax', None) if dtype == torch.float8_e4m3fn else None)
+        x = self._add_image(plan, batch, height, width, 'img')
+        preds = self.emit(plan, x)
+        self.bbox_head.emit_postprocess(plan, preds, rescale=rescale)
+        plan.pred_views = preds
+        return plan.finalize()
+
+    def _add_image(self, plan, batch, height, width, name):
         # 16-bit plans keep the image fp32 when the backbone starts with the 3x3 stem (its own
         # fp32 kernel, 16-bit output); otherwise the image is converted like any other tensor
         conv0 = next((m for m in self.backbone.modules() if isinstance(m, torch.nn.Conv2d)), None)
         stem32 = (plan.h16 and isinstance(conv0, torch.nn.Conv2d) and conv0.kernel_size == (3, 3)
                   and conv0.stride == (1, 1) and conv0.padding == (1, 1) and conv0.in_channels == 3
                   and conv0.out_channels <= 64 and conv0.out_channels % 8 == 0)
-        x = plan.add_input_nchw(batch, 3, height, width, name='img', dtype=torch.float32 if stem32 else None)
+        x = plan.add_input_nchw(batch, 3, height, width, name=name, dtype=torch.float32 if stem32 else None)
         plan.hint_single_consumer(x)             # the image feeds the backbone's first conv and nothing else
-        preds = self.emit(plan, x)
-        self.bbox_head.emit_postprocess(plan, preds, rescale=rescale)
-        plan.pred_views = preds
-        return plan.finalize()
+        return x
+
+    # ---- test-time augmentation ----------------------------------------------------------------
+    def compile_tta(self, batch, geometries, flips, device='cuda', graph=False, dtype=None):
+        """Build (and cache) the TTA plan of ``aug_test``: ``geometries[a]`` the padded (H, W) of augmentation a's
+        batch, ``flips[a]`` its YV4_FLIP_* code.  Augmentations of one geometry (an image and its flips) run the
+        network as ONE batch of ``batch * len(group)`` rows; each distinct geometry gets its own network pass.  Then
+        decode, slot tables, one merge and the NMS (``tta.emit_tta_post``), all on one stream: ``graph=True`` captures
+        the whole plan into one hipGraph.  dtype: torch.float32 (default), torch.float16 or torch.bfloat16."""
+        dtype = dtype or getattr(self, 'compute_dtype', torch.float32)
+        if dtype == torch.float8_e4m3fn:
+            raise NotImplementedError('fp8 TTA plans are not built')
+        geometries = tuple(tuple(int(v) for v in g) for g in geometries)
+        flips = tuple(int(f) for f in flips)
+        if len(geometries) != len(flips) or len(flips) < 2:
+            raise ValueError('a TTA plan takes one geometry and one flip code per augmentation, two or more of them')
+        key = ('tta', batch, geometries, flips, str(device), bool(graph), self._param_version(), dtype)
+        eng = plan_cache_get(self._engines, key)
+        if eng is None:
+            from .tta import emit_tta_post
+            plan = Plan(device, dtype)
+            groups = [[a for a, g in enumerate(geometries) if g == geo] for geo in dict.fromkeys(geometries)]
+            gviews = []
+            for gi, augs in enumerate(groups):
+                H, W = geometries[augs[0]]
+                x = self._add_image(plan, batch * len(augs), H, W, f'img{gi}')
+                gviews.append((list(self.emit(plan, x)), augs))
+            emit_tta_post(plan, self.bbox_head, gviews, flips, batch)
+            plan.tta_groups = groups
+            plan.pred_views = [v for v, _ in gviews]
+            plan.finalize()
+            if graph:
+                plan.capture()
+            eng = plan
+            plan_cache_put(self._engines, key, eng, 6)
+        return eng
+
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """single_stage.py:114-137 with the merge of dense_test_mixins.py:38-100: ``imgs[a]`` the (N, 3, H, W) batch
+        of augmentation a, ``img_metas[a]`` its N metas.  Returns one per-class list per image.  The reference runs
+        a batch of one image; N > 1 is an extension (image n gets the result of its batch-1 run, bit for bit)."""
+        self._check_eval()
+        if not hasattr(self.bbox_head, 'aug_test_preds'):
+            raise NotImplementedError('aug_test (TTA) is not built')
+        from .tta import collect_tta, flip_code, set_tta_metas
+        if len(imgs) != len(img_metas):
+            raise ValueError(f'num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})')
+        N = imgs[0].shape[0]
+        if any(t.shape[0] != N for t in imgs) or any(len(m) != N for m in img_metas):
+            raise ValueError('every augmentation must hold the same images')
+        geos = tuple((t.shape[2], t.shape[3]) for t in imgs)
+        flips = tuple(flip_code(m[0]) for m in img_metas)
+        plan = self.compile_tta(N, geos, flips, device=imgs[0].device, graph=True)
+        set_tta_metas(plan.post, img_metas)
+        plan.run(*[torch.cat([imgs[a] for a in augs]) if len(augs) > 1 else imgs[augs[0]] for augs in plan.tta_groups])
+        return collect_tta(plan.post, img_metas, rescale, self.bbox_head.num_classes)
 
     # ---- reference API ------------------------------------------------------------------------
     def extract_feat(self, img):
@@ -140,7 +199,11 @@ class SingleStageDetector(HipModule):
             raise ValueError(f'num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})')
         if len(imgs) == 1:
             return self.simple_test(imgs[0], img_metas[0], **kwargs)
-        raise NotImplementedError('aug_test (TTA) is not built')
+        # detectors/base.py:147-150
+        assert imgs[0].size(0) == 1, 'aug test does not support ' \
+                                     'inference with batch size ' \
+                                     f'{imgs[0].size(0)}'
+        return self.aug_test(imgs, img_metas, **kwargs)
 
     def forward(self, img, img_metas, return_loss=True, **kwargs):
         if return_loss:

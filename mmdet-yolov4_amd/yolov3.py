@@ -483,7 +483,7 @@ class YOLOV3Head(HipModule):
     def get_bboxes(self, pred_maps, img_metas, cfg=None, rescale=False, with_nms=True):
         assert len(pred_maps) == self.num_levels
         if not with_nms:
-            raise NotImplementedError('YOLOV3Head.get_bboxes(with_nms=False) is not built')
+            return self._get_bboxes_nonms(pred_maps, img_metas, cfg, rescale)
         for t in pred_maps:
             ops._need_cuda(t, 'pred_map')
         cfg = self.test_cfg if cfg is None else cfg
@@ -605,8 +605,87 @@ class YOLOV3Head(HipModule):
             return losses
         return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
 
+    def _get_bboxes_nonms(self, pred_maps, img_metas, cfg, rescale):
+        """yolo_head.py:208-391 with with_nms=False: per image ``(bboxes (S, 4), scores (S, C + 1), conf (S))``, the
+        levels concatenated, a level with more than ``nms_pre`` boxes in descending objectness (``conf.topk``), no
+        ``conf_thr``, the last score column a zero background column; ``rescale`` divides by ``scale_factor``.
+        The order is the slot table of ``yv4_topk_slots``."""
+        for t in pred_maps:
+            ops._need_cuda(t, 'pred_map')
+        cfg = self.test_cfg if cfg is None else cfg
+        nms_pre = int(cfg.get('nms_pre', -1))
+        key = ('nonms', tuple(tuple(p.shape) for p in pred_maps), nms_pre)
+        plan = self._post_cache.get(key)
+        if plan is None:
+            from .tta import emit_decode_slots
+            self._post_cache.clear()
+            plan = Plan(pred_maps[0].device)
+            views = [plan.add_input_nchw(*p.shape, name=f'pred{i}', pad4=False) for i, p in enumerate(pred_maps)]
+            res = {}
+            alloc = emit_decode_slots(plan, views, self.featmap_strides, self.anchor_generator.base_anchors,
+                                      self.num_classes, nms_pre, res, 'g0')
+            plan.post = dict(_alloc=alloc, res=res)
+            plan.finalize()
+            self._post_cache[key] = plan
+        plan.run(*[p.float() for p in pred_maps])
+        d = plan.post['res']['g0']
+        out = []
+        for n in range(d['B']):
+            sel = d['slots'][n].long()
+            b = d['boxes'][n].index_select(0, sel)
+            if rescale:
+                b = b / b.new_tensor([float(v) for v in img_metas[n]['scale_factor']])
+            sc = d['cls'][n].index_select(0, sel)
+            sc = torch.cat([sc, sc.new_zeros(sc.shape[0], 1)], dim=1)
+            out.append((b, sc, d['conf'][n].index_select(0, sel)))
+        return out
+
     def aug_test(self, feats, img_metas, rescale=False):
-        raise NotImplementedError('YOLOV3Head.aug_test (TTA) is not built')
+        """yolo_head.py:588-604 -> dense_test_mixins.py:38-100: ``feats`` and ``img_metas`` hold one entry per
+        augmentation; the reference's batch of ONE image -> its per-class list.  The merge runs on the GPU
+        (``aug_test_preds``)."""
+        if len(feats) != len(img_metas):
+            raise ValueError(f'num of augmentations ({len(feats)}) != num of image meta ({len(img_metas)})')
+        if any(len(m) != 1 for m in img_metas):
+            raise ValueError('YOLOV3Head.aug_test takes a batch of one image (the reference takes get_bboxes(...)[0])')
+        preds = [self(f)[0] for f in feats]
+        return self.aug_test_preds(preds, img_metas, rescale=rescale)[0]
+
+    def aug_test_preds(self, pred_maps, img_metas, rescale=False, cfg=None):
+        """The merge of ``BBoxTestMixin.aug_test_bboxes`` on the GPU for N images: ``pred_maps[a]`` the head's
+        outputs on augmentation a (a tuple of (N, A*(5+C), H, W) maps), ``img_metas[a][n]`` its metas (``img_shape``,
+        ``scale_factor``, ``flip``, ``flip_direction``).  Returns one per-class list per image; image n is what the
+        reference computes for that image alone (an extension of its batch-1 path)."""
+        from .tta import collect_tta, emit_tta_post, flip_code, set_tta_metas
+        if len(pred_maps) != len(img_metas):
+            raise ValueError(f'num of augmentations ({len(pred_maps)}) != num of image meta ({len(img_metas)})')
+        cfg = self.test_cfg if cfg is None else cfg
+        N = pred_maps[0][0].shape[0]
+        for p in pred_maps:
+            assert len(p) == self.num_levels and all(t.shape[0] == N for t in p)
+            for t in p:
+                ops._need_cuda(t, 'pred_map')
+        flips = tuple(flip_code(m[0]) for m in img_metas)
+        shapes = [tuple(tuple(t.shape) for t in p) for p in pred_maps]
+        order = list(dict.fromkeys(shapes))
+        groups = [[a for a, s in enumerate(shapes) if s == g] for g in order]
+        key = ('tta', tuple(shapes), flips, repr(dict(cfg)))
+        plan = self._post_cache.get(key)
+        if plan is None:
+            self._post_cache.clear()
+            plan = Plan(pred_maps[0][0].device)
+            gviews = []
+            for gi, augs in enumerate(groups):
+                views = [plan.add_input_nchw(N * len(augs), *pred_maps[augs[0]][l].shape[1:], name=f'g{gi}pred{l}',
+                                             pad4=False) for l in range(self.num_levels)]
+                gviews.append((views, augs))
+            emit_tta_post(plan, self, gviews, flips, N, cfg)
+            plan.finalize()
+            self._post_cache[key] = plan
+        set_tta_metas(plan.post, img_metas)
+        inputs = [torch.cat([pred_maps[a][l].float() for a in augs]) for augs in groups for l in range(self.num_levels)]
+        plan.run(*inputs)
+        return collect_tta(plan.post, img_metas, rescale, self.num_classes)
 
 
 def _images_to_levels(target, num_levels):

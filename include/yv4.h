@@ -472,7 +472,8 @@ int yv4_bn_act_bwd_accum(const void* x, int dtype, int x_cstride, int x_coff, co
  * kernels above with the cross-rank exchange between their two halves.  Forward: yv4_bn_partial_sums
  * leaves [sum x (C) | sum x^2 (C)] of the local rows in `work` (double); the caller all-reduces `work`
  * (SUM) and the row count, then yv4_bn_finalize (replicas = 1; > 1: `work` is that many consecutive
- * [2*C] blocks to be added up first, see yv4_conv_fwd_stats) turns the totals into mean / invstd and updates the
+ * [2*C] blocks to be added up first, any count, see yv4_conv_fwd_stats; with clear_work every one of them is zeroed;
+ * in deterministic mode replicas = YV4_STATS_REPLICAS means the conv epilogue's fixed-point words) turns the totals into mean / invstd and updates the
  * running statistics (unbiased variance over M_total).  Backward: yv4_bn_act_bwd_sums leaves
  * [sum dz (C) | sum dz*xhat (C)] in `work` and writes the LOCAL dgamma / dbeta (what
  * torch.nn.SyncBatchNorm returns: DDP averages them afterwards); the caller all-reduces `work`;

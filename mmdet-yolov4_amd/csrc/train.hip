@@ -2051,8 +2051,8 @@ __global__ void bn_finalize_kernel(double* __restrict__ sums, int64_t M_host, in
   const int c = blockIdx.x * 32 + (threadIdx.x >> 3);
   const int rl = threadIdx.x & 7;
   double s1 = 0.0, s2 = 0.0;
-  // Every load of a lane is issued before the first is used (the replica count is at most YV4_STATS_REPLICAS = 64: eight
-  // per lane): as a loop over a run-time count the loads went out one iteration at a time behind the zeroing stores of the
+  // Every load of a lane is issued before the first is used (the first YV4_STATS_REPLICAS = 64 replicas: eight per lane;
+  // a larger count adds a loop over the rest): as a loop over a run-time count the loads went out one iteration at a time behind the zeroing stores of the
   // iteration before -- a chain of eight memory round trips, 7.5 us per call and 0.85 ms of the bf16 train step.
   if (det) {
     // replica PAIRS of fixed-point words (stat_rep / bn_stats_kernel): integer sums over the pairs, any order
@@ -2112,6 +2112,16 @@ __global__ void bn_finalize_kernel(double* __restrict__ sums, int64_t M_host, in
             sums[(size_t)r * 2 * C + c] = 0.0;
             sums[(size_t)r * 2 * C + C + c] = 0.0;
           }
+        }
+      }
+      // replicas beyond the unrolled 64 (a caller's own block count, yv4_bn_finalize): the same lane stride, summed and
+      // cleared one at a time.  The conv epilogue's 64 and SyncBN's 1 never enter this loop.
+      for (int r = 64 + rl; r < replicas; r += 8) {
+        s1 += sums[(size_t)r * 2 * C + c];
+        s2 += sums[(size_t)r * 2 * C + C + c];
+        if (clear_work) {
+          sums[(size_t)r * 2 * C + c] = 0.0;
+          sums[(size_t)r * 2 * C + C + c] = 0.0;
         }
       }
     }

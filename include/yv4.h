@@ -303,6 +303,58 @@ int yv4_nms_split(const uint64_t* keys, int64_t n, float max_coord,
 int yv4_nms_set_iou_form(int form);
 int yv4_nms_get_iou_form(void);
 
+/* ---- soft-NMS (csrc/soft_nms.hip; additive within ABI 8) ---------------------------------------------------------------
+ * mmcv-full 1.3.x soft_nms(boxes, scores, iou_threshold, sigma, min_score, method, offset=0) (mmcv's softnms_cpu; the
+ * reference reaches it through batched_nms(nms_cfg type='soft_nms'), core/post_processing/bbox_nms.py:84).  mmcv is third
+ * party and absent; this is the definition the library implements.  One array of candidates in input (flat-index) order:
+ *
+ *   i = 0; nb = n
+ *   while i < nb:
+ *     m = FIRST position in [i, nb) with the largest current score            (strict '<' scan)
+ *     swap entries i and m; emit entry i (box, current score, original index)
+ *     pos = i + 1
+ *     while pos < nb:
+ *       ovr = inter / (area_i + area_pos - inter)                                (fp32, IEEE division, no contraction)
+ *       NAIVE:    weight = 0        if ovr >= iou_thr else 1
+ *       LINEAR:   weight = 1 - ovr  if ovr >= iou_thr else 1
+ *       GAUSSIAN: weight = expf(-(ovr*ovr) / sigma)
+ *       score[pos] *= weight
+ *       if score[pos] < min_score: entry pos = entry nb-1; nb -= 1; continue     (re-examine pos)
+ *       pos += 1
+ *     i += 1
+ *
+ * The comparison is `>=` (mmcv's softnms_cpu); the division form only (yv4_nms_set_iou_form does not apply: mmcv 1.3.x
+ * has no GPU soft-NMS).  GAUSSIAN's exp may differ from a host expf in the last bit.  The output is the selection order.
+ * Equivalent form of the end swaps of one step: the k-th discarded position from the left below the new end receives the
+ * k-th surviving entry from the right at or above it. */
+#define YV4_SOFT_NMS_NAIVE 0
+#define YV4_SOFT_NMS_LINEAR 1
+#define YV4_SOFT_NMS_GAUSSIAN 2
+/* yv4_nms_images' buffers and semantics (class offset box + label*(max_coord[n] + 1), fused classes or labels, images
+ * with counts[n] >= split_thr flagged out_count[n] = -1), with soft-NMS over the image's candidates in FLAT-INDEX order
+ * (the keys are sorted in place by their low word).  out_dets carries the decayed scores, in selection order; the loop
+ * stops after max_out selections.  Images with more than 10240 candidates are flagged like split ones (the host then
+ * runs yv4_soft_nms_split, per_label = 0 below split_thr).
+ * Returns YV4_E_INVALID (no device work) for an unknown method, sigma <= 0 with GAUSSIAN, or bad sizes. */
+int yv4_soft_nms_images(uint64_t* keys, int64_t key_cap, const int32_t* counts, const float* max_coord,
+                        const float* boxes, int64_t boxes_per_image, const int32_t* labels, int64_t label_stride,
+                        int fused_classes, int N, int method, float iou_thr, float sigma, float min_score, int max_out,
+                        int split_thr, float* out_dets, int32_t* out_labels, int64_t* out_index, int32_t* out_count,
+                        void* stream);
+/* ONE image, n (host value) candidate keys in any order, work of yv4_soft_nms_split_work(n) bytes:
+ *   per_label = 1: mmcv's n >= split_thr branch -- soft-NMS per label over that label's candidates in flat-index order,
+ *                  survivors re-sorted by (DECAYED score desc, flat index asc), the first max_out returned.  A label stops
+ *                  after max_out selections unless its next selection ties the score of its max_out-th one.
+ *   per_label = 0: one soft-NMS over all n candidates (the single call, for n above the images kernel's limit), selection
+ *                  order, the first max_out.
+ * max_coord: the class-offset unit minus one (-1: no offset).  One problem (a label, or all n with per_label = 0) holds
+ * at most 524288 candidates; per_label = 0 checks it up front, a larger label makes the call report out_count = -2. */
+size_t yv4_soft_nms_split_work(int64_t n);
+int yv4_soft_nms_split(const uint64_t* keys, int64_t n, float max_coord, const float* boxes, const int32_t* labels,
+                       int fused_classes, int per_label, int method, float iou_thr, float sigma, float min_score,
+                       int max_out, void* work, float* out_dets, int32_t* out_labels, int64_t* out_index,
+                       int32_t* out_count, void* stream);
+
 /* ---- deterministic mode (ABI 6) ----------------------------------------------------------------
  * The reference's training step is bit-reproducible run to run wherever torch's is (torch.nn.BatchNorm2d,
  * mmdet/models/backbones/darknetcsp.py:15-35, sums its statistics in a fixed order); this library's default sums

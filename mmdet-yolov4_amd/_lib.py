@@ -23,6 +23,8 @@ F8E4M3 = 3                 # YV4_F8E4M3: the fp8 entry points' element code (the
 F8TILE_128x128, F8TILE_128x64, F8TILE_64x64 = 1, 2, 3
 ACT_NONE, ACT_MISH, ACT_LEAKY, ACT_SWISH = 0, 1, 2, 3
 NMS_IOU_DIV, NMS_IOU_MUL = 0, 1
+SOFT_NMS_NAIVE, SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 0, 1, 2                # YV4_SOFT_NMS_*
+SOFT_NMS_METHODS = {'naive': SOFT_NMS_NAIVE, 'linear': SOFT_NMS_LINEAR, 'gaussian': SOFT_NMS_GAUSSIAN}
 FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL, FLIP_DIAGONAL = 0, 1, 2, 3     # YV4_FLIP_*
 FLIP_CODES = {'horizontal': FLIP_HORIZONTAL, 'vertical': FLIP_VERTICAL, 'diagonal': FLIP_DIAGONAL}
 TTA_MAX_AUGS = 16          # YV4_TTA_MAX_AUGS
@@ -221,6 +223,10 @@ SIGNATURES = {
     'yv4_topk_slots_work': (_sz, [_i, _vp, _i]),
     'yv4_topk_slots': (C.c_int, [_vp, _i, _i64, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     'yv4_tta_merge': (C.c_int, [C.POINTER(TtaAug), _i, _i, _i, _f, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'yv4_soft_nms_images': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _f, _f, _f, _i, _i, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    'yv4_soft_nms_split_work': (_sz, [_i64]),
+    'yv4_soft_nms_split': (C.c_int, [_vp, _i64, _f, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -231,6 +237,8 @@ ABI8_SYMBOLS = frozenset(('yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'))
 FP8_SYMBOLS = frozenset(('yv4_conv_bn_act_fwd_f8', 'yv4_conv_f8_pick_tile', 'yv4_quantize_f8', 'yv4_spp_pool_fwd_f8'))
 #: the YOLOv3 test-time augmentation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_tta()
 TTA_SYMBOLS = frozenset(('yv4_letterbox_u8_flip', 'yv4_topk_slots_work', 'yv4_topk_slots', 'yv4_tta_merge'))
+#: the soft-NMS entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_soft_nms()
+SOFT_NMS_SYMBOLS = frozenset(('yv4_soft_nms_images', 'yv4_soft_nms_split_work', 'yv4_soft_nms_split'))
 
 _lock = threading.Lock()
 _lib = None
@@ -268,7 +276,7 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             if name in ABI8_SYMBOLS and got < 8:
                 continue
-            if (name in FP8_SYMBOLS or name in TTA_SYMBOLS) and not hasattr(handle, name):
+            if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS) and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
             fn.restype = res
@@ -300,6 +308,12 @@ def has_tta():
     """The loaded library exports the YOLOv3 test-time augmentation entry points."""
     h = lib()
     return all(hasattr(h, n) for n in TTA_SYMBOLS)
+
+
+def has_soft_nms():
+    """The loaded library exports the soft-NMS entry points."""
+    h = lib()
+    return all(hasattr(h, n) for n in SOFT_NMS_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

@@ -180,6 +180,144 @@ def nms(boxes, scores, iou_threshold, offset=0, score_threshold=0, max_num=-1):
     return dets, keep
 
 
+SOFT_NMS_CAP = 10240   # candidates the soft-NMS images kernel holds in registers (csrc/soft_nms.hip kSoftRegCap)
+SOFT_NMS_PROBLEM_CAP = 1 << 19   # candidates of one problem of yv4_soft_nms_split (kSoftGlobalCap)
+_SOFT_NMS_ARGS = ('iou_threshold', 'sigma', 'min_score', 'method', 'offset')
+
+
+def _soft_method(method):
+    if method not in _lib.SOFT_NMS_METHODS:
+        raise ValueError(f'soft_nms: method {method!r} is not one of {sorted(_lib.SOFT_NMS_METHODS)}')
+    return _lib.SOFT_NMS_METHODS[method]
+
+
+def nms_spec(nms_cfg):
+    """``test_cfg.nms`` -> what a plan's post-processing launches: ``dict(type='nms', iou_thr, split_thr)`` or
+    ``dict(type='soft_nms', iou_thr, sigma, min_score, method (YV4_SOFT_NMS_* code), split_thr)`` (mmcv soft_nms'
+    defaults 0.3 / 0.5 / 1e-3 / 'linear').  Other types raise NotImplementedError; a soft-NMS key the op does not take
+    raises TypeError.  ``max_num`` with soft-NMS (mmcv applies it in the split branch only, and the single call refuses
+    it) is not built into plans."""
+    cfg = dict(nms_cfg)
+    nms_type = cfg.pop('type', 'nms')
+    split_thr = cfg.pop('split_thr', SPLIT_THR_DEFAULT)
+    if nms_type == 'nms':
+        return dict(type='nms', iou_thr=cfg.get('iou_threshold', cfg.get('iou_thr')), split_thr=split_thr)
+    if nms_type != 'soft_nms':
+        raise NotImplementedError(f'nms type {nms_type!r} is not built ("nms", "soft_nms")')
+    cfg.pop('class_agnostic', None)              # the head's own class_agnostic decides, as for "nms"
+    if 'max_num' in cfg:
+        raise NotImplementedError('soft_nms with max_num is not built into plans')
+    bad = sorted(set(cfg) - set(_SOFT_NMS_ARGS))
+    if bad:
+        raise TypeError(f'soft_nms: unexpected nms_cfg keys {bad}')
+    if cfg.get('offset', 0) != 0:
+        raise NotImplementedError('soft_nms: only offset=0 is built')
+    method = _soft_method(cfg.get('method', 'linear'))
+    sigma = float(cfg.get('sigma', 0.5))
+    if method == _lib.SOFT_NMS_GAUSSIAN and not sigma > 0:
+        raise ValueError('soft_nms: sigma must be > 0 for the gaussian method')
+    return dict(type='soft_nms', iou_thr=float(cfg.get('iou_threshold', 0.3)), sigma=sigma,
+                min_score=float(cfg.get('min_score', 1e-3)), method=method, split_thr=split_thr)
+
+
+def soft_nms_split(keys, n, max_coord, boxes, labels, fused_classes, per_label, spec, max_out, dets, olab, oidx, ocnt):
+    """One image through ``yv4_soft_nms_split`` (host n; work allocated here, as the hard split path does)."""
+    L = _lib.lib()
+    nbytes = int(L.yv4_soft_nms_split_work(n))
+    if nbytes == 0 or (not per_label and n > SOFT_NMS_PROBLEM_CAP):
+        raise NotImplementedError(f'soft-NMS over {n} candidates in one problem is not built (at most '
+                                  f'{SOFT_NMS_PROBLEM_CAP})')
+    work = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device)
+    check(L.yv4_soft_nms_split(_ptr(keys), n, float(max_coord), _ptr(boxes), _ptr(labels), fused_classes, int(per_label),
+                               spec['method'], spec['iou_thr'], spec['sigma'], spec['min_score'], max_out,
+                               _ptr(work), _ptr(dets), _ptr(olab), _ptr(oidx), _ptr(ocnt), stream_ptr()),
+          'yv4_soft_nms_split')
+    if int(ocnt.item()) == -2:
+        raise NotImplementedError(f'soft-NMS: a label with more than {SOFT_NMS_PROBLEM_CAP} candidates is not built')
+
+
+def _soft_single(boxes, scores, labels, spec, max_out, split_thr, class_agnostic, single_in_global=False):
+    """One problem set (one image) of soft-NMS: yv4_soft_nms_images below split_thr (up to SOFT_NMS_CAP candidates, else
+    the single call in global memory), yv4_soft_nms_split per label from split_thr.  ``single_in_global``: the single
+    call in global memory at any size (tests run the same candidates through both forms).  Returns (dets(k,5),
+    keep(k,))."""
+    n = boxes.shape[0]
+    dev = boxes.device
+    L = _lib.lib()
+    keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    counts = torch.empty(1, dtype=torch.int32, device=dev)
+    maxc = torch.empty(1, dtype=torch.float32, device=dev)
+    check(L.yv4_nms_prepare(_ptr(boxes), _ptr(scores), n, _ptr(keys), _ptr(counts), _ptr(maxc), stream_ptr()),
+          'yv4_nms_prepare')
+    if class_agnostic:
+        maxc.fill_(-1.0)                          # no class offset (mmcv: boxes_for_nms = boxes)
+    cap = max(min(max_out if max_out > 0 else n, n), 1)
+    dets = torch.empty((cap, 5), dtype=torch.float32, device=dev)
+    olab = torch.empty(cap, dtype=torch.int32, device=dev)
+    oidx = torch.empty(cap, dtype=torch.int64, device=dev)
+    ocnt = torch.empty(1, dtype=torch.int32, device=dev)
+    lab = None if class_agnostic else labels
+    if n < split_thr and n <= SOFT_NMS_CAP and not single_in_global:
+        check(L.yv4_soft_nms_images(_ptr(keys), n, _ptr(counts), _ptr(maxc), _ptr(boxes), n, _ptr(lab), n, 0, 1,
+                                    spec['method'], spec['iou_thr'], spec['sigma'], spec['min_score'], cap, split_thr,
+                                    _ptr(dets), _ptr(olab), _ptr(oidx), _ptr(ocnt), stream_ptr()), 'yv4_soft_nms_images')
+    elif n < split_thr:
+        soft_nms_split(keys, n, maxc.item(), boxes, lab, 0, 0, spec, cap, dets, olab, oidx, ocnt)
+    else:
+        # mmcv's split branch loops over unique(idxs) even when class_agnostic (then without the offset)
+        soft_nms_split(keys, n, maxc.item(), boxes, labels, 0, 1, spec, cap, dets, olab, oidx, ocnt)
+    k = int(ocnt.item())
+    if k < 0:
+        raise RuntimeError('yv4_soft_nms_images flagged the split path unexpectedly')
+    return dets[:k], oidx[:k]
+
+
+def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method='linear', offset=0):
+    """``mmcv.ops.nms.soft_nms`` (1.3.x signature; the definition in include/yv4.h).  Device tensors only, ``offset``
+    must be 0.  Returns ``(dets(k,5), inds(k,) int64)`` in selection order: the boxes as given and the DECAYED scores."""
+    assert boxes.size(1) == 4
+    assert boxes.size(0) == scores.size(0)
+    if offset != 0:
+        raise NotImplementedError('soft_nms: only offset=0 is built')
+    _need_cuda(boxes, 'boxes')
+    spec = dict(method=_soft_method(method), iou_thr=float(iou_threshold), sigma=float(sigma),
+                min_score=float(min_score))
+    if spec['method'] == _lib.SOFT_NMS_GAUSSIAN and not spec['sigma'] > 0:
+        raise ValueError('soft_nms: sigma must be > 0 for the gaussian method')
+    boxes = boxes.contiguous().float()
+    scores = scores.contiguous().float()
+    if boxes.shape[0] == 0:
+        return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
+    return _soft_single(boxes, scores, None, spec, -1, 1 << 30, True)
+
+
+def _batched_soft_nms(boxes, scores, idxs, nms_cfg_, class_agnostic):
+    """batched_nms with type='soft_nms' (mmcv 1.3.x, the decayed split form): below split_thr one soft_nms over the
+    class-offset boxes with the decayed scores in selection order; from split_thr one soft_nms per label, survivors
+    re-sorted by decayed score (ties to the lower index) and cut to ``max_num``.  ``max_num`` below split_thr is a key
+    soft_nms does not take (TypeError), as in mmcv."""
+    split_thr = nms_cfg_.pop('split_thr', SPLIT_THR_DEFAULT)
+    n = boxes.shape[0]
+    max_num = -1
+    if n >= split_thr:
+        max_num = nms_cfg_.pop('max_num', -1)
+    bad = sorted(set(nms_cfg_) - set(_SOFT_NMS_ARGS))
+    if bad:
+        raise TypeError(f'batched_nms: soft_nms takes no nms_cfg keys {bad}')
+    if nms_cfg_.get('offset', 0) != 0:
+        raise NotImplementedError('batched_nms: only offset=0 is built')
+    spec = dict(method=_soft_method(nms_cfg_.get('method', 'linear')), iou_thr=float(nms_cfg_.get('iou_threshold', 0.3)),
+                sigma=float(nms_cfg_.get('sigma', 0.5)), min_score=float(nms_cfg_.get('min_score', 1e-3)))
+    if spec['method'] == _lib.SOFT_NMS_GAUSSIAN and not spec['sigma'] > 0:
+        raise ValueError('soft_nms: sigma must be > 0 for the gaussian method')
+    boxes = boxes.contiguous().float()
+    scores = scores.contiguous().float()
+    if n == 0:
+        return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
+    labels = idxs.to(device=boxes.device, dtype=torch.int32).contiguous()
+    return _soft_single(boxes, scores, labels, spec, max_num, split_thr, class_agnostic)
+
+
 def set_deterministic(on=True):
     """``yv4_set_deterministic``: every floating-point sum that meets in atomics (BatchNorm statistics and their backward,
     loss sums and row gradients, bias gradients, the SPP scatter, the gradient norm) runs on fixed-point integer words or
@@ -215,8 +353,10 @@ def batched_nms(boxes, scores, idxs, nms_cfg, class_agnostic=False):
     nms_cfg_ = dict(nms_cfg)
     class_agnostic = nms_cfg_.pop('class_agnostic', class_agnostic)
     nms_type = nms_cfg_.pop('type', 'nms')
+    if nms_type == 'soft_nms':
+        return _batched_soft_nms(boxes, scores, idxs, nms_cfg_, class_agnostic)
     if nms_type != 'nms':
-        raise NotImplementedError(f'batched_nms: nms type {nms_type!r} is not built (only "nms")')
+        raise NotImplementedError(f'batched_nms: nms type {nms_type!r} is not built ("nms", "soft_nms")')
     split_thr = nms_cfg_.pop('split_thr', SPLIT_THR_DEFAULT)
     iou_threshold = nms_cfg_.pop('iou_threshold', nms_cfg_.pop('iou_thr', None))
     if iou_threshold is None:

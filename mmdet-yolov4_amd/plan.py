@@ -544,14 +544,18 @@ class Plan:
 
     def postprocess(self, pred_views, strides, base_anchors, num_classes, score_thr, iou_thr, max_per_img,
                     split_thr=10000, rescale=True, want_cls=False, nms_pre=-1, class_agnostic=False, v3=False,
-                    conf_thr=-1.0):
+                    conf_thr=-1.0, nms=None):
         """decode+filter and per-image NMS over the head's NHWC pred maps.
         base_anchors: list (per level) of (A,4) float tensors.  Returns a dict of result
         tensors (allocated at finalize).  ``class_agnostic``: 5 attributes per box, the score is the
         objectness (one pseudo-class); ``nms_pre`` > 0: only the top-k boxes by objectness are
         candidates (yolocsp_head.py:349-360).  ``v3``: YOLOV3Head semantics (yolo_head.py:210-391): the
         v3 box decode, top-k PER LEVEL, objectness >= ``conf_thr``, class score > ``score_thr`` with the
-        objectness multiplied in afterwards."""
+        objectness multiplied in afterwards.  ``nms``: the NMS of ``ops.nms_spec(test_cfg.nms)`` (default: hard NMS
+        with ``iou_thr`` / ``split_thr``); ``type='soft_nms'`` launches yv4_soft_nms_images instead of yv4_nms_images."""
+        if nms is None:
+            nms = dict(type='nms', iou_thr=iou_thr, split_thr=split_thr)
+        iou_thr, split_thr = nms['iou_thr'], nms['split_thr']
         N = pred_views[0].N
         A = base_anchors[0].shape[0]
         kclasses = 0 if class_agnostic else num_classes          # what the kernels see
@@ -566,7 +570,7 @@ class Plan:
         levels = (LevelDesc * len(pred_views))()
         res = dict(N=N, total_anchors=total, num_classes=num_classes, max_per_img=max_per_img,
                    key_cap=total * num_classes, want_cls=want_cls, rescale=rescale,
-                   iou_thr=iou_thr, split_thr=split_thr, score_thr=score_thr, class_agnostic=class_agnostic)
+                   iou_thr=iou_thr, split_thr=split_thr, score_thr=score_thr, class_agnostic=class_agnostic, nms=nms)
         if v3:
             assert not class_agnostic, 'YOLOV3Head has no class-agnostic form'
             use_topk = nms_pre > 0 and any(v.H * v.W * A > nms_pre for v in pred_views)
@@ -634,17 +638,27 @@ class Plan:
                 res['max_coord'].data_ptr(), res['topk_keys'].data_ptr() if use_topk else None, stream),
                 'yv4_decode_filter')
 
-        def nms(stream):
+        def nms_op(stream):
             check(_lib.lib().yv4_nms_images(
                 res['keys'].data_ptr(), res['key_cap'], res['counts'].data_ptr(), res['max_coord'].data_ptr(),
                 res['boxes'].data_ptr(), total, None, 0, num_classes, N, float(iou_thr), max_per_img,
                 int(split_thr), res['dets'].data_ptr(), res['labels'].data_ptr(), res['index'].data_ptr(),
                 res['count'].data_ptr(), stream), 'yv4_nms_images')
+
+        def soft_nms(stream):
+            check(_lib.lib().yv4_soft_nms_images(
+                res['keys'].data_ptr(), res['key_cap'], res['counts'].data_ptr(), res['max_coord'].data_ptr(),
+                res['boxes'].data_ptr(), total, None, 0, num_classes, N, nms['method'], nms['iou_thr'], nms['sigma'],
+                nms['min_score'], max_per_img, int(split_thr), res['dets'].data_ptr(), res['labels'].data_ptr(),
+                res['index'].data_ptr(), res['count'].data_ptr(), stream), 'yv4_soft_nms_images')
         self.ops.append(Op('reset', 'decode_reset', reset))
         if use_topk:
             self.ops.append(Op('topk', 'conf_topk', topk))
         self.ops.append(Op('decode', 'decode_filter', decode_v3 if v3 else decode, nbytes=4.0 * N * total * attr))
-        self.ops.append(Op('nms', 'nms_images', nms))
+        if nms['type'] == 'soft_nms':
+            self.ops.append(Op('nms', 'soft_nms_images', soft_nms))
+        else:
+            self.ops.append(Op('nms', 'nms_images', nms_op))
         return res
 
     # ---- lifecycle ---------------------------------------------------------------

@@ -110,17 +110,14 @@ def emit_tta_post(plan, head, groups, flips, N, cfg=None):
     if not _lib.has_tta():
         raise RuntimeError('libyv4_hip.so has no test-time augmentation entry points: rebuild it')
     cfg = head.test_cfg if cfg is None else cfg
-    nms_cfg = dict(cfg['nms'])
-    if nms_cfg.get('type', 'nms') != 'nms':
-        raise NotImplementedError('only nms type "nms" is built')
+    spec = ops.nms_spec(cfg['nms'])                  # "nms" or "soft_nms"; other types raise
     num_augs = len(flips)
     if num_augs > _lib.TTA_MAX_AUGS:
         raise NotImplementedError(f'at most {_lib.TTA_MAX_AUGS} test-time augmentations are built, got {num_augs}')
     C_ = head.num_classes
     nms_pre = int(cfg.get('nms_pre', -1))
     res = dict(N=N, num_classes=C_, max_per_img=cfg['max_per_img'], score_thr=cfg['score_thr'],
-               iou_thr=nms_cfg.get('iou_threshold', nms_cfg.get('iou_thr')),
-               split_thr=nms_cfg.get('split_thr', ops.SPLIT_THR_DEFAULT), num_augs=num_augs, flips=list(flips))
+               iou_thr=spec['iou_thr'], split_thr=spec['split_thr'], num_augs=num_augs, flips=list(flips), nms=spec)
     allocs = []
     where = [None] * num_augs
     for g, (views, augs) in enumerate(groups):
@@ -172,9 +169,19 @@ def emit_tta_post(plan, head, groups, flips, N, cfg=None):
             res['boxes'].data_ptr(), S_total, None, 0, C_, N, float(res['iou_thr']), res['max_per_img'],
             int(res['split_thr']), res['dets'].data_ptr(), res['labels'].data_ptr(), res['index'].data_ptr(),
             res['count'].data_ptr(), stream), 'yv4_nms_images')
+
+    def soft_nms(stream):
+        check(_lib.lib().yv4_soft_nms_images(
+            res['keys'].data_ptr(), res['key_cap'], res['counts'].data_ptr(), res['max_coord'].data_ptr(),
+            res['boxes'].data_ptr(), S_total, None, 0, C_, N, spec['method'], spec['iou_thr'], spec['sigma'],
+            spec['min_score'], res['max_per_img'], int(res['split_thr']), res['dets'].data_ptr(),
+            res['labels'].data_ptr(), res['index'].data_ptr(), res['count'].data_ptr(), stream), 'yv4_soft_nms_images')
     from .plan import Op
     plan.ops.append(Op('merge', 'tta_merge', merge))
-    plan.ops.append(Op('nms', 'nms_images', nms))
+    if spec['type'] == 'soft_nms':
+        plan.ops.append(Op('nms', 'soft_nms_images', soft_nms))
+    else:
+        plan.ops.append(Op('nms', 'nms_images', nms))
     plan.post = res
     return res
 

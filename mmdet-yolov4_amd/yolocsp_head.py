@@ -364,15 +364,13 @@ class YOLOCSPHead(HipModule):
 
     def emit_postprocess(self, plan, pred_views, cfg=None, rescale=True, want_cls=False):
         cfg = self.test_cfg if cfg is None else cfg
-        nms_cfg = dict(cfg['nms'])
-        if nms_cfg.get('type', 'nms') != 'nms':
-            raise NotImplementedError('only nms type "nms" is built')
+        spec = ops.nms_spec(cfg['nms'])              # "nms" or "soft_nms"; other types raise
         nms_pre = cfg.get('nms_pre', -1)
         return plan.postprocess(
             pred_views, self.featmap_strides, self.anchor_generator.base_anchors, self.num_classes,
-            score_thr=cfg['score_thr'], iou_thr=nms_cfg.get('iou_threshold', nms_cfg.get('iou_thr')),
-            max_per_img=cfg['max_per_img'], split_thr=nms_cfg.get('split_thr', ops.SPLIT_THR_DEFAULT),
-            rescale=rescale, want_cls=want_cls, nms_pre=nms_pre, class_agnostic=self.class_agnostic)
+            score_thr=cfg['score_thr'], iou_thr=spec['iou_thr'],
+            max_per_img=cfg['max_per_img'], split_thr=spec['split_thr'],
+            rescale=rescale, want_cls=want_cls, nms_pre=nms_pre, class_agnostic=self.class_agnostic, nms=spec)
 
     # ---- reference API ----------------------------------------------------------------------
     def fwd_raw(self, feats):
@@ -605,6 +603,15 @@ def _run_split_path(post, counts):
         cnt = int(post['counts'][n].item())
         if cnt > post['key_cap']:
             raise RuntimeError('candidate key buffer overflow')
+        spec = post.get('nms') or dict(type='nms')
+        if spec['type'] == 'soft_nms':
+            # mmcv's split branch from split_thr on; below it (more candidates than the images kernel holds) the
+            # single call over all of them
+            per_label = 1 if cnt >= post['split_thr'] else 0
+            ops.soft_nms_split(post['keys'][n], cnt, float(maxc[n]), post['boxes'][n], None, post['num_classes'],
+                               per_label, spec, post['max_per_img'], post['dets'][n], post['labels'][n],
+                               post['index'][n], post['count'][n:n + 1])
+            continue
         work = torch.empty(max(L.yv4_nms_split_work(cnt), 16), dtype=torch.uint8, device=post['dets'].device)
         check(L.yv4_nms_split(post['keys'][n].data_ptr(), cnt, float(maxc[n]), post['boxes'][n].data_ptr(), None,
                               post['num_classes'], float(post['iou_thr']), post['max_per_img'], work.data_ptr(),

@@ -449,15 +449,13 @@ class YOLOV3Head(HipModule):
 
     def emit_postprocess(self, plan, pred_views, cfg=None, rescale=True, want_cls=False):
         cfg = self.test_cfg if cfg is None else cfg
-        nms_cfg = dict(cfg['nms'])
-        if nms_cfg.get('type', 'nms') != 'nms':
-            raise NotImplementedError('only nms type "nms" is built')
+        spec = ops.nms_spec(cfg['nms'])              # "nms" or "soft_nms"; other types raise
         return plan.postprocess(
             pred_views, self.featmap_strides, self.anchor_generator.base_anchors, self.num_classes,
-            score_thr=cfg['score_thr'], iou_thr=nms_cfg.get('iou_threshold', nms_cfg.get('iou_thr')),
-            max_per_img=cfg['max_per_img'], split_thr=nms_cfg.get('split_thr', ops.SPLIT_THR_DEFAULT),
+            score_thr=cfg['score_thr'], iou_thr=spec['iou_thr'],
+            max_per_img=cfg['max_per_img'], split_thr=spec['split_thr'],
             rescale=rescale, want_cls=want_cls, nms_pre=cfg.get('nms_pre', -1), v3=True,
-            conf_thr=cfg.get('conf_thr', -1))
+            conf_thr=cfg.get('conf_thr', -1), nms=spec)
 
     # ---- reference API ------------------------------------------------------------------------
     def fwd(self, feats):

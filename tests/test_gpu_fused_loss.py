@@ -2,7 +2,11 @@
 conv-output gradient) against the oracle's head_loss (yolocsp_head.py:384-575 restated with torch CPU ops,
 differentiated by autograd; index_put runs in order there, so duplicate positives resolve to the last one) and
 against the package's own tensor-op path.  Tolerances: losses 2e-5 relative, gradients 2e-5 of the largest
-entry for fp32 maps; 16-bit maps: the gradient is stored in 16 bits (bf16 4e-3 / fp16 1e-3 relative to max)."""
+entry for fp32 maps; 16-bit maps: the gradient is stored in 16 bits (bf16 4e-3 / fp16 1e-3 relative to max).
+
+These are toy sizes (3 to 6 classes, square maps of 2 to 16 cells, at most 7 boxes per image).  The real sizes (80 classes,
+608 x 608, the grid-stride loops), non-square maps, the hand-built edge cases, the assignment's integer outputs and the
+per-element comparison with float64 are in test_gpu_loss_exact.py."""
 import os
 
 import numpy as np

@@ -928,6 +928,47 @@ typedef struct yv4_tta_aug {
 int yv4_tta_merge(const yv4_tta_aug* augs, int num_augs, int N, int num_classes, float score_thr, const float* meta,
                   float* boxes_out, uint64_t* keys, int64_t key_cap, int32_t* counts, float* max_coord, void* stream);
 
+/* ---- train-side input pipeline of the YOLOv3 mstrain recipe (csrc/augment_v3.hip; additive within ABI 8) -----------
+ * configs/yolo/yolov3_d53_mstrain-608_273e_coco.py:59-78: PhotoMetricDistortion -> Expand -> MinIoURandomCrop ->
+ * Resize(keep_ratio) -> RandomFlip -> Normalize -> Pad(size_divisor) -> collate, the pixels of a batch in one launch.
+ * One yv4_v3aug_image per OUTPUT image carries its source and the host's draws (the draws, MinIoURandomCrop's acceptance
+ * loop and the boxes stay on the host).  The float pixel definitions are stated in csrc/augment_v3.hip.
+ *   src, sh, sw, pitch      decoded 8-bit BGR source (HWC, 3 channels, device memory), row pitch in bytes
+ *   bright_on/_delta        random brightness: v += delta
+ *   contrast_mode/_alpha    YV4_V3AUG_CONTRAST_*: v *= alpha before BGR -> HSV (the reference's mode 1), after HSV -> BGR
+ *                           (mode 0), or not at all
+ *   sat_on/_alpha           S *= alpha, unclipped; hue_on/_delta: H += delta, then > 360 -> -360, < 0 -> +360
+ *   perm_on, perm[3]        channel permutation: out[c] = in[perm[c]]
+ *   eh, ew, etop, eleft     Expand's canvas and the offsets of the image in it (sh, sw, 0, 0 when Expand is skipped);
+ *   fill[3]                 its fill value per channel, not distorted
+ *   cx, cy, cw, ch          MinIoURandomCrop's patch in the canvas (0, 0, ew, eh when the image is returned unchanged)
+ *   rh, rw                  size after Resize; ph, pw: after Pad (informative: everything outside rh x rw is written 0)
+ *   flip                    YV4_FLIP_* of the resized region */
+#define YV4_V3AUG_CONTRAST_NONE 0
+#define YV4_V3AUG_CONTRAST_FIRST 1
+#define YV4_V3AUG_CONTRAST_LAST 2
+typedef struct yv4_v3aug_image {
+  const void* src;
+  int32_t sh, sw, pitch;
+  int32_t bright_on, contrast_mode, sat_on, hue_on, perm_on;
+  float bright_delta, contrast_alpha, sat_alpha, hue_delta;
+  int32_t perm[3];
+  int32_t eh, ew, etop, eleft;
+  float fill[3];
+  int32_t cx, cy, cw, ch;
+  int32_t rh, rw, ph, pw;
+  int32_t flip;
+  int32_t reserved;
+} yv4_v3aug_image;
+
+/* Pixels of N output images into out_nchw (N, 3, Hmax, Wmax) fp32: image n's resized region at the top left, zeros
+ * elsewhere (Pad and the collate's padding to the batch maximum).  imgs: N descriptors in DEVICE memory; mean3 / std3:
+ * HOST values.  Returns YV4_E_INVALID (-1) on null pointers, N / Hmax / Wmax <= 0 or a zero std before touching the
+ * device.  A tap outside the placed source reads the fill value, and stores are bounded by Hmax x Wmax, whatever the
+ * descriptors say. */
+int yv4_v3_augment_u8(const yv4_v3aug_image* imgs, int N, float* out_nchw, int Hmax, int Wmax, const float* mean3,
+                      const float* std3, int to_rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

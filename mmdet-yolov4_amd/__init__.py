@@ -23,6 +23,7 @@ from .yolov3 import Darknet, DetectionBlock, ResBlock, YOLOBBoxCoder, YOLOV3, YO
 from .plan import Plan
 from .preprocess import FusedTestPipeline
 from .augment import FusedTrainPipeline
+from .augment_v3 import FusedV3TrainPipeline, build_train_pipeline
 from . import tta  # noqa: F401  (YOLOv3 test-time augmentation)
 from .apis import inference_detector, single_gpu_test, multi_gpu_test
 from .eval_utils import (coco_test_annotation, evaluate_fast_bbox, EVAL_BREAKDOWN, EVAL_IOU_CALCULATOR, EVAL_MATCHER, FlexibleStatisticsEval, IOU2DCoCo,

@@ -28,6 +28,7 @@ SOFT_NMS_METHODS = {'naive': SOFT_NMS_NAIVE, 'linear': SOFT_NMS_LINEAR, 'gaussia
 FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL, FLIP_DIAGONAL = 0, 1, 2, 3     # YV4_FLIP_*
 FLIP_CODES = {'horizontal': FLIP_HORIZONTAL, 'vertical': FLIP_VERTICAL, 'diagonal': FLIP_DIAGONAL}
 TTA_MAX_AUGS = 16          # YV4_TTA_MAX_AUGS
+V3AUG_CONTRAST_NONE, V3AUG_CONTRAST_FIRST, V3AUG_CONTRAST_LAST = 0, 1, 2    # YV4_V3AUG_CONTRAST_*
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4
 TILE_DMA_64x64, TILE_DMA_128x64, TILE_DMA_128x128, TILE_STEM, TILE_WS_1x1 = 5, 6, 7, 8, 9
 HTILE_NAMES = {1: 'h16_128x128', 2: 'h16_128x64', 3: 'h16_64x64', 4: 'h16_pp3x3', 5: 'h16_w3x3', 6: 'h16_ws_1x1', 7: 'h16_s3x3', 8: 'h16_wide'}
@@ -110,6 +111,16 @@ class AugImage(C.Structure):
                 ('rh', C.c_int32 * 4), ('rw', C.c_int32 * 4)] + \
                [(n, C.c_int32) for n in ('cxy', 'left', 'top', 'x1', 'y1', 'C', 'S', 'o', 'flip', 'hsv_on')] + \
                [('lut', (C.c_uint8 * 256) * 3)]
+
+
+class V3AugImage(C.Structure):
+    """``yv4_v3aug_image``."""
+    _fields_ = [('src', C.c_void_p)] + \
+               [(n, C.c_int32) for n in ('sh', 'sw', 'pitch', 'bright_on', 'contrast_mode', 'sat_on', 'hue_on', 'perm_on')] + \
+               [(n, C.c_float) for n in ('bright_delta', 'contrast_alpha', 'sat_alpha', 'hue_delta')] + \
+               [('perm', C.c_int32 * 3)] + [(n, C.c_int32) for n in ('eh', 'ew', 'etop', 'eleft')] + \
+               [('fill', C.c_float * 3)] + \
+               [(n, C.c_int32) for n in ('cx', 'cy', 'cw', 'ch', 'rh', 'rw', 'ph', 'pw', 'flip', 'reserved')]
 
 
 class PackDesc(C.Structure):
@@ -227,6 +238,7 @@ SIGNATURES = {
                                       _vp, _vp, _vp]),
     'yv4_soft_nms_split_work': (_sz, [_i64]),
     'yv4_soft_nms_split': (C.c_int, [_vp, _i64, _f, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'yv4_v3_augment_u8': (C.c_int, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -239,6 +251,8 @@ FP8_SYMBOLS = frozenset(('yv4_conv_bn_act_fwd_f8', 'yv4_conv_f8_pick_tile', 'yv4
 TTA_SYMBOLS = frozenset(('yv4_letterbox_u8_flip', 'yv4_topk_slots_work', 'yv4_topk_slots', 'yv4_tta_merge'))
 #: the soft-NMS entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_soft_nms()
 SOFT_NMS_SYMBOLS = frozenset(('yv4_soft_nms_images', 'yv4_soft_nms_split_work', 'yv4_soft_nms_split'))
+#: the YOLOv3 train-side input pipeline (additive within ABI 8, bound like FP8_SYMBOLS); has_v3_augment()
+V3_AUGMENT_SYMBOLS = frozenset(('yv4_v3_augment_u8',))
 
 _lock = threading.Lock()
 _lib = None
@@ -276,7 +290,8 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             if name in ABI8_SYMBOLS and got < 8:
                 continue
-            if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS) and not hasattr(handle, name):
+            if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
+                    or name in V3_AUGMENT_SYMBOLS) and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
             fn.restype = res
@@ -314,6 +329,12 @@ def has_soft_nms():
     """The loaded library exports the soft-NMS entry points."""
     h = lib()
     return all(hasattr(h, n) for n in SOFT_NMS_SYMBOLS)
+
+
+def has_v3_augment():
+    """The loaded library exports the YOLOv3 train-side input pipeline."""
+    h = lib()
+    return all(hasattr(h, n) for n in V3_AUGMENT_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

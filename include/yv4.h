@@ -707,6 +707,46 @@ typedef struct yv4_loss_desc {
 int yv4_yolo_loss_fwd(const yv4_loss_desc* d, void* stream);
 int yv4_yolo_loss_bwd(const yv4_loss_desc* d, const float* grad_out, void* stream);
 
+/* ---- the same loss with the other box losses and SoftFocalLoss (additive within ABI 8) ----------------
+ * yv4_yolo_loss_fwd_ex / _bwd_ex take the descriptor above plus yv4_loss_opts; yv4_yolo_loss_fwd / _bwd are these calls
+ * with {YV4_BOX_GIOU, no focal}.  Assignment, winner resolution, work buffers, sums, the deterministic mode and the
+ * one-pass gradient write do not depend on the options.
+ * box_kind (models/losses/iou_loss.py:14-36,105-219; fp32, the reference's expression order; ov = overlap, a1 / a2 the
+ * areas, cw / ch the enclosing box's clamped extents, eps = yv4_loss_desc.eps):
+ *   YV4_BOX_GIOU        iou = ov / max(a1 + a2 - ov, eps);  loss = 1 - (iou - (E - U) / E),  E = max(cw * ch, eps)
+ *   YV4_BOX_IOU_LINEAR  iou = max(ov / max(a1 + a2 - ov, 1e-6), eps);  loss = 1 - iou   (1e-6: bbox_overlaps' own default)
+ *   YV4_BOX_IOU_LOG     the same iou;  loss = -log(iou)
+ *   YV4_BOX_DIOU        iou = ov / (a1 + a2 - ov + eps);  c2 = cw^2 + ch^2 + eps  (eps is ADDED, not a clamp);
+ *                       rho2 = ((tx1 + tx2) - (x1 + x2))^2 / 4 + ((ty1 + ty2) - (y1 + y2))^2 / 4;  loss = 1 - (iou - rho2 / c2)
+ *   YV4_BOX_CIOU        DIoU's iou, c2, rho2;  v = 4 / pi^2 * (atan(w2 / (h2 + eps)) - atan(w1 / (h1 + eps)))^2;
+ *                       loss = 1 - (iou - (rho2 / c2 + v^2 / (1 - iou + v))), differentiated through v, iou and the
+ *                       denominator (nothing detached).  Where this is 0 / 0 (iou == 1 and v == 0) value and gradient
+ *                       are nan, as in the reference: the point is not special-cased.
+ *   Subgradients are torch's: one half on a tie of max / min against the target and of max(union, 1e-6); clamp(min = c)
+ *   passes the gradient where x >= c.  The objectness target of a positive is (1 - r) + r * clamp(1 - loss, 0, 1) for
+ *   every kind (so 0 wherever -log(iou) >= 1).
+ * conf_focal / cls_focal (SoftFocalLoss, models/dense_heads/yolocsp_head.py:21-50), independently for the objectness and
+ *   the class term, with soft targets t:  loss = bce * (t*alpha + (1-t)*(1-alpha)) * (1 - p_t)^gamma,
+ *   p_t = t*p + (1-t)*(1-p), p = sigmoid(x); the derivative goes through all three factors.  gamma >= 1 (below 1 the
+ *   derivative is unbounded at p_t = 1), 0 <= alpha <= 1.  gamma / alpha are ignored where the switch is 0.
+ * Both calls validate the options before the device is touched (-1 + yv4_last_error: null opts, unknown kind,
+ * gamma < 1, alpha outside [0, 1]). */
+#define YV4_BOX_GIOU 0
+#define YV4_BOX_IOU_LINEAR 1
+#define YV4_BOX_IOU_LOG 2
+#define YV4_BOX_DIOU 3
+#define YV4_BOX_CIOU 4
+typedef struct yv4_loss_opts {
+  int32_t box_kind;      /* YV4_BOX_* */
+  int32_t conf_focal;    /* 0 / 1 */
+  float conf_gamma, conf_alpha;
+  int32_t cls_focal;     /* 0 / 1 */
+  float cls_gamma, cls_alpha;
+  int32_t reserved[9];   /* zero */
+} yv4_loss_opts;
+int yv4_yolo_loss_fwd_ex(const yv4_loss_desc* d, const yv4_loss_opts* opts, void* stream);
+int yv4_yolo_loss_bwd_ex(const yv4_loss_desc* d, const yv4_loss_opts* opts, const float* grad_out, void* stream);
+
 /* ---- YOLOV3Head training loss, forward and backward (ABI 8) ------------------------------------------
  * Replaces GridAssigner.assign (core/bbox/assigners/grid_assigner.py:73-156), responsible_flags + grid_anchors
  * (core/anchor/anchor_generator.py:667-727), BboxOverlaps2D (core/bbox/iou_calculators/iou2d_calculator.py),

@@ -84,6 +84,16 @@ class LossDesc(C.Structure):
                 ('gpos', C.c_void_p), ('sums', C.c_void_p), ('losses', C.c_void_p)]
 
 
+class LossOpts(C.Structure):
+    """``yv4_loss_opts``: the box loss and the SoftFocalLoss switches of ``yv4_yolo_loss_fwd_ex`` / ``_bwd_ex``."""
+    _fields_ = [('box_kind', C.c_int32), ('conf_focal', C.c_int32), ('conf_gamma', C.c_float), ('conf_alpha', C.c_float),
+                ('cls_focal', C.c_int32), ('cls_gamma', C.c_float), ('cls_alpha', C.c_float), ('reserved', C.c_int32 * 9)]
+
+
+#: ``yv4_loss_opts.box_kind`` (YV4_BOX_* in include/yv4.h)
+BOX_GIOU, BOX_IOU_LINEAR, BOX_IOU_LOG, BOX_DIOU, BOX_CIOU = range(5)
+
+
 class V3LossLevel(C.Structure):
     """``yv4_v3_loss_level`` (ABI 8)."""
     _fields_ = [('pred', C.c_void_p), ('dpred', C.c_void_p),
@@ -215,6 +225,8 @@ SIGNATURES = {
     'yv4_pack_weights_multi': (C.c_int, [_vp, _i, _i, _vp]),
     'yv4_yolo_loss_fwd': (C.c_int, [C.POINTER(LossDesc), _vp]),
     'yv4_yolo_loss_bwd': (C.c_int, [C.POINTER(LossDesc), _vp, _vp]),
+    'yv4_yolo_loss_fwd_ex': (C.c_int, [C.POINTER(LossDesc), C.POINTER(LossOpts), _vp]),
+    'yv4_yolo_loss_bwd_ex': (C.c_int, [C.POINTER(LossDesc), C.POINTER(LossOpts), _vp, _vp]),
     'yv4_yolov3_loss_fwd': (C.c_int, [C.POINTER(V3LossDesc), _vp]),
     'yv4_yolov3_loss_bwd': (C.c_int, [C.POINTER(V3LossDesc), _vp, _vp]),
     'yv4_mosaic_augment_u8': (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
@@ -253,6 +265,9 @@ TTA_SYMBOLS = frozenset(('yv4_letterbox_u8_flip', 'yv4_topk_slots_work', 'yv4_to
 SOFT_NMS_SYMBOLS = frozenset(('yv4_soft_nms_images', 'yv4_soft_nms_split_work', 'yv4_soft_nms_split'))
 #: the YOLOv3 train-side input pipeline (additive within ABI 8, bound like FP8_SYMBOLS); has_v3_augment()
 V3_AUGMENT_SYMBOLS = frozenset(('yv4_v3_augment_u8',))
+#: the YOLOCSPHead loss with options: IoU / DIoU / CIoU box terms and SoftFocalLoss (additive within ABI 8, bound like
+#: FP8_SYMBOLS); has_loss_ex()
+LOSS_EX_SYMBOLS = frozenset(('yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'))
 
 _lock = threading.Lock()
 _lib = None
@@ -291,7 +306,7 @@ def lib():
             if name in ABI8_SYMBOLS and got < 8:
                 continue
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
-                    or name in V3_AUGMENT_SYMBOLS) and not hasattr(handle, name):
+                    or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS) and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
             fn.restype = res
@@ -335,6 +350,12 @@ def has_v3_augment():
     """The loaded library exports the YOLOv3 train-side input pipeline."""
     h = lib()
     return all(hasattr(h, n) for n in V3_AUGMENT_SYMBOLS)
+
+
+def has_loss_ex():
+    """The loaded library exports ``yv4_yolo_loss_fwd_ex`` / ``_bwd_ex`` (the box-loss family and SoftFocalLoss)."""
+    h = lib()
+    return all(hasattr(h, n) for n in LOSS_EX_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

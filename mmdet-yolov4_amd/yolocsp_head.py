@@ -72,6 +72,30 @@ class HeadTapFunction(torch.autograd.Function):
         return draw, dbias, None, None, None, None
 
 
+def _bce_of(loss):
+    """The sigmoid ``CrossEntropyLoss`` behind a class / objectness loss: itself, or a ``SoftFocalLoss``'s ``loss_fcn``."""
+    return loss.loss_fcn if isinstance(loss, _losses.SoftFocalLoss) else loss
+
+
+def _box_kind(loss):
+    """``yv4_loss_opts.box_kind`` of a box loss the fused kernels cover, else None."""
+    kinds = {_losses.GIoULoss: _lib.BOX_GIOU, _losses.DIoULoss: _lib.BOX_DIOU, _losses.CIoULoss: _lib.BOX_CIOU}
+    if type(loss) is _losses.IoULoss:
+        return _lib.BOX_IOU_LINEAR if loss.linear else _lib.BOX_IOU_LOG
+    return kinds.get(type(loss))
+
+
+def loss_options(head):
+    """``yv4_loss_opts`` of a head whose configuration ``_fused_loss_ok`` accepted."""
+    o = _lib.LossOpts()
+    o.box_kind = _box_kind(head.loss_bbox)
+    if isinstance(head.loss_conf, _losses.SoftFocalLoss):
+        o.conf_focal, o.conf_gamma, o.conf_alpha = 1, float(head.loss_conf.gamma), float(head.loss_conf.alpha)
+    if not head.class_agnostic and isinstance(head.loss_cls, _losses.SoftFocalLoss):
+        o.cls_focal, o.cls_gamma, o.cls_alpha = 1, float(head.loss_cls.gamma), float(head.loss_cls.alpha)
+    return o
+
+
 class YoloLossFunction(torch.autograd.Function):
     """All levels' ``loss_single_no_assigner`` (+ ``responsible_indices`` and the target gathering) on
     ``yv4_yolo_loss_fwd`` / ``yv4_yolo_loss_bwd``: returns the (num_levels, 3) fp32 matrix
@@ -122,14 +146,16 @@ class YoloLossFunction(torch.autograd.Function):
         d.shape_thr, d.smooth, d.ratio = float(head.shape_match_thres), float(head.one_hot_smoother), \
             float(head.conf_iou_loss_ratio)
         d.eps = float(head.loss_bbox.eps)
-        d.w_cls = float(head.loss_cls.loss_weight) if C_ else 0.
-        d.w_conf, d.w_bbox = float(head.loss_conf.loss_weight), float(head.loss_bbox_weight)
+        # (a SoftFocalLoss has no loss_weight of its own: the weight is its wrapped CrossEntropyLoss's)
+        d.w_cls = float(_bce_of(head.loss_cls).loss_weight) if C_ else 0.
+        d.w_conf, d.w_bbox = float(_bce_of(head.loss_conf).loss_weight), float(head.loss_bbox_weight)
+        opts = loss_options(head)
         d.slot_anchor, d.winner, d.npos, d.conf_t, d.sums = (t.data_ptr() for t in (slot_anchor, winner, npos, conf_t,
                                                                                    sums))
         out = torch.empty(L, 3, dtype=torch.float32, device=dev)
         d.losses = out.data_ptr()
-        check(_lib.lib().yv4_yolo_loss_fwd(C.byref(d), ops.stream_ptr()), 'yv4_yolo_loss_fwd')
-        ctx.desc = d
+        check(_lib.lib().yv4_yolo_loss_fwd_ex(C.byref(d), C.byref(opts), ops.stream_ptr()), 'yv4_yolo_loss_fwd_ex')
+        ctx.desc, ctx.opts = d, opts
         ctx.keep = (raws, keep, gt, gt_label, gt_img, slot_anchor, winner, npos, conf_t, sums)
         ctx.meta = (L, S, A, attr)
         # (the (L, 3) losses come out of the forward call itself: d.losses, set above)
@@ -149,7 +175,8 @@ class YoloLossFunction(torch.autograd.Function):
         for l in range(L):
             d.levels[l].draw, d.levels[l].dbias = draws[l].data_ptr(), dbias[l].data_ptr()
         d.gpos = gpos.data_ptr()
-        check(_lib.lib().yv4_yolo_loss_bwd(C.byref(d), gout.data_ptr(), ops.stream_ptr()), 'yv4_yolo_loss_bwd')
+        check(_lib.lib().yv4_yolo_loss_bwd_ex(C.byref(d), C.byref(ctx.opts), gout.data_ptr(), ops.stream_ptr()),
+              'yv4_yolo_loss_bwd_ex')
         return (None, None, None, None) + tuple(draws) + tuple(b.float() for b in dbias)
 
 
@@ -457,19 +484,25 @@ class YOLOCSPHead(HipModule):
         return dict(loss_conf=l_conf, loss_bbox=l_box, num_gts=num_gts)
 
     def _fused_loss_ok(self, pred_maps):
-        """The fused kernels cover the configuration the recipes use: raw (training-mode) maps, sigmoid
-        CrossEntropyLoss without class weights and GIoULoss, both with mean reduction.  Anything else takes the
-        tensor-op path below (on the GPU as well).  YV4_FUSED_LOSS=0 forces that path (A/B, tests)."""
+        """The fused kernels cover raw (training-mode) maps with: GIoULoss, IoULoss (linear or log), DIoULoss or CIoULoss
+        for the box term; for the objectness and the class term, independently, a sigmoid CrossEntropyLoss without class
+        weights or a SoftFocalLoss around one with ``gamma >= 1`` (below 1 the focal derivative is unbounded at
+        ``p_t = 1``: such a config keeps the tensor-op path) and ``alpha`` in [0, 1]; all with mean reduction.  Anything
+        else takes the tensor-op path below (on the GPU as well).  YV4_FUSED_LOSS=0 forces that path (A/B, tests)."""
         if os.environ.get('YV4_FUSED_LOSS', '1') == '0':
             return False
         if not all(isinstance(p, RawPredMap) for p in pred_maps) or len(pred_maps) > 5:
             return False
-        ok = type(self.loss_conf) is _losses.CrossEntropyLoss and type(self.loss_bbox) is _losses.GIoULoss
-        ok = ok and self.loss_conf.class_weight is None and self.loss_conf.reduction == 'mean'
-        ok = ok and self.loss_bbox.reduction == 'mean'
+        def bce_ok(loss):
+            if type(loss) is _losses.SoftFocalLoss:
+                # (the wrapper took the reduction over and set its loss_fcn's to 'none')
+                return type(loss.loss_fcn) is _losses.CrossEntropyLoss and loss.loss_fcn.class_weight is None \
+                    and loss.reduction == 'mean' and loss.gamma >= 1 and 0 <= loss.alpha <= 1
+            return type(loss) is _losses.CrossEntropyLoss and loss.class_weight is None and loss.reduction == 'mean'
+
+        ok = bce_ok(self.loss_conf) and _box_kind(self.loss_bbox) is not None and self.loss_bbox.reduction == 'mean'
         if not self.class_agnostic:
-            ok = ok and type(self.loss_cls) is _losses.CrossEntropyLoss and self.loss_cls.class_weight is None \
-                and self.loss_cls.reduction == 'mean'
+            ok = ok and bce_ok(self.loss_cls)
         return ok and len(set(self.num_anchors)) == 1 and self.num_anchors[0] <= 8
 
     def _loss_fused(self, pred_maps, gt_bboxes, gt_labels, num_gts):

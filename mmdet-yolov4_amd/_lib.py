@@ -273,16 +273,18 @@ _lock = threading.Lock()
 _lib = None
 
 
-def build(verbose=False):
-    """Compile the HIP sources for gfx950 into ``lib/libyv4_hip.so`` (in-tree)."""
-    cmd = ['make', '-C', CSRC_DIR, '-j4']
+def build(verbose=False, measure=False):
+    """Compile the HIP sources for gfx950 into ``lib/libyv4_hip.so`` (in-tree).  ``measure``: the -DYV4_MEASURE build,
+    ``lib_alt/libyv4_hip_measure.so``, instead -- the only library in which the kernel forms behind the measurement
+    switches can be reached (tests/test_gpu_bn_exact.py runs them in child processes)."""
+    cmd = ['make', '-C', CSRC_DIR, '-j4'] + (['measure'] if measure else [])
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                          text=True)
     if verbose or res.returncode != 0:
         print(res.stdout)
     if res.returncode != 0:
         raise RuntimeError('building libyv4_hip.so failed (see output above)')
-    return LIB_PATH
+    return os.path.join(os.path.dirname(LIB_DIR), 'lib_alt', 'libyv4_hip_measure.so') if measure else LIB_PATH
 
 
 def lib():

@@ -1842,7 +1842,7 @@ __device__ __forceinline__ float act_grad(float z, int act, float slope) {
       const float g = __builtin_fmaf(4.f * (z * (a * e)), iw * iw, __builtin_fmaf(-2.f, iw, 1.f));
       return z >= 20.f ? 1.f : g;
     }
-    case YV4_ACT_LEAKY: return z >= 0.f ? 1.f : slope;
+    case YV4_ACT_LEAKY: return z > 0.f ? 1.f : slope;   // (torch's leaky_relu_backward: slope AT zero, either sign of it)
     case YV4_ACT_SWISH: {
       const float s = 1.f / (1.f + expf(-z));
       return s + z * s * (1.f - s);
@@ -1934,7 +1934,7 @@ __device__ __forceinline__ RedMap red_map(int C4) {
 // Block-level combine of per-thread partials (a: first C values, b: second C values) and one
 // double atomic per channel per workgroup.  part[] lives in LDS: [2][C] doubles.
 // det (yv4_set_deterministic): part[] is [2][2*C] 64-bit words -- hi words of (a | b), then their lo words (fx_add)
-template <int SHIFT>
+template <int SHIFT, int FR = 0>
 __device__ __forceinline__ void red_flush(double* part, int C, int c, const double (&a)[4], const double (&b)[4],
                                           bool active, int det) {
   if (active) {
@@ -1942,8 +1942,8 @@ __device__ __forceinline__ void red_flush(double* part, int C, int c, const doub
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (det) {
-        fx_add<SHIFT>(w + c + k, w + 2 * C + c + k, a[k]);
-        fx_add<SHIFT>(w + C + c + k, w + 3 * C + c + k, b[k]);
+        fx_add<SHIFT, FR>(w + c + k, w + 2 * C + c + k, a[k]);
+        fx_add<SHIFT, FR>(w + C + c + k, w + 3 * C + c + k, b[k]);
       } else {
         atomicAdd(&part[c + k], a[k]);
         atomicAdd(&part[C + c + k], b[k]);
@@ -2016,7 +2016,7 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) { ds[k] += fs[k]; dq[k] += fq[k]; }
-      red_flush<kFxStat>(part, C, cq * 4, ds, dq, true, det);
+      red_flush<kFxStat, kFxStatFr>(part, C, cq * 4, ds, dq, true, det);
     }
   }
   __syncthreads();
@@ -2029,12 +2029,12 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const T* __restrict__ x, 
   for (int i = threadIdx.x; i < 2 * C; i += 256) atomicAdd(&sums[i], part[i]);
 }
 // det: the words of [hi (n) | lo (n)] -> n doubles in place (consumers outside the library: SyncBN's all-reduce)
-template <int SHIFT>
+template <int SHIFT, int FR = 0>
 __global__ void fx_decode_kernel(double* __restrict__ buf, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const u64_t* w = reinterpret_cast<const u64_t*>(buf);
-  buf[i] = fx_value<SHIFT>(w[i], w[n + i]);
+  buf[i] = fx_value<SHIFT, FR>(w[i], w[n + i]);
 }
 
 // mean / biased var / invstd from the sums; running stats update (unbiased var, momentum)
@@ -2090,8 +2090,8 @@ __global__ void bn_finalize_kernel(double* __restrict__ sums, int64_t M_host, in
       fx_fold(h1, l1, __shfl_xor(h1, o), __shfl_xor(l1, o));
       fx_fold(h2, l2, __shfl_xor(h2, o), __shfl_xor(l2, o));
     }
-    s1 = fx_value<kFxStat>(h1, l1);
-    s2 = fx_value<kFxStat>(h2, l2);
+    s1 = fx_value<kFxStat, kFxStatFr>(h1, l1);
+    s2 = fx_value<kFxStat, kFxStatFr>(h2, l2);
   } else {
     if (c < C) {
       double a1[8], a2[8];
@@ -2162,7 +2162,7 @@ __global__ void stats_fold_kernel(double* __restrict__ sums, int C, int replicas
       fx_fold(h, l, hp[0], hp[2 * C]);
       if (clear_work) { hp[0] = 0; hp[2 * C] = 0; }
     }
-    out[i] = fx_value<kFxStat>(h, l);
+    out[i] = fx_value<kFxStat, kFxStatFr>(h, l);
   } else {
     double a = 0.0;
     for (int r = 0; r < replicas; ++r) {
@@ -3534,7 +3534,7 @@ static int bn_stats_impl(int dtype, const void* x, int64_t M, int C, int x_cstri
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, s, work, M, C, eps, momentum, mean, invstd,
                        running_mean, running_var, (const double*)nullptr, det ? 2 : 1, 0, (double*)nullptr, det);
   else if (det && phase == 1)     // the caller (SyncBN) all-reduces doubles
-    hipLaunchKernelGGL(fx_decode_kernel<kFxStat>, dim3((2 * C + 255) / 256), dim3(256), 0, s, work, 2 * C);
+    hipLaunchKernelGGL((fx_decode_kernel<kFxStat, kFxStatFr>), dim3((2 * C + 255) / 256), dim3(256), 0, s, work, 2 * C);
   YV4_CHECK_LAUNCH("bn_train_stats");
   return YV4_OK;
 }

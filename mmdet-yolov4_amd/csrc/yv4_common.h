@@ -110,29 +110,35 @@ static inline int ensure_dyn_lds(LdsAttrOnce& g, const void* fn, size_t bytes, c
 bool deterministic();          // api.hip: the process-wide switch, read by the launchers
 constexpr int kFxStat = 40;    // forward statistics, loss sums: |v| < 1.8e16, resolution 9.1e-13
 constexpr int kFxGrad = 60;    // gradient sums (loss-scaled): addends and sums |v| < 1.7e10, resolution 8.7e-19
+// FR extra fraction bits carried in the lo word alone: lo = t - hi * 2^32 in [0, 2^32) in steps of 2^-FR, stored as an
+// integer below 2^(32 + FR).  Range and hi words are what they are without them; the resolution becomes 2^-(SHIFT + FR)
+// and the lo sums stay below 2^63 for < 2^(31 - FR) addends.  The BatchNorm statistics take 8 (resolution 3.6e-15, up to
+// 8.4 M addends per word: a word meets one addend per thread and channel, or per tile of a conv epilogue and replica pair):
+// at 2^-40 the variance of a channel of |x| ~ 1e-5 (x^2 ~ 1e-10: fp16 denormals) came out 1e-4 off.
+constexpr int kFxStatFr = 8;
 typedef unsigned long long u64_t;
 
-template <int SHIFT>
+template <int SHIFT, int FR = 0>
 __device__ __forceinline__ void fx_add(u64_t* hi, u64_t* lo, double v) {
   double t = v * __builtin_ldexp(1.0, SHIFT);
   if (!(__builtin_fabs(t) < 0x1p94)) {          // NaN, infinity, out of range
     atomicOr(lo, 1ull << 63);
     return;
   }
-  t = __builtin_rint(t);
-  const double h = __builtin_floor(t * 0x1p-32);
-  const double l = t - h * 0x1p32;              // exact, in [0, 2^32)
+  t = __builtin_rint(t * __builtin_ldexp(1.0, FR));          // in units of 2^-(SHIFT + FR)
+  const double h = __builtin_floor(t * __builtin_ldexp(1.0, -(32 + FR)));
+  const double l = t - h * __builtin_ldexp(1.0, 32 + FR);    // exact, in [0, 2^(32 + FR))
   const long long hv = (long long)h;
   if (hv) atomicAdd(hi, (u64_t)hv);
   atomicAdd(lo, (u64_t)(long long)l);
 }
 // words -> value.  (hi, lo) may be sums of several accumulators' words (fx_fold).
-template <int SHIFT>
+template <int SHIFT, int FR = 0>
 __device__ __forceinline__ double fx_value(u64_t hi, u64_t lo) {
   if (lo >> 63) return __builtin_nan("");
-  const long long H = (long long)hi + (long long)(lo >> 32);
+  const long long H = (long long)hi + (long long)(lo >> (32 + FR));
   if (H >= (1ll << 62) || H <= -(1ll << 62)) return __builtin_nan("");     // the SUM is out of range (see above)
-  return ((double)H * 0x1p32 + (double)(lo & 0xffffffffull)) * __builtin_ldexp(1.0, -SHIFT);
+  return ((double)H * 0x1p32 + (double)(lo & ((1ull << (32 + FR)) - 1)) * __builtin_ldexp(1.0, -FR)) * __builtin_ldexp(1.0, -SHIFT);
 }
 __device__ __forceinline__ void fx_fold(u64_t& hi, u64_t& lo, u64_t h2, u64_t l2) {
   hi += h2;
@@ -156,7 +162,7 @@ __device__ __forceinline__ StatRep stat_rep(double* stats, unsigned idx, int C) 
   return r;
 }
 __device__ __forceinline__ void stat_add(const StatRep& r, int i, float v) {
-  if (r.lo_off) fx_add<kFxStat>(reinterpret_cast<u64_t*>(r.p) + i, reinterpret_cast<u64_t*>(r.p) + r.lo_off + i, (double)v);
+  if (r.lo_off) fx_add<kFxStat, kFxStatFr>(reinterpret_cast<u64_t*>(r.p) + i, reinterpret_cast<u64_t*>(r.p) + r.lo_off + i, (double)v);
   else atomicAdd(&r.p[i], (double)v);
 }
 static inline double* tag_stats(double* stats) {

@@ -233,7 +233,8 @@ def test_conv_epilogue_leaves_the_bn_sums(dtype, shape):
     """yv4_conv_fwd_stats: the conv kernel's epilogue accumulates [sum | sum of squares] of the STORED outputs
     (rounded to the output type) over YV4_STATS_REPLICAS copies; kernels without that epilogue (Cin % 32 != 0 in
     fp32) fall back to the reduction kernel behind the same entry point.  Checked against float64 sums of the
-    output tensor (1e-6 relative) and through bn_act with / without the precomputed sums (identical up to 2e-6)."""
+    output tensor (per channel: the sums to 1e-6 of sum |y|, the sums of squares to 1e-6 of themselves) and through
+    bn_act with / without the precomputed sums (identical up to 2e-6)."""
     from mmdet_yolov4_amd import train_ops as T
     from mmdet_yolov4_amd import _lib
     N, Cin, Cout, hw, k, stride = shape
@@ -249,7 +250,14 @@ def test_conv_epilogue_leaves_the_bn_sums(dtype, shape):
     tot = stats.view(_lib.STATS_REPLICAS, 2, Cout).sum(0)
     yd = y.double()
     want = torch.stack([yd.sum((0, 2, 3)), (yd * yd).sum((0, 2, 3))])
-    assert float((tot - want).abs().max() / want.abs().max()) < 1e-6
+    # the two rows separately and per channel: a sum against the sum of |y| behind it, a sum of squares against itself --
+    # and neither looser than the single 1e-6 of the largest entry of both rows that used to cover every channel
+    cap = 1e-6 * want.abs().max()
+    e_sum = (tot[0] - want[0]).abs() / torch.minimum(1e-6 * yd.abs().sum((0, 2, 3)), cap)
+    e_sq = (tot[1] - want[1]).abs() / torch.minimum(1e-6 * want[1], cap)
+    print(f'epilogue sums {dtype} {shape}: sums at {float(e_sum.max()):.3f}, squares at {float(e_sq.max()):.3f} of their bounds')
+    assert float(e_sum.max()) < 1, f'sum of channel {int(e_sum.argmax())}: {float(e_sum.max()):.3g} x its bound'
+    assert float(e_sq.max()) < 1, f'sum of squares of channel {int(e_sq.argmax())}: {float(e_sq.max()):.3g} x its bound'
     bn_a, bn_b = torch.nn.BatchNorm2d(Cout).to(dev).train(), torch.nn.BatchNorm2d(Cout).to(dev).train()
     out_a = T.bn_act(y, bn_a, (1, 0.0), sums=stats)
     out_b = T.bn_act(y, bn_b, (1, 0.0))

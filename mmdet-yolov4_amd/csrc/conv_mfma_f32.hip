@@ -1504,7 +1504,7 @@ extern "C" int yv4_conv_bn_act_fwd_splitk(const yv4_conv_desc* d, const float* x
 int conv_stats_h16(const yv4_conv_desc* d, int dtype, const void* x, const void* w, const float* ones, const float* zeros,
                    void* y, double* stats, void* stream);
 int bn_partial_sums_replica0(const void* x, int dtype, int64_t M, int C, int x_cstride, int x_coff, double* stats,
-                             void* stream);   // train.hip
+                             void* stream);   // bn_train.hip
 
 // Training-mode convolution feeding a BatchNorm: y = conv(x, w) (identity epilogue, `ones` / `zeros` = Cout unit
 // scales / zero shifts) and the per-channel sums of y for the batch statistics, accumulated by the conv kernel's

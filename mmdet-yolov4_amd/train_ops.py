@@ -1,4 +1,4 @@
-"""Autograd front ends of the training-side HIP kernels (``csrc/train.hip`` + the forward conv).
+"""Autograd front ends of the training-side HIP kernels (``csrc/train.hip``, ``csrc/conv_wgrad*_h16.hip``, ``csrc/bn_train.hip`` + the forward conv).
 
 Training does not go through launch plans: modules build an ordinary autograd graph out of
 the two Functions below, on ``torch.channels_last`` tensors (logical NCHW, physical NHWC --

@@ -1,7 +1,7 @@
 """Float64 reference of the train-mode BatchNorm + activation passes, with a first-order error scale for every output
 (a helper module for the tests, not a conftest).
 
-The operation (train.hip's header, darknetcsp.py's Conv: conv -> BatchNorm2d -> activation, plus the shortcut) on an NHWC
+The operation (bn_train.hip's header, darknetcsp.py's Conv: conv -> BatchNorm2d -> activation, plus the shortcut) on an NHWC
 view of M rows and C channels:
 
   statistics   s1 = sum x, s2 = sum x^2, mean = s1 / M, var = max(s2 / M - mean^2, 0) (biased),

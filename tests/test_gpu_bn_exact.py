@@ -1,4 +1,4 @@
-"""The train-mode BatchNorm + activation kernels (train.hip: bn_stats, bn_finalize, bn_act_fwd, bn_act_bwd_reduce,
+"""The train-mode BatchNorm + activation kernels (bn_train.hip: bn_stats, bn_finalize, bn_act_fwd, bn_act_bwd_reduce,
 bn_act_bwd_apply and the pipelined bn16_* forms) through the C ABI, against tests/_bn_ref.py.
 
   a. exact coverage on integer operands (tests/_exact_ref.py): mean = 0, invstd = 1, gamma = 1 are handed in, so
@@ -57,7 +57,7 @@ def _refs_checked():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the launch arithmetic of train.hip, restated
+# the launch arithmetic of bn_train.hip, restated
 # ---------------------------------------------------------------------------------------------------------------------
 def switches():
     """(bn16 on, bn16 channels per thread, general kernels' 8-channel form): the product library reads no environment
@@ -376,7 +376,7 @@ def _ulps(a, b64):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# R: fp32 roundings on the longest path of an output, counted from train.hip (DESIGN 4.8 lists every path); an
+# R: fp32 roundings on the longest path of an output, counted from bn_train.hip (DESIGN 4.8 lists every path); an
 # operation written in the source counts once whether or not the compiler contracts it, v_exp_f32 / v_rcp_f32 /
 # expf / a division count as two, a select, a min and a multiplication by a power of two as none
 # ---------------------------------------------------------------------------------------------------------------------

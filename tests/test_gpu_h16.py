@@ -627,7 +627,7 @@ W3_SHAPES = [
 @pytest.mark.parametrize('dtype,tol', [(torch.bfloat16, 2e-2), (torch.float16, 3e-3)])
 @pytest.mark.parametrize('shape', W3_SHAPES)
 def test_h16_wgrad3x3_kernel(gpu_device, dtype, tol, shape):
-    """The kw-shared weight-gradient kernel (train.hip conv_wgrad3x3_h16_kernel; auto-selected for 3x3 / stride 1 with
+    """The kw-shared weight-gradient kernel (conv_wgrad3x3_h16.hip conv_wgrad3x3_h16_kernel; auto-selected for 3x3 / stride 1 with
     Cin % 128 == 0) through ConvFunction, vs fp64 autograd on the same rounded operands; deterministic run to run."""
     N, Cin, Cout, H, W = shape
     torch.manual_seed(1)
@@ -669,7 +669,7 @@ FC_SHAPES = [
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('shape', FC_SHAPES)
 def test_h16_wgrad_few_channel_kernel(gpu_device, dtype, shape):
-    """The few-channel 3x3 weight-gradient kernel (train.hip conv_wgrad_fc_h16_kernel: all of dW per workgroup, one
+    """The few-channel 3x3 weight-gradient kernel (conv_wgrad_fc_h16.hip conv_wgrad_fc_h16_kernel: all of dW per workgroup, one
     source image per kh shared by its three kw taps) through ConvFunction, vs fp64 autograd on the same rounded
     operands; deterministic run to run; per-tap error (a shifted-row or masking mistake is one wrong (kh, kw) plane)."""
     N, Cin, Cout, H, W = shape

@@ -643,7 +643,7 @@ def _ulp16(ref, dtype):
 @pytest.mark.parametrize('shape', [(128, 3, 37, 41), (32, 2, 97, 53), (256, 5, 19, 19), (36, 1, 23, 9), (512, 2, 10, 10)])
 @pytest.mark.parametrize('with_res', [False, True])
 def test_bn16_passes_within_one_ulp_of_fp32_evaluation(gpu_device, dtype, shape, with_res):
-    """The pipelined 16-bit BatchNorm + Mish passes (train.hip bn16_*: folded affine constants, exponent clamp instead of
+    """The pipelined 16-bit BatchNorm + Mish passes (bn_train.hip bn16_*: folded affine constants, exponent clamp instead of
     the asymptote select; semantics mmdet/ops/mish_cuda/src/mish.h:16-50 + torch.nn.BatchNorm2d of darknetcsp.py:15-35)
     against the SAME 16-bit values pushed through the fp32 kernels: every 16-bit output within one ulp of the fp32-evaluated
     value rounded to the type, dgamma / dbeta / running statistics to fp32 rounding.  Shapes

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the pipelined 16-bit BatchNorm passes (train.hip bn16_*) against the general kernels, same box, measure build:
+# A/B of the pipelined 16-bit BatchNorm passes (bn_train.hip bn16_*) against the general kernels, same box, measure build:
 # tools/bn_bench.py --kernels over YOLOv4-L's activation shapes at batch 64.
 source "$(dirname "$0")/_measure_lib.sh"
 for cfg in "0 4" "1 4" "1 8" "0 4" "1 4"; do

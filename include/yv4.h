@@ -830,6 +830,55 @@ int yv4_match_coco_batched(const float* iou, const int64_t* det_off, const int64
                            const uint8_t* is_ignore, const uint8_t* is_crowd, int P, uint8_t* work,
                            int32_t* matched, void* stream);
 
+/* ---- VOC-style mAP (csrc/map_eval.hip; additive within ABI 8) ------------------------------------------------------
+ * mmdet/core/evaluation/bbox_overlaps.py:4-48 and the two true/false-positive rules of mean_ap.py (tpfp_default
+ * :153-237, tpfp_imagenet :59-150), which eval_map calls per image and class and once per IoU threshold, batched over
+ * P (image, class) problems with the table layout of the calls above: the offset tables have P+1 int64 entries
+ * (device), problem p owns rows [off[p], off[p+1]) of each box array and the row-major (n1 x n2) block at iou_off[p].
+ * All pointers but `stream` are device pointers; boxes are x1 y1 x2 y2 float32, 16-byte aligned.
+ *
+ * yv4_bbox_overlaps_batched: overlap / max(union, eps) per pair in the reference's fp32 operation order
+ *   (area = (x2-x1)*(y2-y1), overlap = max(xe-xs,0)*max(ye-ys,0), union = (area1+area2)-overlap for YV4_OVERLAPS_IOU,
+ *   area1 for YV4_OVERLAPS_IOF); bit-exact.  The reference's operand swap for rows > cols changes no bit (one
+ *   commutative add) and is not made.  total_pairs = iou_off[P]; 0 is legal (nothing is launched). */
+#define YV4_OVERLAPS_IOU 0
+#define YV4_OVERLAPS_IOF 1
+int yv4_bbox_overlaps_batched(const float* boxes1, const float* boxes2, const int64_t* off1, const int64_t* off2,
+                              const int64_t* iou_off, int P, int64_t total_pairs, int mode, float eps, float* iou,
+                              void* stream);
+/* yv4_tpfp_batched: tp / fp flags of every detection for num_thrs IoU thresholds and num_ranges area ranges from ONE
+ *   IoU block per problem (the reference recomputes it per threshold).
+ *   det (total_det, 4): the detections in their ORIGINAL order; order[det_off[p] + s] = index inside problem p of the
+ *     s-th detection visited (the host's np.argsort(-scores)), rank = its inverse (rank[det_off[p] + order[..s]] = s).
+ *     YV4_TPFP_DEFAULT reads rank only, YV4_TPFP_IMAGENET reads order only; the other may be null.
+ *   gt (total_gt, 4): per problem the class's gts followed by its ignored gts, gt_ignore one byte each (1 = ignored).
+ *   iou: yv4_bbox_overlaps_batched(det, gt) -- for YV4_TPFP_IMAGENET against gt - 1 (the host subtracts), while `gt`
+ *     here stays the unshifted boxes (their areas select the range).
+ *   gt_ratio (total_gt; imagenet only): w*h / ((w+10)*(h+10)) per gt as the host's numpy evaluates it; the gt's
+ *     threshold is min(gt_ratio, iou_thrs[t]).
+ *   area_ranges: num_ranges (min, max) float32 pairs, or null with num_ranges == 1 for "no range".  A box is in range
+ *     when area >= min && area < max.
+ *   tp, fp: (num_thrs, num_ranges, total_det) bytes; problem p's (T, K, nd) block is the column slice
+ *     [det_off[p], det_off[p+1]), columns in the original detection order.
+ *   YV4_TPFP_DEFAULT: a detection whose row maximum (first-occurrence argmax g) reaches iou_thrs[t] is nothing when g
+ *     is ignored or out of range, else tp when it has the smallest rank among the detections that reach t with the
+ *     same argmax (an integer atomicMin per (gt, t), then a parallel pass), else fp.
+ *   YV4_TPFP_IMAGENET: one sequential walk per (problem, t): detections in `order` take the best still-uncovered gt
+ *     with iou >= its threshold (first maximum wins); the gt is covered even when ignored; tp when the gt is neither
+ *     ignored nor out of range.
+ *   Both: an unmatched detection is fp when its own area is in range; a problem without gts marks every in-range
+ *     detection fp; problems without detections and total_det == 0 are legal.
+ *   work: yv4_tpfp_work(mode, total_det, total_gt, num_thrs) bytes, 4-byte aligned, contents undefined before and
+ *     after.  total_det and total_gt must be below 0x7f7f7f7f. */
+#define YV4_TPFP_DEFAULT 0
+#define YV4_TPFP_IMAGENET 1
+size_t yv4_tpfp_work(int mode, int64_t total_det, int64_t total_gt, int num_thrs);
+int yv4_tpfp_batched(int mode, const float* det, const float* gt, const uint8_t* gt_ignore, const float* gt_ratio,
+                     const int32_t* order, const int32_t* rank, const int64_t* det_off, const int64_t* gt_off,
+                     const int64_t* iou_off, int P, int64_t total_det, int64_t total_gt, const float* iou,
+                     const float* iou_thrs, int num_thrs, const float* area_ranges, int num_ranges, void* work,
+                     uint8_t* tp, uint8_t* fp, void* stream);
+
 /* ---- split-K form of yv4_conv_bn_act_fwd for single-image (latency) plans ---------------------------------------
  * The reference's only published protocol is batch 1 (tools/analysis_tools/benchmark.py:83-109).  There the deep layers
  * have a handful of output tiles and hundreds of K slices each; this entry splits K over several workgroups per tile

@@ -23,6 +23,8 @@ F8E4M3 = 3                 # YV4_F8E4M3: the fp8 entry points' element code (the
 F8TILE_128x128, F8TILE_128x64, F8TILE_64x64 = 1, 2, 3
 ACT_NONE, ACT_MISH, ACT_LEAKY, ACT_SWISH = 0, 1, 2, 3
 NMS_IOU_DIV, NMS_IOU_MUL = 0, 1
+OVERLAPS_IOU, OVERLAPS_IOF = 0, 1                                           # YV4_OVERLAPS_*
+TPFP_DEFAULT, TPFP_IMAGENET = 0, 1                                          # YV4_TPFP_*
 SOFT_NMS_NAIVE, SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 0, 1, 2                # YV4_SOFT_NMS_*
 SOFT_NMS_METHODS = {'naive': SOFT_NMS_NAIVE, 'linear': SOFT_NMS_LINEAR, 'gaussian': SOFT_NMS_GAUSSIAN}
 FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL, FLIP_DIAGONAL = 0, 1, 2, 3     # YV4_FLIP_*
@@ -251,6 +253,10 @@ SIGNATURES = {
     'yv4_soft_nms_split_work': (_sz, [_i64]),
     'yv4_soft_nms_split': (C.c_int, [_vp, _i64, _f, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'yv4_v3_augment_u8': (C.c_int, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    'yv4_bbox_overlaps_batched': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i, _f, _vp, _vp]),
+    'yv4_tpfp_work': (_sz, [_i, _i64, _i64, _i]),
+    'yv4_tpfp_batched': (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _i, _vp, _i,
+                                   _vp, _vp, _vp, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -268,6 +274,8 @@ V3_AUGMENT_SYMBOLS = frozenset(('yv4_v3_augment_u8',))
 #: the YOLOCSPHead loss with options: IoU / DIoU / CIoU box terms and SoftFocalLoss (additive within ABI 8, bound like
 #: FP8_SYMBOLS); has_loss_ex()
 LOSS_EX_SYMBOLS = frozenset(('yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'))
+#: the VOC-style mAP entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_map_eval()
+MAP_EVAL_SYMBOLS = frozenset(('yv4_bbox_overlaps_batched', 'yv4_tpfp_work', 'yv4_tpfp_batched'))
 
 _lock = threading.Lock()
 _lib = None
@@ -308,7 +316,8 @@ def lib():
             if name in ABI8_SYMBOLS and got < 8:
                 continue
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
-                    or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS) and not hasattr(handle, name):
+                    or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS) \
+                    and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
             fn.restype = res
@@ -358,6 +367,12 @@ def has_loss_ex():
     """The loaded library exports ``yv4_yolo_loss_fwd_ex`` / ``_bwd_ex`` (the box-loss family and SoftFocalLoss)."""
     h = lib()
     return all(hasattr(h, n) for n in LOSS_EX_SYMBOLS)
+
+
+def has_map_eval():
+    """The loaded library exports the VOC-style mAP entry points (``yv4_bbox_overlaps_batched`` / ``yv4_tpfp_batched``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in MAP_EVAL_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

@@ -203,7 +203,10 @@ int yv4_resample_nearest_fwd(const float* src, float* dst, int N, int Hs, int Ws
  * counts[n] / max_coord[n] must be zero / -inf-initialised by
  * yv4_decode_reset().  If more than key_cap candidates pass for an image the
  * count keeps counting (so the caller can see the overflow) but keys beyond the
- * capacity are dropped. */
+ * capacity are dropped.  cls rows are written for the boxes that are admitted
+ * as candidates' sources only: the rows of boxes turned away by nms_pre (or, in
+ * yv4_decode_filter_v3, by conf_thr) are left unwritten; boxes and conf are
+ * written for every box. */
 typedef struct yv4_level_desc {
   const float* pred;  /* device pointer, NHWC */
   int32_t H, W;
@@ -1013,7 +1016,9 @@ typedef struct yv4_tta_aug {
  * (~order(cls * conf) << 32 | (m*num_classes + c)) is appended to keys[n*key_cap ...] and the mapped box folded into
  * max_coord[n] -- the buffers yv4_nms_images / yv4_nms_split take with fused_classes = num_classes and
  * boxes_per_image = S_total.  meta: device (num_augs, N, 6) fp32 rows img_h, img_w, scale_factor[4].
- * counts / max_coord must be reset by yv4_decode_reset first.  augs: num_augs HOST descriptors. */
+ * counts / max_coord must be reset by yv4_decode_reset first.  augs: num_augs HOST descriptors.
+ * If more than key_cap candidates pass for an image the count keeps counting (so the caller can see the overflow) but
+ * keys beyond the capacity are dropped. */
 int yv4_tta_merge(const yv4_tta_aug* augs, int num_augs, int N, int num_classes, float score_thr, const float* meta,
                   float* boxes_out, uint64_t* keys, int64_t key_cap, int32_t* counts, float* max_coord, void* stream);
 

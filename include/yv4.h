@@ -882,6 +882,55 @@ int yv4_tpfp_batched(int mode, const float* det, const float* gt, const uint8_t*
                      const float* iou_thrs, int num_thrs, const float* area_ranges, int num_ranges, void* work,
                      uint8_t* tp, uint8_t* fp, void* stream);
 
+/* ---- COCO bbox evaluation (csrc/coco_eval.hip; additive within ABI 8) ------------------------------------------------
+ * pycocotools' COCOeval with iouType='bbox' and useCats=1 (computeIoU / evaluateImg / accumulate), as
+ * mmdet/datasets/coco.py:547-551 configures it; the definition is restated in mmdet-yolov4_amd/coco_eval.py.
+ * Problem p = image * K + category (images and categories in the order of their sorted ids) owns the ground truths
+ * [gt_off[p], gt_off[p+1]) and, after yv4_coco_rank, the sorted positions [det_off[p], det_off[p+1]).  All pointers
+ * but `stream` and `max_dets` are device pointers.  Every float64 value is one IEEE operation of the definition in
+ * its order and every sum is an integer: bit-exact against the definition, identical bytes from run to run.
+ *
+ * yv4_coco_rank: one stable key-value sort of the flat detection table by (problem, descending score).
+ *   det (total_det, 5) float32 x1 y1 x2 y2 score in the caller's order; prob (total_det) int32: the detection's
+ *     problem, or a value outside [0, P) for a detection that takes no part (it is sorted behind every problem).
+ *   order (total_det) uint32: order[s] = row of `det` at sorted position s; sprob (total_det) int32: its problem
+ *     (P for "no part"); det_off (P+1) int64.  The rank of position s inside its problem is s - det_off[sprob[s]];
+ *     equal scores keep the caller's order.
+ *   match_need (1) int64: the doubles of workspace yv4_coco_match needs for num_at = A * T walks with this
+ *     max_det = maxDets[-1] (the problems whose IoU block or matched bits do not fit LDS); the caller reads it back.
+ *   work: yv4_coco_rank_work(total_det) bytes, 8-byte aligned.  total_det == 0 is legal (det_off is zeroed). */
+size_t yv4_coco_rank_work(int64_t total_det);
+int yv4_coco_rank(const float* det, const int32_t* prob, int64_t total_det, int P, int max_det, int num_at,
+                  const int64_t* gt_off, void* work, uint32_t* order, int32_t* sprob, int64_t* det_off,
+                  int64_t* match_need, void* stream);
+/* yv4_coco_match: one wave per problem; its first min(num_det, max_det) detections in rank order against its gts.
+ *   gt_box (total_gt, 4) float64 x y w h; gt_area (total_gt) float64 (the annotation's own area); gt_flag (total_gt)
+ *     bytes: bit 0 = iscrowd, bit 1 = ignore (COCOeval overwrites ignore by iscrowd; the caller decides).
+ *   iou_thrs (T) float64; area_rng (A, 2) float64 [lo, hi], both bounds inclusive; A <= 64.
+ *   The IoU block (float64, union = detection area for a crowd gt, 0 when w <= 0 or h <= 0) is computed once and
+ *     shared by the A x T greedy walks, one per lane (groups of 64 when A * T > 64).
+ *   flags (total_det, A * T) bytes, zeroed first: flags[s * A*T + a * T + t] bit 0 = sorted position s is matched,
+ *     bit 1 = it is ignored (its gt is ignored in range a, or it is unmatched and its own area is outside the range).
+ *   counts (K, A) int32, zeroed first: the gts with ignore == 0 and area inside range a, per category.
+ *   work / work_len: at least *match_need doubles (may be null / 0 when that is 0).  state (2) int64: [1] != 0
+ *     afterwards means the workspace was too small and problems were skipped. */
+int yv4_coco_match(const float* det, const uint32_t* order, const int64_t* det_off, const double* gt_box,
+                   const double* gt_area, const uint8_t* gt_flag, const int64_t* gt_off, int P, int K, int64_t total_det,
+                   int max_det, const double* iou_thrs, int T, const double* area_rng, int A, double* work,
+                   int64_t work_len, int64_t* state, uint8_t* flags, int32_t* counts, void* stream);
+/* yv4_coco_accumulate: a second stable sort, by (category, descending score) from the (image-major, rank) order of
+ *   yv4_coco_rank -- ties fall as COCOeval's mergesort over the concatenated images leaves them -- then per
+ *   (k, a, m, t) over the category's detections with rank < maxDets[m] (and < maxDets[-1]): integer cumulative tp / fp,
+ *   rc = tp / npig, pr = tp / (fp + tp + 2^-52), pr's suffix maximum, and np.searchsorted(rc, rec_thrs, 'left').
+ *   max_dets (M <= 16) int32 on the HOST; rec_thrs (R <= 256) float64, ascending.
+ *   precision, scores (T, R, K, A, M) and recall (T, K, A, M) float64: -1 where counts[k][a] == 0.
+ *   work: yv4_coco_accumulate_work(total_det, K, A * T) bytes, 8-byte aligned. */
+size_t yv4_coco_accumulate_work(int64_t total_det, int K, int num_at);
+int yv4_coco_accumulate(const float* det, const uint32_t* order, const int32_t* sprob, const int64_t* det_off,
+                        const uint8_t* flags, const int32_t* counts, int P, int K, int64_t total_det,
+                        const int32_t* max_dets, int M, int T, int A, const double* rec_thrs, int R, void* work,
+                        double* precision, double* recall, double* scores, void* stream);
+
 /* ---- split-K form of yv4_conv_bn_act_fwd for single-image (latency) plans ---------------------------------------
  * The reference's only published protocol is batch 1 (tools/analysis_tools/benchmark.py:83-109).  There the deep layers
  * have a handful of output tiles and hundreds of K slices each; this entry splits K over several workgroups per tile

@@ -257,6 +257,13 @@ SIGNATURES = {
     'yv4_tpfp_work': (_sz, [_i, _i64, _i64, _i]),
     'yv4_tpfp_batched': (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _i, _vp, _i,
                                    _vp, _vp, _vp, _vp]),
+    'yv4_coco_rank_work': (_sz, [_i64]),
+    'yv4_coco_rank': (C.c_int, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'yv4_coco_match': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp,
+                                 _vp, _vp]),
+    'yv4_coco_accumulate_work': (_sz, [_i64, _i, _i]),
+    'yv4_coco_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp,
+                                      _vp, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -276,6 +283,9 @@ V3_AUGMENT_SYMBOLS = frozenset(('yv4_v3_augment_u8',))
 LOSS_EX_SYMBOLS = frozenset(('yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'))
 #: the VOC-style mAP entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_map_eval()
 MAP_EVAL_SYMBOLS = frozenset(('yv4_bbox_overlaps_batched', 'yv4_tpfp_work', 'yv4_tpfp_batched'))
+#: the COCO bbox evaluation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_coco_eval()
+COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_match', 'yv4_coco_accumulate_work',
+                               'yv4_coco_accumulate'))
 
 _lock = threading.Lock()
 _lib = None
@@ -316,7 +326,8 @@ def lib():
             if name in ABI8_SYMBOLS and got < 8:
                 continue
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
-                    or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS) \
+                    or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
+                    or name in COCO_EVAL_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -373,6 +384,12 @@ def has_map_eval():
     """The loaded library exports the VOC-style mAP entry points (``yv4_bbox_overlaps_batched`` / ``yv4_tpfp_batched``)."""
     h = lib()
     return all(hasattr(h, n) for n in MAP_EVAL_SYMBOLS)
+
+
+def has_coco_eval():
+    """The loaded library exports the COCO bbox evaluation entry points (``yv4_coco_rank`` / ``_match`` / ``_accumulate``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in COCO_EVAL_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

@@ -90,9 +90,11 @@ __global__ __launch_bounds__(kRsLanes) void rs_scatter_kernel(const K* __restric
 }
 
 // Sorts `bits` low bits (a multiple of 16: an even number of passes) of n keys, ascending and stable; values follow when
-// HAS_V.  The input is only read; the result lands in (kx, vx), (ky, vy) is the other side of the ping-pong.
+// HAS_V.  The input is only read; the result lands in (kx, vx), (ky, vy) is the other side of the ping-pong.  `what`
+// names the caller in the error message of a failed launch.
 template <class K, class V, bool HAS_V>
-static int rs_sort(const K* kin, K* kx, K* ky, const V* vin, V* vx, V* vy, int64_t n, int bits, uint32_t* hist, hipStream_t s) {
+static int rs_sort(const K* kin, K* kx, K* ky, const V* vin, V* vx, V* vy, int64_t n, int bits, uint32_t* hist, hipStream_t s,
+                   const char* what = "nms_split: radix sort") {
   const int ntiles = (int)((n + kRsTile - 1) / kRsTile);
   const K* sk = kin;
   const V* sv = vin;
@@ -106,7 +108,7 @@ static int rs_sort(const K* kin, K* kx, K* ky, const V* vin, V* vx, V* vy, int64
     sk = dk;
     sv = dv;
   }
-  YV4_CHECK_LAUNCH("nms_split: radix sort");
+  YV4_CHECK_LAUNCH(what);
   return YV4_OK;
 }
 

@@ -94,8 +94,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void conv1x1_ws_kernel(ConvArgsH p, 
   const int gw = walker * kWsWaves + wave;
   const int n0 = col * BN;
 
-  const u32x4_t rsA = make_rsrc_h(p.x, x_bytes);
-  const u32x4_t rsB = make_rsrc_h(p.w, w_bytes);
+  const u32x4_t rsA = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsB = make_rsrc(p.w, w_bytes);
 
   // ---- the weight slab, once.  Row pitch Cin*2 bytes; a 16-lane pass of ds_read_b128 must touch 16 different
   // 16-byte bank groups: rows of 128 B use the (row>>1)&7 swizzle of the generic kernel, wider rows row&15.
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void conv1x1_ws_kernel(ConvArgsH p, 
       const int co = n0 + row;
       const int lch = pch ^ swz;
       const unsigned voff = (co < p.Cout && lch < cin_chunks) ? (unsigned)(((int64_t)co * p.Kw + lch * 8) * 2) : kOOB;
-      lds_dma16_h(rsB, lds_base + (unsigned)(g * 1024), voff, 0u);
+      lds_dma16(rsB, lds_base + (unsigned)(g * 1024), voff, 0u);
     }
   }
 
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void conv1x1_ws_kernel(ConvArgsH p, 
       const unsigned voff_ = (live_ && row_ < p.M && iss_kc * 64 + (int)lch_ < p.Cin)                       \
                                  ? (unsigned)(((int64_t)row_ * p.x_cs + p.x_co + iss_kc * 64 + (int)lch_) * 2) \
                                  : kOOB;                                                                    \
-      lds_dma16_h(rsA, lds_ + (unsigned)(j * 1024), voff_, 0u);                                             \
+      lds_dma16(rsA, lds_ + (unsigned)(j * 1024), voff_, 0u);                                             \
     }                                                                                                       \
     iss_kc += 1;                                                                                            \
     const int wrap_ = iss_kc == kc_n ? 1 : 0;                                                               \

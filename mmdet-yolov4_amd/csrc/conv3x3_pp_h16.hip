@@ -73,8 +73,8 @@ __global__ __launch_bounds__(kP3Threads, 2) void conv3x3_pp_h16_kernel(ConvArgsH
   const int r = lane & 31;
   const int h = lane >> 5;
 
-  const u32x4_t rsA = make_rsrc_h(p.x, x_bytes);
-  const u32x4_t rsB = make_rsrc_h(p.w, w_bytes);
+  const u32x4_t rsA = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsB = make_rsrc(p.w, w_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_p3;
   const int NHW = p.N * p.H * p.W;
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kP3Threads, 2) void conv3x3_pp_h16_kernel(ConvArgsH
     const unsigned lb_ = lds_base + (unsigned)((2 * kP3ARows + (int)(i_t & 3u) * kP3BN + 8 * wave) * kRowB); \
     const unsigned kb = (unsigned)((((i_kh * 3 + (KW)) * p.Cin) + i_c0) * 2);                        \
     _Pragma("unroll") for (int q = 0; q < PB; ++q)                                                  \
-        lds_dma16_h(rsB, lb_ + 64 * q * kRowB, b_off[q], kb);   /* (the range check sees voffset only) */ \
+        lds_dma16(rsB, lb_ + 64 * q * kRowB, b_off[q], kb);   /* (the range check sees voffset only) */ \
   }
 #define YV4_P3_ISSUE_A(Q0, Q1)                                                                      \
   {                                                                                                 \
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kP3Threads, 2) void conv3x3_pp_h16_kernel(ConvArgsH
     const unsigned step = (unsigned)(((int64_t)ds * p.x_cs + i_c0) * 2);                            \
     _Pragma("unroll") for (int q = (Q0); q < (Q1); ++q) {                                           \
       const bool ok = (unsigned)(a_s[q] + ds) < (unsigned)NHW;                                      \
-      lds_dma16_h(rsA, la_ + 64 * q * kRowB, ok ? a_off[q] + step : kOOB, 0u);                       \
+      lds_dma16(rsA, la_ + 64 * q * kRowB, ok ? a_off[q] + step : kOOB, 0u);                       \
     }                                                                                               \
   }
 #define YV4_P3_ADVANCE(KW)                                                                          \

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv3x3_small_kernel
   const int r = lane & 31;
   const int h = lane >> 5;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_s3;
-  const u32x4_t rsA = make_rsrc_h(p.x, x_bytes);
+  const u32x4_t rsA = make_rsrc(p.x, x_bytes);
 
   // chunk swizzles: a 16-lane group of ds_read_b128 must touch 16 different 16-byte slots of the 256-byte bank row
   auto xswz = [](int q) { return CINH == 1 ? ((q >> 3) & 1) : (CINH == 2 ? ((q >> 2) & 3) : ((q >> 1) & 7)); };
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv3x3_small_kernel
       const int iy = iy0 + py, ix = ix0 + px;
       const bool ok = q < kS3Pix && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
       const unsigned voff = ok ? (unsigned)((((int64_t)(n * p.H + iy) * p.W + ix) * p.x_cs + p.x_co + (pch ^ xswz(q)) * 8) * 2) : kOOB;
-      lds_dma16_h(rsA, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)(buf * XBytes + g * 1024))), voff, 0u);
+      lds_dma16(rsA, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)(buf * XBytes + g * 1024))), voff, 0u);
     }
   };
 

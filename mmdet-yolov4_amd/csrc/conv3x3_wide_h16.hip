@@ -118,8 +118,8 @@ __global__ __launch_bounds__(kWideThreads, 2) void conv3x3_wide_h16_kernel(ConvA
   // rows of one parity -- one half of the banks, eight consecutive row pairs, eight different slots -- at every shift.
   const int pr = fr < 4 ? 2 * fr : (fr >= 12 ? 2 * fr - 16 : 2 * fr - 7);
 
-  const u32x4_t rsA = make_rsrc_h(p.x, x_bytes);
-  const u32x4_t rsB = make_rsrc_h(p.w, w_bytes);
+  const u32x4_t rsA = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsB = make_rsrc(p.w, w_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_w3;
   const int NHW = p.N * p.H * p.W;
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(kWideThreads, 2) void conv3x3_wide_h16_kernel(ConvA
   // weight piece q of a K tile: rows n0 + srow + 64 q.  A row at or beyond Cout has its vector offset beyond the tensor and
   // reads as zeros (the descriptor's range check sees the vector offset only: the K offset is the soffset)
 #define YV4_W3_PIECE_B(SLOT, SB, KB, q, vv)                                                          \
-  lds_dma16_h(rsB, lds_base + (unsigned)(2 * G_::ABytes + (SLOT) * G_::BBytes + (8 * iw + 64 * (q) + 32 * (vv)) * kRowB), \
+  lds_dma16(rsB, lds_base + (unsigned)(2 * G_::ABytes + (SLOT) * G_::BBytes + (8 * iw + 64 * (q) + 32 * (vv)) * kRowB), \
               ((vv) ? b_lane1 : b_lane) + ((SB) + (unsigned)(64 * (q)) * (unsigned)(p.Kw * 2)), (KB));
   // image piece q of a (chunk, kh) group: LDS row r = srow + 64 q holds source pixel m0 - 1 + r + (kh - 1) W.  Pixels outside
   // the tensor and the rows from BM + 2 on (row BM + 2 is the fragments' zero row) are zero-filled.
@@ -209,7 +209,7 @@ __global__ __launch_bounds__(kWideThreads, 2) void conv3x3_wide_h16_kernel(ConvA
     const unsigned sOff_ = ((unsigned)sS_ * (unsigned)p.x_cs + (unsigned)(C0)) * 2u;                 \
     const int r0_ = 64 * (q) + 32 * (vv);                                                           \
     const bool ok_ = n_live && (r0_ + PR <= BM + 2 || srow < BM + 2 - r0_) && (unsigned)(srow + sS_ + r0_) < (unsigned)NHW; \
-    lds_dma16_h(rsA, lds_base + (unsigned)((ABUF) * G_::ABytes + (8 * iw + r0_) * kRowB),            \
+    lds_dma16(rsA, lds_base + (unsigned)((ABUF) * G_::ABytes + (8 * iw + r0_) * kRowB),            \
                 ok_ ? a_lane + (sOff_ + (unsigned)r0_ * (unsigned)(p.x_cs * 2)) : kOOB, 0u);         \
   }
 

@@ -1,7 +1,10 @@
-// Shared pieces of the fp32 fused convolution kernels (conv_mfma_f32.hip: the implicit-GEMM tiles on 32x32x2 MFMAs;
-// conv3x3_wide_f32.hip: the wide-tile 3x3 kernel on 16x16x4 MFMAs): argument block, scattered-row map, LDS-DMA helpers.
+// Shared pieces of the fp32 fused convolution kernels (conv_mfma_f32.hip: the implicit-GEMM tiles on 32x32x2 MFMAs and
+// the dispatcher; conv1x1_ws_f32.hip, conv_stem_f32.hip, conv3x3_wide_f32.hip, conv_wide_f32.hip: one kernel family
+// each): argument block and its fill from a descriptor, scattered-row map, the 32-bit-descriptor rule, the row
+// activation and the families' host functions.
 #pragma once
 #include "yv4_common.h"
+#include "lds_dma.h"
 
 namespace yv4 {
 
@@ -49,28 +52,65 @@ __device__ __forceinline__ int64_t out_row(const ConvArgs& p, int m) {
   return ((int64_t)n * p.ys_H + ho * p.ys_sh + p.ys_oh) * p.ys_W + wo * p.ys_sw + p.ys_ow;
 }
 
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-// One LDS-DMA wave-instruction: lane l's 16 bytes at (descriptor base + voff + soff) land at
-// LDS byte address lds_addr + 16*l.  Issued through inline asm on purpose: hipcc would
-// otherwise wait vmcnt(0) before the next ds_read of ANY LDS address (it cannot tell the two
-// halves of the double buffer apart), exposing the whole memory latency every K step.  The
-// kernel counts these loads itself: s_waitcnt vmcnt(0) + s_barrier before the slice is read.
-__device__ __forceinline__ void lds_dma16(u32x4_t rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory");
+// The argument block of a descriptor and its tensors.  An entry sets what is particular to it afterwards (scattered
+// output, split-K, statistics); the tile choice alone needs no tensors.
+static inline ConvArgs conv_args(const yv4_conv_desc* d, const float* x = nullptr, const float* w = nullptr,
+                          const float* s1 = nullptr, const float* t1 = nullptr, const float* s2 = nullptr,
+                          const float* t2 = nullptr, const float* res = nullptr, float* y = nullptr) {
+  ConvArgs a{};
+  a.x = x; a.w = w; a.s1 = s1; a.t1 = t1; a.s2 = s2; a.t2 = t2; a.res = res; a.y = y;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
+  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
+  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
+  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
+  a.M = (int)((long long)d->N * d->Ho * d->Wo); a.K = d->KH * d->KW * d->Cin; a.Kw = a.K;
+  return a;
 }
 
-__device__ __forceinline__ u32x4_t make_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  u32x4_t v;
-  v.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  v.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-  v.z = __builtin_amdgcn_readfirstlane(bytes);
-  v.w = 0x00020000u;
-  return v;
+// the LDS-DMA kernels address x and w through 32-bit buffer descriptors
+static inline long long x_bytes(const ConvArgs& a) { return (long long)a.N * a.H * a.W * a.x_cs * 4; }
+static inline long long w_bytes(const ConvArgs& a) { return (long long)a.Cout * a.Kw * 4; }
+static inline bool dma_addressable(const ConvArgs& a) { return desc_addressable(x_bytes(a)) && desc_addressable(w_bytes(a)); }
+
+// the activation of a lane's 16 values behind ONE uniform branch on the activation id (see act_row4, conv_mfma_f32.hip)
+__device__ __forceinline__ void act_row16(float (&v)[16], int act, float slope) {
+  switch (act) {
+    case YV4_ACT_MISH:
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = apply_act(v[e], YV4_ACT_MISH, 0.f);
+      break;
+    case YV4_ACT_LEAKY:
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = v[e] >= 0.f ? v[e] : v[e] * slope;
+      break;
+    case YV4_ACT_SWISH:
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[e] = apply_act(v[e], YV4_ACT_SWISH, 0.f);
+      break;
+    default:
+      break;
+  }
 }
+
+// ---- the kernel families as the dispatcher (conv_mfma_f32.hip) sees them: the domain test and one launch function
+// each, for the wide families also the shape choice (hidden: these cross translation units, not the library's boundary)
+#pragma GCC visibility push(hidden)
+// conv3x3_wide_f32.hip
+bool conv3x3_wide_f32_applies(const ConvArgs& a);
+int conv3x3_wide_f32_pick(const ConvArgs& a, double* rounds_eff);
+int conv3x3_wide_f32_launch(const ConvArgs& a, int shape, hipStream_t s);
+// conv_wide_f32.hip
+bool conv_wide_f32_applies(const ConvArgs& a);
+int conv_wide_f32_pick(const ConvArgs& a, double* rounds_eff);
+int conv_wide_f32_launch(const ConvArgs& a, int shape, hipStream_t s);
+// conv1x1_ws_f32.hip
+int wsf_slab_cols(const ConvArgs& a);
+bool conv1x1_ws_f32_applies(const ConvArgs& a);
+int conv1x1_ws_f32_launch(const ConvArgs& a, hipStream_t s);
+// conv_stem_f32.hip (out_dtype: YV4_F32, or YV4_F16 / YV4_BF16 for the stem of the 16-bit path)
+bool stem_ok(const ConvArgs& a);
+int conv_stem_f32_launch(const ConvArgs& a, int out_dtype, hipStream_t s);
+#pragma GCC visibility pop
 
 }  // namespace yv4

@@ -1,13 +1,14 @@
 // Shared pieces of the 16-bit fused convolution kernels (conv_mfma_h16.hip: the generic implicit-GEMM tiles;
-// conv3x3_h16.hip: the 3x3 / stride-1 kernel that keeps its im2col rows in LDS): argument block, element traits,
-// LDS-DMA helpers and the fused epilogue of one 32x32 accumulator tile.
+// conv3x3_h16.hip: the 3x3 / stride-1 kernel that keeps its im2col rows in LDS): argument block and its fill from a
+// descriptor, the 32-bit-descriptor rule, element traits and the fused epilogue of one 32x32 accumulator tile.
+// (LDS-DMA helpers: lds_dma.h)
 #pragma once
 #include "yv4_common.h"
+#include "lds_dma.h"
 
 namespace yv4 {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -54,20 +55,26 @@ __device__ __forceinline__ int64_t out_row_h(const ConvArgsH& p, int m) {
   return ((int64_t)n * p.ys_H + ho * p.ys_sh + p.ys_oh) * p.ys_W + wo * p.ys_sw + p.ys_ow;
 }
 
-__device__ __forceinline__ void lds_dma16_h(u32x4_t rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory");
+// The argument block of a descriptor and its tensors.  An entry sets what is particular to it afterwards (scattered
+// output, split-K, statistics, nt_out, ablate); the tile choice alone needs no tensors.
+static inline ConvArgsH conv_args_h(const yv4_conv_desc* d, int out_f32, const void* x = nullptr, const void* w = nullptr,
+                             const float* s1 = nullptr, const float* t1 = nullptr, const float* s2 = nullptr,
+                             const float* t2 = nullptr, const void* res = nullptr, void* y = nullptr) {
+  ConvArgsH a{};
+  a.x = x; a.w = w; a.s1 = s1; a.t1 = t1; a.s2 = s2; a.t2 = t2; a.res = res; a.y = y;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
+  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
+  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
+  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
+  a.M = (int)((long long)d->N * d->Ho * d->Wo); a.K = d->KH * d->KW * d->Cin; a.Kw = a.K;
+  a.out_f32 = out_f32;
+  return a;
 }
-__device__ __forceinline__ u32x4_t make_rsrc_h(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  u32x4_t v;
-  v.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  v.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-  v.z = __builtin_amdgcn_readfirstlane(bytes);
-  v.w = 0x00020000u;
-  return v;
+
+// the kernels address x and w through 32-bit buffer descriptors
+static inline bool dma_addressable(const ConvArgsH& a) {
+  return desc_addressable((long long)a.N * a.H * a.W * a.x_cs * 2) && desc_addressable((long long)a.Cout * a.Kw * 2);
 }
 
 template <bool BF16>

@@ -632,8 +632,8 @@ static int launch_conv_dma(const ConvArgs& a, hipStream_t stream) {
     set_error("conv: grid of %lld tiles out of range", tiles);
     return YV4_E_INVALID;
   }
-  const long long xb = (long long)p.N * p.H * p.W * p.x_cs * 4, wb = (long long)p.Cout * p.Kw * 4;
-  if (xb >= 0xFFFFFFF0LL || wb >= 0xFFFFFFF0LL) {
+  const long long xb = x_bytes(p), wb = w_bytes(p);
+  if (!dma_addressable(p)) {
     set_error("conv dma: tensors of 4 GiB or more are not addressable through a buffer descriptor");
     return YV4_E_UNSUPPORTED;
   }
@@ -644,172 +644,6 @@ static int launch_conv_dma(const ConvArgs& a, hipStream_t stream) {
   YV4_CHECK_LAUNCH("conv_mfma_f32_dma");
   return YV4_OK;
 }
-
-
-// ---------------------------------------------------------------------------------
-// Stem: 3x3 / stride 1 / pad 1 convolution of the 3-channel image (stored NHWC with C padded to
-// 4), Cout <= 64.  K = 9 taps x 4 channels = 36 is too shallow for the LDS-staged kernels (they
-// spend their time in prologue/epilogue) and the layer is bound by its own OUTPUT
-// (N*H*W*Cout*4 B = 1.5 GB at batch 32, 608^2, Cout 32), so this kernel keeps everything in
-// registers: a wave owns 32 consecutive pixels of one image row x 32 output channels
-// (one 32x32 MFMA tile), fetches its 9 x 8-byte input taps straight into the MFMA A operand
-// (lane (r,h): pixel r, channels 2h,2h+1 of each tap; out-of-image taps come back as zeros from
-// the buffer descriptor), holds the 18 weight values it needs for the whole kernel, issues
-// 18 MFMAs per tile and streams the epilogue to HBM in 128-byte rows.
-// ---------------------------------------------------------------------------------
-__device__ __forceinline__ void act_row16(float (&v)[16], int act, float slope) {
-  switch (act) {
-    case YV4_ACT_MISH:
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = apply_act(v[e], YV4_ACT_MISH, 0.f);
-      break;
-    case YV4_ACT_LEAKY:
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = v[e] >= 0.f ? v[e] : v[e] * slope;
-      break;
-    case YV4_ACT_SWISH:
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = apply_act(v[e], YV4_ACT_SWISH, 0.f);
-      break;
-    default:
-      break;
-  }
-}
-
-// one value to y[row_base + lane_off]: row_base (elements) is wave-uniform, lane_off a 32-bit per-lane constant
-template <int OUT>
-__device__ __forceinline__ void stem_store(float* y, long long row_base, unsigned lane_off, float v) {
-  if (OUT == 0) (y + row_base)[lane_off] = v;
-  else if (OUT == 1) (reinterpret_cast<_Float16*>(y) + row_base)[lane_off] = (_Float16)v;
-  else (reinterpret_cast<__bf16*>(y) + row_base)[lane_off] = (__bf16)v;
-}
-
-// OUT: 0 fp32 (p.y), 1 fp16, 2 bf16 (p.y reinterpreted; the 16-bit inference path keeps the image
-// and this layer's arithmetic in fp32 and only rounds the layer's output).
-template <int TN, int OUT>
-__global__ __launch_bounds__(kThreads) void conv_stem3x3_kernel(ConvArgs p, unsigned x_bytes, int tiles_w, long long ntiles) {
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int r = lane & 31;
-  const int h = lane >> 5;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, x_bytes, 0x00020000);
-  constexpr unsigned kOOB = 0xFFFFFFF0u;
-
-  // weights: B[k][cout r] with k = (tap, ci = 2h + j)
-  float wv[TN][9][2];
-  float s1[TN], t1[TN];
-#pragma unroll
-  for (int jn = 0; jn < TN; ++jn) {
-    const int co = jn * 32 + r;
-    const bool cok = co < p.Cout;
-    s1[jn] = cok ? p.s1[co] : 0.f;
-    t1[jn] = cok ? p.t1[co] : 0.f;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) wv[jn][tap][j] = cok ? p.w[(size_t)co * p.Kw + tap * 4 + 2 * h + j] : 0.f;
-  }
-
-  // tile walk in wave-uniform 32-bit arithmetic with magic-number divisors (the 64-bit per-lane divides of the
-  // first version were a third of the instructions of a tile)
-  // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2: XCD c walks the c-th eighth of the tile
-  // list with all its waves side by side, so the rows a tile shares with the tiles above and below it (3 input rows
-  // per output row) are fetched by one L2 once instead of by three (measured 3.4x the input before, FETCH_SIZE).
-  const int nblk_all = (int)gridDim.x;
-  const int nch = nblk_all < 8 ? nblk_all : 8;
-  const int chunk = (int)blockIdx.x % nch, local = (int)blockIdx.x / nch;
-  const int nblk = (nblk_all - chunk + nch - 1) / nch;               // workgroups walking this chunk
-  const int cq = (int)ntiles / nch, crem = (int)ntiles % nch;
-  const int t_lo = chunk * cq + (chunk < crem ? chunk : crem);
-  const int t_hi = t_lo + cq + (chunk < crem ? 1 : 0);
-  const int wave_id = __builtin_amdgcn_readfirstlane(local * 4 + (tid >> 6));
-  const int nwaves = nblk * 4;
-  for (int t = t_lo + wave_id; t < t_hi; t += nwaves) {
-    const long long ty = fd_div(t, p.fd_wo);     // n*H + y   (fd_wo: tiles per row, fd_hw: H -- set by launch_conv_stem)
-    const int tx = t - (int)ty * tiles_w;
-    const int y = (int)ty - fd_div((int)ty, p.fd_hw) * p.H;
-    const int x = tx * 32 + r;
-    // byte offset of x[n, y, x, x_co + 2h]
-    const unsigned base = (unsigned)(((ty * p.W + x) * p.x_cs + p.x_co + 2 * h) * 4);
-    u32x2 a[9];
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-      const bool rok = (unsigned)(y + kh - 1) < (unsigned)p.H;
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const bool ok = rok && (unsigned)(x + kw - 1) < (unsigned)p.W;
-        const unsigned off = base + (unsigned)((((kh - 1) * p.W + (kw - 1)) * p.x_cs) * 4);
-        a[kh * 3 + kw] = __builtin_amdgcn_raw_buffer_load_b64(rsA, ok ? off : kOOB, 0, 0);
-      }
-    }
-    f32x16 acc[TN];
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[jn][e] = 0.f;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int jn = 0; jn < TN; ++jn) {
-        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[tap].x), wv[jn][tap][0], acc[jn], 0, 0, 0);
-        acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a[tap].y), wv[jn][tap][1], acc[jn], 0, 0, 0);
-      }
-    // epilogue: lane (r, h) holds channel jn*32 + r of the tile's pixels (e&3) + 8*(e>>2) + 4h.  The row address is
-    // wave-uniform (scalar base + one per-lane offset that never changes), the activation sits behind one uniform
-    // switch and the bounds test is per tile: the per-element form of all three cost 2.7x the 18 MFMAs in VALU time.
-    const long long mrow = ty * p.W + tx * 32;
-    const bool full = tx * 32 + 32 <= p.W;
-#pragma unroll
-    for (int jn = 0; jn < TN; ++jn) {
-      if (jn * 32 + r >= p.Cout) continue;
-      float v[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = acc[jn][e] * s1[jn] + t1[jn];
-      act_row16(v, p.act1, p.slope1);
-      const unsigned lane_off = (unsigned)(4 * h * p.y_cs + jn * 32 + r);
-      if (full) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-          stem_store<OUT>(p.y, (mrow + (e & 3) + 8 * (e >> 2)) * p.y_cs + p.y_co, lane_off, v[e]);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-          if (tx * 32 + (e & 3) + 8 * (e >> 2) + 4 * h < p.W)
-            stem_store<OUT>(p.y, (mrow + (e & 3) + 8 * (e >> 2)) * p.y_cs + p.y_co, lane_off, v[e]);
-      }
-    }
-  }
-}
-
-template <int OUT>
-static int launch_conv_stem(const ConvArgs& a, hipStream_t stream) {
-  const long long xb = (long long)a.N * a.H * a.W * a.x_cs * 4;
-  if (xb >= 0xFFFFFFF0LL) {
-    set_error("conv stem: input of 4 GiB or more is not addressable through a buffer descriptor");
-    return YV4_E_UNSUPPORTED;
-  }
-  const int tiles_w = (a.W + 31) / 32;
-  const long long ntiles = (long long)a.N * a.H * tiles_w;
-  if (ntiles >= (1LL << 31)) {
-    set_error("conv stem: %lld tiles do not fit 31 bits", ntiles);
-    return YV4_E_UNSUPPORTED;
-  }
-  long long blocks = (ntiles + 3) / 4;
-  if (blocks > 256 * 8) blocks = 256 * 8;   // 8 workgroups per CU, grid-stride over the tiles
-  ConvArgs p = a;
-  p.fd_wo = make_fastdiv((unsigned)tiles_w);   // the stem kernel's tile walk: t / tiles_w, (n*H + y) / H
-  p.fd_hw = make_fastdiv((unsigned)a.H);
-  if (a.Cout <= 32)
-    hipLaunchKernelGGL((conv_stem3x3_kernel<1, OUT>), dim3((unsigned)blocks), dim3(kThreads), 0, stream, p, (unsigned)xb,
-                       tiles_w, ntiles);
-  else
-    hipLaunchKernelGGL((conv_stem3x3_kernel<2, OUT>), dim3((unsigned)blocks), dim3(kThreads), 0, stream, p, (unsigned)xb,
-                       tiles_w, ntiles);
-  YV4_CHECK_LAUNCH("conv_stem3x3");
-  return YV4_OK;
-}
-
 
 template <int BM, int BN, int WAVES_M, int WAVES_N>
 static int launch_conv(const ConvArgs& a, bool uniform_tap, hipStream_t stream) {
@@ -837,358 +671,6 @@ static int launch_conv(const ConvArgs& a, bool uniform_tap, hipStream_t stream) 
   return YV4_OK;
 }
 
-// ---- 1x1 / stride 1, weight-stationary and persistent (the fp32 form of conv1x1_ws_h16.hip) ---------------------------
-// The pointwise layers with Cin <= 256 run at 50-57 % of the fp32 matrix peak on the tiles above (profiles/
-// r02_layers.json): a tile's K loop is 2-8 slices, so a workgroup's life is mostly its first-slice latency and its
-// epilogue.  Here one 8-wave workgroup per CU keeps its weight slab (BN x Cin floats, <= 64 KB) in LDS for the whole
-// layer and every wave walks its own strips of 32 pixels with a private 3-stage LDS-DMA ring (stage = 32 pixels x 32
-// channels) that runs on across strips; no barrier after the slab has landed.  The summation order of an output is
-// EXACTLY the tile kernels' (slices of 32 channels in order; inside a slice the MFMA K pairs (8j+i, 8j+4+i), i = 0..3;
-// two accumulator sets alternating with j, added once at the end), so a layer gives the same bits whichever kernel a
-// batch size selects -- the plans' cross-batch bit-exactness (bench.py's output check) holds.
-constexpr int kWsfWaves = 8;
-constexpr int kWsfThreads = kWsfWaves * 64;
-constexpr int kWsfStages = 3;
-constexpr int kWsfStageBytes = 4096;   // 32 pixels x 32 channels x 4 bytes
-constexpr int kWsfGrid = 256;
-
-template <int NT>
-__global__ __launch_bounds__(kWsfThreads, 1) void conv1x1_ws_f32_kernel(ConvArgs p, unsigned x_bytes, unsigned w_bytes, int ncol,
-                                                                        int nstrips, int cpr_shift) {
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  constexpr int BN = NT * 32;
-  constexpr unsigned kOOB = 0xFFFFFFF0u;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  char* smem_c = reinterpret_cast<char*>(smem);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31;
-  const int h = lane >> 5;
-#ifdef YV4_MEASURE
-  // YV4_WSF_STAMP=1 (bit 8 of cpr_shift): cycles per wave in [1] the counted wait for a stage, [2] fragment reads + MFMAs +
-  // the stage's DMA pieces, [3] epilogue up to its vmcnt(0), [4] rest of the epilogue; printed by two workgroups
-  const bool stamp_on = (cpr_shift & 256) != 0;
-  // YV4_WSF_ABL (wrong results on purpose): 1 a quarter of the output stores, 2 no stage DMAs, 4 no MFMAs, 8 no epilogue,
-  // 16 stage DMAs issued but out of range (zero fill, nothing fetched)
-  const bool few_stores = (cpr_shift & 512) != 0;
-  const bool abl_nodma = (cpr_shift & 1024) != 0, abl_nomfma = (cpr_shift & 2048) != 0, abl_noepi = (cpr_shift & 4096) != 0;
-  const bool abl_oob = (cpr_shift & 8192) != 0;
-  cpr_shift &= 255;
-  unsigned long long tsum[5] = {0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-  const unsigned long long tbegin = tlast;
-#define YV4_WSF_STAMP(SLOT) if (stamp_on) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); tsum[SLOT] += n_ - tlast; tlast = n_; }
-#define YV4_WSF_OOB abl_oob
-#define YV4_WSF_NODMA abl_nodma
-#define YV4_WSF_NOMFMA abl_nomfma
-#else
-#define YV4_WSF_STAMP(SLOT)
-#define YV4_WSF_OOB false
-#define YV4_WSF_NODMA false
-#define YV4_WSF_NOMFMA false
-#endif
-  const int kc_n = p.Cin >> 5;          // 32-channel stages per strip
-  const int cpr = 1 << cpr_shift;       // 16-byte chunks per weight row (Cin / 4 >= 16)
-  const int wpitch = p.Cin * 4;
-
-  char* Ws = smem_c;
-  char* ring = smem_c + BN * wpitch + wave * (kWsfStages * kWsfStageBytes);
-  const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem;
-  const unsigned ring_lds = lds_base + (unsigned)(BN * wpitch + wave * (kWsfStages * kWsfStageBytes));
-
-  const unsigned b = blockIdx.x;
-  const int xcd = (int)(b & 7u), local = (int)(b >> 3);
-  const int col = local % ncol;
-  const int walker = (local / ncol) * 8 + xcd;
-  const int nwalkers = ((int)(gridDim.x >> 3) / ncol) * 8;
-  const int NW = nwalkers * kWsfWaves;
-  const int gw = walker * kWsfWaves + wave;
-  const int n0 = col * BN;
-
-  const u32x4_t rsA = make_rsrc(p.x, x_bytes);
-  const u32x4_t rsB = make_rsrc(p.w, w_bytes);
-
-  // the weight slab, once: rows of Cin floats, 16-byte chunks XOR-swizzled with row & 15
-  {
-    const int groups = (BN * cpr) >> 6;
-    for (int g = wave; g < groups; g += kWsfWaves) {
-      const int c = g * 64 + lane;
-      const int row = c >> cpr_shift;
-      const int pch = c & (cpr - 1);
-      const int co = n0 + row;
-      const unsigned voff = co < p.Cout ? (unsigned)(((int64_t)co * p.Kw + (pch ^ (row & 15)) * 4) * 4) : kOOB;
-      lds_dma16(rsB, lds_base + (unsigned)(g * 1024), voff, 0u);
-    }
-  }
-
-  float s1[NT], t1[NT], s2[NT], t2[NT];
-  const bool has2 = p.s2 != nullptr;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int c = n0 + t * 32 + r;
-    const bool ok = c < p.Cout;
-    s1[t] = ok ? p.s1[c] : 0.f;
-    t1[t] = ok ? p.t1[c] : 0.f;
-    s2[t] = (ok && has2) ? p.s2[c] : 1.f;
-    t2[t] = (ok && has2) ? p.t2[c] : 0.f;
-  }
-
-  const unsigned a_rd = (unsigned)(r * 128 + ((h ^ ((r >> 1) & 7)) << 4));
-  unsigned w_rd[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int row = t * 32 + r;
-    w_rd[t] = (unsigned)(row * wpitch + ((h ^ (row & 15)) << 4));
-  }
-
-  const int my_n = gw < nstrips ? (nstrips - gw + NW - 1) / NW : 0;
-  const int lrow = lane >> 3;
-  const unsigned lch_even = (unsigned)(((lane & 7) ^ ((lane >> 4) & 7)) * 4);
-  const unsigned lch_odd = (unsigned)(((lane & 7) ^ (((lane >> 4) + 4) & 7)) * 4);
-  // Issue side: the stage DMAs of a strip start at per-lane offsets that are computed once per strip (iss_voff: rows
-  // 8 j + lrow, chunk swizzled by row); the stage adds its 128 bytes through the scalar offset.  In the loop the four
-  // 1 KB pieces of stage kc + 2 are issued one per j step BETWEEN the wave's own MFMAs, where a piece's issue cost
-  // (~60-180 cycles, MI355X_MICROARCH.md) runs under the MFMA in flight; issued in one block at the top of the stage
-  // they were 1.0-1.4 k cycles per stage that only the partner wave's MFMAs could cover (stamps: DESIGN 12.9).
-  int iss_i = 0, iss_kc = 0, iss_slot = 0;
-  unsigned iss_voff[4];
-#define YV4_WSF_ISSUE_STRIP()                                                                               \
-  {                                                                                                         \
-    const int row0_ = (gw + iss_i * NW) * 32 + lrow;                                                        \
-    const bool live_ = iss_i < my_n && !YV4_WSF_OOB;                                                        \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                         \
-      const int row_ = row0_ + 8 * j;                                                                       \
-      const unsigned lch_ = (j & 1) ? lch_odd : lch_even;                                                   \
-      iss_voff[j] = (live_ && row_ < p.M) ? (unsigned)(((int64_t)row_ * p.x_cs + p.x_co + (int)lch_) * 4) : kOOB; \
-    }                                                                                                       \
-  }
-#define YV4_WSF_ISSUE_PIECE(J)                                                                              \
-  if (!YV4_WSF_NODMA)                                                                                       \
-    lds_dma16(rsA, ring_lds + (unsigned)(iss_slot * kWsfStageBytes + (J) * 1024), iss_voff[J], (unsigned)(iss_kc << 7));
-#define YV4_WSF_ISSUE_ADVANCE()                                                                             \
-  {                                                                                                         \
-    iss_kc += 1;                                                                                            \
-    if (iss_kc == kc_n) {                                                                                   \
-      iss_kc = 0;                                                                                           \
-      iss_i += 1;                                                                                           \
-      YV4_WSF_ISSUE_STRIP();                                                                                \
-    }                                                                                                       \
-    iss_slot = iss_slot + 1 == kWsfStages ? 0 : iss_slot + 1;                                               \
-  }
-#define YV4_WSF_ISSUE()                                                                                     \
-  {                                                                                                         \
-    YV4_WSF_ISSUE_PIECE(0) YV4_WSF_ISSUE_PIECE(1) YV4_WSF_ISSUE_PIECE(2) YV4_WSF_ISSUE_PIECE(3)             \
-    YV4_WSF_ISSUE_ADVANCE();                                                                                \
-  }
-
-  YV4_WSF_ISSUE_STRIP();
-  YV4_WSF_ISSUE();
-  YV4_WSF_ISSUE();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  float st_su[NT], st_sq[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) { st_su[t] = 0.f; st_sq[t] = 0.f; }
-
-  int rslot = 0;
-  for (int i = 0; i < my_n; ++i) {
-    f32x16 acc[NT], acc2[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { acc[t][e] = 0.f; acc2[t][e] = 0.f; }
-
-    for (int kc = 0; kc < kc_n; ++kc) {
-      YV4_WSF_STAMP(4);
-      // stages 0 and 1 of a strip were confirmed in front of the previous strip's stores; later ones by count: only the
-      // four pieces of stage kc + 1 (issued during stage kc - 1) may still be in flight (see conv1x1_ws_h16.hip)
-      if (kc >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      YV4_WSF_STAMP(1);
-      const char* st = ring + rslot * kWsfStageBytes;
-      const unsigned kx = (unsigned)(kc << 7);               // (kc * 8) << 4: chunk index inside the weight row
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (YV4_WSF_NOMFMA) { YV4_WSF_ISSUE_PIECE(j) continue; }
-        const float4 fa = *reinterpret_cast<const float4*>(st + (a_rd ^ (unsigned)(j << 5)));
-        float4 fb[NT];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) fb[t] = *reinterpret_cast<const float4*>(Ws + ((w_rd[t] ^ (unsigned)(j << 5)) ^ kx));
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          f32x16& ac_ = (j & 1) ? acc2[t] : acc[t];
-          ac_ = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.x, fb[t].x, ac_, 0, 0, 0);
-          ac_ = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.y, fb[t].y, ac_, 0, 0, 0);
-          ac_ = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.z, fb[t].z, ac_, 0, 0, 0);
-          ac_ = __builtin_amdgcn_mfma_f32_32x32x2f32(fa.w, fb[t].w, ac_, 0, 0, 0);
-          if (t == 0) {                      // piece j of stage kc + 2, under the MFMA just issued
-            __builtin_amdgcn_sched_barrier(0);
-            YV4_WSF_ISSUE_PIECE(j)
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      YV4_WSF_ISSUE_ADVANCE();
-      rslot = rslot + 1 == kWsfStages ? 0 : rslot + 1;
-      YV4_WSF_STAMP(2);
-    }
-
-    // epilogue: lane (r, h) holds channel n0 + 32t + r of pixels m0 + (e&3) + 8(e>>2) + 4h; the arithmetic is
-    // epilogue_tile's, operation for operation
-    const int m0 = (gw + i * NW) * 32;
-    const bool full = m0 + 32 <= p.M;
-#ifdef YV4_MEASURE
-    if (abl_noepi) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (acc[0][0] == 12345.678f) p.y[0] = acc[NT - 1][3] + acc2[0][1];
-      continue;
-    }
-#endif
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int c = n0 + t * 32 + r;
-      if (c >= p.Cout) continue;
-      float v[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = acc[t][e] + acc2[t][e];
-      if (p.stats) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const bool in = full || (m0 + (e & 3) + 8 * (e >> 2) + 4 * h < p.M);
-          st_su[t] += in ? v[e] : 0.f;
-          st_sq[t] += in ? v[e] * v[e] : 0.f;
-        }
-      }
-#pragma unroll
-      for (int e = 0; e < 16; ++e) v[e] = __builtin_fmaf(v[e], s1[t], t1[t]);     // epilogue_tile's a * s + t is an fma
-      act_row16(v, p.act1, p.slope1);
-      if (has2) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) v[e] = __builtin_fmaf(v[e], s2[t], t2[t]);
-        act_row16(v, p.act2, p.slope2);
-      }
-      float* yb = p.y + ((int64_t)(m0 + 4 * h) * p.y_cs + p.y_co + c);
-      if (t == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stages in flight, before the stores join the counter
-      if (t == 0) { YV4_WSF_STAMP(3); }
-#ifdef YV4_MEASURE
-      if (few_stores) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) yb[(int64_t)((e & 3) + 8 * (e >> 2)) * p.y_cs] = v[e] + v[e + 4] + v[e + 8] + v[e + 12];
-      } else
-#endif
-      if (full) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) yb[(int64_t)((e & 3) + 8 * (e >> 2)) * p.y_cs] = v[e];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-          if (m0 + (e & 3) + 8 * (e >> 2) + 4 * h < p.M) yb[(int64_t)((e & 3) + 8 * (e >> 2)) * p.y_cs] = v[e];
-      }
-    }
-  }
-#undef YV4_WSF_ISSUE
-#undef YV4_WSF_ISSUE_PIECE
-#undef YV4_WSF_ISSUE_ADVANCE
-#undef YV4_WSF_ISSUE_STRIP
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tail's out-of-range stage DMAs still write this wave's ring
-#ifdef YV4_MEASURE
-  YV4_WSF_STAMP(4);
-  if (stamp_on && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 101))
-    printf("wsf wg %d wave %d strips %d: total %llu | issue %llu wait %llu reads+mfma %llu epi-to-vmcnt0 %llu epi-rest %llu (cycles)\n",
-           (int)blockIdx.x, wave, my_n, __builtin_amdgcn_s_memtime() - tbegin, tsum[0], tsum[1], tsum[2], tsum[3], tsum[4]);
-#endif
-#undef YV4_WSF_STAMP
-#undef YV4_WSF_OOB
-#undef YV4_WSF_NODMA
-#undef YV4_WSF_NOMFMA
-
-  if (p.stats && my_n > 0) {
-    const StatRep rep = stat_rep(p.stats, (unsigned)(gw), p.Cout);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      float su = st_su[t], sq = st_sq[t];
-      su += __shfl_xor(su, 32);
-      sq += __shfl_xor(sq, 32);
-      const int c = n0 + t * 32 + r;
-      if (h == 0 && c < p.Cout) {
-        stat_add(rep, c, su);
-        stat_add(rep, p.Cout + c, sq);
-      }
-    }
-  }
-}
-
-static int wsf_slab_cols(const ConvArgs& a) {
-  const int cout32 = (a.Cout + 31) / 32 * 32;
-  for (int bn = 128; bn >= 32; bn >>= 1) {
-    if (bn > cout32) continue;
-    if ((long long)bn * a.Cin * 4 + kWsfWaves * kWsfStages * kWsfStageBytes > 160 * 1024) continue;
-    const int ncol = (a.Cout + bn - 1) / bn;
-    if (32 % ncol != 0) continue;
-    return bn;
-  }
-  return 0;
-}
-
-static bool conv1x1_ws_f32_applies(const ConvArgs& a) {
-  return a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && !a.ys_on && a.res == nullptr && a.ksplit <= 1 &&
-         (a.Cin == 64 || a.Cin == 128 || a.Cin == 256) && a.Kw == a.Cin && a.Cout >= 32 && wsf_slab_cols(a) > 0;
-}
-
-template <int NT>
-static int launch_wsf(const ConvArgs& a, hipStream_t stream) {
-  constexpr int BN = NT * 32;
-  const int ncol = (a.Cout + BN - 1) / BN;
-  const size_t lds = (size_t)BN * a.Cin * 4 + (size_t)kWsfWaves * kWsfStages * kWsfStageBytes;
-  const int nstrips = (a.M + 31) / 32;
-  int cpr_shift = 0;
-  while ((4 << cpr_shift) < a.Cin) ++cpr_shift;
-  const long long xb = (long long)a.N * a.H * a.W * a.x_cs * 4, wb = (long long)a.Cout * a.Kw * 4;
-  auto kern = conv1x1_ws_f32_kernel<NT>;
-  static LdsAttrOnce once;
-  if (int rc = ensure_dyn_lds(once, reinterpret_cast<const void*>(kern), 160 * 1024, "conv1x1_ws_f32")) return rc;
-#ifdef YV4_MEASURE
-  static const int stamp = YV4_ENV_INT("YV4_WSF_STAMP", 0);
-  if (stamp) cpr_shift |= 256;
-  static const int abl = YV4_ENV_INT("YV4_WSF_ABL", 0);
-  cpr_shift |= (abl & 31) << 9;
-#endif
-  hipLaunchKernelGGL(kern, dim3(kWsfGrid), dim3(kWsfThreads), lds, stream, a, (unsigned)xb, (unsigned)wb, ncol, nstrips,
-                     cpr_shift);
-  YV4_CHECK_LAUNCH("conv1x1_ws_f32");
-  return YV4_OK;
-}
-
-static int conv1x1_ws_f32_launch(const ConvArgs& a, hipStream_t s) {
-  switch (wsf_slab_cols(a)) {
-    case 128: return launch_wsf<4>(a, s);
-    case 64: return launch_wsf<2>(a, s);
-    case 32: return launch_wsf<1>(a, s);
-    default: break;
-  }
-  set_error("conv1x1 ws f32: no weight slab of this layer fits the LDS");
-  return YV4_E_UNSUPPORTED;
-}
-
-// the pointwise layers in the kernel's domain that give each persistent wave at least YV4_WS_MINSTRIPS strips
-static bool prefer_ws_f32(const ConvArgs& a) {
-  static const int mode = YV4_ENV_INT("YV4_WS", 1);
-  static const int min_strips = YV4_ENV_INT("YV4_WS_MINSTRIPS", 2);
-  if (!mode || !conv1x1_ws_f32_applies(a)) return false;
-  // strips per persistent wave: the 256 workgroups are dealt over the column slabs, 8 waves each (with the DMA pieces
-  // issued under the MFMAs the kernel beats the 128x64 tile on 256 -> 256 @38 too: 62 against 67 us, tools/ab_wsf.sh)
-  const int bn = wsf_slab_cols(a);
-  const long long ncol = (a.Cout + bn - 1) / bn;
-  return (((long long)a.M + 31) / 32) * ncol >= (long long)min_strips * 2048;
-}
-
-static bool stem_ok(const yv4_conv_desc* d, bool has_res, bool has2) {
-  return d->Cin == 4 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->Cout <= 64 && !has_res &&
-         !has2 && d->x_coff % 2 == 0 && (long long)d->N * d->H * d->W * d->x_cstride * 4 < 0xFFFFFFF0LL;
-}
-
 static int pick_tile(long long M, int Cout, bool fast_ok, long long K = 0) {
   // Static choice for callers that do not autotune (training; Plan.autotune re-decides per layer on the box it runs
   // on).  From profiles/r01_conv_shapes.txt (batch 32 YOLOv4-L shapes): deep reductions with several rounds of
@@ -1213,25 +695,17 @@ static int pick_tile(long long M, int Cout, bool fast_ok, long long K = 0) {
   return YV4_TILE_64x64;  // Cout <= 32: half of the columns idle; stem / tiny models only
 }
 
-}  // namespace yv4
-
-using namespace yv4;
-
-extern "C" double yv4_conv_flops(const yv4_conv_desc* d) {
-  if (!d) return 0.0;
-  return 2.0 * (double)d->N * d->Ho * d->Wo * d->Cout * (double)d->KH * d->KW * d->Cin;
+// the pointwise layers in the kernel's domain that give each persistent wave at least YV4_WS_MINSTRIPS strips
+static bool prefer_ws_f32(const ConvArgs& a) {
+  static const int mode = YV4_ENV_INT("YV4_WS", 1);
+  static const int min_strips = YV4_ENV_INT("YV4_WS_MINSTRIPS", 2);
+  if (!mode || !conv1x1_ws_f32_applies(a)) return false;
+  // strips per persistent wave: the 256 workgroups are dealt over the column slabs, 8 waves each (with the DMA pieces
+  // issued under the MFMAs the kernel beats the 128x64 tile on 256 -> 256 @38 too: 62 against 67 us, tools/ab_wsf.sh)
+  const int bn = wsf_slab_cols(a);
+  const long long ncol = (a.Cout + bn - 1) / bn;
+  return (((long long)a.M + 31) / 32) * ncol >= (long long)min_strips * 2048;
 }
-
-namespace yv4 {
-// conv3x3_wide_f32.hip
-bool conv3x3_wide_f32_applies(const ConvArgs& a);
-int conv3x3_wide_f32_pick(const ConvArgs& a, double* rounds_eff);
-int conv3x3_wide_f32_launch(const ConvArgs& a, int shape, hipStream_t s);
-
-// conv_wide_f32.hip
-bool conv_wide_f32_applies(const ConvArgs& a);
-int conv_wide_f32_pick(const ConvArgs& a, double* rounds_eff);
-int conv_wide_f32_launch(const ConvArgs& a, int shape, hipStream_t s);
 
 // The wide-tile fp32 3x3 kernel takes the layers in its domain with >= 64 input channels and at least YV4_W3F_MINOUT
 // outputs per CU when one of its tile shapes fills the rounds to within YV4_W3F_MAXWASTE percent (YV4_W3F=0: off).
@@ -1267,26 +741,42 @@ static int prefer_wide_f32(const ConvArgs& a) {    // the shape index, or -1
   if (shape < 0 || eff * 100.0 > 100.0 + waste) return -1;
   return shape;
 }
+
+static bool fast_ok(const ConvArgs& a) { return a.Cin % kBK == 0 && dma_addressable(a); }
+
+// What the AUTO path launches: the family as its tile id and, for the two wide families, the shape index (else -1).
+// conv_f32_impl launches it and yv4_conv_pick_tile reports it: a plan, the benchmark's output check and the tests
+// read the latter to learn the former.
+struct Route { int tile, shape; };
+static Route auto_route(const ConvArgs& a) {
+  const bool fast = fast_ok(a);
+  if (fast) {
+    const int w3 = prefer_w3_f32(a);
+    if (w3 >= 0) return {YV4_TILE_W3x3, w3};
+    if (prefer_ws_f32(a)) return {YV4_TILE_WS_1x1, -1};
+    const int wg = prefer_wide_f32(a);
+    if (wg >= 0) return {YV4_TILE_WIDE, wg};
+  }
+  if (stem_ok(a)) return {YV4_TILE_STEM, -1};
+  return {pick_tile(a.M, a.Cout, fast, a.K), -1};
+}
+
 }  // namespace yv4
 
+using namespace yv4;
+
+extern "C" double yv4_conv_flops(const yv4_conv_desc* d) {
+  if (!d) return 0.0;
+  return 2.0 * (double)d->N * d->Ho * d->Wo * d->Cout * (double)d->KH * d->KW * d->Cin;
+}
+
+// (a residual or a second affine, unknown here, keeps the tile kernels)
 extern "C" int yv4_conv_pick_tile(const yv4_conv_desc* d) {
   if (!d) return YV4_TILE_AUTO;
-  const bool fast_ok = d->Cin % kBK == 0 && (long long)d->N * d->H * d->W * d->x_cstride * 4 < 0xFFFFFFF0LL &&
-                       (long long)d->Cout * d->KH * d->KW * d->Cin * 4 < 0xFFFFFFF0LL;
-  if (stem_ok(d, false, false)) return YV4_TILE_STEM;
-  {
-    ConvArgs a{};
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.Cin = d->Cin; a.Cout = d->Cout;
-    a.K = a.Kw = d->KH * d->KW * d->Cin; a.M = (int)((long long)d->N * d->Ho * d->Wo);
-    if (fast_ok && prefer_ws_f32(a)) return YV4_TILE_WS_1x1;     // (a residual, unknown here, keeps the tile kernels)
-    a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
-    a.r_cs = d->r_cstride; a.r_co = d->r_coff; a.ys_on = 0;
-    const int w3 = fast_ok ? prefer_w3_f32(a) : -1;
-    if (w3 >= 0) return YV4_TILE_W3x3_SHAPE(w3);                  // the pinned form: a plan can copy it (see include/yv4.h)
-    const int wg = fast_ok ? prefer_wide_f32(a) : -1;             // (a residual, unknown here, keeps the tile kernels)
-    if (wg >= 0) return YV4_TILE_WIDE_SHAPE(wg);
-  }
-  return pick_tile((long long)d->N * d->Ho * d->Wo, d->Cout, fast_ok, (long long)d->KH * d->KW * d->Cin);
+  const Route r = auto_route(conv_args(d));
+  if (r.tile == YV4_TILE_W3x3) return YV4_TILE_W3x3_SHAPE(r.shape);   // the pinned form: a plan can copy it (see include/yv4.h)
+  if (r.tile == YV4_TILE_WIDE) return YV4_TILE_WIDE_SHAPE(r.shape);
+  return r.tile;
 }
 
 // stats != null: identity-epilogue conv that also accumulates the BatchNorm sums of its output; *stats_done tells
@@ -1317,59 +807,44 @@ static int conv_f32_impl(const yv4_conv_desc* d, const float* x, const float* w,
   YV4_REQUIRE(M < (1LL << 31), "conv: N*Ho*Wo = %lld does not fit 31 bits", M);
   YV4_REQUIRE((long long)d->N * d->H * d->W < (1LL << 31), "conv: N*H*W does not fit 31 bits");
 
-  ConvArgs a;
-  a.x = x; a.w = w; a.s1 = scale1; a.t1 = shift1; a.s2 = scale2; a.t2 = shift2;
-  a.res = residual; a.y = y;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
-  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
-  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
-  a.M = (int)M; a.K = d->KH * d->KW * d->Cin; a.Kw = a.K; a.tiles_n = 0;
-  a.ys_on = 0;
-  a.stats = nullptr;
-  a.ksplit = 0; a.ks_slices = 0; a.ws_cs = 0; a.ws = nullptr;
-
+  ConvArgs a = conv_args(d, x, w, scale1, shift1, scale2, shift2, residual, y);
   const bool uniform = (d->Cin % kBK) == 0;
-  // the LDS-DMA kernels address x and w through 32-bit buffer descriptors
-  const bool fast_ok = uniform && (long long)d->N * d->H * d->W * d->x_cstride * 4 < 0xFFFFFFF0LL &&
-                       (long long)d->Cout * a.K * 4 < 0xFFFFFFF0LL;
-  const bool can_stem = stem_ok(d, residual != nullptr, scale2 != nullptr);
+  const bool fast = fast_ok(a);
+  const bool can_stem = stem_ok(a);
+  const Route route = d->tile == YV4_TILE_AUTO ? auto_route(a) : Route{d->tile, -1};
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (stats_done) *stats_done = false;
   {
     const int forced = (d->tile > 16 && (d->tile & 15) == YV4_TILE_W3x3 && d->tile <= YV4_TILE_W3x3_SHAPE(4)) ? (d->tile >> 4) - 1 : -1;
     if (d->tile == YV4_TILE_W3x3 || forced >= 0)
-      YV4_REQUIRE(fast_ok && conv3x3_wide_f32_applies(a), "conv: the wide 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with "
+      YV4_REQUIRE(fast && conv3x3_wide_f32_applies(a), "conv: the wide 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with "
                   "Cin %% 32 == 0, Cout %% 16 == 0 (64 .. 1024) and 4-aligned channel strides / offsets");
-    const int autoshape = (d->tile == YV4_TILE_AUTO && fast_ok) ? prefer_w3_f32(a) : -1;
-    if (d->tile == YV4_TILE_W3x3 || forced >= 0 || autoshape >= 0) {
+    if (route.tile == YV4_TILE_W3x3 || forced >= 0) {
       if (stats) { a.stats = stats; *stats_done = true; }
       static const int env_shape = YV4_ENV_INT("YV4_W3F_SHAPE", -1);
-      return conv3x3_wide_f32_launch(a, forced >= 0 ? forced : (autoshape >= 0 && env_shape < 0 ? autoshape : env_shape), s);
+      return conv3x3_wide_f32_launch(a, forced >= 0 ? forced : (route.shape >= 0 && env_shape < 0 ? route.shape : env_shape), s);
     }
   }
   {
     const int forced = (d->tile > 16 && (d->tile & 15) == YV4_TILE_WIDE && d->tile <= YV4_TILE_WIDE_SHAPE(4)) ? (d->tile >> 4) - 1 : -1;
     if (d->tile == YV4_TILE_WIDE || forced >= 0)
-      YV4_REQUIRE(fast_ok && conv_wide_f32_applies(a), "conv: the wide tile needs Cin %% 32 == 0, Cout %% 16 == 0 (64 .. 2048) and "
+      YV4_REQUIRE(fast && conv_wide_f32_applies(a), "conv: the wide tile needs Cin %% 32 == 0, Cout %% 16 == 0 (64 .. 2048) and "
                   "4-aligned channel strides / offsets");
-    const int autoshape = (d->tile == YV4_TILE_AUTO && fast_ok && !(prefer_ws_f32(a) && conv1x1_ws_f32_applies(a))) ? prefer_wide_f32(a) : -1;
-    if (d->tile == YV4_TILE_WIDE || forced >= 0 || autoshape >= 0) {
+    if (route.tile == YV4_TILE_WIDE || forced >= 0) {
       if (stats) { a.stats = stats; *stats_done = true; }
       static const int env_shape = YV4_ENV_INT("YV4_WGF_SHAPE", -1);
-      return conv_wide_f32_launch(a, forced >= 0 ? forced : (autoshape >= 0 && env_shape < 0 ? autoshape : env_shape), s);
+      return conv_wide_f32_launch(a, forced >= 0 ? forced : (route.shape >= 0 && env_shape < 0 ? route.shape : env_shape), s);
     }
   }
   if (d->tile == YV4_TILE_WS_1x1)
-    YV4_REQUIRE(fast_ok && conv1x1_ws_f32_applies(a), "conv: the weight-stationary tile needs a 1x1 / stride 1 conv with Cin 64, "
+    YV4_REQUIRE(fast && conv1x1_ws_f32_applies(a), "conv: the weight-stationary tile needs a 1x1 / stride 1 conv with Cin 64, "
                 "128 or 256, Cout >= 32 and no residual");
-  if (d->tile == YV4_TILE_WS_1x1 || (d->tile == YV4_TILE_AUTO && fast_ok && prefer_ws_f32(a))) {
+  if (route.tile == YV4_TILE_WS_1x1) {
     if (stats) { a.stats = stats; *stats_done = true; }
     return conv1x1_ws_f32_launch(a, s);
   }
-  int tile = d->tile == YV4_TILE_AUTO ? (can_stem ? YV4_TILE_STEM : pick_tile(M, d->Cout, fast_ok, a.K)) : d->tile;
-  if (stats && fast_ok && (tile == YV4_TILE_DMA_64x64 || tile == YV4_TILE_DMA_128x64 || tile == YV4_TILE_DMA_128x128)) {
+  const int tile = route.tile;
+  if (stats && fast && (tile == YV4_TILE_DMA_64x64 || tile == YV4_TILE_DMA_128x64 || tile == YV4_TILE_DMA_128x128)) {
     a.stats = stats;
     *stats_done = true;
   }
@@ -1378,10 +853,10 @@ static int conv_f32_impl(const yv4_conv_desc* d, const float* x, const float* w,
     case YV4_TILE_128x64: return launch_conv<128, 64, 2, 2>(a, uniform, s);
     case YV4_TILE_64x128: return launch_conv<64, 128, 2, 2>(a, uniform, s);
     case YV4_TILE_64x64: return launch_conv<64, 64, 2, 2>(a, uniform, s);
-    case YV4_TILE_STEM: if (can_stem) return launch_conv_stem<0>(a, s); break;
-    case YV4_TILE_DMA_64x64: if (fast_ok) return launch_conv_dma<64, 64, 2, 2, 2>(a, s); break;
-    case YV4_TILE_DMA_128x64: if (fast_ok) return launch_conv_dma<128, 64, 2, 2, 2>(a, s); break;
-    case YV4_TILE_DMA_128x128: if (fast_ok) return launch_conv_dma<128, 128, 2, 2, 2>(a, s); break;
+    case YV4_TILE_STEM: if (can_stem) return conv_stem_f32_launch(a, YV4_F32, s); break;
+    case YV4_TILE_DMA_64x64: if (fast) return launch_conv_dma<64, 64, 2, 2, 2>(a, s); break;
+    case YV4_TILE_DMA_128x64: if (fast) return launch_conv_dma<128, 64, 2, 2, 2>(a, s); break;
+    case YV4_TILE_DMA_128x128: if (fast) return launch_conv_dma<128, 128, 2, 2, 2>(a, s); break;
     default:
       break;
   }
@@ -1435,12 +910,11 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs p) {
 // per split; 1 = do not split (enough tiles already, or a kernel without the split path)
 static int splitk_choice(const yv4_conv_desc* d, int* tile_out) {
   const long long M = (long long)d->N * d->Ho * d->Wo;
-  const int K = d->KH * d->KW * d->Cin;
-  if (d->Cin % kBK != 0 || stem_ok(d, false, false)) return 1;
-  if ((long long)d->N * d->H * d->W * d->x_cstride * 4 >= 0xFFFFFFF0LL || (long long)d->Cout * K * 4 >= 0xFFFFFFF0LL) return 1;
+  const ConvArgs a = conv_args(d);
+  if (!fast_ok(a)) return 1;
   const int tile = YV4_TILE_DMA_64x64;
   const long long tiles = ((M + 63) / 64) * ((d->Cout + 63) / 64);
-  const int nk = K / kBK;
+  const int nk = a.K / kBK;
   static const long long target = (long long)YV4_ENV_INT("YV4_SPLITK_TARGET", (int)(512LL));
   static const int min_slices = YV4_ENV_INT("YV4_SPLITK_MINSL", 8);
   int ks = 1;
@@ -1479,14 +953,7 @@ extern "C" int yv4_conv_bn_act_fwd_splitk(const yv4_conv_desc* d, const float* x
   YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH && d->act2 >= 0 && d->act2 <= YV4_ACT_SWISH, "conv splitk: activation id");
   YV4_REQUIRE(workspace_bytes >= yv4_conv_splitk_workspace(d, nullptr), "conv splitk: workspace too small");
   const long long M = (long long)d->N * d->Ho * d->Wo;
-  ConvArgs a;
-  a.x = x; a.w = w; a.s1 = scale1; a.t1 = shift1; a.s2 = scale2; a.t2 = shift2; a.res = residual; a.y = y;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
-  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
-  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
-  a.M = (int)M; a.K = d->KH * d->KW * d->Cin; a.Kw = a.K; a.tiles_n = 0; a.ys_on = 0; a.stats = nullptr;
+  ConvArgs a = conv_args(d, x, w, scale1, shift1, scale2, shift2, residual, y);
   const int nk = a.K / kBK;
   a.ks_slices = (nk + ks - 1) / ks;
   a.ksplit = (nk + a.ks_slices - 1) / a.ks_slices;      // no empty split
@@ -1500,11 +967,6 @@ extern "C" int yv4_conv_bn_act_fwd_splitk(const yv4_conv_desc* d, const float* x
   YV4_CHECK_LAUNCH("conv splitk finish");
   return YV4_OK;
 }
-
-int conv_stats_h16(const yv4_conv_desc* d, int dtype, const void* x, const void* w, const float* ones, const float* zeros,
-                   void* y, double* stats, void* stream);
-int bn_partial_sums_replica0(const void* x, int dtype, int64_t M, int C, int x_cstride, int x_coff, double* stats,
-                             void* stream);   // bn_train.hip
 
 // Training-mode convolution feeding a BatchNorm: y = conv(x, w) (identity epilogue, `ones` / `zeros` = Cout unit
 // scales / zero shifts) and the per-channel sums of y for the batch statistics, accumulated by the conv kernel's
@@ -1533,35 +995,6 @@ extern "C" int yv4_conv_fwd_stats(const yv4_conv_desc* d, int dtype, const void*
   return bn_partial_sums_replica0(y, YV4_F32, (int64_t)d->N * d->Ho * d->Wo, d->Cout, d->y_cstride, d->y_coff, stats, stream);
 }
 
-// The stem of the 16-bit path: fp32 image (NHWC, C padded to 4) and fp32 weights in, fp32 MFMA,
-// output rounded to fp16 / bf16 (the layer is bound by its output bytes, which this halves).
-extern "C" int yv4_conv_stem_fwd(const yv4_conv_desc* d, const float* x, const float* w, const float* scale1,
-                                 const float* shift1, void* y, int out_dtype, void* stream) {
-  YV4_REQUIRE(d && x && w && scale1 && shift1 && y, "conv stem: null argument");
-  YV4_REQUIRE(out_dtype == YV4_F32 || out_dtype == YV4_F16 || out_dtype == YV4_BF16, "conv stem: bad out_dtype");
-  YV4_REQUIRE(stem_ok(d, false, false), "conv stem: needs Cin 4 (3 padded), 3x3, stride 1, pad 1, Cout <= 64");
-  YV4_REQUIRE(d->Ho == d->H && d->Wo == d->W, "conv stem: Ho/Wo must equal H/W");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride && d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride,
-              "conv stem: view exceeds its pixel stride");
-  YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH, "conv stem: unknown activation id");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  YV4_REQUIRE(M < (1LL << 31), "conv stem: N*Ho*Wo does not fit 31 bits");
-  ConvArgs a;
-  a.x = x; a.w = w; a.s1 = scale1; a.t1 = shift1; a.s2 = nullptr; a.t2 = nullptr; a.res = nullptr;
-  a.stats = nullptr;
-  a.y = reinterpret_cast<float*>(y);
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = 3; a.KW = 3; a.stride = 1; a.pad = 1;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff; a.r_cs = 0; a.r_co = 0;
-  a.act1 = d->act1; a.act2 = 0; a.slope1 = d->slope1; a.slope2 = 0.f;
-  a.M = (int)M; a.K = 36; a.Kw = 36; a.tiles_n = 0;
-  a.ys_on = 0;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (out_dtype == YV4_F16) return launch_conv_stem<1>(a, s);
-  if (out_dtype == YV4_BF16) return launch_conv_stem<2>(a, s);
-  return launch_conv_stem<0>(a, s);
-}
-
 // Convolution with a scattered store: output pixel (n, ho, wo) goes to y[n, ho*sh + oh, wo*sw + ow, :]
 // of an (N, Hy, Wy, y_cstride) tensor, and d->Ho / d->Wo are taken as given (input rows past the
 // bottom / right edge read zeros).  This is one parity class of the data gradient of a stride-2
@@ -1580,17 +1013,9 @@ extern "C" int yv4_conv_scatter_fwd(const yv4_conv_desc* d, const float* x, cons
   YV4_REQUIRE(sh > 0 && sw > 0 && oh >= 0 && ow >= 0 && (d->Ho - 1) * sh + oh < Hy && (d->Wo - 1) * sw + ow < Wy,
               "conv scatter: the scattered grid does not fit the output tensor");
   const long long M = (long long)d->N * d->Ho * d->Wo;
-  const long long K = (long long)d->KH * d->KW * d->Cin;
-  YV4_REQUIRE(M < (1LL << 31) && (long long)d->N * d->H * d->W * d->x_cstride * 4 < 0xFFFFFFF0LL &&
-              (long long)d->Cout * K * 4 < 0xFFFFFFF0LL, "conv scatter: tensors of 4 GiB or more are not supported");
-  ConvArgs a;
-  a.x = x; a.w = w; a.s1 = scale1; a.t1 = shift1; a.s2 = nullptr; a.t2 = nullptr; a.res = nullptr; a.y = y;
-  a.stats = nullptr;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = 1; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff; a.r_cs = 0; a.r_co = 0;
-  a.act1 = 0; a.act2 = 0; a.slope1 = 0.f; a.slope2 = 0.f;
-  a.M = (int)M; a.K = (int)K; a.Kw = (int)K; a.tiles_n = 0;
+  ConvArgs a = conv_args(d, x, w, scale1, shift1, nullptr, nullptr, nullptr, y);
+  YV4_REQUIRE(M < (1LL << 31) && dma_addressable(a), "conv scatter: tensors of 4 GiB or more are not supported");
+  a.act1 = 0; a.act2 = 0;      // identity epilogue, whatever the descriptor's activation fields hold
   a.ys_on = 1; a.ys_H = Hy; a.ys_W = Wy; a.ys_sh = sh; a.ys_sw = sw; a.ys_oh = oh; a.ys_ow = ow;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int tile = d->tile == YV4_TILE_AUTO ? YV4_TILE_DMA_64x64 : d->tile;

@@ -62,8 +62,8 @@ __global__ __launch_bounds__(kHThreads, 2) void conv_mfma_h16_kernel(ConvArgsH p
   const int n0 = tile_n * BN;
   if (ksplit > 1) p.y = p.ws + (size_t)split * p.M * p.ws_cs;
 
-  const u32x4_t rsA = make_rsrc_h(p.x, x_bytes);
-  const u32x4_t rsB = make_rsrc_h(p.w, w_bytes);
+  const u32x4_t rsA = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsB = make_rsrc(p.w, w_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_h;
 
@@ -129,19 +129,19 @@ __global__ __launch_bounds__(kHThreads, 2) void conv_mfma_h16_kernel(ConvArgsH p
       const unsigned step = (unsigned)((((int64_t)kh * p.W + kw) * p.x_cs + c) * 2);             \
       _Pragma("unroll") for (int q = 0; q < PA; ++q) {                                           \
         const bool ok = kin && ((a_mask[q] >> tap) & 1ull);                                      \
-        lds_dma16_h(rsA, la_ + 32 * q * kRowB, ok ? a_off[q] + step : kOOB, 0u);                  \
+        lds_dma16(rsA, la_ + 32 * q * kRowB, ok ? a_off[q] + step : kOOB, 0u);                  \
       }                                                                                          \
       _Pragma("unroll") for (int q = 0; q < PB; ++q)                                             \
-        lds_dma16_h(rsB, lb_ + 32 * q * kRowB, (kin && b_off[q] != kOOB) ? b_off[q] + (unsigned)(g_k * 2) : kOOB, 0u); \
+        lds_dma16(rsB, lb_ + 32 * q * kRowB, (kin && b_off[q] != kOOB) ? b_off[q] + (unsigned)(g_k * 2) : kOOB, 0u); \
       g_k += kHBK;                                                                               \
     } else {                                                                                     \
       const unsigned step = (unsigned)((((int64_t)s_kh * p.W + s_kw) * p.x_cs + s_c0) * 2);      \
       _Pragma("unroll") for (int q = 0; q < PA; ++q) {                                           \
         const bool ok = (a_mask[q] >> s_tap) & 1ull;                                             \
-        lds_dma16_h(rsA, la_ + 32 * q * kRowB, ok ? a_off[q] + step : kOOB, 0u);                  \
+        lds_dma16(rsA, la_ + 32 * q * kRowB, ok ? a_off[q] + step : kOOB, 0u);                  \
       }                                                                                          \
       _Pragma("unroll") for (int q = 0; q < PB; ++q)                                             \
-        lds_dma16_h(rsB, lb_ + 32 * q * kRowB, b_off[q], s_kb);                                   \
+        lds_dma16(rsB, lb_ + 32 * q * kRowB, b_off[q], s_kb);                                   \
       s_tap += 1;                                                                                \
       s_kw += 1;                                                                                 \
       const int wrap_w = s_kw == p.KW ? 1 : 0;                                                   \
@@ -479,28 +479,25 @@ static int pick_tile_h16(long long M, int Cout, long long K) {
   return YV4_HTILE_64x64;
 }
 
+// What the AUTO path launches, as its tile id: conv_h16_impl launches it and yv4_conv_h16_pick_tile reports it (a plan,
+// the benchmark's output check and the tests read the latter to learn the former).
+static int auto_route_h16(const ConvArgsH& a) {
+  if (prefer_w3(a)) return YV4_HTILE_W3x3;
+  if (prefer_pp3(a)) return YV4_HTILE_PP3x3;
+  if (prefer_wide(a)) return YV4_HTILE_WIDE;
+  if (prefer_ws(a)) return YV4_HTILE_WS_1x1;
+  if (prefer_s3(a)) return YV4_HTILE_S3x3;
+  return pick_tile_h16(a.M, a.Cout, a.K);
+}
+
 }  // namespace yv4
 
 using namespace yv4;
 
+// (a residual, a second affine and the output type are unknown here: none, and fp32 for an odd Cout -- a pred map)
 extern "C" int yv4_conv_h16_pick_tile(const yv4_conv_desc* d) {
   if (!d) return YV4_TILE_AUTO;
-  {
-    ConvArgsH a{};
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo;
-    a.Cin = d->Cin; a.Cout = d->Cout; a.ys_on = 0; a.M = (int)((long long)d->N * d->Ho * d->Wo);
-    a.ksplit = 0; a.ws = nullptr;
-    a.K = a.Kw = d->KH * d->KW * d->Cin; a.res = nullptr; a.out_f32 = (d->Cout & 1) ? 1 : 0;   // (odd Cout: a pred map)
-    a.y_cs = d->y_cstride; a.y_co = d->y_coff; a.r_cs = d->r_cstride; a.r_co = d->r_coff;
-    if (prefer_w3(a)) return YV4_HTILE_W3x3;
-    if (prefer_pp3(a)) return YV4_HTILE_PP3x3;
-    a.K = a.Kw;
-    if (prefer_wide(a)) return YV4_HTILE_WIDE;
-    if (prefer_ws(a)) return YV4_HTILE_WS_1x1;
-    a.N = d->N; a.stats = nullptr; a.y_cs = d->y_cstride; a.y_co = d->y_coff; a.r_cs = d->r_cstride; a.r_co = d->r_coff;
-    if (prefer_s3(a)) return YV4_HTILE_S3x3;
-  }
-  return pick_tile_h16((long long)d->N * d->Ho * d->Wo, d->Cout, (long long)d->KH * d->KW * d->Cin);
+  return auto_route_h16(conv_args_h(d, (d->Cout & 1) ? 1 : 0));
 }
 
 static int conv_h16_impl(const yv4_conv_desc* d, int dtype, int out_dtype, const void* x, const void* w,
@@ -529,33 +526,21 @@ static int conv_h16_impl(const yv4_conv_desc* d, int dtype, int out_dtype, const
   const long long M = (long long)d->N * d->Ho * d->Wo;
   YV4_REQUIRE(M < (1LL << 31), "conv h16: N*Ho*Wo = %lld does not fit 31 bits", M);
   YV4_REQUIRE((long long)d->N * d->H * d->W < (1LL << 31), "conv h16: N*H*W does not fit 31 bits");
-  const long long K = (long long)d->KH * d->KW * d->Cin;
-  YV4_REQUIRE((long long)d->N * d->H * d->W * d->x_cstride * 2 < 0xFFFFFFF0LL && (long long)d->Cout * K * 2 < 0xFFFFFFF0LL,
-              "conv h16: tensors of 4 GiB or more are not addressable through a buffer descriptor");
 
-  ConvArgsH a;
-  a.x = x; a.w = w; a.s1 = scale1; a.t1 = shift1; a.s2 = scale2; a.t2 = shift2;
-  a.res = residual; a.y = y;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
-  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
-  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
-  a.M = (int)M; a.K = (int)K; a.Kw = (int)K; a.tiles_n = 0;
-  a.out_f32 = out_dtype == YV4_F32 ? 1 : 0;
-  a.ys_on = 0;
-  a.ksplit = 0; a.ks_slices = 0; a.ws_cs = 0; a.ws = nullptr;
+  ConvArgsH a = conv_args_h(d, out_dtype == YV4_F32 ? 1 : 0, x, w, scale1, shift1, scale2, shift2, residual, y);
+  YV4_REQUIRE(dma_addressable(a), "conv h16: tensors of 4 GiB or more are not addressable through a buffer descriptor");
   static const int ablate = YV4_ENV_INT("YV4_H16_ABLATE", 0);
   a.ablate = ablate;
   a.nt_out = (d->flags & YV4_CONV_NT_OUT) ? 1 : 0;
   a.stats = stats;
   const bool general = (d->Cin % kHBK) != 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int tile = d->tile == YV4_TILE_AUTO ? auto_route_h16(a) : d->tile;
   const int w3_forced = (d->tile > 8 && (d->tile & 7) == YV4_HTILE_W3x3 && d->tile <= YV4_HTILE_W3x3_SHAPE(6)) ? (d->tile >> 3) - 1 : -1;
   if (d->tile == YV4_HTILE_W3x3 || w3_forced >= 0)
     YV4_REQUIRE(conv3x3_wide_h16_applies(a), "conv h16: the wide 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with Cin %% 64 == 0, "
                 "Cout %% 16 == 0 (64 .. 1024), 16-bit output and 8-aligned channel strides / offsets");
-  if (d->tile == YV4_HTILE_W3x3 || w3_forced >= 0 || (d->tile == YV4_TILE_AUTO && prefer_w3(a))) {
+  if (tile == YV4_HTILE_W3x3 || w3_forced >= 0) {
     static const int shape = YV4_ENV_INT("YV4_W3_SHAPE", -1);
     return conv3x3_wide_h16_launch(a, dtype == YV4_BF16, w3_forced >= 0 ? w3_forced : shape, s);
   }
@@ -563,23 +548,22 @@ static int conv_h16_impl(const yv4_conv_desc* d, int dtype, int out_dtype, const
   if (d->tile == YV4_HTILE_WIDE || wide_forced >= 0)
     YV4_REQUIRE(conv_wide_h16_applies(a), "conv h16: the wide general tile needs Cin %% 64 == 0, Cout %% 16 == 0 (64 .. 2048), 16-bit "
                 "output and 8-aligned channel strides / offsets");
-  if (d->tile == YV4_HTILE_WIDE || wide_forced >= 0 || (d->tile == YV4_TILE_AUTO && !prefer_pp3(a) && prefer_wide(a))) {
+  if (tile == YV4_HTILE_WIDE || wide_forced >= 0) {
     static const int shape = YV4_ENV_INT("YV4_WIDE_SHAPE", -1);
     return conv_wide_h16_launch(a, dtype == YV4_BF16, wide_forced >= 0 ? wide_forced : shape, s);
   }
   if (d->tile == YV4_HTILE_PP3x3)
     YV4_REQUIRE(conv3x3_pp_h16_applies(a), "conv h16: the ping-pong 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with "
                 "Cin %% 64 == 0, even Cout >= 64, 16-bit output and even channel strides / offsets");
-  if (d->tile == YV4_HTILE_PP3x3 || (d->tile == YV4_TILE_AUTO && prefer_pp3(a))) return conv3x3_pp_h16_launch(a, dtype == YV4_BF16, s);
+  if (tile == YV4_HTILE_PP3x3) return conv3x3_pp_h16_launch(a, dtype == YV4_BF16, s);
   if (d->tile == YV4_HTILE_WS_1x1)
     YV4_REQUIRE(conv1x1_ws_applies(a), "conv h16: the weight-stationary tile needs a 1x1 / stride 1 conv with Cin <= 256, "
                 "Cout >= 16 (even unless the output is fp32); a residual needs a 16-bit output");
-  if (d->tile == YV4_HTILE_WS_1x1 || (d->tile == YV4_TILE_AUTO && prefer_ws(a))) return conv1x1_ws_launch(a, dtype == YV4_BF16, s);
+  if (tile == YV4_HTILE_WS_1x1) return conv1x1_ws_launch(a, dtype == YV4_BF16, s);
   if (d->tile == YV4_HTILE_S3x3)
     YV4_REQUIRE(conv3x3_small_applies(a), "conv h16: the few-channel 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with Cin 16, 32 "
                 "or 64, even Cout in [16, 64] and 16-bit output");
-  if (d->tile == YV4_HTILE_S3x3 || (d->tile == YV4_TILE_AUTO && prefer_s3(a))) return conv3x3_small_launch(a, dtype == YV4_BF16, s);
-  const int tile = d->tile == YV4_TILE_AUTO ? pick_tile_h16(M, d->Cout, K) : d->tile;
+  if (tile == YV4_HTILE_S3x3) return conv3x3_small_launch(a, dtype == YV4_BF16, s);
   return dtype == YV4_BF16 ? dispatch_h16<true>(a, tile, general, s) : dispatch_h16<false>(a, tile, general, s);
 }
 
@@ -680,11 +664,10 @@ __global__ __launch_bounds__(256) void splitk_finish_h16_kernel(ConvArgsH p) {
 // keeps at least 4 slices of 64; 1 = do not split (enough tiles already, or a layer outside the uniform-K tiles)
 static int splitk_choice_h16(const yv4_conv_desc* d) {
   const long long M = (long long)d->N * d->Ho * d->Wo;
-  const long long K = (long long)d->KH * d->KW * d->Cin;
-  if (d->Cin % kHBK != 0 || M >= (1LL << 31)) return 1;
-  if ((long long)d->N * d->H * d->W * d->x_cstride * 2 >= 0xFFFFFFF0LL || (long long)d->Cout * K * 2 >= 0xFFFFFFF0LL) return 1;
+  const ConvArgsH a = conv_args_h(d, 0);
+  if (d->Cin % kHBK != 0 || M >= (1LL << 31) || !dma_addressable(a)) return 1;
   const long long tiles = ((M + 63) / 64) * ((d->Cout + 63) / 64);
-  const int nk = (int)(K / kHBK);
+  const int nk = a.K / kHBK;
   static const int target = YV4_ENV_INT("YV4_SPLITK_TARGET_H16", 512);
   static const int min_slices = YV4_ENV_INT("YV4_SPLITK_MINSL_H16", 4);
   int ks = 1;
@@ -726,15 +709,7 @@ extern "C" int yv4_conv_bn_act_fwd_h16_splitk(const yv4_conv_desc* d, int dtype,
   YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH && d->act2 >= 0 && d->act2 <= YV4_ACT_SWISH, "conv h16 splitk: activation id");
   YV4_REQUIRE(workspace_bytes >= yv4_conv_h16_splitk_workspace(d, nullptr), "conv h16 splitk: workspace too small");
   const long long M = (long long)d->N * d->Ho * d->Wo;
-  ConvArgsH a;
-  a.x = x; a.w = w; a.s1 = scale1; a.t1 = shift1; a.s2 = scale2; a.t2 = shift2; a.res = residual; a.y = y;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
-  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
-  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
-  a.M = (int)M; a.K = d->KH * d->KW * d->Cin; a.Kw = a.K; a.tiles_n = 0; a.ys_on = 0; a.stats = nullptr; a.ablate = 0; a.nt_out = 0;
-  a.out_f32 = out_dtype == YV4_F32 ? 1 : 0;
+  ConvArgsH a = conv_args_h(d, out_dtype == YV4_F32 ? 1 : 0, x, w, scale1, shift1, scale2, shift2, residual, y);
   const int nk = a.K / kHBK;
   a.ks_slices = (nk + ks - 1) / ks;
   a.ksplit = (nk + a.ks_slices - 1) / a.ks_slices;      // no empty split (72 slices 16 ways = 15 splits of 5, the last of 2)
@@ -768,17 +743,10 @@ extern "C" int yv4_conv_scatter_fwd_h16(const yv4_conv_desc* d, int dtype, const
   YV4_REQUIRE(sh > 0 && sw > 0 && oh >= 0 && ow >= 0 && (d->Ho - 1) * sh + oh < Hy && (d->Wo - 1) * sw + ow < Wy,
               "conv scatter h16: the scattered grid does not fit the output tensor");
   const long long M = (long long)d->N * d->Ho * d->Wo;
-  const long long K = (long long)d->KH * d->KW * d->Cin;
-  YV4_REQUIRE(M < (1LL << 31) && (long long)d->N * d->H * d->W * d->x_cstride * 2 < 0xFFFFFFF0LL &&
-              (long long)d->Cout * K * 2 < 0xFFFFFFF0LL, "conv scatter h16: tensors of 4 GiB or more are not supported");
-  ConvArgsH a;
-  a.x = x; a.w = w; a.s1 = scale1; a.t1 = shift1; a.s2 = nullptr; a.t2 = nullptr; a.res = nullptr; a.y = y;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = 1; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff; a.r_cs = 0; a.r_co = 0;
-  a.act1 = 0; a.act2 = 0; a.slope1 = 0.f; a.slope2 = 0.f; a.stats = nullptr;
-  a.M = (int)M; a.K = (int)K; a.Kw = (int)K; a.tiles_n = 0; a.out_f32 = 0; a.ablate = 0; a.nt_out = (d->flags & YV4_CONV_NT_OUT) ? 1 : 0;
-  a.ksplit = 0; a.ks_slices = 0; a.ws_cs = 0; a.ws = nullptr;
+  ConvArgsH a = conv_args_h(d, 0, x, w, scale1, shift1, nullptr, nullptr, nullptr, y);
+  YV4_REQUIRE(M < (1LL << 31) && dma_addressable(a), "conv scatter h16: tensors of 4 GiB or more are not supported");
+  a.act1 = 0; a.act2 = 0;      // identity epilogue, whatever the descriptor's activation fields hold
+  a.nt_out = (d->flags & YV4_CONV_NT_OUT) ? 1 : 0;
   a.ys_on = 1; a.ys_H = Hy; a.ys_W = Wy; a.ys_sh = sh; a.ys_sw = sw; a.ys_oh = oh; a.ys_ow = ow;
   const bool general = (d->Cin % kHBK) != 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -787,6 +755,6 @@ extern "C" int yv4_conv_scatter_fwd_h16(const yv4_conv_desc* d, int dtype, const
     YV4_REQUIRE(conv_wide_h16_applies(a), "conv scatter h16: the wide tile needs Cin %% 64 == 0, Cout %% 16 == 0 and 8-aligned views");
     return conv_wide_h16_launch(a, dtype == YV4_BF16, -1, s);
   }
-  const int tile = d->tile == YV4_TILE_AUTO ? pick_tile_h16(M, d->Cout, K) : d->tile;
+  const int tile = d->tile == YV4_TILE_AUTO ? pick_tile_h16(M, d->Cout, a.K) : d->tile;
   return dtype == YV4_BF16 ? dispatch_h16<true>(a, tile, general, s) : dispatch_h16<false>(a, tile, general, s);
 }

@@ -1,12 +1,12 @@
-// Training-side kernels of the YOLOv4 path on gfx950: the generic convolution weight gradient (fp32 MFMA, 16-bit MFMA
-// and its second form), the deterministic slab reduce and the dispatcher over these and the two special 3x3 families
-// (conv_wgrad3x3_h16.hip, conv_wgrad_fc_h16.hip); zero-dilation for the data gradient of strided convolutions; SPP
-// max-pool backward, weight packing and nearest-resample backward.  Train-mode BatchNorm is in bn_train.hip.
+// The generic convolution weight gradient on gfx950 (fp32 MFMA, 16-bit MFMA and its second form), the deterministic
+// slab reduce and the dispatcher over these and the two special 3x3 families (conv_wgrad3x3_h16.hip,
+// conv_wgrad_fc_h16.hip).  Weight packing is in pack_weights.hip, the backward halves of the data-movement ops
+// (zero-dilation, SPP max-pool, nearest resample) in elementwise_bwd.hip, train-mode BatchNorm in bn_train.hip.
 //
 // What they replace in the reference's training step:
 //   cuDNN conv backward-filter / backward-data  (autograd of mmcv ConvModule, darknetcsp.py:15-35)
 // The data gradient itself is the forward kernel again (conv_mfma_f32.hip) on dY with the
-// weights transposed and flipped; for stride 2 dY is first zero-dilated (yv4_dilate2_fwd).
+// weights transposed and flipped; for stride 2 dY is first zero-dilated (yv4_dilate2_fwd, elementwise_bwd.hip).
 #include "train_common.h"
 #include "wgrad_common.h"
 
@@ -51,8 +51,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs p, unsigne
   const int m_hi = min(m_lo + p.rows_per_chunk, p.M);
   if (m_lo >= m_hi) return;
 
-  const u32x4_t rsX = make_rsrc_t(p.x, x_bytes);
-  const u32x4_t rsD = make_rsrc_t(p.dy, dy_bytes);
+  const u32x4_t rsX = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsD = make_rsrc(p.dy, dy_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_w;
 
@@ -93,8 +93,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradArgs p, unsigne
         }
       }
       const unsigned lrow = (unsigned)((buf * kWgRows + row0) * 64 * ES);
-      lds_dma16_t(rsD, lds_base + lrow, doff, 0u);
-      lds_dma16_t(rsX, lds_base + (unsigned)(2 * kWgRows * 64 * ES) + lrow, aoff, 0u);
+      lds_dma16(rsD, lds_base + lrow, doff, 0u);
+      lds_dma16(rsX, lds_base + (unsigned)(2 * kWgRows * 64 * ES) + lrow, aoff, 0u);
     }
   };
 
@@ -171,8 +171,8 @@ __global__ __launch_bounds__(256, NBUF == 2 ? 2 : 1) void conv_wgrad_h16_kernel(
   const int m_hi = min(m_lo + p.rows_per_chunk, p.M);
   if (m_lo >= m_hi) return;
 
-  const u32x4_t rsX = make_rsrc_t(p.x, x_bytes);
-  const u32x4_t rsD = make_rsrc_t(p.dy, dy_bytes);
+  const u32x4_t rsX = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsD = make_rsrc(p.dy, dy_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_wh;
 
@@ -223,8 +223,8 @@ __global__ __launch_bounds__(256, NBUF == 2 ? 2 : 1) void conv_wgrad_h16_kernel(
       const unsigned doff = dok ? dval : kOOB;
       const unsigned aoff = aok ? aval : kOOB;
       const unsigned lrow = lrow0 + (unsigned)(4 * q * kRowB);
-      lds_dma16_t(rsD, lds_base + lrow, doff, 0u);
-      lds_dma16_t(rsX, lds_base + (unsigned)kOpBytes + lrow, aoff, 0u);
+      lds_dma16(rsD, lds_base + lrow, doff, 0u);
+      lds_dma16(rsX, lds_base + (unsigned)kOpBytes + lrow, aoff, 0u);
     }
   };
 
@@ -373,8 +373,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_v2_h16_kernel(WgradArgs p, 
   const int m_hi = min(m_lo + p.rows_per_chunk, p.M);
   if (m_lo >= m_hi) return;
 
-  const u32x4_t rsX = make_rsrc_t(p.x, x_bytes);
-  const u32x4_t rsD = make_rsrc_t(p.dy, dy_bytes);
+  const u32x4_t rsX = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsD = make_rsrc(p.dy, dy_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_wv;
 
@@ -446,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_v2_h16_kernel(WgradArgs p, 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const unsigned lrow = lrow0 + (unsigned)(4 * q * kRowB);
-      lds_dma16_t(rsD, lds_base + lrow, d_off[q] < d_lim[q] ? d_off[q] : kOOB, 0u);
+      lds_dma16(rsD, lds_base + lrow, d_off[q] < d_lim[q] ? d_off[q] : kOOB, 0u);
       d_off[q] += d_step;
       unsigned aoff;
       if (LINEAR) {
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_v2_h16_kernel(WgradArgs p, 
         const int wi = (int)(short)(te[q].y & 0xFFFFu) + a_kw[q];
         aoff = ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W) ? te[q].x + a_tap[q] : kOOB;
       }
-      lds_dma16_t(rsX, lds_base + (unsigned)kOpBytes + lrow, aoff, 0u);
+      lds_dma16(rsX, lds_base + (unsigned)kOpBytes + lrow, aoff, 0u);
     }
   };
 
@@ -604,433 +604,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   }
 }
 
-// ---------------------------------------------------------------------------------
-// dst[n, 2y, 2x, c] = src[n, y, x, c], everything else 0  (dst is (N, 2H, 2W, C) dense NHWC).
-// ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dilate2_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int H,
-                                                      int W, int C4, int src_cs, int src_co) {
-  const size_t total = (size_t)N * 2 * H * 2 * W * C4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int c4 = (int)(i % C4);
-    size_t t = i / C4;
-    const int x = (int)(t % (2 * W));
-    t /= 2 * W;
-    const int y = (int)(t % (2 * H));
-    const int n = (int)(t / (2 * H));
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (((x | y) & 1) == 0)
-      v = *reinterpret_cast<const float4*>(src + ((size_t)(n * H + (y >> 1)) * W + (x >> 1)) * src_cs + src_co + c4 * 4);
-    reinterpret_cast<float4*>(dst)[i] = v;
-  }
-}
-// ---------------------------------------------------------------------------------
-// SPP backward (darknetcsp.py:176-181,203-206,222-226: cat([x, mp5(x), mp9(x), mp13(x)])):
-//   dx[p] = dcat[0][p] + sum over k in {5,9,13}, over output positions q whose window argmax is p,
-//   of dcat[k][q].
-// One thread owns (n, y, x, 4 channels) as an OUTPUT position: it rescans the 13x13 window of the
-// saved input once in row-major order, tracking the first maximum of the nested 5 / 9 / 13 windows
-// (torch's max_pool2d keeps the first maximum in scan order), and scatters its three gradients with
-// float atomics into the fp32 accumulator dx (N, H, W, C dense, zero on entry), plus its own
-// identity-branch gradient.  Replaces three ATen max_pool2d backward passes + three adds.
-// ---------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void spp_pool_bwd_kernel(const T* __restrict__ xcat, int x_cs, int x_co,
-                                                           const T* __restrict__ dcat, int d_cs, int d_co,
-                                                           float* __restrict__ dx, int N, int H, int W, int C) {
-  const int C4 = C >> 2;
-  const size_t total = (size_t)N * H * W * C4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const float ninf = -__builtin_huge_valf();
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int c4 = (int)(i % C4);
-    size_t t = i / C4;
-    const int x = (int)(t % W);
-    t /= W;
-    const int y = (int)(t % H);
-    const int n = (int)(t / H);
-    const T* base = xcat + (size_t)n * H * W * x_cs + x_co + c4 * 4;
-    float m[3][4];
-    int am[3][4];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { m[k][u] = ninf; am[k][u] = y * W + x; }
-    for (int dy = -6; dy <= 6; ++dy) {
-      const int yy = y + dy;
-      if ((unsigned)yy >= (unsigned)H) continue;
-      const int ady = dy < 0 ? -dy : dy;
-      for (int dxx = -6; dxx <= 6; ++dxx) {
-        const int xx = x + dxx;
-        if ((unsigned)xx >= (unsigned)W) continue;
-        const int adx = dxx < 0 ? -dxx : dxx;
-        const int rad = ady > adx ? ady : adx;
-        const float4 v4 = El<T>::ld4(base + ((size_t)yy * W + xx) * x_cs);
-        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-        const int pos = yy * W + xx;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (v[u] > m[2][u]) { m[2][u] = v[u]; am[2][u] = pos; }
-          if (rad <= 4 && v[u] > m[1][u]) { m[1][u] = v[u]; am[1][u] = pos; }
-          if (rad <= 2 && v[u] > m[0][u]) { m[0][u] = v[u]; am[0][u] = pos; }
-        }
-      }
-    }
-    const T* g = dcat + ((size_t)(n * H + y) * W + x) * d_cs + d_co + c4 * 4;
-    float* dxn = dx + (size_t)n * H * W * C + c4 * 4;
-    const float4 g0 = El<T>::ld4(g);
-    const float gi[4] = {g0.x, g0.y, g0.z, g0.w};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) atomicAdd(dxn + (size_t)(y * W + x) * C + u, gi[u]);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float4 gk = El<T>::ld4(g + (k + 1) * C);
-      const float gv[4] = {gk.x, gk.y, gk.z, gk.w};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) atomicAdd(dxn + (size_t)am[k][u] * C + u, gv[u]);
-    }
-  }
-}
-
-// The same scatter for the maps an SPP block actually sees (19x19 at 608 px): everything in LDS, and the window
-// argmax found by CASCADED 5x5 pools instead of a 13x13 scan per pixel.
-//   * Every element becomes a KEY: (order-preserving bits of the value) : (all-ones - position).  The maximum key of a
-//     window is its largest value and, among equal values, the smallest position -- the first hit of the row-major scan
-//     `v > best` that torch's pooling (and the kernel above) performs.  Keys make the argmax a plain associative,
-//     idempotent max, so pool9 = pool5 o pool5 and pool13 = pool5 o pool9 exactly (windows clipped at the border), and
-//     each 5x5 pool separates into a row pass and a column pass: 30 LDS reads per element for the three pools instead
-//     of 169 global loads and 507 compare/select pairs (the round-2 form: 0.99 ms at batch 64 x 512 channels).
-//   * one workgroup = one image x CG channels (8 for 16-bit keys, 4 for 64-bit keys of fp32 values): three key planes (in, row-pass, out -- rotated through the cascade)
-//     and the fp32 accumulator plane, H*W x CG each; the three pool gradients go to the accumulator by LDS atomics,
-//     the identity branch by a plain add, and dx is written once.
-template <typename T> struct SppKey;
-template <> struct SppKey<float> {
-  typedef unsigned long long K;
-  static constexpr int CG = 4;
-  static __device__ __forceinline__ K make(float v, int pos) {
-    unsigned b = __float_as_uint(v);
-    if (b == 0x80000000u) b = 0u;                                     // -0 == +0 for `>`
-    b ^= (b & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u;
-    return ((K)b << 32) | (K)(0xFFFFFFFFu - (unsigned)pos);
-  }
-  static __device__ __forceinline__ int pos(K k) { return (int)(0xFFFFFFFFu - (unsigned)k); }
-};
-template <typename T> struct SppKey {                                 // _Float16 / __bf16
-  typedef unsigned K;
-  static constexpr int CG = 8;
-  static __device__ __forceinline__ K make(T v, int pos) {
-    unsigned b = (unsigned)__builtin_bit_cast(unsigned short, v);
-    if (b == 0x8000u) b = 0u;
-    b ^= (b & 0x8000u) ? 0xFFFFu : 0x8000u;
-    return (b << 16) | (0xFFFFu - (unsigned)pos);
-  }
-  static __device__ __forceinline__ int pos(K k) { return (int)(0xFFFFu - (k & 0xFFFFu)); }
-};
-
-constexpr int kSppItems = 16;      // (position, channel) items per thread: H*W*CG <= 4096 (the 64 KB LDS bound of the launch)
-template <typename T>
-__global__ __launch_bounds__(256) void spp_pool_bwd_lds_kernel(const T* __restrict__ xcat, int x_cs, int x_co,
-                                                               const T* __restrict__ dcat, int d_cs, int d_co,
-                                                               float* __restrict__ dx, int H, int W, int C, int det) {
-  // det (yv4_set_deterministic): the accumulator plane holds 64-bit FIXED-POINT integers with one exponent for the
-  // workgroup -- 2^40 / (the power of two above the largest |gradient| it will add, found by an integer max) -- so the
-  // scatter's atomics are integer adds and the plane's value does not depend on their order.  A non-finite gradient
-  // anywhere in the block makes the block's outputs NaN (the step is skipped by the loss scaler either way).
-  typedef SppKey<T> SK;
-  typedef typename SK::K K;
-  constexpr int CG = SK::CG;
-  extern __shared__ __attribute__((aligned(16))) unsigned char spp_raw[];
-  const int HW = H * W;
-  K* ka = reinterpret_cast<K*>(spp_raw);             // [HW][CG]
-  K* kb = ka + (size_t)HW * CG;
-  K* kc = kb + (size_t)HW * CG;
-  float* acc = reinterpret_cast<float*>(kc + (size_t)HW * CG);
-  long long* acc64 = reinterpret_cast<long long*>(acc);
-  __shared__ unsigned smax;
-  if (det && threadIdx.x == 0) smax = 0u;
-  if (det) __syncthreads();
-  unsigned gmax = 0u;
-  const int n = blockIdx.y;
-  const int cg0 = blockIdx.x * CG;
-  const int nc = min(CG, C - cg0);
-  const int items = HW * CG;
-  const T* xb = xcat + (size_t)n * HW * x_cs + x_co + cg0;
-  const T* gb = dcat + (size_t)n * HW * d_cs + d_co + cg0;
-  const FastDiv fd_w = make_fastdiv((unsigned)W);
-  // a thread keeps the same items (i = tid + 256 j) through every pass: their coordinates and their three pool gradients
-  // are fetched once, all loads in flight together
-  float g[3][kSppItems];
-  float gid0[kSppItems];           // (deterministic mode only)
-  short iy[kSppItems], ix[kSppItems];
-#pragma unroll
-  for (int j = 0; j < kSppItems; ++j) {
-    const int i = threadIdx.x + 256 * j;
-    const int pos = i / CG, c = i - pos * CG;
-    const int y = fd_div(pos, fd_w);
-    iy[j] = (short)y;
-    ix[j] = (short)(pos - y * W);
-    const bool ok = i < items && c < nc;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      g[k][j] = ok ? (float)gb[(size_t)pos * d_cs + (size_t)(k + 1) * C + c] : 0.f;
-      gmax = max(gmax, __float_as_uint(g[k][j]) & 0x7fffffffu);
-    }
-    if (i < items) {
-      ka[i] = ok ? SK::make(xb[(size_t)pos * x_cs + c], pos) : (K)0;
-      const float gid = ok ? (float)gb[(size_t)pos * d_cs + c] : 0.f;     // the identity branch's gradient
-      if (det) { gid0[j] = gid; gmax = max(gmax, __float_as_uint(gid) & 0x7fffffffu); }
-      else acc[i] = gid;
-    }
-  }
-  double fx_scale = 1.0;
-  bool fx_bad = false;
-  if (det) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) gmax = max(gmax, (unsigned)__shfl_xor((int)gmax, o));
-    if ((threadIdx.x & 63) == 0) atomicMax(&smax, gmax);
-    __syncthreads();
-    const unsigned mb = smax;
-    fx_bad = mb >= 0x7f800000u;
-    fx_scale = __builtin_ldexp(1.0, 166 - (int)(mb >> 23));      // |g| < 2^(e - 126)  ->  |g * scale| < 2^40
-#pragma unroll
-    for (int j = 0; j < kSppItems; ++j) {
-      const int i = threadIdx.x + 256 * j;
-      if (i < items) acc64[i] = fx_bad ? 0ll : (long long)__builtin_rint((double)gid0[j] * fx_scale);
-    }
-  }
-  __syncthreads();
-  K* src = ka; K* tmp = kb; K* out = kc;
-#pragma unroll 1
-  for (int k = 0; k < 3; ++k) {
-    // row pass: tmp(y, x) = max src(y, x-2 .. x+2)
-#pragma unroll
-    for (int j = 0; j < kSppItems; ++j) {
-      const int i = threadIdx.x + 256 * j;
-      if (i < items) {
-        const int c = i & (CG - 1), y = iy[j], x = ix[j];
-        const K* row = src + (size_t)y * W * CG + c;
-        K m = row[x * CG];
-#pragma unroll
-        for (int d = -2; d <= 2; ++d) {
-          if (d == 0) continue;
-          const int xx = min(max(x + d, 0), W - 1);              // a clamped neighbour repeats an element of the window
-          const K v = row[xx * CG];
-          m = v > m ? v : m;
-        }
-        tmp[i] = m;
-      }
-    }
-    __syncthreads();
-    // column pass + scatter of this pool's gradient to its argmax
-#pragma unroll
-    for (int j = 0; j < kSppItems; ++j) {
-      const int i = threadIdx.x + 256 * j;
-      if (i < items) {
-        const int c = i & (CG - 1), y = iy[j], x = ix[j];
-        const K* col = tmp + (size_t)x * CG + c;
-        K m = col[(size_t)y * W * CG];
-#pragma unroll
-        for (int d = -2; d <= 2; ++d) {
-          if (d == 0) continue;
-          const int yy = min(max(y + d, 0), H - 1);
-          const K v = col[(size_t)yy * W * CG];
-          m = v > m ? v : m;
-        }
-        out[i] = m;
-        const float gv = k == 0 ? g[0][j] : (k == 1 ? g[1][j] : g[2][j]);
-        if (c < nc) {
-          if (det) {
-            if (!fx_bad) atomicAdd(reinterpret_cast<u64_t*>(&acc64[SK::pos(m) * CG + c]), (u64_t)(long long)__builtin_rint((double)gv * fx_scale));
-          } else {
-            atomicAdd(&acc[SK::pos(m) * CG + c], gv);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    K* t = src; src = out; out = t;                  // the pooled keys feed the next 5x5 pool
-  }
-  float* o = dx + (size_t)n * HW * C + cg0;
-#pragma unroll
-  for (int j = 0; j < kSppItems; ++j) {
-    const int i = threadIdx.x + 256 * j;
-    if (i < items) {
-      const int pos = i / CG, c = i - pos * CG;
-      if (c < nc) o[(size_t)pos * C + c] = !det ? acc[i] : (fx_bad ? __builtin_nanf("") : (float)((double)acc64[i] / fx_scale));
-    }
-  }
-}
-
-// Conv weight -> the kernels' packed operand in ONE pass (cast included): rows x (KHo*KWo*ICp) with K ordered
-// (kh, kw, channel), zero-padded channels; output tap (kh, kw) reads source tap (kh0 + kh*kh_step, kw0 + kw*kw_step).
-// transpose = 0: rows = Cout, channel = Cin (forward operand); 1: rows = Cin, channel = Cout -- with the taps
-// mirrored (kh0 = KH-1, step -1) the operand of the data gradient (ATen needs flip + transpose + contiguous + cast = 3
-// launches per conv per step for it), with a tap subset the operand of one parity class of a stride-2 data gradient
-// (list-indexing the taps cost two host-to-device index uploads and two gather kernels per class).  The source is addressed through its element strides,
-// so contiguous and channels_last parameters both go without a copy.
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restrict__ w, long long s_co, long long s_ci,
-                                                          long long s_kh, long long s_kw, int Cout, int Cin, int KHo, int KWo,
-                                                          int kh0, int kh_step, int kw0, int kw_step, int tf, int ICp,
-                                                          T* __restrict__ dst, int nrows) {
-  // one output row (r, kh, kw) of ICp channels per workgroup iteration: two small divides per row, none per element
-  const int IC = tf ? Cout : Cin;
-  const int taps = KHo * KWo;
-  for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
-    const int r = row / taps;
-    const int tap = row - r * taps;
-    const int kh = tap / KWo, kw = tap - kh * KWo;
-    const float* src = w + (kh0 + kh * kh_step) * s_kh + (kw0 + kw * kw_step) * s_kw + (tf ? r * s_ci : r * s_co);
-    const long long s_ic = tf ? s_co : s_ci;
-    T* d = dst + (size_t)row * ICp;
-    for (int ic = threadIdx.x; ic < ICp; ic += 256) d[ic] = (T)(ic < IC ? src[ic * s_ic] : 0.f);
-  }
-}
-
-// The same pass over a TABLE of weights in one launch (yv4_pack_weights_multi): workgroup b serves the descriptor whose
-// [first_block, first_block + nblocks) range holds b, rows_per_block output rows of it.
-//
-// An output row (r, kh, kw) runs over the channel ic; in the SOURCE (an fp32 (Cout, Cin, KH, KW) parameter, normally
-// contiguous) the element sits at r*s_r + ic*s_ic + tap offset, and whichever of the forward operand (s_ic = KH*KW) and
-// the data-gradient operand (s_ic = Cin*KH*KW) is packed, neighbouring ic are 36 bytes or kilobytes apart: reading row
-// by row (round 2) moved 4 bytes per 64- or 128-byte line touched and took 0.87 ms per YOLOv4-L step (64 M parameters,
-// both operands).  Here a workgroup stages a box of the source -- NR rows r x ICc channels x every tap the descriptor
-// uses -- in LDS, walking the source in ITS order (taps fastest, then whichever of r / ic has the smaller stride), and
-// writes the output rows from LDS with the channel across lanes.
-constexpr int kPackStage = 9216;       // floats staged per pass (36 KB)
-
-template <typename T>
-__device__ __forceinline__ void pack_rows(const yv4_pack_desc& d, int row0, int row1, float* stage) {
-  const int tf = d.transpose;
-  const int IC = tf ? d.Cout : d.Cin;
-  const int ICp = (IC + d.pad_to - 1) / d.pad_to * d.pad_to;
-  const int taps = d.KHo * d.KWo;
-  const long long s_ic = tf ? d.s_co : d.s_ci, s_r = tf ? d.s_ci : d.s_co;
-  T* dst = reinterpret_cast<T*>(d.dst);
-  // bounding box of the source taps the descriptor reads
-  const int khl = d.kh0 + (d.KHo - 1) * d.kh_step, kwl = d.kw0 + (d.KWo - 1) * d.kw_step;
-  const int khmin = min(d.kh0, khl), kwmin = min(d.kw0, kwl);
-  const int nbh = abs(khl - d.kh0) + 1, nbw = abs(kwl - d.kw0) + 1;
-  const int TB = nbh * nbw, TBs = TB | 1;                    // odd LDS pitch per (r, ic): channel-strided reads hit all banks
-  const int rA = row0 / taps, rB = (row1 - 1) / taps;        // rows r touched (inclusive)
-  const bool ic_inner = s_ic <= s_r;
-  int NR, ICc;
-  if (ic_inner) {
-    if (ICp * TBs <= kPackStage) { ICc = ICp; NR = min(rB - rA + 1, kPackStage / (ICp * TBs)); }
-    else { NR = 1; ICc = (kPackStage / TBs) & ~7; }
-  } else {
-    NR = min(rB - rA + 1, max(8, 64 / TB));                  // >= 256 contiguous source bytes per ic
-    ICc = min(ICp, (kPackStage / (NR * TBs)) & ~7);
-  }
-  constexpr int VEC = sizeof(T) == 2 ? 2 : 1;                // 16-bit outputs are stored in pairs
-  const FastDiv fd_tb = make_fastdiv((unsigned)TB), fd_bw = make_fastdiv((unsigned)nbw), fd_kwo = make_fastdiv((unsigned)d.KWo),
-                fd_taps = make_fastdiv((unsigned)taps);
-  const int tid = threadIdx.x;
-  for (int r0 = rA; r0 <= rB; r0 += NR) {
-    const int nr = min(NR, rB - r0 + 1);
-    const FastDiv fd_nr = make_fastdiv((unsigned)nr);
-    const int orow0 = max(row0, r0 * taps), orow1 = min(row1, (r0 + nr) * taps);
-    for (int c0 = 0; c0 < ICp; c0 += ICc) {
-      const int cn = min(ICc, ICp - c0);
-      const FastDiv fd_cn = make_fastdiv((unsigned)cn);
-      __syncthreads();                                       // the previous pass has been written out
-      const int total = nr * cn * TB;
-      // eight independent loads in flight per thread (the staging is latency-bound otherwise)
-      for (int e0 = tid; e0 < total; e0 += 256 * 8) {
-        float v[8];
-        int li[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int e = e0 + 256 * u;
-          v[u] = 0.f;
-          li[u] = -1;
-          if (e < total) {
-            const int q = fd_div(e, fd_tb), t = e - q * TB;
-            int rl, cl;
-            if (ic_inner) { rl = fd_div(q, fd_cn); cl = q - rl * cn; }
-            else { cl = fd_div(q, fd_nr); rl = q - cl * nr; }
-            const int bh = fd_div(t, fd_bw), bw = t - bh * nbw;
-            const int ic = c0 + cl;
-            li[u] = (rl * cn + cl) * TBs + t;
-            if (ic < IC) v[u] = d.w[(long long)(r0 + rl) * s_r + (long long)ic * s_ic + (khmin + bh) * d.s_kh + (kwmin + bw) * d.s_kw];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-          if (li[u] >= 0) stage[li[u]] = v[u];
-      }
-      __syncthreads();
-      const int cv = cn / VEC;
-      const FastDiv fd_cv = make_fastdiv((unsigned)cv);
-      const int wtotal = (orow1 - orow0) * cv;
-      for (int i = tid; i < wtotal; i += 256) {
-        const int ro = fd_div(i, fd_cv), pc = i - ro * cv;
-        const int row = orow0 + ro;
-        const int r = fd_div(row, fd_taps), tap = row - r * taps;
-        const int kh = fd_div(tap, fd_kwo), kw = tap - kh * d.KWo;
-        const int tb = (d.kh0 + kh * d.kh_step - khmin) * nbw + (d.kw0 + kw * d.kw_step - kwmin);
-        const float* sp = stage + ((r - r0) * cn + pc * VEC) * TBs + tb;
-        T* o = dst + (size_t)row * ICp + c0 + pc * VEC;
-        if constexpr (VEC == 2) {
-          union { T h[2]; unsigned u; } pk;
-          pk.h[0] = (T)sp[0];
-          pk.h[1] = (T)sp[TBs];
-          *reinterpret_cast<unsigned*>(o) = pk.u;
-        } else {
-          o[0] = (T)sp[0];
-        }
-      }
-    }
-  }
-}
-__global__ __launch_bounds__(256) void pack_weights_multi_kernel(const yv4_pack_desc* __restrict__ table, int n) {
-  __shared__ float stage[kPackStage];
-  // binary search of the descriptor (uniform per workgroup)
-  int lo = 0, hi = n - 1;
-  const int b = (int)blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (table[mid].first_block <= b) lo = mid; else hi = mid - 1;
-  }
-  const yv4_pack_desc d = table[lo];
-  const int R = d.transpose ? d.Cin : d.Cout;
-  const int nrows = R * d.KHo * d.KWo;
-  const int row0 = (b - d.first_block) * d.rows_per_block;
-  const int row1 = row0 + d.rows_per_block < nrows ? row0 + d.rows_per_block : nrows;
-  if (row0 >= row1) return;
-  switch (d.dtype) {
-    case YV4_F32: pack_rows<float>(d, row0, row1, stage); break;
-    case YV4_F16: pack_rows<_Float16>(d, row0, row1, stage); break;
-    default: pack_rows<__bf16>(d, row0, row1, stage); break;
-  }
-}
-
-// Backward of the nearest resample by an INTEGER factor (yolo_neck_csp.py:213-219: F.interpolate(scale 2) into the concat
-// buffer): dx[n, sy, sx, c] = the sum of the fy x fx gradient pixels that read it, fp32 sum, one rounding.  The gradient is a
-// channel slice of the concat buffer's gradient (dy_cs / dy_co).
-template <typename T>
-__global__ __launch_bounds__(256) void resample_nearest_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, int N, int Hs,
-                                                                   int Ws, int fy, int fx, int C4, int dy_cs, int dy_co) {
-  const size_t total = (size_t)N * Hs * Ws * C4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const int Wd = Ws * fx, Hd = Hs * fy;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int c4 = (int)(i % C4);
-    size_t t = i / C4;
-    const int sx = (int)(t % Ws);
-    t /= Ws;
-    const int sy = (int)(t % Hs);
-    const int n = (int)(t / Hs);
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int j = 0; j < fy; ++j)
-      for (int k = 0; k < fx; ++k) {
-        const float4 v = El<T>::ld4(dy + ((size_t)(n * Hd + sy * fy + j) * Wd + sx * fx + k) * dy_cs + dy_co + c4 * 4);
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-      }
-    El<T>::st4(dx + i * 4, a);
-  }
-}
-
 }  // namespace yv4
 
 using namespace yv4;
@@ -1134,7 +707,7 @@ static int wgrad_impl(const yv4_conv_desc* d, int dtype, const void* x, const vo
   YV4_REQUIRE(Ho == d->Ho && Wo == d->Wo, "wgrad: Ho/Wo do not match the geometry");
   const long long M = (long long)d->N * d->Ho * d->Wo;
   const long long xb = (long long)d->N * d->H * d->W * d->x_cstride * es, db = M * d->y_cstride * es;
-  YV4_REQUIRE(M < (1LL << 31) && xb < 0xFFFFFFF0LL && db < 0xFFFFFFF0LL, "wgrad: tensors of 4 GiB or more are not supported");
+  YV4_REQUIRE(M < (1LL << 31) && desc_addressable(xb) && desc_addressable(db), "wgrad: tensors of 4 GiB or more are not supported");
   WgradArgs a;
   a.x = x; a.dy = dy; a.dw = dw;
   a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
@@ -1280,95 +853,4 @@ extern "C" int yv4_conv_wgrad_det(const yv4_conv_desc* d, int dtype, const void*
                                   float* workspace, size_t workspace_bytes, void* stream) {
   YV4_REQUIRE(dtype == YV4_F32 || dtype == YV4_F16 || dtype == YV4_BF16, "wgrad_det: dtype must be f32, f16 or bf16");
   return wgrad_impl(d, dtype, x, dy, dw, stream, workspace, workspace_bytes);
-}
-
-extern "C" int yv4_dilate2_fwd(const float* src, float* dst, int N, int H, int W, int C, int src_cstride, int src_coff,
-                               void* stream) {
-  YV4_REQUIRE(src && dst && N > 0 && H > 0 && W > 0 && C > 0, "dilate2: bad argument");
-  YV4_REQUIRE(C % 4 == 0 && src_cstride % 4 == 0 && src_coff % 4 == 0, "dilate2: channels must be multiples of 4");
-  const size_t total = (size_t)N * 2 * H * 2 * W * (C / 4);
-  hipLaunchKernelGGL(dilate2_kernel, dim3(ew_grid_t(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, dst,
-                     N, H, W, C / 4, src_cstride, src_coff);
-  YV4_CHECK_LAUNCH("dilate2");
-  return YV4_OK;
-}
-
-extern "C" int yv4_pack_weight(const float* w, int64_t s_co, int64_t s_ci, int64_t s_kh, int64_t s_kw, int Cout, int Cin,
-                               int KH, int KW, int KHo, int KWo, int kh0, int kh_step, int kw0, int kw_step, int transpose,
-                               int pad_to, void* dst, int dtype, void* stream) {
-  YV4_REQUIRE(w && dst && Cout > 0 && Cin > 0 && KH > 0 && KW > 0 && KHo > 0 && KWo > 0 && pad_to > 0,
-              "pack_weight: bad argument");
-  YV4_REQUIRE(dtype == YV4_F32 || dtype == YV4_F16 || dtype == YV4_BF16, "pack_weight: dtype must be f32, f16 or bf16");
-  const int khl = kh0 + (KHo - 1) * kh_step, kwl = kw0 + (KWo - 1) * kw_step;
-  YV4_REQUIRE(kh0 >= 0 && kh0 < KH && khl >= 0 && khl < KH && kw0 >= 0 && kw0 < KW && kwl >= 0 && kwl < KW,
-              "pack_weight: tap selection leaves the %dx%d kernel", KH, KW);
-  const int IC = transpose ? Cout : Cin, R = transpose ? Cin : Cout;
-  const int ICp = (IC + pad_to - 1) / pad_to * pad_to;
-  const long long nrows = (long long)R * KHo * KWo;
-  YV4_REQUIRE(nrows < (1LL << 31), "pack_weight: too many rows");
-  const unsigned grid = (unsigned)(nrows < 8192 ? nrows : 8192);
-  YV4_DISPATCH_T(dtype, hipLaunchKernelGGL(pack_weight_kernel<T>, dim3(grid), dim3(256), 0,
-                                           reinterpret_cast<hipStream_t>(stream), w, (long long)s_co, (long long)s_ci,
-                                           (long long)s_kh, (long long)s_kw, Cout, Cin, KHo, KWo, kh0, kh_step, kw0, kw_step,
-                                           transpose ? 1 : 0, ICp, reinterpret_cast<T*>(dst), (int)nrows));
-  YV4_CHECK_LAUNCH("pack_weight");
-  return YV4_OK;
-}
-
-extern "C" int yv4_pack_weights_multi(const yv4_pack_desc* table_dev, int n, int total_blocks, void* stream) {
-  YV4_REQUIRE(table_dev && n > 0 && total_blocks > 0, "pack_weights_multi: bad argument");
-  hipLaunchKernelGGL(pack_weights_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                     table_dev, n);
-  YV4_CHECK_LAUNCH("pack_weights_multi");
-  return YV4_OK;
-}
-
-extern "C" int yv4_spp_pool_bwd(const void* xcat, int x_cstride, int x_coff, const void* dcat, int d_cstride, int d_coff,
-                                float* dx, int N, int H, int W, int C, int dtype, void* stream) {
-  YV4_REQUIRE(xcat && dcat && dx && N > 0 && H > 0 && W > 0 && C > 0, "spp_pool_bwd: bad argument");
-  YV4_REQUIRE(dtype == YV4_F32 || dtype == YV4_F16 || dtype == YV4_BF16, "spp_pool_bwd: dtype must be f32, f16 or bf16");
-  YV4_REQUIRE(((C | x_cstride | x_coff | d_cstride | d_coff) & 3) == 0, "spp_pool_bwd: channels must be multiples of 4");
-  YV4_REQUIRE(x_coff + C <= x_cstride && d_coff + 4 * C <= d_cstride, "spp_pool_bwd: view exceeds its pixel stride");
-  YV4_REQUIRE((long long)H * W < (1LL << 31), "spp_pool_bwd: H*W does not fit 31 bits");
-  const bool f32 = dtype == YV4_F32;
-  const int cg = f32 ? SppKey<float>::CG : SppKey<__bf16>::CG;
-  const int det = deterministic() ? 1 : 0;
-  const size_t lds = (size_t)H * W * cg * (3 * (f32 ? 8 : 4) + (det ? 8 : 4));
-  if (lds <= 64 * 1024 && N <= 65535 && (long long)H * W * cg <= 256 * kSppItems) {   // small maps: keys and accumulator LDS-resident
-    dim3 grid((unsigned)((C + cg - 1) / cg), (unsigned)N);
-    YV4_DISPATCH_T(dtype, hipLaunchKernelGGL(spp_pool_bwd_lds_kernel<T>, grid, dim3(256), lds,
-                                             reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(xcat),
-                                             x_cstride, x_coff, reinterpret_cast<const T*>(dcat), d_cstride, d_coff, dx, H,
-                                             W, C, det));
-    YV4_CHECK_LAUNCH("spp_pool_bwd");
-    return YV4_OK;
-  }
-  if (det) {
-    set_error("spp_pool_bwd: deterministic mode needs the LDS-resident form (H*W*%d <= %d, got %dx%d): the large-map "
-              "kernel scatters with float atomics", cg, 256 * kSppItems, H, W);
-    return YV4_E_UNSUPPORTED;
-  }
-  const size_t total = (size_t)N * H * W * (C / 4);
-  YV4_DISPATCH_T(dtype, hipLaunchKernelGGL(spp_pool_bwd_kernel<T>, dim3(ew_grid_t(total)), dim3(256), 0,
-                                           reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(xcat),
-                                           x_cstride, x_coff, reinterpret_cast<const T*>(dcat), d_cstride, d_coff, dx, N,
-                                           H, W, C));
-  YV4_CHECK_LAUNCH("spp_pool_bwd");
-  return YV4_OK;
-}
-
-
-extern "C" int yv4_resample_nearest_bwd(const void* dy, void* dx, int N, int Hs, int Ws, int Hd, int Wd, int C, int dy_cstride,
-                                        int dy_coff, int dtype, void* stream) {
-  YV4_REQUIRE(dy && dx && N > 0 && Hs > 0 && Ws > 0 && C > 0, "resample_bwd: bad argument");
-  YV4_REQUIRE(dtype == YV4_F32 || dtype == YV4_F16 || dtype == YV4_BF16, "resample_bwd: dtype must be f32, f16 or bf16");
-  YV4_REQUIRE(Hd % Hs == 0 && Wd % Ws == 0 && Hd / Hs <= 8 && Wd / Ws <= 8, "resample_bwd: integer scale factors up to 8 only");
-  YV4_REQUIRE(((C | dy_cstride | dy_coff) & 3) == 0 && dy_coff >= 0 && dy_coff + C <= dy_cstride,
-              "resample_bwd: channels must be multiples of 4 and the view inside its pixel stride");
-  const size_t total = (size_t)N * Hs * Ws * (C / 4);
-  YV4_DISPATCH_T(dtype, hipLaunchKernelGGL(resample_nearest_bwd_kernel<T>, dim3(ew_grid_t(total)), dim3(256), 0,
-                                           reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const T*>(dy),
-                                           reinterpret_cast<T*>(dx), N, Hs, Ws, Hd / Hs, Wd / Ws, C / 4, dy_cstride, dy_coff));
-  YV4_CHECK_LAUNCH("resample_nearest_bwd");
-  return YV4_OK;
 }

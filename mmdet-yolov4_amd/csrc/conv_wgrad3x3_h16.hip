@@ -1,6 +1,6 @@
 // The kw-shared 3x3 weight gradient on gfx950: both forms of the kernel (the first in the measurement build only),
 // its domain test (wgrad3x3_applies) and its launch function (wgrad3x3_launch).  The dispatcher, wgrad_impl, is in
-// train.hip; what the weight gradient replaces in the reference's training step is said there.
+// conv_wgrad.hip; what the weight gradient replaces in the reference's training step is said there.
 #include "wgrad_common.h"
 
 namespace yv4 {
@@ -9,7 +9,7 @@ namespace yv4 {
 // Weight gradient of the 3x3 / stride-1 / pad-1 layers with Cin % 128 == 0 (71 % of YOLOv4-L's weight-gradient FLOPs):
 // the three kw taps of one (kh, 128-channel chunk) share ONE LDS image of the slice's source pixels.
 //   dW[co][kh][kw][ci] = sum_m dY[m][co] * X[m + (kh - 1) W + (kw - 1)][ci]      (flattened pixel index m; borders masked)
-// The generic 16-bit kernel (train.hip) fetches 32 KB per 64-row slice for a 128 x 128 tile of dW (64 FLOP per byte of LDS fill, the regime
+// The generic 16-bit kernel (conv_wgrad.hip) fetches 32 KB per 64-row slice for a 128 x 128 tile of dW (64 FLOP per byte of LDS fill, the regime
 // in which the forward tiles sit at the L2 -> LDS limit).  Here an 8-wave workgroup owns 128 co x (3 kw x 128 ci) of dW
 // and one chunk of the M reduction: per slice the 64 rows of dY and the 66 source pixels of X (one image for all three
 // kw: operand row = reduction row + kw) are 32.5 KB of fill for 6.3 MFLOP -- 190 FLOP per byte -- and a wave (64 co x 32
@@ -54,8 +54,8 @@ __global__ __launch_bounds__(kW3Threads, 2) void conv_wgrad3x3_h16_kernel(WgradA
   if (m_lo >= m_hi) return;
   const int NHW = p.N * p.H * p.W;
 
-  const u32x4_t rsX = make_rsrc_t(p.x, x_bytes);
-  const u32x4_t rsD = make_rsrc_t(p.dy, dy_bytes);
+  const u32x4_t rsX = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsD = make_rsrc(p.dy, dy_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_w3;
 
@@ -90,17 +90,17 @@ __global__ __launch_bounds__(kW3Threads, 2) void conv_wgrad3x3_h16_kernel(WgradA
       const int m = m_base + 8 * wave + 4 * q + srow;
       unsigned doff = kOOB;
       if (live && m < m_hi && d_col[q] >= 0) doff = (unsigned)((((int64_t)m * p.dy_cs) + p.dy_co + d_col[q]) * 2);
-      lds_dma16_t(rsD, lb + (unsigned)(4 * q * kRowB), doff, 0u);
+      lds_dma16(rsD, lb + (unsigned)(4 * q * kRowB), doff, 0u);
       const int pix = m_base + x_row[q] + x_shift;
       unsigned xoff = kOOB;
       if (live && (unsigned)pix < (unsigned)NHW) xoff = (unsigned)((((int64_t)pix * p.x_cs) + p.x_co + x_col[q]) * 2);
-      lds_dma16_t(rsX, lb + (unsigned)(kDBytes + 4 * q * kRowB), xoff, 0u);
+      lds_dma16(rsX, lb + (unsigned)(kDBytes + 4 * q * kRowB), xoff, 0u);
     }
     if (wave == 0) {
       const int pix = m_base + x_row[2] + x_shift;
       unsigned xoff = kOOB;
       if (live && x_row[2] < 66 && (unsigned)pix < (unsigned)NHW) xoff = (unsigned)((((int64_t)pix * p.x_cs) + p.x_co + x_col[2]) * 2);
-      lds_dma16_t(rsX, lds_base + (unsigned)(buf * kW3BufBytes + kDBytes + 64 * kRowB), xoff, 0u);
+      lds_dma16(rsX, lds_base + (unsigned)(buf * kW3BufBytes + kDBytes + 64 * kRowB), xoff, 0u);
     }
   };
 
@@ -309,8 +309,8 @@ __global__ __launch_bounds__(kW3Threads, 2) void conv_wgrad3x3_v2_h16_kernel(Wgr
   if (m_lo >= m_hi) return;
   const int NHW = p.N * p.H * p.W;
 
-  const u32x4_t rsX = make_rsrc_t(p.x, x_bytes);
-  const u32x4_t rsD = make_rsrc_t(p.dy, dy_bytes);
+  const u32x4_t rsX = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsD = make_rsrc(p.dy, dy_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_w3b;
 
@@ -348,13 +348,13 @@ __global__ __launch_bounds__(kW3Threads, 2) void conv_wgrad3x3_v2_h16_kernel(Wgr
     const unsigned lb = lds_base + (unsigned)(buf * kW3BufBytes + 8 * wave * kRowB);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      lds_dma16_t(rsD, lb + (unsigned)(4 * q * kRowB), d_off[q] < d_lim[q] ? d_off[q] : kOOB, 0u);
-      lds_dma16_t(rsX, lb + (unsigned)(kDBytes + 4 * q * kRowB), x_off[q] < x_lim[q] ? x_off[q] : kOOB, 0u);
+      lds_dma16(rsD, lb + (unsigned)(4 * q * kRowB), d_off[q] < d_lim[q] ? d_off[q] : kOOB, 0u);
+      lds_dma16(rsX, lb + (unsigned)(kDBytes + 4 * q * kRowB), x_off[q] < x_lim[q] ? x_off[q] : kOOB, 0u);
       d_off[q] += d_step;
       x_off[q] += x_step;
     }
     if (wave == 0) {
-      lds_dma16_t(rsX, lds_base + (unsigned)(buf * kW3BufBytes + kDBytes + 64 * kRowB), x_off[2] < x_lim[2] ? x_off[2] : kOOB, 0u);
+      lds_dma16(rsX, lds_base + (unsigned)(buf * kW3BufBytes + kDBytes + 64 * kRowB), x_off[2] < x_lim[2] ? x_off[2] : kOOB, 0u);
       x_off[2] += x_step;
     }
     if (wave == 1) {

@@ -1,6 +1,6 @@
 // The few-channel 3x3 weight gradient on gfx950: both forms of the kernel (the first in the measurement build only),
 // its domain test (wgrad_fc_cin) and its launch function (wgrad_fc_launch).  The dispatcher, wgrad_impl, is in
-// train.hip; what the weight gradient replaces in the reference's training step is said there.
+// conv_wgrad.hip; what the weight gradient replaces in the reference's training step is said there.
 #include "wgrad_common.h"
 
 namespace yv4 {
@@ -8,7 +8,7 @@ namespace yv4 {
 // ---------------------------------------------------------------------------------
 // Weight gradient of the 3x3 / stride-1 / pad-1 layers with FEW channels (Cin 16, 32 or 64 per pixel, Cout 32 or 64):
 // the stem, the first Bottleneck and the first CSP stage of CSPDarknet at 608 / 304 / 152 pixels.  These layers are bound
-// by their bytes (dY + X once = 0.23-0.45 ms at batch 64) and the 128 x 128 tiles of train.hip serve them badly: dW is 32-64
+// by their bytes (dY + X once = 0.23-0.45 ms at batch 64) and the 128 x 128 tiles of conv_wgrad.hip serve them badly: dW is 32-64
 // rows by 72-576 columns, so a tile is mostly padding, every column tile re-reads dY, and the im2col operand fetches
 // every source pixel nine times -- 960 bytes of LDS fill per output pixel for the 32 -> 64 layer, three times what the
 // memory system delivers per unit time to 64 KB of slice buffers per CU (0.65-0.9 ms per layer).
@@ -69,8 +69,8 @@ __global__ __launch_bounds__(kFcThreads, (FcGeom<CIN, COUT>::WGs)) void conv_wgr
   const int m_hi = min(m_lo + p.rows_per_chunk, p.M);
   if (m_lo >= m_hi) return;
   const int NHW = p.N * p.H * p.W;
-  const u32x4_t rsX = make_rsrc_t(p.x, x_bytes);
-  const u32x4_t rsD = make_rsrc_t(p.dy, dy_bytes);
+  const u32x4_t rsX = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsD = make_rsrc(p.dy, dy_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_fc;
   auto swz128 = [](int row) { return ((row >> 1) & 1) << 2; };         // 128-byte rows only
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kFcThreads, (FcGeom<CIN, COUT>::WGs)) void conv_wgr
       if (pc_kind[i] == 0) {
         if (live && m_base + pc_row[i] < m_hi) off = pc_off0[i] + (unsigned)sl * d_step;
         dst = lds_base + (unsigned)(buf * G::BufBytes) + pc_lds[i];
-        lds_dma16_t(rsD, dst, off, 0u);
+        lds_dma16(rsD, dst, off, 0u);
       } else {
         if (pc_kind[i] > 0) {
           const int pix = m_base + pc_row[i];
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(kFcThreads, (FcGeom<CIN, COUT>::WGs)) void conv_wgr
           if (ok) off = pc_off0[i] + (unsigned)sl * x_step;
           dst = lds_base + (unsigned)(buf * G::BufBytes) + pc_lds[i];
         }
-        lds_dma16_t(rsX, dst, off, 0u);
+        lds_dma16(rsX, dst, off, 0u);
       }
     }
   };
@@ -340,8 +340,8 @@ __global__ __launch_bounds__(kFcThreads, (FcGeom<CIN, COUT>::WGs)) void conv_wgr
   const int m_hi = min(m_lo + p.rows_per_chunk, p.M);
   if (m_lo >= m_hi) return;
   const int NHW = p.N * p.H * p.W;
-  const u32x4_t rsX = make_rsrc_t(p.x, x_bytes);
-  const u32x4_t rsD = make_rsrc_t(p.dy, dy_bytes);
+  const u32x4_t rsX = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsD = make_rsrc(p.dy, dy_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_fc;
   auto swz128 = [](int row) { return ((row >> 1) & 1) << 2; };         // 128-byte rows only
@@ -396,13 +396,13 @@ __global__ __launch_bounds__(kFcThreads, (FcGeom<CIN, COUT>::WGs)) void conv_wgr
     for (int i = 0; i < G::PW; ++i) {
       const unsigned off = pc_off[i] < pc_lim[i] ? pc_off[i] : kOOB;
       if (pc_kind[i] == 0) {
-        lds_dma16_t(rsD, lds_base + (unsigned)(buf * G::BufBytes) + pc_lds[i], off, 0u);
+        lds_dma16(rsD, lds_base + (unsigned)(buf * G::BufBytes) + pc_lds[i], off, 0u);
         pc_off[i] += d_step;
       } else if (pc_kind[i] > 0) {
-        lds_dma16_t(rsX, lds_base + (unsigned)(buf * G::BufBytes) + pc_lds[i], off, 0u);
+        lds_dma16(rsX, lds_base + (unsigned)(buf * G::BufBytes) + pc_lds[i], off, 0u);
         pc_off[i] += x_step;
       } else {
-        lds_dma16_t(rsX, lds_base + (unsigned)(G::NBuf * G::BufBytes), kOOB, 0u);     // dummy: the scratch KB
+        lds_dma16(rsX, lds_base + (unsigned)(G::NBuf * G::BufBytes), kOOB, 0u);     // dummy: the scratch KB
       }
     }
     if (role_w == 7) {

@@ -356,7 +356,7 @@ inline int wide_launch(Kern kern, LdsAttrOnce& once, const char* who, const Args
     return YV4_E_UNSUPPORTED;
   }
   const long long xb = (long long)p.N * p.H * p.W * p.x_cs * esize, wb = (long long)p.Cout * p.Kw * esize;
-  if (xb >= 0xFFFFFFF0LL || wb >= 0xFFFFFFF0LL) {
+  if (!desc_addressable(xb) || !desc_addressable(wb)) {
     set_error("%s: tensors of 4 GiB or more are not addressable through a buffer descriptor", who);
     return YV4_E_UNSUPPORTED;
   }

@@ -48,8 +48,8 @@ __global__ __launch_bounds__(kWideThreads, 2) void conv_wide_h16_kernel(ConvArgs
   const int fr = lane & 15;
   const int fq = lane >> 4;
 
-  const u32x4_t rsA = make_rsrc_h(p.x, x_bytes);
-  const u32x4_t rsB = make_rsrc_h(p.w, w_bytes);
+  const u32x4_t rsA = make_rsrc(p.x, x_bytes);
+  const u32x4_t rsB = make_rsrc(p.w, w_bytes);
   constexpr unsigned kOOB = 0xFFFFFFF0u;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)smem_wg;
   const int nwg = (int)gridDim.x;
@@ -126,10 +126,10 @@ __global__ __launch_bounds__(kWideThreads, 2) void conv_wide_h16_kernel(ConvArgs
     const unsigned lb_ = lds_base + (unsigned)(2 * G_::ABytes + (SLOT) * G_::BBytes + 8 * wave * kRowB); \
     const unsigned step_ = (unsigned)((((int64_t)n_kh * p.W + n_kw) * p.x_cs + n_c0) * 2);           \
     const unsigned kb_ = (unsigned)((n_tap * p.Cin + n_c0) * 2);                                     \
-    _Pragma("unroll") for (int q = 0; q < PB; ++q) lds_dma16_h(rsB, lb_ + 64 * q * kRowB, b_off[q], kb_); \
+    _Pragma("unroll") for (int q = 0; q < PB; ++q) lds_dma16(rsB, lb_ + 64 * q * kRowB, b_off[q], kb_); \
     _Pragma("unroll") for (int q = 0; q < QA; ++q) {                                                \
       const bool ok_ = (a_mask[q] >> n_tap) & 1ull;                                                 \
-      lds_dma16_h(rsA, la_ + 64 * q * kRowB, ok_ ? a_off[q] + step_ : kOOB, 0u);                     \
+      lds_dma16(rsA, la_ + 64 * q * kRowB, ok_ ? a_off[q] + step_ : kOOB, 0u);                     \
     }                                                                                               \
     n_k += 1; n_tap += 1; n_kw += 1;                                                                \
     if (n_kw == p.KW) { n_kw = 0; n_kh += 1; }                                                      \

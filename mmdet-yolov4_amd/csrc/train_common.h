@@ -1,5 +1,6 @@
-// What the training-side translation units (train.hip, bn_train.hip) share: element access for the three operand
-// types, the dtype dispatch of the host entries and the grid of the element-wise kernels.
+// What the training-side translation units (conv_wgrad.hip, pack_weights.hip, elementwise_bwd.hip, bn_train.hip)
+// share: element access for the three operand types, the dtype dispatch of the host entries and the grid of the
+// element-wise kernels.
 #pragma once
 #include "yv4_common.h"
 

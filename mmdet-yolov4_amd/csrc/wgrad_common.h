@@ -1,29 +1,13 @@
-// Shared by the weight-gradient translation units (train.hip: the generic kernels and the dispatcher;
-// conv_wgrad3x3_h16.hip and conv_wgrad_fc_h16.hip: the two special 3x3 families): the LDS-DMA helpers, the MFMA
-// fragment types, the kernels' argument block, the (tile, chunk) mapping and the families' host functions.
+// Shared by the weight-gradient translation units (conv_wgrad.hip: the generic kernels and the dispatcher;
+// conv_wgrad3x3_h16.hip and conv_wgrad_fc_h16.hip: the two special 3x3 families): the MFMA fragment types, the
+// kernels' argument block, the (tile, chunk) mapping and the families' host functions.  (LDS-DMA helpers: lds_dma.h)
 #pragma once
 #include "yv4_common.h"
+#include "lds_dma.h"
 
 namespace yv4 {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void lds_dma16_t(u32x4_t rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory");
-}
-__device__ __forceinline__ u32x4_t make_rsrc_t(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  u32x4_t v;
-  v.x = __builtin_amdgcn_readfirstlane((unsigned)a);
-  v.y = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-  v.z = __builtin_amdgcn_readfirstlane(bytes);
-  v.w = 0x00020000u;
-  return v;
-}
 
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_w __attribute__((ext_vector_type(8)));
@@ -81,7 +65,7 @@ static inline dim3 wgrad_grid(long long tiles, long long chunks, int xcd_map) {
   return dim3((unsigned)((chunks + 7) / 8 * 8 * tiles), 1u);
 }
 
-// ---- the two special families, as the dispatcher (wgrad_chunks, wgrad_impl in train.hip) sees them: the domain
+// ---- the two special families, as the dispatcher (wgrad_chunks, wgrad_impl in conv_wgrad.hip) sees them: the domain
 // test and one launch function each.  A launch function sets the ensure_dyn_lds attributes, fills the family's fields
 // of the argument block, launches on `stream` and returns a status; the deterministic slab reduce stays with the caller.
 // (hidden: these cross translation units, not the library's boundary)

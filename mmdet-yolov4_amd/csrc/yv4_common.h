@@ -250,3 +250,13 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
 }
 
 }  // namespace yv4
+
+// Host functions that cross translation units but not the library's boundary (hidden).
+#pragma GCC visibility push(hidden)
+// conv_mfma_h16.hip: pure 16-bit convolution (identity epilogue) that also leaves the BatchNorm statistics of its output
+int conv_stats_h16(const yv4_conv_desc* d, int dtype, const void* x, const void* w, const float* ones, const float* zeros,
+                   void* y, double* stats, void* stream);
+// bn_train.hip
+int bn_partial_sums_replica0(const void* x, int dtype, int64_t M, int C, int x_cstride, int x_coff, double* stats,
+                             void* stream);
+#pragma GCC visibility pop

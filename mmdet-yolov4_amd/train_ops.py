@@ -1,4 +1,4 @@
-"""Autograd front ends of the training-side HIP kernels (``csrc/train.hip``, ``csrc/conv_wgrad*_h16.hip``, ``csrc/bn_train.hip`` + the forward conv).
+"""Autograd front ends of the training-side HIP kernels (``csrc/conv_wgrad*.hip``, ``csrc/pack_weights.hip``, ``csrc/elementwise_bwd.hip``, ``csrc/bn_train.hip`` + the forward conv).
 
 Training does not go through launch plans: modules build an ordinary autograd graph out of
 the two Functions below, on ``torch.channels_last`` tensors (logical NCHW, physical NHWC --
@@ -198,7 +198,7 @@ class _PackCache:
             rows = (d.Cin if d.transpose else d.Cout) * d.KHo * d.KWo
             icp = ((d.Cout if d.transpose else d.Cin) + d.pad_to - 1) // d.pad_to * d.pad_to
             # whole rows r (all their taps) per workgroup; the data-gradient operand is read ACROSS r (the source is
-            # contiguous along it), so its workgroups take groups of rows (pack_rows in csrc/train.hip)
+            # contiguous along it), so its workgroups take groups of rows (pack_rows in csrc/pack_weights.hip)
             taps = d.KHo * d.KWo
             group = taps * (max(8, 64 // taps) if d.transpose else 1)
             d.rows_per_block = group * max(1, self.ROWS_TARGET // (icp * group))

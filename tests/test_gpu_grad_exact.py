@@ -47,7 +47,7 @@ def _refs_checked():
 # a. weight gradient through the ABI
 # ---------------------------------------------------------------------------------------------------------------------
 def wgrad_route(dtype, N, H, W, Cin, Cout, K, s, p, x_cs, x_co):
-    """The route wgrad_impl (train.hip) picks in the default build, from wgrad_fc_cin, wgrad3x3_applies and the v2
+    """The route wgrad_impl (conv_wgrad.hip) picks in the default build, from wgrad_fc_cin, wgrad3x3_applies and the v2
     conditions (maps far below 3 GB)."""
     Ho, Wo = X.out_size(H, K, s, p), X.out_size(W, K, s, p)
     M = N * Ho * Wo

@@ -9,6 +9,8 @@ import os
 import subprocess
 import threading
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, 'lib')
 LIB_PATH = os.environ.get('YV4_LIB_PATH') or os.path.join(LIB_DIR, 'libyv4_hip.so')   # override: A/B measurement builds
@@ -19,6 +21,7 @@ ABI_VERSION = 8
 STATS_REPLICAS = 64        # YV4_STATS_REPLICAS
 GRAD_PREPARE_MAX_WG = 2048  # YV4_GRAD_PREPARE_MAX_WG
 F32, F16, BF16, F64 = 0, 1, 2, 3
+DTYPE_CODE = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}    # the element code of a tensor's dtype
 F8E4M3 = 3                 # YV4_F8E4M3: the fp8 entry points' element code (the standalone op's F64 elsewhere)
 F8TILE_128x128, F8TILE_128x64, F8TILE_64x64 = 1, 2, 3
 ACT_NONE, ACT_MISH, ACT_LEAKY, ACT_SWISH = 0, 1, 2, 3

@@ -139,6 +139,10 @@ class FlatState:
                     p._yv4_grad_in_arena = True      # conv weights: dW may be accumulated here directly (train_ops)
 
     def zero_grad(self):
+        # weight gradients still running on a side stream (a backward that raised never ran its end-of-backward join)
+        # must not land after the zeroing; a no-op after every backward that finished
+        from .direct_grad import join_side_streams
+        join_side_streams()
         self.grads.zero_()
         self.attach_grads()
 

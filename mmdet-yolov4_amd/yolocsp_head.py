@@ -115,7 +115,7 @@ class YoloLossFunction(torch.autograd.Function):
         G = int(gt.shape[0])
         d = _lib.LossDesc()
         d.num_levels, d.N, d.A, d.num_classes, d.G = L, N, A, C_, G
-        d.dtype = T._DCODE[raws[0].dtype]
+        d.dtype = _lib.DTYPE_CODE[raws[0].dtype]
         keep = []
         TA = 0
         for l in range(L):

@@ -240,21 +240,54 @@ def test_default_mode_is_not_claimed_deterministic():
 
 
 def test_side_stream_weight_gradients_are_the_same_gradients(det_mode, monkeypatch):
-    """The weight gradients run on a side stream by default (train_ops._wgrad_side_stream: off backward's critical path,
+    """The weight gradients run on a side stream by default (direct_grad._side.for_launch: off backward's critical path,
     joined by an end-of-backward callback of the autograd engine).  In deterministic mode the whole state after two
     recipe steps must be bit-identical with and without it -- a missing wait (a weight gradient reading dY before the
     BatchNorm backward wrote it, the optimizer reading .grad before the side stream finished, the arena zeroed under a
     running kernel) would show as different bits or as NaN."""
-    from mmdet_yolov4_amd import train_ops as T2
+    from mmdet_yolov4_amd import direct_grad as T2
     monkeypatch.setattr(T2, '_WGRAD_STREAM', True)
     a = _recipe_steps(torch.bfloat16, 2, 8)
-    assert T2._SIDE_STREAMS, 'the side stream was never used'
+    assert T2._side.streams, 'the side stream was never used'
     monkeypatch.setattr(T2, '_WGRAD_STREAM', False)
     b = _recipe_steps(torch.bfloat16, 2, 8)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), (a[0], b[0], a[1], b[1])
     for k in a[2]:
         assert torch.equal(a[2][k], b[2][k]), k
     assert torch.equal(a[3], b[3]) and torch.equal(a[4], b[4])
+
+
+def test_zero_grad_after_a_raised_backward_waits_for_the_side_stream(det_mode, monkeypatch):
+    """The autograd engine drops the end-of-backward join when a backward raises: a weight gradient issued on the side
+    stream before the exception is then still unjoined, and ``FlatState.zero_grad`` must wait for it before it zeroes the
+    arena -- else the gradient could land after the zeroing.  One 8 -> 8 3x3 conv on a 1 x 8 x 8 x 8 bf16 input; the
+    Function in front of the conv raises in its backward, i.e. after the conv's weight gradient has been issued."""
+    from mmdet_yolov4_amd import direct_grad as T2
+    from mmdet_yolov4_amd.flat_state import FlatState
+    monkeypatch.setattr(T2, '_WGRAD_STREAM', True)
+
+    class RaiseInBackward(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x.view_as(x)
+
+        @staticmethod
+        def backward(ctx, dy):
+            raise RuntimeError('raised behind the weight gradient')
+
+    torch.manual_seed(0)
+    conv = torch.nn.Conv2d(8, 8, 3, padding=1, bias=False).to(DEV)
+    flat = FlatState(conv)
+    flat.zero_grad()
+    x = torch.randn(1, 8, 8, 8, device=DEV).bfloat16().requires_grad_(True)
+    y = T.conv2d(RaiseInBackward.apply(x), conv.weight, 1, 1, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match='raised behind the weight gradient'):
+        y.float().sum().backward()
+    assert T.wgrad_side_stream(DEV) is not None
+    flat.zero_grad()
+    assert T.wgrad_side_stream(DEV) is None
+    torch.cuda.synchronize()
+    assert not flat.grads.any()
 
 
 @pytest.mark.parametrize('det', [False, True])

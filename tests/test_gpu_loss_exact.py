@@ -24,7 +24,6 @@ import torch
 
 import mmdet_yolov4_amd as pkg
 from mmdet_yolov4_amd import _lib, ops
-from mmdet_yolov4_amd import train_ops as T
 from mmdet_yolov4_amd.yolocsp_head import RawPredMap
 
 import _loss_ref as R
@@ -63,7 +62,7 @@ def run_abi(head, case, raws, biases, gout, dev):
     assert head.num_anchors[0] == A and (0 if head.class_agnostic else head.num_classes) == case.C
     d = _lib.LossDesc()
     d.num_levels, d.N, d.A, d.num_classes, d.G = L, N, A, case.C, G
-    d.dtype = T._DCODE[raws[0].dtype]
+    d.dtype = _lib.DTYPE_CODE[raws[0].dtype]
     TA = 0
     for l in range(L):
         n_, H, W, Cp = raws[l].shape

@@ -380,3 +380,59 @@ def test_grad_reducer_cuts_buckets_from_the_end_with_a_small_head():
     whole = GradReducer(fs, bucket_mb=1, head_mb=1)
     assert len(whole.buckets) == 1 and whole.buckets[0][:2] == [0, fs.n_param]
     whole.remove()
+
+
+# every name that package modules, tests and tools take from ``train_ops`` (``T.<name>``, ``_T.<name>``,
+# ``train_ops.<name>``, ``from .train_ops import <name>``)
+TRAIN_OPS_NAMES = (
+    # mmdet-yolov4_amd/: darknetcsp, yolo_neck_csp, yolocsp_head, yolov3, bricks, dist, flat_state, hooks, optim
+    'train_dtype', 'image_to_nhwc16', 'stats_numel', 'conv_stats_buffer', 'conv2d', 'bn_act', 'spp_cat', '_sync_group',
+    'grad_sink_for', 'GradSink', 'CatSlot', 'resample_into_ok', 'resample_into', '_fwd_depth', 'flush_batch_counters',
+    'add_direct_grad_listener', 'remove_direct_grad_listener', 'wgrad_side_stream', 'invalidate_packed_weights',
+    'join_side_streams',
+    # tests/ (tools/bn_bench.py takes bn_act)
+    'packed_weight', 'clear_pack_cache', '_PACK_CACHES', '_ROWPAIR_ON',
+)
+
+
+def test_train_ops_keeps_the_names_its_users_take():
+    """``train_ops`` was split into ``packed_weights`` / ``direct_grad`` / itself: every name its users take from it still
+    resolves there, and the re-exported ones are the very objects of their home module (a second copy of a registry or
+    of the side-stream state would silently split it)."""
+    from mmdet_yolov4_amd import direct_grad, packed_weights
+    from mmdet_yolov4_amd import train_ops as T
+    for name in TRAIN_OPS_NAMES:
+        assert hasattr(T, name), name
+    for name in ('join_side_streams', 'wgrad_side_stream', 'add_direct_grad_listener', 'remove_direct_grad_listener'):
+        assert getattr(T, name) is getattr(direct_grad, name), name
+    for name in ('invalidate_packed_weights', 'clear_pack_cache', 'packed_weight', '_PACK_CACHES'):
+        assert getattr(T, name) is getattr(packed_weights, name), name
+
+
+def test_packed_operand_staleness_predicate():
+    """The one test both operand caches use: a recorded (weak reference, version, generation) is current for its owner
+    until the owner is updated in place, ``invalidate_packed_weights()`` is called, or another tensor takes its place."""
+    import weakref
+    from mmdet_yolov4_amd import packed_weights as P
+
+    def record(t):
+        return weakref.ref(t), t._version, P._generation
+
+    w = nn.Parameter(torch.randn(4, 4, 3, 3))
+    rec = record(w)
+    assert P._is_current(*rec, w)                        # fresh
+    with torch.no_grad():
+        w.add_(1.0)
+    assert not P._is_current(*rec, w)                    # the version moved
+    rec = record(w)
+    assert P._is_current(*rec, w)
+    P.invalidate_packed_weights()
+    assert not P._is_current(*rec, w)                    # the generation moved
+    rec = record(w)
+    assert P._is_current(*rec, w)
+    other = nn.Parameter(w.detach().clone())
+    with torch.no_grad():
+        other.add_(0.0)
+    assert other._version == w._version and not P._is_current(*rec, other)      # another owner, same values and version
+    del w
+    assert rec[0]() is None and not P._is_current(*rec, other)                  # ... also once the first one is gone

@@ -22,7 +22,7 @@ def kernels(a):
     from mmdet_yolov4_amd.ops import stream_ptr
     L = _lib.lib()
     dt = dict(f32=torch.float32, bf16=torch.bfloat16, f16=torch.float16)[a.dtype]
-    code = T._DCODE[dt]
+    code = _lib.DTYPE_CODE[dt]
     es = 4 if a.dtype == 'f32' else 2
     dev = torch.device('cuda', 0)
     R = 20

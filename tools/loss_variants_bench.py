@@ -28,7 +28,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mmdet_yolov4_amd as pkg  # noqa: E402
 from mmdet_yolov4_amd import _lib, ops  # noqa: E402
-from mmdet_yolov4_amd import train_ops as T  # noqa: E402
 from mmdet_yolov4_amd.yolocsp_head import RawPredMap  # noqa: E402
 
 DEV = 'cuda:0'
@@ -79,7 +78,7 @@ class AbiCall:
         G = gt.shape[0]
         d = _lib.LossDesc()
         d.num_levels, d.N, d.A, d.num_classes, d.G = L, N, A, 80, G
-        d.dtype = T._DCODE[raws[0].dtype]
+        d.dtype = _lib.DTYPE_CODE[raws[0].dtype]
         TA = 0
         keep = [gt]
         for l in range(L):

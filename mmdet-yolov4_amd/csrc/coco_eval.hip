@@ -323,9 +323,8 @@ __global__ __launch_bounds__(kCeLanes) void ce_scan_kernel(const int32_t* __rest
   }
 }
 
-static inline size_t ce_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int ce_sort_bits(int q) { return q < 65535 ? 48 : 64; }     // the key's high word holds 0 .. q
-static inline size_t ce_hist_bytes(int64_t n) { return ce_align(sizeof(uint32_t) * 256 * (size_t)((n + kRsTile - 1) / kRsTile + 1)); }
+static inline size_t ce_hist_bytes(int64_t n) { return rs_hist_bytes(n + kRsTile); }   // reserves one tile more than rs_sort counts
 
 }  // namespace
 }  // namespace yv4
@@ -335,7 +334,7 @@ using namespace yv4;
 extern "C" size_t yv4_coco_rank_work(int64_t total_det) {
   if (total_det <= 0) return 256;
   const size_t D = (size_t)total_det;
-  return 2 * ce_align(8 * D) + ce_align(4 * D) + ce_hist_bytes(total_det);    // keys x2 | values | histogram
+  return 2 * align256(8 * D) + align256(4 * D) + ce_hist_bytes(total_det);    // keys x2 | values | histogram
 }
 
 extern "C" int yv4_coco_rank(const float* det, const int32_t* prob, int64_t total_det, int P, int max_det, int num_at,
@@ -356,9 +355,9 @@ extern "C" int yv4_coco_rank(const float* det, const int32_t* prob, int64_t tota
   const int64_t D = total_det;
   char* w = reinterpret_cast<char*>(work);
   uint64_t* kx = reinterpret_cast<uint64_t*>(w);
-  uint64_t* ky = reinterpret_cast<uint64_t*>(w + ce_align(8 * (size_t)D));
-  uint32_t* vy = reinterpret_cast<uint32_t*>(w + 2 * ce_align(8 * (size_t)D));
-  uint32_t* hist = reinterpret_cast<uint32_t*>(w + 2 * ce_align(8 * (size_t)D) + ce_align(4 * (size_t)D));
+  uint64_t* ky = reinterpret_cast<uint64_t*>(w + align256(8 * (size_t)D));
+  uint32_t* vy = reinterpret_cast<uint32_t*>(w + 2 * align256(8 * (size_t)D));
+  uint32_t* hist = reinterpret_cast<uint32_t*>(w + 2 * align256(8 * (size_t)D) + align256(4 * (size_t)D));
   const unsigned blocks = (unsigned)((D + 255) / 256);
   hipLaunchKernelGGL(ce_keys1_kernel, dim3(blocks), dim3(256), 0, s, det, prob, D, P, kx, order);
   // the first pass only reads its input, so the keys / values are sorted "in place": the result lands in (kx, order)
@@ -404,8 +403,8 @@ extern "C" size_t yv4_coco_accumulate_work(int64_t total_det, int K, int num_at)
   if (total_det < 0 || K <= 0 || num_at <= 0) return 0;
   const size_t D = (size_t)(total_det > 0 ? total_det : 1);
   // keys x2 | values x2 | histogram | cat_off | rank2 | score2 | flags2
-  return 2 * ce_align(8 * D) + 2 * ce_align(4 * D) + ce_hist_bytes((int64_t)D) + ce_align(8 * ((size_t)K + 1)) +
-         2 * ce_align(4 * D) + ce_align(D * (size_t)num_at);
+  return 2 * align256(8 * D) + 2 * align256(4 * D) + ce_hist_bytes((int64_t)D) + align256(8 * ((size_t)K + 1)) +
+         2 * align256(4 * D) + align256(D * (size_t)num_at);
 }
 
 extern "C" int yv4_coco_accumulate(const float* det, const uint32_t* order, const int32_t* sprob, const int64_t* det_off,
@@ -429,14 +428,14 @@ extern "C" int yv4_coco_accumulate(const float* det, const uint32_t* order, cons
   const size_t Dn = (size_t)(D > 0 ? D : 1);
   const int AT = A * T;
   char* w = reinterpret_cast<char*>(work);
-  uint64_t* kx = reinterpret_cast<uint64_t*>(w);                        w += ce_align(8 * Dn);
-  uint64_t* ky = reinterpret_cast<uint64_t*>(w);                        w += ce_align(8 * Dn);
-  uint32_t* vx = reinterpret_cast<uint32_t*>(w);                        w += ce_align(4 * Dn);
-  uint32_t* vy = reinterpret_cast<uint32_t*>(w);                        w += ce_align(4 * Dn);
+  uint64_t* kx = reinterpret_cast<uint64_t*>(w);                        w += align256(8 * Dn);
+  uint64_t* ky = reinterpret_cast<uint64_t*>(w);                        w += align256(8 * Dn);
+  uint32_t* vx = reinterpret_cast<uint32_t*>(w);                        w += align256(4 * Dn);
+  uint32_t* vy = reinterpret_cast<uint32_t*>(w);                        w += align256(4 * Dn);
   uint32_t* hist = reinterpret_cast<uint32_t*>(w);                      w += ce_hist_bytes((int64_t)Dn);
-  int64_t* cat_off = reinterpret_cast<int64_t*>(w);                     w += ce_align(8 * ((size_t)K + 1));
-  int32_t* rank2 = reinterpret_cast<int32_t*>(w);                       w += ce_align(4 * Dn);
-  float* score2 = reinterpret_cast<float*>(w);                          w += ce_align(4 * Dn);
+  int64_t* cat_off = reinterpret_cast<int64_t*>(w);                     w += align256(8 * ((size_t)K + 1));
+  int32_t* rank2 = reinterpret_cast<int32_t*>(w);                       w += align256(4 * Dn);
+  float* score2 = reinterpret_cast<float*>(w);                          w += align256(4 * Dn);
   uint8_t* flags2 = reinterpret_cast<uint8_t*>(w);
   const int64_t n_pr = (int64_t)T * R * K * A * M, n_rc = (int64_t)T * K * A * M;
   hipLaunchKernelGGL(ce_fill_kernel, dim3((unsigned)((n_pr + 255) / 256 < 4096 ? (n_pr + 255) / 256 : 4096)), dim3(256), 0, s,

@@ -11,6 +11,8 @@
 //   3. one workgroup per class: greedy NMS over its segment in chunks of 256, survivors
 //      of earlier chunks kept as class-offset boxes in a global scratch list
 //   4. survivors' keys (others = ~0) sorted again, the first max_out become detections
+// Candidate decode, the class-offset box, the chunk mask and the bodies of the label / segment / emit kernels are
+// nms_common.h's, the workspace layout's common part radix_sort.h's (soft_nms.hip's split path shares them).
 // Built with -ffp-contract=off (see nms_common.h).
 #include "nms_common.h"
 #include "radix_sort.h"
@@ -18,15 +20,11 @@
 namespace yv4 {
 
 constexpr int kSplitThreads = 1024;
-constexpr int kSplitChunk = 256;
 
 __global__ __launch_bounds__(256) void split_labels_kernel(const uint64_t* __restrict__ keys, int64_t n,
                                                            const int32_t* __restrict__ labels, int fused,
                                                            int32_t* __restrict__ out_labels) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t flat = (uint32_t)keys[i];
-  out_labels[i] = fused > 0 ? (int32_t)(flat % (uint32_t)fused) : (labels ? labels[flat] : 0);
+  key_labels_body(keys, n, labels, fused, out_labels);
 }
 
 // seg[c] = first sorted position with label >= c  (seg has num_classes + 1 entries)
@@ -34,12 +32,7 @@ __global__ __launch_bounds__(256) void split_segments_kernel(const int32_t* __re
                                                              int num_classes, int64_t* __restrict__ seg) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c > num_classes) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (sorted_labels[mid] < c) lo = mid + 1; else hi = mid;
-  }
-  seg[c] = lo;
+  seg[c] = label_lower_bound(sorted_labels, n, c);
 }
 
 struct SplitArgs {
@@ -56,9 +49,9 @@ struct SplitArgs {
 };
 
 __global__ __launch_bounds__(kSplitThreads) void split_class_nms_kernel(SplitArgs p) {
-  __shared__ float4 cbox[kSplitChunk];
-  __shared__ float carea[kSplitChunk];
-  __shared__ uint64_t cmask[kSplitChunk * 4];
+  __shared__ float4 cbox[kNmsChunk];
+  __shared__ float carea[kNmsChunk];
+  __shared__ uint64_t cmask[kNmsChunk * 4];
   __shared__ uint64_t calive[4];
   __shared__ int kcount;
   const int cls = blockIdx.x;
@@ -73,17 +66,15 @@ __global__ __launch_bounds__(kSplitThreads) void split_class_nms_kernel(SplitArg
   const float off = (float)cls * p.off_unit;
   if (tid == 0) kcount = 0;
   __syncthreads();
-  for (int64_t c0 = 0; c0 < n; c0 += kSplitChunk) {
-    const int cn = (int)min((int64_t)kSplitChunk, n - c0);
+  for (int64_t c0 = 0; c0 < n; c0 += kNmsChunk) {
+    const int cn = (int)min((int64_t)kNmsChunk, n - c0);
     const int kept = kcount;
-    if (tid < kSplitChunk) {
+    if (tid < kNmsChunk) {
       float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
       float ar = 0.f;
       if (tid < cn) {
-        const uint32_t flat = (uint32_t)keys[c0 + tid];
-        const uint32_t bi = p.fused > 0 ? flat / (uint32_t)p.fused : flat;
-        const float4 ob = reinterpret_cast<const float4*>(p.boxes)[bi];
-        bb = make_float4(ob.x + off, ob.y + off, ob.z + off, ob.w + off);
+        // (the label is the segment's: only the box row is decoded)
+        bb = offset_box(candidate_box(p.boxes, decode_candidate((uint32_t)keys[c0 + tid], p.fused, nullptr)), off);
         ar = (bb.z - bb.x) * (bb.w - bb.y);
       }
       cbox[tid] = bb;
@@ -91,7 +82,7 @@ __global__ __launch_bounds__(kSplitThreads) void split_class_nms_kernel(SplitArg
     }
     __syncthreads();
     {  // (a) chunk vs survivors of earlier chunks (global scratch, written by this workgroup)
-      const int i = tid & (kSplitChunk - 1);
+      const int i = tid & (kNmsChunk - 1);
       const int q = tid >> 8;
       bool dead = i >= cn;
       if (!dead) {
@@ -105,25 +96,13 @@ __global__ __launch_bounds__(kSplitThreads) void split_class_nms_kernel(SplitArg
           dead = iou_gt(bk, va[k], bj, aj, p.iou_thr, p.iou_form);
         }
       }
+      // combine the four quarters (as in nms_images_kernel; see nms_common.h for why it is not a shared function)
       const unsigned long long live = __ballot(!dead);
       if (q == 0 && (tid & 63) == 0) calive[tid >> 6] = live;
       __syncthreads();
       if (q != 0 && (tid & 63) == 0) atomicAnd(reinterpret_cast<unsigned long long*>(&calive[(tid & 255) >> 6]), live);
     }
-    {  // (b) chunk x chunk bitmask
-      const int i = tid >> 2;
-      const int w = tid & 3;
-      uint64_t bits = 0;
-      if (i < cn) {
-        const float4 bi = cbox[i];
-        const float ai = carea[i];
-        for (int jj = 0; jj < 64; ++jj) {
-          const int j = w * 64 + jj;
-          if (j > i && j < cn && iou_gt(bi, ai, cbox[j], carea[j], p.iou_thr, p.iou_form)) bits |= 1ull << jj;
-        }
-      }
-      cmask[i * 4 + w] = bits;
-    }
+    chunk_mask_row(cbox, carea, cn, tid, p.iou_thr, p.iou_form, 0, cmask);   // (b) chunk x chunk bitmask
     __syncthreads();
     if (tid == 0) {  // (c) greedy resolve
       uint64_t removed[4] = {0, 0, 0, 0};
@@ -161,55 +140,18 @@ __global__ __launch_bounds__(256) void split_emit_kernel(const uint64_t* __restr
                                                          const int32_t* __restrict__ labels, int fused, int max_out,
                                                          float* out_dets, int32_t* out_labels, int64_t* out_index,
                                                          int32_t* out_count) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  const int lim = (int)min((int64_t)max_out, n);
-  if (k < lim) {
-    const uint64_t key = sorted_keys[k];
-    if (key != ~0ull) {
-      const uint32_t flat = (uint32_t)key;
-      const uint32_t bi = fused > 0 ? flat / (uint32_t)fused : flat;
-      const float4 ob = reinterpret_cast<const float4*>(boxes)[bi];
-      out_dets[k * 5 + 0] = ob.x; out_dets[k * 5 + 1] = ob.y; out_dets[k * 5 + 2] = ob.z; out_dets[k * 5 + 3] = ob.w;
-      out_dets[k * 5 + 4] = key_to_score((uint32_t)(key >> 32));
-      out_labels[k] = fused > 0 ? (int32_t)(flat % (uint32_t)fused) : (labels ? labels[flat] : 0);
-      out_index[k] = (int64_t)flat;
-    }
-  }
-  if (k == 0) {  // count = number of valid keys among the first lim (valid keys sort first)
-    int64_t lo = 0, hi = lim;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sorted_keys[mid] != ~0ull) lo = mid + 1; else hi = mid;
-    }
-    *out_count = (int32_t)lo;
-  }
+  emit_body(sorted_keys, n, boxes, labels, fused, max_out, out_dets, out_labels, out_index, out_count);
 }
 
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct SplitLayout {
-  size_t keys_a, keys_b, keys_t, lab_a, lab_b, lab_t, hist, seg, kbox, karea, total;
+// the common pieces, then the survivors of earlier chunks: class-offset box and area per candidate
+struct SplitLayout : SplitSortLayout {
+  size_t kbox, karea, total;
+  explicit SplitLayout(int64_t n) : SplitSortLayout(n) {
+    kbox = carve.take((size_t)n * 16);
+    karea = carve.take((size_t)n * 4);
+    total = carve.off;
+  }
 };
-
-static SplitLayout split_layout(int64_t n, int num_classes) {
-  SplitLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
-  L.keys_a = take((size_t)n * 8);
-  L.keys_b = take((size_t)n * 8);
-  L.lab_a = take((size_t)n * 4);
-  L.lab_b = take((size_t)n * 4);
-  L.seg = take((size_t)(num_classes + 2) * 8);
-  L.kbox = take((size_t)n * 16);
-  L.karea = take((size_t)n * 4);
-  L.keys_t = take((size_t)n * 8);                                              // the sorts' other ping-pong side
-  L.lab_t = take((size_t)n * 4);
-  L.hist = take((size_t)256 * (size_t)((n + kRsTile - 1) / kRsTile) * 4);     // digit-major counters of a pass
-  L.total = off;
-  return L;
-}
-
-constexpr int kSplitMaxClasses = 65535;
 
 }  // namespace yv4
 
@@ -217,7 +159,7 @@ using namespace yv4;
 
 extern "C" size_t yv4_nms_split_work(int64_t n) {
   if (n <= 0 || n >= (1LL << 31)) return 0;
-  return split_layout(n, kSplitMaxClasses).total;
+  return SplitLayout(n).total;
 }
 
 extern "C" int yv4_nms_split(const uint64_t* keys, int64_t n, float max_coord, const float* boxes,
@@ -232,7 +174,7 @@ extern "C" int yv4_nms_split(const uint64_t* keys, int64_t n, float max_coord, c
   // labels are < 65536 (16 radix bits); with fused classes the class count is known, otherwise
   // the caller's labels are bounded by the same limit
   const int num_classes = fused_classes > 0 ? fused_classes : kSplitMaxClasses;
-  const SplitLayout L = split_layout(n, kSplitMaxClasses);
+  const SplitLayout L(n);
   char* w = reinterpret_cast<char*>(work);
   uint64_t* keys_a = reinterpret_cast<uint64_t*>(w + L.keys_a);
   uint64_t* keys_b = reinterpret_cast<uint64_t*>(w + L.keys_b);

@@ -21,14 +21,6 @@
 
 namespace yv4 {
 
-__device__ __forceinline__ void atomic_max_float(float* addr, float v) {
-  // valid for any mix of signs when *addr starts at -inf
-  if (v >= 0.f)
-    atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else
-    atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
-}
-
 __global__ void decode_reset_kernel(int32_t* counts, float* max_coord, int N) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < N) {
@@ -280,7 +272,6 @@ __global__ __launch_bounds__(256) void decode_filter_kernel(DecodeArgs p) {
 // The greedy result equals the sequential loop of mmcv's nms (see oracle/nms_ref.c).
 // ---------------------------------------------------------------------------------
 constexpr int kNmsThreads = 1024;
-constexpr int kChunk = 256;
 constexpr int kSortCap = 16384;   // >= split_thr (10000) rounded up to a power of two
 constexpr int kKeptLds = 1024;    // kept boxes cached in LDS; the rest are re-read from the outputs
 
@@ -362,13 +353,13 @@ __global__ __launch_bounds__(kNmsThreads) void nms_images_kernel(NmsArgs p) {
   // ---- 2. greedy NMS over sorted chunks -------------------------------------------
   // LDS carve (aliases the sort buffer)
   float4* cbox = reinterpret_cast<float4*>(lds_raw);                       // [256] class-offset boxes
-  float* carea = reinterpret_cast<float*>(cbox + kChunk);                  // [256]
-  uint64_t* cmask = reinterpret_cast<uint64_t*>(carea + kChunk);           // [256][4]
-  uint64_t* calive = cmask + kChunk * 4;                                   // [4]
+  float* carea = reinterpret_cast<float*>(cbox + kNmsChunk);               // [256]
+  uint64_t* cmask = reinterpret_cast<uint64_t*>(carea + kNmsChunk);        // [256][4]
+  uint64_t* calive = cmask + kNmsChunk * 4;                                // [4]
   float4* cobox = reinterpret_cast<float4*>(calive + 4);                   // [256] original boxes
-  uint64_t* ckey = reinterpret_cast<uint64_t*>(cobox + kChunk);            // [256]
-  int32_t* clabel = reinterpret_cast<int32_t*>(ckey + kChunk);             // [256]
-  float4* kbox = reinterpret_cast<float4*>(clabel + kChunk);               // [kKeptLds]
+  uint64_t* ckey = reinterpret_cast<uint64_t*>(cobox + kNmsChunk);         // [256]
+  int32_t* clabel = reinterpret_cast<int32_t*>(ckey + kNmsChunk);          // [256]
+  float4* kbox = reinterpret_cast<float4*>(clabel + kNmsChunk);            // [kKeptLds]
   float* karea = reinterpret_cast<float*>(kbox + kKeptLds);                // [kKeptLds]
   int32_t* kcount = reinterpret_cast<int32_t*>(karea + kKeptLds);          // [1]
   int16_t* csel = reinterpret_cast<int16_t*>(kcount + 4);                  // [256] kept candidates of the chunk, in order
@@ -391,32 +382,24 @@ __global__ __launch_bounds__(kNmsThreads) void nms_images_kernel(NmsArgs p) {
     f_ob = make_float4(0.f, 0.f, 0.f, 0.f);
     f_key = 0;
     f_lab = 0;
-    if (tid < kChunk && c0 + tid < n) {
+    if (tid < kNmsChunk && c0 + tid < n) {
       f_key = gkeys[c0 + tid];
-      const uint32_t flat = (uint32_t)f_key;
-      uint32_t bi;
-      if (p.fused_classes > 0) {
-        bi = flat / (uint32_t)p.fused_classes;
-        f_lab = (int)(flat - bi * (uint32_t)p.fused_classes);
-      } else {
-        bi = flat;
-        f_lab = ilab ? ilab[flat] : 0;
-      }
-      f_ob = reinterpret_cast<const float4*>(ibox)[bi];
+      const Candidate c = decode_candidate((uint32_t)f_key, p.fused_classes, ilab);
+      f_lab = c.label;
+      f_ob = candidate_box(ibox, c);
     }
   };
   fetch(0);
-  for (int c0 = 0; c0 < n; c0 += kChunk) {
-    const int cn = min(kChunk, n - c0);
+  for (int c0 = 0; c0 < n; c0 += kNmsChunk) {
+    const int cn = min(kNmsChunk, n - c0);
     const int kept = *kcount;
     if (kept >= p.max_out || (YV4_ABLATE(p.ablate, 8) && c0 > 0)) break;
     // stage the chunk
-    if (tid < kChunk) {
+    if (tid < kNmsChunk) {
       float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
       float ar = 0.f;
       if (tid < cn) {
-        const float off = (float)f_lab * off_unit;  // idxs.to(boxes) * (max + 1)
-        bb = make_float4(f_ob.x + off, f_ob.y + off, f_ob.z + off, f_ob.w + off);
+        bb = offset_box(f_ob, (float)f_lab * off_unit);  // idxs.to(boxes) * (max + 1)
         ar = (bb.z - bb.x) * (bb.w - bb.y);
       }
       cbox[tid] = bb;
@@ -426,10 +409,10 @@ __global__ __launch_bounds__(kNmsThreads) void nms_images_kernel(NmsArgs p) {
       clabel[tid] = f_lab;
     }
     __syncthreads();
-    fetch(c0 + kChunk);
+    fetch(c0 + kNmsChunk);
     // (a) chunk vs kept: thread -> (candidate i = tid & 255, quarter q = tid >> 8)
     {
-      const int i = tid & (kChunk - 1);
+      const int i = tid & (kNmsChunk - 1);
       const int q = tid >> 8;
       bool dead = false;
       if (i < cn) {
@@ -454,28 +437,15 @@ __global__ __launch_bounds__(kNmsThreads) void nms_images_kernel(NmsArgs p) {
       } else {
         dead = true;
       }
-      // combine the four quarters: every wave holds 64 candidates of one quarter
+      // combine the four quarters: every wave holds 64 candidates of one quarter (split_class_nms_kernel has the same
+      // lines; see nms_common.h for why they are not a shared function)
       const unsigned long long live = __ballot(!dead);
       if (q == 0 && (tid & 63) == 0) calive[tid >> 6] = live;
       __syncthreads();
       if (q != 0 && (tid & 63) == 0) atomicAnd(reinterpret_cast<unsigned long long*>(&calive[(tid & 255) >> 6]), live);
     }
     // (b) chunk x chunk bitmask: thread -> (row i = tid >> 2, word w = tid & 3)
-    {
-      const int i = tid >> 2;
-      const int w = tid & 3;
-      uint64_t bits = 0;
-      if (i < cn) {
-        const float4 bi = cbox[i];
-        const float ai = carea[i];
-        const int j0 = w * 64;
-        for (int jj = 0; jj < 64 && !YV4_ABLATE(p.ablate, 4); ++jj) {
-          const int j = j0 + jj;
-          if (j > i && j < cn && iou_gt(bi, ai, cbox[j], carea[j], p.iou_thr, p.iou_form)) bits |= 1ull << jj;
-        }
-      }
-      cmask[i * 4 + w] = bits;
-    }
+    chunk_mask_row(cbox, carea, cn, tid, p.iou_thr, p.iou_form, p.ablate, cmask);
     __syncthreads();
     // (c) the greedy resolve is sequential, but only its DECISIONS are: the walk over the live bits records the kept
     // candidates of the chunk (a ctz, four mask words and a list entry per kept box); the outputs -- five floats,
@@ -562,7 +532,7 @@ __global__ __launch_bounds__(kNmsThreads) void nms_images_kernel(NmsArgs p) {
 }
 
 constexpr size_t kNmsLdsSort = (size_t)kSortCap * sizeof(uint64_t);
-constexpr size_t kNmsLdsChunk = (size_t)kChunk * (16 + 4 + 32 + 16 + 8 + 4) + 32 + (size_t)kKeptLds * 20 + 16 + (size_t)kChunk * 2;
+constexpr size_t kNmsLdsChunk = (size_t)kNmsChunk * (16 + 4 + 32 + 16 + 8 + 4) + 32 + (size_t)kKeptLds * 20 + 16 + (size_t)kNmsChunk * 2;
 constexpr size_t kNmsLds = kNmsLdsSort > kNmsLdsChunk ? kNmsLdsSort : kNmsLdsChunk;
 
 // keys / max for the standalone batched_nms op

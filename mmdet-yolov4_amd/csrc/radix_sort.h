@@ -1,6 +1,7 @@
-// The library's stable LSD radix sort (rs_sort), shared by the NMS split path (nms_split.hip) and the top-k slot
-// tables of test-time augmentation (tta.hip).  Kernels live in an unnamed namespace: each translation unit that
-// includes this header gets its own copies.
+// The library's stable LSD radix sort (rs_sort) and the carving of the workspaces it sorts in, shared by the hard and
+// soft NMS split paths (nms_split.hip, soft_nms.hip), the top-k slot tables of test-time augmentation (tta.hip) and the
+// COCO evaluation (coco_eval.hip).  Kernels live in an unnamed namespace: each translation unit that includes this
+// header gets its own copies.
 #pragma once
 #include "yv4_common.h"
 
@@ -16,6 +17,35 @@ namespace {
 constexpr int kRsLanes = 64;
 constexpr int kRsRounds = 16;
 constexpr int kRsTile = kRsLanes * kRsRounds;
+
+// bytes of `hist` for rs_sort over n keys: the digit-major counters of a pass, hist[256][tiles]
+inline size_t rs_hist_bytes(int64_t n) { return (size_t)256 * (size_t)((n + kRsTile - 1) / kRsTile) * 4; }
+
+// Workspaces are carved into 256-byte aligned pieces: take(bytes) returns the piece's offset, `off` is the total so far.
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += align256(bytes); return o; }
+};
+
+// The pieces the hard and the soft split path have in common (n candidates of one image): three key and three label
+// buffers (a / b and the sorts' other ping-pong side t), the segment bounds of up to kSplitMaxClasses labels and the
+// sorts' counters.  Each path appends its own scratch to `carve`.
+constexpr int kSplitMaxClasses = 65535;   // labels are < 65536 (16 radix bits)
+struct SplitSortLayout {
+  size_t keys_a, keys_b, keys_t, lab_a, lab_b, lab_t, seg, hist;
+  Carve carve;
+  explicit SplitSortLayout(int64_t n) {
+    keys_a = carve.take((size_t)n * 8);
+    keys_b = carve.take((size_t)n * 8);
+    keys_t = carve.take((size_t)n * 8);
+    lab_a = carve.take((size_t)n * 4);
+    lab_b = carve.take((size_t)n * 4);
+    lab_t = carve.take((size_t)n * 4);
+    seg = carve.take((size_t)(kSplitMaxClasses + 2) * 8);
+    hist = carve.take(rs_hist_bytes(n));
+  }
+};
 
 template <class K>
 __global__ __launch_bounds__(kRsLanes) void rs_hist_kernel(const K* __restrict__ keys, int64_t n, int shift,
@@ -95,7 +125,7 @@ __global__ __launch_bounds__(kRsLanes) void rs_scatter_kernel(const K* __restric
 template <class K, class V, bool HAS_V>
 static int rs_sort(const K* kin, K* kx, K* ky, const V* vin, V* vx, V* vy, int64_t n, int bits, uint32_t* hist, hipStream_t s,
                    const char* what = "nms_split: radix sort") {
-  const int ntiles = (int)((n + kRsTile - 1) / kRsTile);
+  const int ntiles = (int)((n + kRsTile - 1) / kRsTile);   // rs_hist_bytes(n) = 256 * ntiles counters
   const K* sk = kin;
   const V* sv = vin;
   for (int pass = 0; pass * 8 < bits; ++pass) {

@@ -13,6 +13,8 @@
 //       rule against the loop).
 // Images (yv4_soft_nms_images): candidates sorted into flat-index order in LDS, up to 20 per thread in registers.
 // Split problems and large n (yv4_soft_nms_split): the same loop over entries in global memory (L2-resident scratch).
+// The split path's label / segment / emit kernels wrap nms_common.h's bodies (nms_split.hip's grouping and output
+// format); its workspace starts with radix_sort.h's SplitSortLayout.
 // Built with -ffp-contract=off (see nms_common.h).
 #include "nms_common.h"
 #include "radix_sort.h"
@@ -317,19 +319,6 @@ __device__ __forceinline__ int soft_loop(St& st, const int n, const int max_out,
   return r;
 }
 
-__device__ __forceinline__ void load_box(const float* boxes, const int32_t* labels, int fused, uint32_t flat, float4& ob,
-                                         int& lab) {
-  uint32_t bi;
-  if (fused > 0) {
-    bi = flat / (uint32_t)fused;
-    lab = (int)(flat - bi * (uint32_t)fused);
-  } else {
-    bi = flat;
-    lab = labels ? labels[flat] : 0;
-  }
-  ob = reinterpret_cast<const float4*>(boxes)[bi];
-}
-
 // ---- images ---------------------------------------------------------------------------------------------------------
 struct SoftImagesArgs {
   uint64_t* keys;
@@ -421,11 +410,8 @@ __global__ __launch_bounds__(kImgThreads) void soft_nms_images_kernel(SoftImages
       if (tid < tn && s < n) {
         const uint64_t key = sk[s];
         const uint32_t flat = (uint32_t)(key >> 32);
-        float4 ob;
-        int lab;
-        load_box(ibox, ilab, p.fused_classes, flat, ob, lab);
-        const float off = (float)lab * off_unit;          // idxs.to(boxes) * (max + 1)
-        st.b[k] = make_float4(ob.x + off, ob.y + off, ob.z + off, ob.w + off);
+        const Candidate c = decode_candidate(flat, p.fused_classes, ilab);
+        st.b[k] = offset_box(candidate_box(ibox, c), (float)c.label * off_unit);   // idxs.to(boxes) * (max + 1)
         st.s[k] = key_to_score((uint32_t)key);
         st.pos[k] = s;
       }
@@ -455,14 +441,13 @@ __global__ __launch_bounds__(kImgThreads) void soft_nms_images_kernel(SoftImages
     for (int q = tid; q < r; q += kImgThreads) {
       const int slot = (int)vidx[q];
       const uint32_t flat = (uint32_t)vkeys[slot];
-      float4 ob;
-      int lab;
-      load_box(ibox, ilab, p.fused_classes, flat, ob, lab);
+      const Candidate c = decode_candidate(flat, p.fused_classes, ilab);
+      const float4 ob = candidate_box(ibox, c);
       odet[q * 5 + 0] = ob.x;
       odet[q * 5 + 1] = ob.y;
       odet[q * 5 + 2] = ob.z;
       odet[q * 5 + 3] = ob.w;
-      olab[q] = lab;
+      olab[q] = c.label;
       oidx[q] = (int64_t)flat;
     }
   }
@@ -510,11 +495,8 @@ __global__ __launch_bounds__(kSoftThreads) void soft_nms_split_kernel(SoftSplitA
   st.kbest = -1;
   for (int j = tid; j < n; j += st.tn) {
     const uint64_t key = p.keys[lo + j];
-    float4 ob;
-    int lab;
-    load_box(p.boxes, p.labels, p.fused, (uint32_t)key, ob, lab);
-    const float off = (float)lab * p.off_unit;
-    p.gbox[lo + j] = make_float4(ob.x + off, ob.y + off, ob.z + off, ob.w + off);
+    const Candidate c = decode_candidate((uint32_t)key, p.fused, p.labels);
+    p.gbox[lo + j] = offset_box(candidate_box(p.boxes, c), (float)c.label * p.off_unit);
     p.gscore[lo + j] = key_to_score((uint32_t)(key >> 32));
     p.gpos[lo + j] = j;
   }
@@ -543,10 +525,7 @@ __global__ __launch_bounds__(kSoftThreads) void soft_nms_split_kernel(SoftSplitA
 __global__ __launch_bounds__(256) void soft_labels_kernel(const uint64_t* __restrict__ keys, int64_t n,
                                                           const int32_t* __restrict__ labels, int fused,
                                                           int32_t* __restrict__ out_labels) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t flat = (uint32_t)keys[i];
-  out_labels[i] = fused > 0 ? (int32_t)(flat % (uint32_t)fused) : (labels ? labels[flat] : 0);
+  key_labels_body(keys, n, labels, fused, out_labels);
 }
 
 // seg[c] = first position with label >= c (num_classes + 1 entries); one segment [0, n) when per_label == 0
@@ -558,12 +537,7 @@ __global__ __launch_bounds__(256) void soft_segments_kernel(const int32_t* __res
     seg[c] = c == 0 ? 0 : n;
     return;
   }
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (sorted_labels[mid] < c) lo = mid + 1; else hi = mid;
-  }
-  seg[c] = lo;
+  seg[c] = label_lower_bound(sorted_labels, n, c);
 }
 
 __global__ __launch_bounds__(256) void soft_emit_kernel(const uint64_t* __restrict__ sel, int64_t n,
@@ -571,63 +545,26 @@ __global__ __launch_bounds__(256) void soft_emit_kernel(const uint64_t* __restri
                                                         const int32_t* __restrict__ labels, int fused, int max_out,
                                                         float* out_dets, int32_t* out_labels, int64_t* out_index,
                                                         int32_t* out_count, const int32_t* overflow) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (*overflow) {
-    if (k == 0) *out_count = -2;
+    if (blockIdx.x * blockDim.x + threadIdx.x == 0) *out_count = -2;
     return;
   }
-  const int lim = (int)min((int64_t)max_out, n);
-  if (k < lim) {
-    const uint64_t key = sel[k];
-    if (key != ~0ull) {
-      const uint32_t flat = (uint32_t)key;
-      float4 ob;
-      int lab;
-      load_box(boxes, labels, fused, flat, ob, lab);
-      out_dets[k * 5 + 0] = ob.x; out_dets[k * 5 + 1] = ob.y; out_dets[k * 5 + 2] = ob.z; out_dets[k * 5 + 3] = ob.w;
-      out_dets[k * 5 + 4] = key_to_score((uint32_t)(key >> 32));
-      out_labels[k] = lab;
-      out_index[k] = (int64_t)flat;
-    }
-  }
-  if (k == 0) {  // count = valid keys among the first lim (valid keys come first)
-    int64_t a = 0, b = lim;
-    while (a < b) {
-      const int64_t mid = (a + b) >> 1;
-      if (sel[mid] != ~0ull) a = mid + 1; else b = mid;
-    }
-    *out_count = (int32_t)a;
-  }
+  emit_body(sel, n, boxes, labels, fused, max_out, out_dets, out_labels, out_index, out_count);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-constexpr int kSoftMaxClasses = 65535;
-
-struct SoftSplitLayout {
-  size_t keys_a, keys_b, keys_t, lab_a, lab_b, lab_t, seg, gbox, gscore, gpos, sel, hist, flag, total;
+// the common pieces, then the entries in global memory (class-offset box, current score, position word), the
+// selections per slot and the overflow flag
+struct SoftSplitLayout : SplitSortLayout {
+  size_t gbox, gscore, gpos, sel, flag, total;
+  explicit SoftSplitLayout(int64_t n) : SplitSortLayout(n) {
+    gbox = carve.take((size_t)n * 16);
+    gscore = carve.take((size_t)n * 4);
+    gpos = carve.take((size_t)n * 4);
+    sel = carve.take((size_t)n * 8);
+    flag = carve.take(4);
+    total = carve.off;
+  }
 };
-
-SoftSplitLayout soft_split_layout(int64_t n) {
-  SoftSplitLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
-  L.keys_a = take((size_t)n * 8);
-  L.keys_b = take((size_t)n * 8);
-  L.keys_t = take((size_t)n * 8);
-  L.lab_a = take((size_t)n * 4);
-  L.lab_b = take((size_t)n * 4);
-  L.lab_t = take((size_t)n * 4);
-  L.seg = take((size_t)(kSoftMaxClasses + 2) * 8);
-  L.gbox = take((size_t)n * 16);
-  L.gscore = take((size_t)n * 4);
-  L.gpos = take((size_t)n * 4);
-  L.sel = take((size_t)n * 8);
-  L.hist = take((size_t)256 * (size_t)((n + kRsTile - 1) / kRsTile) * 4);
-  L.flag = take(4);
-  L.total = off;
-  return L;
-}
 
 int soft_words(int64_t n) { return (int)(n / 64) + 2; }
 size_t soft_split_lds(int64_t n) { return (size_t)soft_words(n) * (8 + 4) + (size_t)kSoftMoveBatch * 4 + 16; }
@@ -675,7 +612,7 @@ extern "C" int yv4_soft_nms_images(uint64_t* keys, int64_t key_cap, const int32_
 
 extern "C" size_t yv4_soft_nms_split_work(int64_t n) {
   if (n <= 0 || n >= (1LL << 31)) return 0;
-  return soft_split_layout(n).total;
+  return SoftSplitLayout(n).total;
 }
 
 extern "C" int yv4_soft_nms_split(const uint64_t* keys, int64_t n, float max_coord, const float* boxes,
@@ -687,14 +624,14 @@ extern "C" int yv4_soft_nms_split(const uint64_t* keys, int64_t n, float max_coo
   YV4_REQUIRE(keys && boxes && work && out_dets && out_labels && out_index && out_count, "soft_nms_split: null pointer");
   YV4_REQUIRE(n > 0 && n < (1LL << 31), "soft_nms_split: n out of range");
   YV4_REQUIRE(per_label == 1 || n <= kSoftGlobalCap, "soft_nms_split: one problem of at most %d candidates", kSoftGlobalCap);
-  YV4_REQUIRE(max_out > 0 && fused_classes >= 0 && fused_classes <= kSoftMaxClasses,
+  YV4_REQUIRE(max_out > 0 && fused_classes >= 0 && fused_classes <= kSplitMaxClasses,
               "soft_nms_split: bad max_out / classes");
   YV4_REQUIRE(per_label == 0 || per_label == 1, "soft_nms_split: per_label must be 0 or 1");
   YV4_REQUIRE(((uintptr_t)boxes & 15) == 0 && ((uintptr_t)work & 255) == 0,
               "soft_nms_split: boxes must be 16-byte and work 256-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int num_classes = per_label ? (fused_classes > 0 ? fused_classes : kSoftMaxClasses) : 1;
-  const SoftSplitLayout L = soft_split_layout(n);
+  const int num_classes = per_label ? (fused_classes > 0 ? fused_classes : kSplitMaxClasses) : 1;
+  const SoftSplitLayout L(n);
   char* w = reinterpret_cast<char*>(work);
   uint64_t* keys_a = reinterpret_cast<uint64_t*>(w + L.keys_a);
   uint64_t* keys_b = reinterpret_cast<uint64_t*>(w + L.keys_b);

@@ -118,14 +118,6 @@ struct MergeArgs {
   float* max_coord;
 };
 
-__device__ __forceinline__ void atomic_max_float_tta(float* addr, float v) {
-  // valid for any mix of signs when *addr starts at -inf (as postproc.hip's)
-  if (v >= 0.f)
-    atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else
-    atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
-}
-
 __global__ __launch_bounds__(256) void tta_merge_kernel(MergeArgs p) {
   __shared__ int wg_count, wg_base;
   __shared__ float wg_max[4];
@@ -187,7 +179,7 @@ __global__ __launch_bounds__(256) void tta_merge_kernel(MergeArgs p) {
   __syncthreads();
   if (threadIdx.x == 0) {
     mx = fmaxf(fmaxf(wg_max[0], wg_max[1]), fmaxf(wg_max[2], wg_max[3]));
-    if (mx > -__builtin_huge_valf()) atomic_max_float_tta(&p.max_coord[n], mx);
+    if (mx > -__builtin_huge_valf()) atomic_max_float(&p.max_coord[n], mx);
   }
 }
 
@@ -202,21 +194,18 @@ static int64_t slot_layout(int num_levels, const int32_t* level_anchors, int nms
   return S;
 }
 
+// the radix path's workspace: the keys of one (image, level), the sort's two sides and its counters
 struct RadixWork {
   size_t keys, kx, ky, hist, total;
+  explicit RadixWork(int64_t n) {
+    Carve c;
+    keys = c.take((size_t)n * 8);
+    kx = c.take((size_t)n * 8);
+    ky = c.take((size_t)n * 8);
+    hist = c.take(rs_hist_bytes(n));
+    total = c.off;
+  }
 };
-
-static RadixWork radix_layout(int64_t n) {
-  RadixWork L;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) & ~(size_t)255; return o; };
-  L.keys = take((size_t)n * 8);
-  L.kx = take((size_t)n * 8);
-  L.ky = take((size_t)n * 8);
-  L.hist = take((size_t)256 * (size_t)((n + kRsTile - 1) / kRsTile) * 4);
-  L.total = off;
-  return L;
-}
 
 }  // namespace yv4
 
@@ -229,7 +218,7 @@ extern "C" size_t yv4_topk_slots_work(int num_levels, const int32_t* level_ancho
   int64_t biggest = 0;
   for (int l = 0; l < num_levels; ++l)
     if (k_l[l] < level_anchors[l] && k_l[l] > kSlotCap && level_anchors[l] > biggest) biggest = level_anchors[l];
-  return biggest ? radix_layout(biggest).total : 0;
+  return biggest ? RadixWork(biggest).total : 0;
 }
 
 extern "C" int yv4_topk_slots(const float* conf, int N, int64_t total_anchors, int num_levels,
@@ -269,7 +258,7 @@ extern "C" int yv4_topk_slots(const float* conf, int N, int64_t total_anchors, i
     for (int l = 0; l < num_levels; ++l) {
       const int nl = p.n_l[l], k = p.k_l[l];
       if (!(k < nl && k > kSlotCap)) continue;
-      const RadixWork L = radix_layout(nl);
+      const RadixWork L(nl);
       char* w = reinterpret_cast<char*>(work);
       uint64_t* keys = reinterpret_cast<uint64_t*>(w + L.keys);
       uint64_t* kx = reinterpret_cast<uint64_t*>(w + L.kx);

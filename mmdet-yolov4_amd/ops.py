@@ -111,49 +111,151 @@ def nhwc_to_nchw(src, dst, C_, H, W, src_cstride, src_coff=0):
 
 # ---- NMS ----------------------------------------------------------------------------
 SPLIT_THR_DEFAULT = 10000
-
-
 FAST_NMS_CAP = 16384   # candidates one workgroup sorts in LDS (csrc/postproc.hip kSortCap)
+SOFT_NMS_CAP = 10240   # candidates the soft-NMS images kernel holds in registers (csrc/soft_nms.hip kSoftRegCap)
+SOFT_NMS_PROBLEM_CAP = 1 << 19   # candidates of one problem of yv4_soft_nms_split (kSoftGlobalCap)
+_SOFT_NMS_ARGS = ('iou_threshold', 'sigma', 'min_score', 'method', 'offset')
+POST_NMS_KERNEL = {'nms': 'nms_images', 'soft_nms': 'soft_nms_images'}     # a plan's op name per ``nms_spec`` type
 
 
-def _nms_single(boxes, scores, labels, iou_threshold, max_out, split_thr, class_agnostic=False):
-    """One image through yv4_nms_prepare + yv4_nms_images (n < split_thr) or yv4_nms_split.
-    Returns (dets(k,5), keep(k,))."""
+def _soft_params(cfg, who):
+    """mmcv soft_nms' arguments in ``cfg`` (its names; defaults 0.3 / 0.5 / 1e-3 / 'linear') -> the kernels' parameters
+    ``dict(iou_thr, sigma, min_score, method)``, method as its YV4_SOFT_NMS_* code.  A key soft_nms does not take raises
+    TypeError, an offset other than 0 NotImplementedError, an unknown method or sigma <= 0 with 'gaussian' ValueError."""
+    bad = sorted(set(cfg) - set(_SOFT_NMS_ARGS))
+    if bad:
+        raise TypeError(f'{who}: soft_nms takes no nms_cfg keys {bad}')
+    if cfg.get('offset', 0) != 0:
+        raise NotImplementedError(f'{who}: only offset=0 is built')
+    method = cfg.get('method', 'linear')
+    if method not in _lib.SOFT_NMS_METHODS:
+        raise ValueError(f'soft_nms: method {method!r} is not one of {sorted(_lib.SOFT_NMS_METHODS)}')
+    method = _lib.SOFT_NMS_METHODS[method]
+    sigma = float(cfg.get('sigma', 0.5))
+    if method == _lib.SOFT_NMS_GAUSSIAN and not sigma > 0:
+        raise ValueError('soft_nms: sigma must be > 0 for the gaussian method')
+    return dict(iou_thr=float(cfg.get('iou_threshold', 0.3)), sigma=sigma, min_score=float(cfg.get('min_score', 1e-3)),
+                method=method)
+
+
+def nms_spec(nms_cfg):
+    """``test_cfg.nms`` -> what a plan's post-processing launches: ``dict(type='nms', iou_thr, split_thr)`` or
+    ``dict(type='soft_nms', iou_thr, sigma, min_score, method (YV4_SOFT_NMS_* code), split_thr)`` (mmcv soft_nms'
+    defaults 0.3 / 0.5 / 1e-3 / 'linear').  Other types raise NotImplementedError; a soft-NMS key the op does not take
+    raises TypeError.  ``max_num`` with soft-NMS (mmcv applies it in the split branch only, and the single call refuses
+    it) is not built into plans."""
+    cfg = dict(nms_cfg)
+    nms_type = cfg.pop('type', 'nms')
+    split_thr = cfg.pop('split_thr', SPLIT_THR_DEFAULT)
+    if nms_type == 'nms':
+        return dict(type='nms', iou_thr=cfg.get('iou_threshold', cfg.get('iou_thr')), split_thr=split_thr)
+    if nms_type != 'soft_nms':
+        raise NotImplementedError(f'nms type {nms_type!r} is not built ("nms", "soft_nms")')
+    cfg.pop('class_agnostic', None)              # the head's own class_agnostic decides, as for "nms"
+    if 'max_num' in cfg:
+        raise NotImplementedError('soft_nms with max_num is not built into plans')
+    return dict(_soft_params(cfg, 'soft_nms'), type='soft_nms', split_thr=split_thr)
+
+
+def _nms_images(spec, keys, key_cap, counts, max_coord, boxes, boxes_per_image, labels, label_stride, fused_classes, N,
+                max_out, split_thr, dets, olab, oidx, ocnt, stream):
+    """``yv4_nms_images``, or ``yv4_soft_nms_images`` when ``spec['type']`` is 'soft_nms', over N images' candidate
+    keys.  The buffers are device addresses (``labels`` may be None); ``spec`` as ``nms_spec`` returns it."""
+    L = _lib.lib()
+    head = (keys, key_cap, counts, max_coord, boxes, boxes_per_image, labels, label_stride, fused_classes, N)
+    tail = (max_out, int(split_thr), dets, olab, oidx, ocnt, stream)
+    if spec['type'] == 'soft_nms':
+        check(L.yv4_soft_nms_images(*head, spec['method'], spec['iou_thr'], spec['sigma'], spec['min_score'], *tail),
+              'yv4_soft_nms_images')
+    else:
+        check(L.yv4_nms_images(*head, float(spec['iou_thr']), *tail), 'yv4_nms_images')
+
+
+def post_nms(post, stream):
+    """The per-image NMS of a plan's post-processing dictionary (``Plan.postprocess`` / ``tta.emit_tta_post``) on
+    ``stream``, hard or soft as ``post['nms']`` says: the classes are fused into the candidate index."""
+    _nms_images(post['nms'], post['keys'].data_ptr(), post['key_cap'], post['counts'].data_ptr(),
+                post['max_coord'].data_ptr(), post['boxes'].data_ptr(), post['total_anchors'], None, 0,
+                post['num_classes'], post['N'], post['max_per_img'], post['split_thr'], post['dets'].data_ptr(),
+                post['labels'].data_ptr(), post['index'].data_ptr(), post['count'].data_ptr(), stream)
+
+
+def split_nms_image(spec, keys, n, max_coord, boxes, labels, fused_classes, max_out, dets, olab, oidx, ocnt, per_label=1):
+    """One image's n candidates (a host value) through ``yv4_nms_split`` or, for soft-NMS, ``yv4_soft_nms_split``; the
+    workspace is allocated here.  ``max_coord``: the host value of the class-offset unit minus one; -1.0 means no class
+    offset (unit 0: the labels still group the candidates, as mmcv's split branch does when class_agnostic).
+    ``per_label`` 0 (soft-NMS only): one problem over all candidates, in selection order."""
+    L = _lib.lib()
+    soft = spec['type'] == 'soft_nms'
+    nbytes = int((L.yv4_soft_nms_split_work if soft else L.yv4_nms_split_work)(n))
+    if nbytes == 0 or (soft and not per_label and n > SOFT_NMS_PROBLEM_CAP):
+        raise NotImplementedError(f'{"soft-" if soft else ""}NMS over {n} candidates in one problem is not built'
+                                  + (f' (at most {SOFT_NMS_PROBLEM_CAP})' if soft else ''))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device)
+    head = (_ptr(keys), n, float(max_coord), _ptr(boxes), _ptr(labels), fused_classes)
+    tail = (max_out, _ptr(work), _ptr(dets), _ptr(olab), _ptr(oidx), _ptr(ocnt), stream_ptr())
+    if not soft:
+        check(L.yv4_nms_split(*head, float(spec['iou_thr']), *tail), 'yv4_nms_split')
+        return
+    check(L.yv4_soft_nms_split(*head, int(per_label), spec['method'], spec['iou_thr'], spec['sigma'], spec['min_score'],
+                               *tail), 'yv4_soft_nms_split')
+    if int(ocnt.item()) == -2:
+        raise NotImplementedError(f'soft-NMS: a label with more than {SOFT_NMS_PROBLEM_CAP} candidates is not built')
+
+
+def soft_nms_split(keys, n, max_coord, boxes, labels, fused_classes, per_label, spec, max_out, dets, olab, oidx, ocnt):
+    """``split_nms_image`` for a soft-NMS parameter dict, under its earlier name and argument order."""
+    split_nms_image(dict(spec, type='soft_nms'), keys, n, max_coord, boxes, labels, fused_classes, max_out, dets, olab,
+                    oidx, ocnt, per_label=per_label)
+
+
+def _nms_single(boxes, scores, labels, spec, max_out, split_thr, class_agnostic=False, single_in_global=False):
+    """One image's boxes through yv4_nms_prepare and the NMS of ``spec`` (``nms_spec``'s dict; hard NMS needs its
+    ``type`` and ``iou_thr`` only): the images kernel below split_thr, the split path per label from split_thr.  Between
+    the two, soft-NMS over more than SOFT_NMS_CAP candidates is one problem in global memory; ``single_in_global`` takes
+    that form at any size (tests run the same candidates through both).  No class offset when ``class_agnostic``: the
+    images kernels get no labels (label 0), the split path, whose labels still group, max_coord = -1.0.  Returns
+    (dets(k,5), keep(k,))."""
+    soft = spec['type'] == 'soft_nms'
     n = boxes.shape[0]
     dev = boxes.device
-    L = _lib.lib()
     keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
     counts = torch.empty(1, dtype=torch.int32, device=dev)
     maxc = torch.empty(1, dtype=torch.float32, device=dev)
-    check(L.yv4_nms_prepare(_ptr(boxes), _ptr(scores), n, _ptr(keys), _ptr(counts), _ptr(maxc),
-                            stream_ptr()), 'yv4_nms_prepare')
-    cap = max_out if max_out > 0 else n
-    cap = max(min(cap, n), 1)
+    check(_lib.lib().yv4_nms_prepare(_ptr(boxes), _ptr(scores), n, _ptr(keys), _ptr(counts), _ptr(maxc), stream_ptr()),
+          'yv4_nms_prepare')
+    cap = max(min(max_out if max_out > 0 else n, n), 1)
     dets = torch.empty((cap, 5), dtype=torch.float32, device=dev)
     olab = torch.empty(cap, dtype=torch.int32, device=dev)
     oidx = torch.empty(cap, dtype=torch.int64, device=dev)
     ocnt = torch.empty(1, dtype=torch.int32, device=dev)
-    if n < split_thr:
-        if n > FAST_NMS_CAP:
-            raise NotImplementedError(
-                f'single-call NMS over {n} > {FAST_NMS_CAP} candidates is not built '
-                "(mmcv's default split_thr=10000 switches to the per-class path before that)")
-        check(L.yv4_nms_images(_ptr(keys), n, _ptr(counts), _ptr(maxc), _ptr(boxes), n,
-                               None if class_agnostic else _ptr(labels), n, 0, 1, float(iou_threshold), cap,
-                               split_thr, _ptr(dets), _ptr(olab), _ptr(oidx), _ptr(ocnt), stream_ptr()),
-              'yv4_nms_images')
+    lab = None if class_agnostic else labels
+    if n < split_thr and not single_in_global and n <= (SOFT_NMS_CAP if soft else FAST_NMS_CAP):
+        _nms_images(spec, _ptr(keys), n, _ptr(counts), _ptr(maxc), _ptr(boxes), n, _ptr(lab), n, 0, 1, cap, split_thr,
+                    _ptr(dets), _ptr(olab), _ptr(oidx), _ptr(ocnt), stream_ptr())
+    elif n < split_thr and not soft:
+        raise NotImplementedError(
+            f'single-call NMS over {n} > {FAST_NMS_CAP} candidates is not built '
+            "(mmcv's default split_thr=10000 switches to the per-class path before that)")
     else:
-        # mmcv's split branch loops over unique(idxs) even when class_agnostic (then without the
-        # coordinate offset): max_coord = -1 makes the offset unit zero.
-        work = torch.empty(max(L.yv4_nms_split_work(n), 256), dtype=torch.uint8, device=dev)
-        mc = -1.0 if class_agnostic else float(maxc.item())
-        check(L.yv4_nms_split(_ptr(keys), n, mc, _ptr(boxes), _ptr(labels), 0,
-                              float(iou_threshold), cap, _ptr(work), _ptr(dets), _ptr(olab),
-                              _ptr(oidx), _ptr(ocnt), stream_ptr()), 'yv4_nms_split')
+        # mmcv's split branch loops over unique(idxs) even when class_agnostic (then without the coordinate offset)
+        mc = -1.0 if class_agnostic else maxc.item()
+        per_label = n >= split_thr
+        split_nms_image(spec, keys, n, mc, boxes, labels if per_label else lab, 0, cap, dets, olab, oidx, ocnt,
+                        per_label=per_label)
     k = int(ocnt.item())
     if k < 0:
-        raise RuntimeError('yv4_nms_images flagged the split path unexpectedly')
+        raise RuntimeError(f'yv4_{"soft_" if soft else ""}nms_images flagged the split path unexpectedly')
     return dets[:k], oidx[:k]
+
+
+def _soft_single(boxes, scores, labels, spec, *args, **kwargs):
+    """``_nms_single`` for a soft-NMS parameter dict (with or without its ``type``)."""
+    return _nms_single(boxes, scores, labels, dict(spec, type='soft_nms'), *args, **kwargs)
+
+
+def _no_detections(boxes):
+    return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
 
 
 def nms(boxes, scores, iou_threshold, offset=0, score_threshold=0, max_num=-1):
@@ -173,103 +275,11 @@ def nms(boxes, scores, iou_threshold, offset=0, score_threshold=0, max_num=-1):
         inds = valid.nonzero(as_tuple=False).squeeze(1)
         boxes, scores = boxes[inds].contiguous(), scores[inds].contiguous()
     if boxes.shape[0] == 0:
-        return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
-    dets, keep = _nms_single(boxes, scores, None, iou_threshold, max_num, 1 << 30, True)
+        return _no_detections(boxes)
+    dets, keep = _nms_single(boxes, scores, None, dict(type='nms', iou_thr=iou_threshold), max_num, 1 << 30, True)
     if inds is not None:
         keep = inds[keep]
     return dets, keep
-
-
-SOFT_NMS_CAP = 10240   # candidates the soft-NMS images kernel holds in registers (csrc/soft_nms.hip kSoftRegCap)
-SOFT_NMS_PROBLEM_CAP = 1 << 19   # candidates of one problem of yv4_soft_nms_split (kSoftGlobalCap)
-_SOFT_NMS_ARGS = ('iou_threshold', 'sigma', 'min_score', 'method', 'offset')
-
-
-def _soft_method(method):
-    if method not in _lib.SOFT_NMS_METHODS:
-        raise ValueError(f'soft_nms: method {method!r} is not one of {sorted(_lib.SOFT_NMS_METHODS)}')
-    return _lib.SOFT_NMS_METHODS[method]
-
-
-def nms_spec(nms_cfg):
-    """``test_cfg.nms`` -> what a plan's post-processing launches: ``dict(type='nms', iou_thr, split_thr)`` or
-    ``dict(type='soft_nms', iou_thr, sigma, min_score, method (YV4_SOFT_NMS_* code), split_thr)`` (mmcv soft_nms'
-    defaults 0.3 / 0.5 / 1e-3 / 'linear').  Other types raise NotImplementedError; a soft-NMS key the op does not take
-    raises TypeError.  ``max_num`` with soft-NMS (mmcv applies it in the split branch only, and the single call refuses
-    it) is not built into plans."""
-    cfg = dict(nms_cfg)
-    nms_type = cfg.pop('type', 'nms')
-    split_thr = cfg.pop('split_thr', SPLIT_THR_DEFAULT)
-    if nms_type == 'nms':
-        return dict(type='nms', iou_thr=cfg.get('iou_threshold', cfg.get('iou_thr')), split_thr=split_thr)
-    if nms_type != 'soft_nms':
-        raise NotImplementedError(f'nms type {nms_type!r} is not built ("nms", "soft_nms")')
-    cfg.pop('class_agnostic', None)              # the head's own class_agnostic decides, as for "nms"
-    if 'max_num' in cfg:
-        raise NotImplementedError('soft_nms with max_num is not built into plans')
-    bad = sorted(set(cfg) - set(_SOFT_NMS_ARGS))
-    if bad:
-        raise TypeError(f'soft_nms: unexpected nms_cfg keys {bad}')
-    if cfg.get('offset', 0) != 0:
-        raise NotImplementedError('soft_nms: only offset=0 is built')
-    method = _soft_method(cfg.get('method', 'linear'))
-    sigma = float(cfg.get('sigma', 0.5))
-    if method == _lib.SOFT_NMS_GAUSSIAN and not sigma > 0:
-        raise ValueError('soft_nms: sigma must be > 0 for the gaussian method')
-    return dict(type='soft_nms', iou_thr=float(cfg.get('iou_threshold', 0.3)), sigma=sigma,
-                min_score=float(cfg.get('min_score', 1e-3)), method=method, split_thr=split_thr)
-
-
-def soft_nms_split(keys, n, max_coord, boxes, labels, fused_classes, per_label, spec, max_out, dets, olab, oidx, ocnt):
-    """One image through ``yv4_soft_nms_split`` (host n; work allocated here, as the hard split path does)."""
-    L = _lib.lib()
-    nbytes = int(L.yv4_soft_nms_split_work(n))
-    if nbytes == 0 or (not per_label and n > SOFT_NMS_PROBLEM_CAP):
-        raise NotImplementedError(f'soft-NMS over {n} candidates in one problem is not built (at most '
-                                  f'{SOFT_NMS_PROBLEM_CAP})')
-    work = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device)
-    check(L.yv4_soft_nms_split(_ptr(keys), n, float(max_coord), _ptr(boxes), _ptr(labels), fused_classes, int(per_label),
-                               spec['method'], spec['iou_thr'], spec['sigma'], spec['min_score'], max_out,
-                               _ptr(work), _ptr(dets), _ptr(olab), _ptr(oidx), _ptr(ocnt), stream_ptr()),
-          'yv4_soft_nms_split')
-    if int(ocnt.item()) == -2:
-        raise NotImplementedError(f'soft-NMS: a label with more than {SOFT_NMS_PROBLEM_CAP} candidates is not built')
-
-
-def _soft_single(boxes, scores, labels, spec, max_out, split_thr, class_agnostic, single_in_global=False):
-    """One problem set (one image) of soft-NMS: yv4_soft_nms_images below split_thr (up to SOFT_NMS_CAP candidates, else
-    the single call in global memory), yv4_soft_nms_split per label from split_thr.  ``single_in_global``: the single
-    call in global memory at any size (tests run the same candidates through both forms).  Returns (dets(k,5),
-    keep(k,))."""
-    n = boxes.shape[0]
-    dev = boxes.device
-    L = _lib.lib()
-    keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-    counts = torch.empty(1, dtype=torch.int32, device=dev)
-    maxc = torch.empty(1, dtype=torch.float32, device=dev)
-    check(L.yv4_nms_prepare(_ptr(boxes), _ptr(scores), n, _ptr(keys), _ptr(counts), _ptr(maxc), stream_ptr()),
-          'yv4_nms_prepare')
-    if class_agnostic:
-        maxc.fill_(-1.0)                          # no class offset (mmcv: boxes_for_nms = boxes)
-    cap = max(min(max_out if max_out > 0 else n, n), 1)
-    dets = torch.empty((cap, 5), dtype=torch.float32, device=dev)
-    olab = torch.empty(cap, dtype=torch.int32, device=dev)
-    oidx = torch.empty(cap, dtype=torch.int64, device=dev)
-    ocnt = torch.empty(1, dtype=torch.int32, device=dev)
-    lab = None if class_agnostic else labels
-    if n < split_thr and n <= SOFT_NMS_CAP and not single_in_global:
-        check(L.yv4_soft_nms_images(_ptr(keys), n, _ptr(counts), _ptr(maxc), _ptr(boxes), n, _ptr(lab), n, 0, 1,
-                                    spec['method'], spec['iou_thr'], spec['sigma'], spec['min_score'], cap, split_thr,
-                                    _ptr(dets), _ptr(olab), _ptr(oidx), _ptr(ocnt), stream_ptr()), 'yv4_soft_nms_images')
-    elif n < split_thr:
-        soft_nms_split(keys, n, maxc.item(), boxes, lab, 0, 0, spec, cap, dets, olab, oidx, ocnt)
-    else:
-        # mmcv's split branch loops over unique(idxs) even when class_agnostic (then without the offset)
-        soft_nms_split(keys, n, maxc.item(), boxes, labels, 0, 1, spec, cap, dets, olab, oidx, ocnt)
-    k = int(ocnt.item())
-    if k < 0:
-        raise RuntimeError('yv4_soft_nms_images flagged the split path unexpectedly')
-    return dets[:k], oidx[:k]
 
 
 def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method='linear', offset=0):
@@ -277,18 +287,14 @@ def soft_nms(boxes, scores, iou_threshold=0.3, sigma=0.5, min_score=1e-3, method
     must be 0.  Returns ``(dets(k,5), inds(k,) int64)`` in selection order: the boxes as given and the DECAYED scores."""
     assert boxes.size(1) == 4
     assert boxes.size(0) == scores.size(0)
-    if offset != 0:
-        raise NotImplementedError('soft_nms: only offset=0 is built')
+    spec = dict(_soft_params(dict(iou_threshold=iou_threshold, sigma=sigma, min_score=min_score, method=method,
+                                  offset=offset), 'soft_nms'), type='soft_nms')
     _need_cuda(boxes, 'boxes')
-    spec = dict(method=_soft_method(method), iou_thr=float(iou_threshold), sigma=float(sigma),
-                min_score=float(min_score))
-    if spec['method'] == _lib.SOFT_NMS_GAUSSIAN and not spec['sigma'] > 0:
-        raise ValueError('soft_nms: sigma must be > 0 for the gaussian method')
     boxes = boxes.contiguous().float()
     scores = scores.contiguous().float()
     if boxes.shape[0] == 0:
-        return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
-    return _soft_single(boxes, scores, None, spec, -1, 1 << 30, True)
+        return _no_detections(boxes)
+    return _nms_single(boxes, scores, None, spec, -1, 1 << 30, True)
 
 
 def _batched_soft_nms(boxes, scores, idxs, nms_cfg_, class_agnostic):
@@ -301,21 +307,13 @@ def _batched_soft_nms(boxes, scores, idxs, nms_cfg_, class_agnostic):
     max_num = -1
     if n >= split_thr:
         max_num = nms_cfg_.pop('max_num', -1)
-    bad = sorted(set(nms_cfg_) - set(_SOFT_NMS_ARGS))
-    if bad:
-        raise TypeError(f'batched_nms: soft_nms takes no nms_cfg keys {bad}')
-    if nms_cfg_.get('offset', 0) != 0:
-        raise NotImplementedError('batched_nms: only offset=0 is built')
-    spec = dict(method=_soft_method(nms_cfg_.get('method', 'linear')), iou_thr=float(nms_cfg_.get('iou_threshold', 0.3)),
-                sigma=float(nms_cfg_.get('sigma', 0.5)), min_score=float(nms_cfg_.get('min_score', 1e-3)))
-    if spec['method'] == _lib.SOFT_NMS_GAUSSIAN and not spec['sigma'] > 0:
-        raise ValueError('soft_nms: sigma must be > 0 for the gaussian method')
+    spec = dict(_soft_params(nms_cfg_, 'batched_nms'), type='soft_nms')
     boxes = boxes.contiguous().float()
     scores = scores.contiguous().float()
     if n == 0:
-        return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
+        return _no_detections(boxes)
     labels = idxs.to(device=boxes.device, dtype=torch.int32).contiguous()
-    return _soft_single(boxes, scores, labels, spec, max_num, split_thr, class_agnostic)
+    return _nms_single(boxes, scores, labels, spec, max_num, split_thr, class_agnostic)
 
 
 def set_deterministic(on=True):
@@ -369,19 +367,17 @@ def batched_nms(boxes, scores, idxs, nms_cfg, class_agnostic=False):
         raise TypeError(f'batched_nms: unexpected nms_cfg keys {sorted(nms_cfg_)}')
     boxes = boxes.contiguous().float()
     scores = scores.contiguous().float()
-    n = boxes.shape[0]
-    if n == 0:
-        return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
+    if boxes.shape[0] == 0:
+        return _no_detections(boxes)
     labels = idxs.to(device=boxes.device, dtype=torch.int32).contiguous()
     inds = None
     if score_threshold > 0:
         inds = (scores > score_threshold).nonzero(as_tuple=False).squeeze(1)
-        boxes, scores = boxes[inds].contiguous(), scores[inds].contiguous()
-        if labels is not None:
-            labels = labels[inds].contiguous()
+        boxes, scores, labels = boxes[inds].contiguous(), scores[inds].contiguous(), labels[inds].contiguous()
         if boxes.shape[0] == 0:
-            return boxes.new_zeros((0, 5)), torch.zeros((0,), dtype=torch.int64, device=boxes.device)
-    dets, keep = _nms_single(boxes, scores, labels, iou_threshold, max_num, split_thr, class_agnostic)
+            return _no_detections(boxes)
+    dets, keep = _nms_single(boxes, scores, labels, dict(type='nms', iou_thr=iou_threshold), max_num, split_thr,
+                             class_agnostic)
     if inds is not None:
         keep = inds[keep]
     return dets, keep

@@ -19,7 +19,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import ConvDesc, LevelDesc, check
 
 
@@ -564,7 +564,6 @@ class Plan:
         total = 0
         for v in pred_views:
             assert v.buf.dtype == torch.float32, 'decode reads fp32 pred maps (emit the head convs with out_f32)'
-            assert v.buf.dtype == torch.float32, 'decode reads fp32 pred maps (emit the head convs with out_f32)'
             assert v.C == A * attr and v.coff == 0 and v.cstride == v.C, 'pred maps must be dense NHWC'
             total += v.H * v.W * A
         levels = (LevelDesc * len(pred_views))()
@@ -638,27 +637,11 @@ class Plan:
                 res['max_coord'].data_ptr(), res['topk_keys'].data_ptr() if use_topk else None, stream),
                 'yv4_decode_filter')
 
-        def nms_op(stream):
-            check(_lib.lib().yv4_nms_images(
-                res['keys'].data_ptr(), res['key_cap'], res['counts'].data_ptr(), res['max_coord'].data_ptr(),
-                res['boxes'].data_ptr(), total, None, 0, num_classes, N, float(iou_thr), max_per_img,
-                int(split_thr), res['dets'].data_ptr(), res['labels'].data_ptr(), res['index'].data_ptr(),
-                res['count'].data_ptr(), stream), 'yv4_nms_images')
-
-        def soft_nms(stream):
-            check(_lib.lib().yv4_soft_nms_images(
-                res['keys'].data_ptr(), res['key_cap'], res['counts'].data_ptr(), res['max_coord'].data_ptr(),
-                res['boxes'].data_ptr(), total, None, 0, num_classes, N, nms['method'], nms['iou_thr'], nms['sigma'],
-                nms['min_score'], max_per_img, int(split_thr), res['dets'].data_ptr(), res['labels'].data_ptr(),
-                res['index'].data_ptr(), res['count'].data_ptr(), stream), 'yv4_soft_nms_images')
         self.ops.append(Op('reset', 'decode_reset', reset))
         if use_topk:
             self.ops.append(Op('topk', 'conf_topk', topk))
         self.ops.append(Op('decode', 'decode_filter', decode_v3 if v3 else decode, nbytes=4.0 * N * total * attr))
-        if nms['type'] == 'soft_nms':
-            self.ops.append(Op('nms', 'soft_nms_images', soft_nms))
-        else:
-            self.ops.append(Op('nms', 'nms_images', nms_op))
+        self.ops.append(Op('nms', ops.POST_NMS_KERNEL[nms['type']], lambda stream: ops.post_nms(res, stream)))
         return res
 
     # ---- lifecycle ---------------------------------------------------------------

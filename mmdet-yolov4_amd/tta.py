@@ -163,25 +163,9 @@ def emit_tta_post(plan, head, groups, flips, N, cfg=None):
                                        res['boxes'].data_ptr(), res['keys'].data_ptr(), res['key_cap'],
                                        res['counts'].data_ptr(), res['max_coord'].data_ptr(), stream), 'yv4_tta_merge')
 
-    def nms(stream):
-        check(_lib.lib().yv4_nms_images(
-            res['keys'].data_ptr(), res['key_cap'], res['counts'].data_ptr(), res['max_coord'].data_ptr(),
-            res['boxes'].data_ptr(), S_total, None, 0, C_, N, float(res['iou_thr']), res['max_per_img'],
-            int(res['split_thr']), res['dets'].data_ptr(), res['labels'].data_ptr(), res['index'].data_ptr(),
-            res['count'].data_ptr(), stream), 'yv4_nms_images')
-
-    def soft_nms(stream):
-        check(_lib.lib().yv4_soft_nms_images(
-            res['keys'].data_ptr(), res['key_cap'], res['counts'].data_ptr(), res['max_coord'].data_ptr(),
-            res['boxes'].data_ptr(), S_total, None, 0, C_, N, spec['method'], spec['iou_thr'], spec['sigma'],
-            spec['min_score'], res['max_per_img'], int(res['split_thr']), res['dets'].data_ptr(),
-            res['labels'].data_ptr(), res['index'].data_ptr(), res['count'].data_ptr(), stream), 'yv4_soft_nms_images')
     from .plan import Op
     plan.ops.append(Op('merge', 'tta_merge', merge))
-    if spec['type'] == 'soft_nms':
-        plan.ops.append(Op('nms', 'soft_nms_images', soft_nms))
-    else:
-        plan.ops.append(Op('nms', 'nms_images', nms))
+    plan.ops.append(Op('nms', ops.POST_NMS_KERNEL[spec['type']], lambda stream: ops.post_nms(res, stream)))
     plan.post = res
     return res
 

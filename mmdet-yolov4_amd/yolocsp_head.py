@@ -625,29 +625,19 @@ def collect_results(post, with_nms=True, head=None):
 
 
 def _run_split_path(post, counts):
-    """Images whose candidate count reached mmcv's split_thr take the per-class path."""
-    from ._lib import lib, check
-    L = lib()
+    """Images whose candidate count reached mmcv's split_thr (or exceeds what the images kernel holds) take the split
+    path."""
     maxc = post['max_coord'].cpu()
-    stream = ops.stream_ptr()
+    spec = post.get('nms') or dict(type='nms', iou_thr=post['iou_thr'])
     for n in range(post['N']):
         if int(counts[n]) >= 0:
             continue
         cnt = int(post['counts'][n].item())
         if cnt > post['key_cap']:
             raise RuntimeError('candidate key buffer overflow')
-        spec = post.get('nms') or dict(type='nms')
-        if spec['type'] == 'soft_nms':
-            # mmcv's split branch from split_thr on; below it (more candidates than the images kernel holds) the
-            # single call over all of them
-            per_label = 1 if cnt >= post['split_thr'] else 0
-            ops.soft_nms_split(post['keys'][n], cnt, float(maxc[n]), post['boxes'][n], None, post['num_classes'],
-                               per_label, spec, post['max_per_img'], post['dets'][n], post['labels'][n],
-                               post['index'][n], post['count'][n:n + 1])
-            continue
-        work = torch.empty(max(L.yv4_nms_split_work(cnt), 16), dtype=torch.uint8, device=post['dets'].device)
-        check(L.yv4_nms_split(post['keys'][n].data_ptr(), cnt, float(maxc[n]), post['boxes'][n].data_ptr(), None,
-                              post['num_classes'], float(post['iou_thr']), post['max_per_img'], work.data_ptr(),
-                              post['dets'][n].data_ptr(), post['labels'][n].data_ptr(),
-                              post['index'][n].data_ptr(), post['count'][n:n + 1].data_ptr(), stream),
-              'yv4_nms_split')
+        # soft-NMS: mmcv's split branch from split_thr on; below it (more candidates than the images kernel holds) the
+        # single call over all of them.  Hard NMS: per class either way.
+        per_label = 1 if spec['type'] != 'soft_nms' or cnt >= post['split_thr'] else 0
+        ops.split_nms_image(spec, post['keys'][n], cnt, float(maxc[n]), post['boxes'][n], None, post['num_classes'],
+                            post['max_per_img'], post['dets'][n], post['labels'][n], post['index'][n],
+                            post['count'][n:n + 1], per_label=per_label)

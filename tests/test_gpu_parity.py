@@ -543,6 +543,38 @@ def test_nms_sizes_and_ties_bit_exact(gpu_device, n):
         np.testing.assert_array_equal(d.cpu().numpy(), rd.numpy())
 
 
+@pytest.mark.parametrize('n', [1, 2, 255, 256, 257, 513])
+def test_split_path_at_its_smallest_shapes(gpu_device, n):
+    """split_thr = 1 sends every size down the split path (hard: yv4_nms_split; soft: yv4_soft_nms_split per label):
+    max_num on that branch, segments of one candidate and empty classes (1, 3, 4) between occupied ones, on the clustered
+    boxes and tied scores of test_nms_sizes_and_ties_bit_exact.  The oracle's hard batched_nms ignores max_num; mmcv's cut
+    is the prefix.  The soft restatement applies max_num itself."""
+    import _soft_nms_ref as R
+    rng = np.random.RandomState(1000 + n)
+    c = rng.rand(max(n // 20, 1), 2) * 200
+    cxy = c[rng.randint(0, len(c), n)] + rng.randn(n, 2) * 4
+    wh = np.abs(rng.randn(n, 2)) * 15 + 8
+    b = np.concatenate([cxy - wh / 2, cxy + wh / 2], 1).astype(np.float32)
+    s = rng.rand(n).astype(np.float32)
+    s[::4] = np.float32(0.5)                                   # heavy ties -> index tie-break
+    idx = np.array([0, 2, 5])[rng.randint(0, 3, n)].astype(np.int64)
+    bt, st = torch.from_numpy(b).to(gpu_device), torch.from_numpy(s).to(gpu_device)
+    for agnostic in (False, True):
+        hard = dict(type='nms', iou_threshold=0.5, split_thr=1, class_agnostic=agnostic)
+        rd, rkeep = O.batched_nms(torch.from_numpy(b), torch.from_numpy(s), torch.from_numpy(idx), hard)
+        soft = dict(type='soft_nms', iou_threshold=0.5, method='linear', split_thr=1, class_agnostic=agnostic)
+        for max_num in sorted({m for m in (-1, 1, n // 2) if m == -1 or m > 0}):
+            cut = {} if max_num < 0 else dict(max_num=max_num)
+            d, keep = pkg.batched_nms(bt, st, torch.from_numpy(idx), dict(hard, **cut))
+            k = rkeep.shape[0] if max_num < 0 else min(max_num, rkeep.shape[0])
+            np.testing.assert_array_equal(keep.cpu().numpy(), rkeep.numpy()[:k])
+            np.testing.assert_array_equal(d.cpu().numpy(), rd.numpy()[:k])
+            d, keep = pkg.batched_nms(bt, st, torch.from_numpy(idx), dict(soft, **cut))
+            sd, skeep = R.batched_soft_nms(b, s, idx, dict(soft, **cut))
+            np.testing.assert_array_equal(keep.cpu().numpy(), skeep)
+            np.testing.assert_array_equal(d.cpu().numpy(), sd)
+
+
 @pytest.mark.parametrize('n', [400003, 1048577])
 def test_nms_split_sorts_at_scale(gpu_device, n):
     """The split path's own radix sorts (nms_split.hip: rs_* kernels) on hundreds of tiles: with iou_threshold = 1 nothing

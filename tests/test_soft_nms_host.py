@@ -192,3 +192,41 @@ def test_restatement_reproduces_the_reference_fixture(golden):
     bd = g['mc/boundary_0.500/dets']
     assert (bd[:, 4] == np.float32(0.4)).any()          # IoU exactly 0.5 decays (>=): 0.8 * (1 - 0.5)
     assert (g['mc/boundary_naive/dets'][:, 4] == 0).sum() >= 3
+
+
+# bytes per n of the candidate count / detection count: the values the library returned before its workspaces were
+# carved by one shared helper (host functions: no GPU)
+_WORK_N = (1, 255, 256, 1024, 1025, 10000, 70001)
+_NMS_SPLIT_WORK = (527616, 539904, 539904, 582912, 585984, 1095936, 4516096)
+_SOFT_NMS_SPLIT_WORK = (528384, 543232, 543232, 595456, 599040, 1216512, 5356544)
+_COCO_RANK_WORK = (2816, 7168, 7168, 22528, 24320, 211712, 1472000)
+_COCO_ACCUMULATE_WORK = {                                                     # (K, A * T)
+    (1, 1): (4096, 10752, 10752, 36096, 38912, 342784, 2382592),
+    (1, 40): (4096, 20736, 20736, 76032, 78848, 732672, 5112576),
+    (80, 1): (4608, 11264, 11264, 36608, 39424, 343296, 2383104),
+    (80, 40): (4608, 21248, 21248, 76544, 79360, 733184, 5113088),
+}
+
+
+def test_workspace_sizes_are_pinned():
+    lib = L.lib()
+    assert tuple(lib.yv4_nms_split_work(n) for n in _WORK_N) == _NMS_SPLIT_WORK
+    assert tuple(lib.yv4_soft_nms_split_work(n) for n in _WORK_N) == _SOFT_NMS_SPLIT_WORK
+    assert tuple(lib.yv4_coco_rank_work(n) for n in _WORK_N) == _COCO_RANK_WORK
+    for (K, at), want in _COCO_ACCUMULATE_WORK.items():
+        assert tuple(lib.yv4_coco_accumulate_work(n, K, at) for n in _WORK_N) == want, (K, at)
+    assert lib.yv4_nms_split_work(0) == 0
+    assert lib.yv4_nms_split_work(1 << 31) == 0
+
+    def slots_work(levels, nms_pre):
+        arr = (ctypes.c_int32 * len(levels))(*levels)
+        return lib.yv4_topk_slots_work(len(levels), arr, nms_pre)
+    # no level's top-k exceeds what one workgroup sorts in LDS (8192): no workspace
+    for levels in ([1], [1000, 250, 63]):
+        for nms_pre in (-1, 100):
+            assert slots_work(levels, nms_pre) == 0
+    # the radix path: the workspace of the largest level that is cut to more than 8192 slots
+    assert slots_work([10000], 8193) == 250624
+    assert slots_work([70001, 9000], 8193) == 1751040
+    assert slots_work([9000, 70001, 63], 9000) == 1751040
+    assert slots_work([70001, 9000], 8192) == 0

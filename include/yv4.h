@@ -931,6 +931,27 @@ int yv4_coco_accumulate(const float* det, const uint32_t* order, const int32_t* 
                         const int32_t* max_dets, int M, int T, int A, const double* rec_thrs, int R, void* work,
                         double* precision, double* recall, double* scores, void* stream);
 
+/* ---- the flat result table of a test loop (csrc/results.hip; additive within ABI 8) ------------------------------------
+ * yv4_results_append: append one batch's post-processing output to the flat table yv4_coco_rank takes, in the order
+ * of the reference's _det2json (mmdet/datasets/coco.py:179-199): image, then class, then the row order NMS left.
+ *   dets (N, max_per_img, 5) float32, labels (N, max_per_img) int32, count (N) int32: the plan's own buffers.
+ *   img_index (N) int64: the image's position in the dataset; a negative value skips that row of the batch.
+ *   Image n writes min(max(count[n], 0), max_per_img) rows from `base` + the counts of the kept images before it; inside
+ *     an image the rows are a stable counting sort by label (rows of one class keep their order: yv4_coco_rank breaks
+ *     score ties by position).  Labels are expected in [0, num_classes) and are NOT checked on the device (num_classes
+ *     is validated as positive and otherwise documents the contract); any value sorts, none can move a write out of
+ *     the image's range.  Rows at or beyond `capacity` are not written: the caller keeps base + total <= capacity.
+ *   out_dets (capacity, 5) float32, out_labels (capacity) int64, out_img (capacity) int64.  Rows outside
+ *     [base, base + total) are left as they are.  No workspace, no atomics: identical bytes from run to run.
+ *   One workgroup per image with the image's labels in LDS: max_per_img <= YV4_RESULTS_MAX_PER_IMG (16 KB of int32
+ *     labels of the 160 KB of LDS per workgroup; the reference's configs use 100 to 1000), YV4_E_UNSUPPORTED above it.
+ *   YV4_E_INVALID without a launch for N < 0, max_per_img or num_classes <= 0, base < 0, capacity < base or a null
+ *     pointer; N == 0 is legal and does nothing. */
+#define YV4_RESULTS_MAX_PER_IMG 4096
+int yv4_results_append(const float* dets, const int32_t* labels, const int32_t* count, const int64_t* img_index, int N,
+                       int max_per_img, int num_classes, int64_t base, int64_t capacity, float* out_dets,
+                       int64_t* out_labels, int64_t* out_img, void* stream);
+
 /* ---- split-K form of yv4_conv_bn_act_fwd for single-image (latency) plans ---------------------------------------
  * The reference's only published protocol is batch 1 (tools/analysis_tools/benchmark.py:83-109).  There the deep layers
  * have a handful of output tiles and hundreds of K slices each; this entry splits K over several workgroups per tile

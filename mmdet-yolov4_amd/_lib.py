@@ -267,6 +267,7 @@ SIGNATURES = {
     'yv4_coco_accumulate_work': (_sz, [_i64, _i, _i]),
     'yv4_coco_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp,
                                       _vp, _vp]),
+    'yv4_results_append': (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -289,6 +290,10 @@ MAP_EVAL_SYMBOLS = frozenset(('yv4_bbox_overlaps_batched', 'yv4_tpfp_work', 'yv4
 #: the COCO bbox evaluation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_coco_eval()
 COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_match', 'yv4_coco_accumulate_work',
                                'yv4_coco_accumulate'))
+#: the flat result table of a test loop (additive within ABI 8, bound like FP8_SYMBOLS); has_results_append()
+RESULTS_SYMBOLS = frozenset(('yv4_results_append',))
+#: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
+RESULTS_MAX_PER_IMG = 4096
 
 _lock = threading.Lock()
 _lib = None
@@ -330,7 +335,7 @@ def lib():
                 continue
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
                     or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
-                    or name in COCO_EVAL_SYMBOLS) \
+                    or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -393,6 +398,12 @@ def has_coco_eval():
     """The loaded library exports the COCO bbox evaluation entry points (``yv4_coco_rank`` / ``_match`` / ``_accumulate``)."""
     h = lib()
     return all(hasattr(h, n) for n in COCO_EVAL_SYMBOLS)
+
+
+def has_results_append():
+    """The loaded library exports ``yv4_results_append`` (the flat result table of a test loop)."""
+    h = lib()
+    return all(hasattr(h, n) for n in RESULTS_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

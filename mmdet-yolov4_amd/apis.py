@@ -43,10 +43,50 @@ def _unwrap(field):
     return field
 
 
-def single_gpu_test(model, data_loader):
+def _test_batches(data_loader, device):
+    """``(img, img_metas, tta)`` per batch of a test loader: ``tta`` batches keep one entry per augmentation
+    (BaseDetector.forward_test -> aug_test, detectors/base.py:147-153).  The flat loop's copy of the unwrapping that
+    ``single_gpu_test``'s list loop keeps inline: that loop is the yardstick the flat one is measured against and stays
+    as it was, so a change to the batch format has to be made in both."""
+    for data in data_loader:
+        img, metas = data['img'], data['img_metas']
+        if isinstance(img, (list, tuple)) and len(img) > 1:
+            yield [t.to(device, non_blocking=True) for t in img], list(metas), True
+        else:
+            yield _unwrap(img).to(device, non_blocking=True), _unwrap(metas), False
+
+
+def _flat_loop(model, data_loader, position):
+    """The test loop with the result table built on the device (``results.DeviceResults``): ``position(j)`` is the
+    dataset position of the loop's j-th image.  Per batch the host reads the (N,) counts and nothing else;
+    test-time-augmentation batches come back as lists (``aug_test``) and are uploaded once."""
+    from .results import DeviceResults
+    model.eval()
+    device = next(model.parameters()).device
+    table = DeviceResults(model.bbox_head.num_classes, device)
+    seen = 0
+    with torch.no_grad():
+        for img, metas, tta in _test_batches(data_loader, device):
+            n = len(metas[0]) if tta else len(metas)
+            index = [position(seen + j) for j in range(n)]
+            if tta:
+                table.append_lists(model.forward_test(img, metas, rescale=True), index)
+            else:
+                model.simple_test(img, metas, rescale=True, results=table, img_index=index)
+            seen += n
+    return table.tensors()
+
+
+def single_gpu_test(model, data_loader, flat=False):
     """Run the detector over ``data_loader`` and return the list of per-image results
     (``mmdet/apis/test.py:16-68`` without the visualisation branch).  Each item is ``dict(img=..., img_metas=...)``
-    as the test pipeline's collate produces; ``rescale=True`` like the reference's test loop."""
+    as the test pipeline's collate produces; ``rescale=True`` like the reference's test loop.
+
+    ``flat=True`` returns the flat form instead -- ``(dets (D, 5) float32, labels (D,) int64, img_index (D,) int64)`` as
+    GPU tensors, ``img_index`` the running image number -- equal to ``coco_eval.flatten_results`` of the list bit for
+    bit, without the detections leaving the device."""
+    if flat:
+        return _flat_loop(model, data_loader, lambda j: j)
     model.eval()
     device = next(model.parameters()).device
     results = []
@@ -63,14 +103,22 @@ def single_gpu_test(model, data_loader):
     return results
 
 
-def multi_gpu_test(model, data_loader, size=None, gpu_collect=True):
+def multi_gpu_test(model, data_loader, size=None, gpu_collect=True, flat=False):
     """Every rank runs its ``sampler_indices`` share, then rank 0 receives the merged, dataset-ordered list and the
     others ``None`` (``mmdet/apis/test.py:71-113``).  ``size`` defaults to ``len(data_loader.dataset)``.  With
     ``gpu_collect`` the byte buffers of the gather live on the rank's GPU (RCCL); otherwise on the host (gloo) --
-    the reference's other branch goes through a shared temp directory instead."""
+    the reference's other branch goes through a shared temp directory instead.
+
+    ``flat=True``: the flat form of ``single_gpu_test``.  Rank r's j-th image sits at dataset position ``j * world + r``
+    (the sampler's round-robin deal), ``dist.collect_flat`` gathers the three tensors and rank 0 returns them ordered
+    by position, without the sampler's padding, on the model's device."""
     from . import dist as D
-    results = single_gpu_test(model, data_loader)
     if size is None:
         size = len(data_loader.dataset)
     device = next(model.parameters()).device if gpu_collect else 'cpu'
+    if flat:
+        rank, world = D.rank_world()
+        dets, labels, img_index = _flat_loop(model, data_loader, lambda j: j * world + rank)
+        return D.collect_flat(dets, labels, img_index, size, device=device)
+    results = single_gpu_test(model, data_loader)
     return D.collect_results(results, size, device=device)

@@ -188,8 +188,8 @@ class COCOeval:
         takes no part)."""
         p = self.params
         if not p.useCats:
-            raise NotImplementedError('useCats=0 (category-agnostic evaluation: the proposal metrics) is not built: it '
-                                      'scores RPN proposals, which no detector of this package produces')
+            raise NotImplementedError('useCats=0 (category-agnostic evaluation: the proposal metrics, which the reference '
+                                      "computes from a detector's own boxes, datasets/coco.py:288,574) is not built")
         p.imgIds = list(np.unique(p.imgIds))
         p.catIds = list(np.unique(p.catIds))
         p.maxDets = sorted(p.maxDets)
@@ -408,8 +408,11 @@ def evaluate_bbox(results, coco_gt, classes=None, cat_ids=None, img_ids=None, lo
             raise KeyError(f'metric {m} is not supported')
     for m in metrics:
         if m in ('proposal', 'proposal_fast'):
-            raise NotImplementedError(f"metric='{m}' is not built: it scores RPN proposals, which no detector of this "
-                                      'package produces')
+            # (the reference scores a detector's own boxes under this name, category-agnostically: the proposal
+            # file IS the bbox file, datasets/coco.py:288, and useCats = 0, :574)
+            raise NotImplementedError(f"metric='{m}' is not built: the reference scores the detector's own boxes under "
+                                      'this name, category-agnostically (datasets/coco.py:288,574), so no detector of '
+                                      'this package is excluded by what it produces; the scoring itself is missing')
         if m == 'segm':
             raise NotImplementedError("metric='segm' is not built: it scores masks, which no detector of this package "
                                       'produces')

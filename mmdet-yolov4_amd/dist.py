@@ -101,6 +101,47 @@ def collect_results(result_part, size, device='cpu'):
     return ordered[:size]
 
 
+def rank_world():
+    """(rank, world size) of the live process group; (0, 1) without one."""
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
+def collect_flat(dets, labels, img_index, size, device='cpu'):
+    """``collect_results`` for the flat result form ``(dets (D, 5), labels (D,), img_index (D,))``, ``img_index`` being
+    dataset positions (rank r's j-th image: ``j * world + r``).  An all-gather of the row counts, then one of each
+    tensor padded to the longest part; the collectives run on ``device`` as ``collect_results``' do ('cpu' for gloo,
+    the rank's GPU for RCCL).  Rank 0 drops the rows of positions >= ``size`` (the sampler's padding), orders the rest
+    stably by position -- rows of one image come from one rank and keep their order -- and returns them on the
+    device the parts came from; other ranks get None.  No pickling: the wire carries the tensors' bytes."""
+    def ordered(d, l, i):
+        keep = i < size
+        d, l, i = d[keep], l[keep], i[keep]
+        order = torch.sort(i, stable=True).indices
+        return d[order], l[order], i[order]
+    if not (dist.is_available() and dist.is_initialized()):
+        return ordered(dets, labels, img_index)
+    rank, world = dist.get_rank(), dist.get_world_size()
+    home = dets.device
+    rows = torch.tensor([dets.shape[0]], dtype=torch.int64, device=device)
+    all_rows = [torch.zeros_like(rows) for _ in range(world)]
+    dist.all_gather(all_rows, rows)
+    all_rows = [int(r) for r in all_rows]
+    longest = max(all_rows)
+    gathered = []
+    for part in (dets.reshape(-1, 5), labels, img_index):
+        send = torch.zeros((longest,) + tuple(part.shape[1:]), dtype=part.dtype, device=device)
+        send[:part.shape[0]] = part
+        recv = [torch.zeros_like(send) for _ in range(world)]
+        dist.all_gather(recv, send)
+        gathered.append(recv)
+    if rank != 0:
+        return None
+    d, l, i = (torch.cat([r[:n] for r, n in zip(recv, all_rows)]).to(home) for recv in gathered)
+    return ordered(d, l, i)
+
+
 def barrier(sync_device=True):
     if dist.is_available() and dist.is_initialized():
         dist.barrier()

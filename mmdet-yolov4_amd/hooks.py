@@ -21,8 +21,9 @@ The schedule arithmetic is exposed as pure functions (``warmup_factor``, ``ema_m
 ``accumulation_steps``) so it is testable without a device.
 """
 import math
-
 import os
+import warnings
+from collections import OrderedDict
 
 import torch
 
@@ -99,6 +100,13 @@ class Hook:
 
     def after_train_iter(self, runner):
         self.after_iter(runner)
+
+    # mmcv.runner.Hook's schedule tests
+    def every_n_epochs(self, runner, n):
+        return (runner.epoch + 1) % n == 0 if n > 0 else False
+
+    def every_n_iters(self, runner, n):
+        return (runner.iter + 1) % n == 0 if n > 0 else False
 
 
 # ---- a22 ---------------------------------------------------------------------------------------------
@@ -488,6 +496,247 @@ class CosineAnnealingLrUpdaterHook(Hook):
             self._set(runner, runner.iter, runner.max_iters)
 
 
+# ---- validation in training: mmdet/core/evaluation/eval_hooks.py, and the slice of mmcv's CheckpointHook it needs ----
+@HOOKS.register_module()
+class CheckpointHook(Hook):
+    """The part of mmcv's ``CheckpointHook`` that ``save_best`` depends on: ``runner.save_checkpoint`` every ``interval``
+    epochs (iterations with ``by_epoch=False``; ``interval=-1`` never), on rank 0 only, into ``out_dir`` (default
+    ``runner.work_dir``), and the written file's path in ``runner.meta['hook_msgs']['last_ckpt']``.  Registered before
+    the evaluation hook at the same priority it runs first, so the evaluation's ``best_ckpt`` is this epoch's file."""
+
+    def __init__(self, interval=-1, by_epoch=True, save_optimizer=True, out_dir=None, **kwargs):
+        self.interval, self.by_epoch, self.save_optimizer, self.out_dir = interval, by_epoch, save_optimizer, out_dir
+        self.args = kwargs
+
+    def _save(self, runner, filename_tmpl):
+        if runner.rank != 0:
+            return
+        out_dir = self.out_dir or runner.work_dir
+        if out_dir is None:
+            raise ValueError('CheckpointHook needs out_dir= or a runner with a work_dir')
+        path = runner.save_checkpoint(out_dir, filename_tmpl=filename_tmpl, save_optimizer=self.save_optimizer,
+                                      **self.args)
+        if runner.meta is not None:
+            runner.meta.setdefault('hook_msgs', dict())['last_ckpt'] = path
+
+    def after_train_epoch(self, runner):
+        if self.by_epoch and self.every_n_epochs(runner, self.interval):
+            self._save(runner, 'epoch_{}.pth')
+
+    def after_train_iter(self, runner):
+        if not self.by_epoch and self.every_n_iters(runner, self.interval):
+            self._save(runner, f'iter_{runner.iter + 1}.pth')
+
+
+def contiguous_runs(spans):
+    """``[(offset, length), ...]`` -> the ``[lo, hi)`` ranges that cover them with one range per run of spans that
+    touch (sorted by offset; a span that starts where the previous one ends extends it)."""
+    runs = []
+    for off, n in sorted(spans):
+        if runs and runs[-1][1] == off:
+            runs[-1][1] = off + n
+        else:
+            runs.append([off, off + n])
+    return [tuple(r) for r in runs]
+
+
+def bn_stat_runs(model, flat):
+    """The arena ranges of ``running_mean`` / ``running_var`` of every tracked ``_BatchNorm`` of ``model``: what the
+    reference's ``_broadcast_bn_buffer`` sends one tensor at a time (eval_hooks.py:247-259).  The arena pads every
+    segment to 4 floats; the padding belongs to its segment's span.  ``ema_*`` buffers, integer buffers and parameters
+    are not part of it."""
+    from torch.nn.modules.batchnorm import _BatchNorm
+    from .flat_state import _pad4
+    wanted = set()
+    for name, m in model.named_modules():
+        if isinstance(m, _BatchNorm) and m.track_running_stats:
+            wanted.update((f'{name}.running_mean' if name else 'running_mean', f'{name}.running_var' if name else 'running_var'))
+    return contiguous_runs([(seg.offset, _pad4(seg.numel)) for seg in flat.buffer_segments if seg.name in wanted])
+
+
+@HOOKS.register_module()
+class EvalHook(Hook):
+    """``EvalHook`` of ``mmdet/core/evaluation/eval_hooks.py:14-187``: run the test loop over ``dataloader`` when the
+    schedule says so, score with ``dataloader.dataset.evaluate(results, logger=runner.logger, **eval_kwargs)``, put
+    every metric into ``runner.log_buffer.output`` and, with ``save_best``, keep ``best_score`` / ``best_ckpt`` in
+    ``runner.meta['hook_msgs']`` and the symlink ``best_<key>.pth`` in ``runner.work_dir``.
+
+    Schedule: with ``start=None`` after every ``interval``-th epoch; otherwise never before epoch ``start`` (counted
+    from 1), then every ``interval`` epochs from it (``start=3, interval=2``: 3, 5, 7); a run resumed at or beyond
+    ``start`` evaluates once before its first epoch, if the same test admits it.  ``by_epoch=False`` counts iterations.
+
+    Differences from the reference, both on purpose: ``dataloader`` is any iterable of test batches with a
+    ``.dataset`` (the reference insists on ``torch.utils.data.DataLoader``; this package's loaders are generators over
+    the fused input pipeline); and the result form.  ``flat=None`` takes the flat test loop -- the result table built
+    and scored on the GPU (``results.DeviceResults``) -- when ``dataloader.dataset.accepts_flat`` is true and the list
+    loop otherwise; ``flat=True`` / ``False`` decide it outright.  The hook puts the model back into the mode it found
+    it in: with ``by_epoch=False`` the next training iteration follows directly."""
+
+    rule_map = {'greater': lambda x, y: x > y, 'less': lambda x, y: x < y}
+    init_value_map = {'greater': -math.inf, 'less': math.inf}
+    greater_keys = ['mAP', 'AR']
+    less_keys = ['loss']
+    distributed = False              # DistEvalHook: evaluate and save on rank 0 only
+
+    def __init__(self, dataloader, start=None, interval=1, by_epoch=True, save_best=None, rule=None, flat=None,
+                 **eval_kwargs):
+        if not hasattr(dataloader, 'dataset'):
+            raise TypeError(f'dataloader must carry a .dataset to evaluate against, but got {type(dataloader)}')
+        if not interval > 0:
+            raise ValueError(f'interval must be positive, but got {interval}')
+        if start is not None and start < 0:
+            warnings.warn(f'The evaluation start epoch {start} is smaller than 0, use 0 instead', UserWarning)
+            start = 0
+        assert isinstance(save_best, str) or save_best is None
+        self.dataloader, self.start, self.interval, self.by_epoch = dataloader, start, interval, by_epoch
+        self.save_best = save_best
+        self.flat = flat
+        self.eval_kwargs = eval_kwargs
+        self.initial_epoch_flag = True
+        if self.save_best is not None:
+            self._init_rule(rule, self.save_best)
+
+    def _init_rule(self, rule, key_indicator):
+        if rule is not None and rule not in self.rule_map:
+            raise KeyError(f'rule must be greater, less or None, but got {rule}.')
+        if rule is None and key_indicator != 'auto':
+            if any(key in key_indicator for key in self.greater_keys):
+                rule = 'greater'
+            elif any(key in key_indicator for key in self.less_keys):
+                rule = 'less'
+            else:
+                raise ValueError(f'Cannot infer the rule for key {key_indicator}, thus a specific rule must be '
+                                 'specified.')
+        self.rule = rule
+        self.key_indicator = key_indicator
+        if self.rule is not None:
+            self.compare_func = self.rule_map[self.rule]
+
+    def before_run(self, runner):
+        if self.save_best is not None:
+            if runner.meta is None:
+                warnings.warn('runner.meta is None. Creating a empty one.')
+                runner.meta = dict()
+            runner.meta.setdefault('hook_msgs', dict())
+
+    def before_train_epoch(self, runner):
+        """A resumed run is evaluated once before its first epoch."""
+        if not self.initial_epoch_flag:
+            return
+        if self.start is not None and runner.epoch >= self.start:
+            self.after_train_epoch(runner)
+        self.initial_epoch_flag = False
+
+    def evaluation_flag(self, runner):
+        if self.start is None:
+            return self.every_n_epochs(runner, self.interval)
+        if (runner.epoch + 1) < self.start:
+            return False
+        return (runner.epoch + 1 - self.start) % self.interval == 0
+
+    def use_flat(self):
+        if self.flat is not None:
+            return bool(self.flat)
+        # measured (DESIGN 17, tools/val_loop_bench.py): the flat pass takes 0.32 of the list pass, far outside the spread
+        return bool(getattr(self.dataloader.dataset, 'accepts_flat', False))
+
+    def _test_loop(self, runner):
+        from .apis import single_gpu_test
+        return single_gpu_test(runner.model, self.dataloader, flat=self.use_flat())
+
+    def _run(self, runner):
+        was_training = runner.model.training
+        results = self._test_loop(runner)
+        runner.model.train(was_training)
+        if runner.rank == 0 or not self.distributed:
+            key_score = self.evaluate(runner, results)
+            if self.save_best:
+                self.save_best_checkpoint(runner, key_score)
+
+    def after_train_epoch(self, runner):
+        if self.by_epoch and self.evaluation_flag(runner):
+            self._run(runner)
+
+    def after_train_iter(self, runner):
+        if not self.by_epoch and self.every_n_iters(runner, self.interval):
+            self._run(runner)
+
+    def save_best_checkpoint(self, runner, key_score):
+        msgs = runner.meta['hook_msgs']
+        best_score = msgs.get('best_score', self.init_value_map[self.rule])
+        if not self.compare_func(key_score, best_score):
+            return
+        msgs['best_score'] = key_score
+        last_ckpt = msgs['last_ckpt']
+        msgs['best_ckpt'] = last_ckpt
+        link = os.path.join(runner.work_dir, f'best_{self.key_indicator}.pth')
+        if os.path.lexists(link):
+            os.remove(link)
+        same_dir = os.path.abspath(os.path.dirname(last_ckpt)) == os.path.abspath(runner.work_dir)
+        os.symlink(os.path.basename(last_ckpt) if same_dir else os.path.abspath(last_ckpt), link)
+        if runner.logger is not None:
+            time_stamp = runner.epoch + 1 if self.by_epoch else runner.iter + 1
+            runner.logger.info(f'Now best checkpoint is epoch_{time_stamp}.pth.'
+                               f'Best {self.key_indicator} is {key_score:0.4f}')
+
+    def evaluate(self, runner, results):
+        eval_res = self.dataloader.dataset.evaluate(results, logger=runner.logger, **self.eval_kwargs)
+        for name, val in eval_res.items():
+            runner.log_buffer.output[name] = val
+        runner.log_buffer.ready = True
+        if self.save_best is None:
+            return None
+        if self.key_indicator == 'auto':
+            self._init_rule(self.rule, list(eval_res.keys())[0])
+        return eval_res[self.key_indicator]
+
+
+@HOOKS.register_module()
+class DistEvalHook(EvalHook):
+    """``DistEvalHook`` of ``eval_hooks.py:190-303``: every rank runs its share of ``dataloader`` through
+    ``multi_gpu_test``; rank 0 evaluates and saves, the others do neither.
+
+    ``tmpdir`` is accepted and unused: the gather is ``dist.collect_results`` / ``dist.collect_flat`` (collectives), not
+    the reference's shared temporary directory.  ``gpu_collect`` puts the gather's buffers on the rank's GPU; an RCCL
+    group has no other place for them, so it is implied there.
+
+    ``broadcast_bn_buffer``: the reference broadcasts ``running_var`` and ``running_mean`` of every tracked BatchNorm
+    from rank 0, two collectives per layer.  Here they are segments of the model's ``FlatState`` arena, sent as one
+    broadcast per contiguous run of them (one, for a model whose float buffers are all BatchNorm statistics), followed
+    by ``bump_versions()`` so that the eval plans fold the received statistics."""
+
+    distributed = True
+
+    def __init__(self, dataloader, start=None, interval=1, by_epoch=True, tmpdir=None, gpu_collect=False, save_best=None,
+                 rule=None, broadcast_bn_buffer=True, flat=None, **eval_kwargs):
+        super().__init__(dataloader, start=start, interval=interval, by_epoch=by_epoch, save_best=save_best, rule=rule,
+                         flat=flat, **eval_kwargs)
+        self.broadcast_bn_buffer = broadcast_bn_buffer
+        self.tmpdir = tmpdir
+        self.gpu_collect = gpu_collect
+
+    def _broadcast_bn_buffer(self, runner):
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return 0
+        model = _unwrap(runner.model)
+        flat = FlatState.of(model)
+        runs = bn_stat_runs(model, flat)
+        for lo, hi in runs:
+            dist.broadcast(flat.values[lo:hi], 0)
+        if runs:
+            flat.bump_versions()
+        return len(runs)
+
+    def _test_loop(self, runner):
+        from . import dist as D
+        from .apis import multi_gpu_test
+        if self.broadcast_bn_buffer:
+            self._broadcast_bn_buffer(runner)
+        return multi_gpu_test(runner.model, self.dataloader, gpu_collect=self.gpu_collect or D.backend_name() == 'nccl',
+                              flat=self.use_flat())
+
+
 # ---- the runner protocol the hooks are driven through ------------------------------------------------
 class _Sampler:
     def __init__(self, samples_per_gpu):
@@ -512,6 +761,8 @@ class BatchSource:
 class LogBuffer:
     def __init__(self):
         self.history = []
+        self.output = OrderedDict()      # mmcv LogBuffer.output: what the evaluation hooks write their metrics into
+        self.ready = False
 
     def update(self, values, count=1):
         # a DeferredLogVars stays as it is (copying it would wait for the device)
@@ -524,8 +775,9 @@ class Runner:
     hooks called in priority order at each stage, ``outputs = model.train_step(data, optimizer)``
     per iteration (mmcv ``epoch_based_runner.py`` ``run_iter``/``train``)."""
 
-    def __init__(self, model, optimizer, logger=None, meta=None, max_epochs=1):
+    def __init__(self, model, optimizer, logger=None, meta=None, max_epochs=1, work_dir=None):
         self.model, self.optimizer, self.logger = model, optimizer, logger
+        self.work_dir = work_dir
         self.meta = meta if meta is not None else {}
         self.max_epochs = max_epochs
         self.iter = 0
@@ -554,6 +806,11 @@ class Runner:
     def call_hook(self, stage):
         for h in self._hooks:
             getattr(h, stage)(self)
+
+    @property
+    def rank(self):
+        import torch.distributed as dist
+        return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
     @property
     def max_iters(self):

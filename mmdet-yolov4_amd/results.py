@@ -1,0 +1,141 @@
+"""The flat result table of a test loop, kept on the GPU, and the dataset object an evaluation hook scores it against.
+
+The reference's test loop returns, per image, a per-class list of numpy arrays (``bbox2result``,
+``mmdet/apis/test.py:16-68``): every batch's ``(N, max_per_img, 5)`` block is downloaded, cut into ``N x num_classes``
+arrays, and ``CocoDataset.evaluate`` walks them again (``_det2json``, ``datasets/coco.py:179-199``).  ``COCOeval`` of this
+package takes the flat form ``(dets (D, 5), labels (D,), img_index (D,))`` as GPU tensors; ``DeviceResults`` produces
+it: ``yv4_results_append`` (csrc/results.hip) copies a batch's rows from the plan's own buffers into the table in
+``_det2json`` order -- image, class, the row order NMS left -- so the table equals
+``flatten_results([bbox2result(...)])`` bit for bit and nothing but the ``(N,)`` counts visits the host.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .coco_eval import CocoGt, evaluate_bbox, flatten_results
+from .ops import stream_ptr
+
+
+def _host_index(img_index, n):
+    idx = np.asarray(img_index, dtype=np.int64).reshape(-1)
+    if idx.shape[0] != n:
+        raise ValueError(f'img_index holds {idx.shape[0]} positions for {n} images')
+    return idx
+
+
+class DeviceResults:
+    """``(dets (D, 5) float32, labels (D,) int64, img_index (D,) int64)`` on ``device``, grown geometrically; the cursor
+    ``D`` lives on the host (it is the sum of counts the test loop reads back anyway).  ``num_images`` counts the images
+    appended so far: the default position of the next batch's images."""
+
+    def __init__(self, num_classes, device, capacity=4096):
+        self.num_classes = int(num_classes)
+        self.device = torch.device(device)
+        if self.num_classes <= 0:
+            raise ValueError('num_classes must be positive')
+        if self.device.type != 'cuda':
+            raise RuntimeError('DeviceResults lives on the GPU (yv4_results_append); there is no CPU fallback for this path')
+        if not _lib.has_results_append():
+            raise RuntimeError('the loaded libyv4_hip.so has no yv4_results_append; rebuild it')
+        self.D = 0
+        self.num_images = 0
+        self._alloc(max(int(capacity), 1))
+
+    def _alloc(self, capacity):
+        self.capacity = capacity
+        self.dets = torch.empty((capacity, 5), dtype=torch.float32, device=self.device)
+        self.labels = torch.empty((capacity,), dtype=torch.int64, device=self.device)
+        self.img_index = torch.empty((capacity,), dtype=torch.int64, device=self.device)
+
+    def _reserve(self, rows):
+        need = self.D + rows
+        if need <= self.capacity:
+            return
+        old = (self.dets, self.labels, self.img_index)
+        self._alloc(max(need, 2 * self.capacity))
+        for new, prev in zip((self.dets, self.labels, self.img_index), old):
+            new[:self.D].copy_(prev[:self.D])
+
+    def next_positions(self, n):
+        return np.arange(self.num_images, self.num_images + n, dtype=np.int64)
+
+    def append(self, post, img_index=None, counts=None):
+        """One batch from a plan's post-processing buffers (``Plan.postprocess``: ``dets``, ``labels``, ``count``).
+        ``img_index``: the N dataset positions (default: the next N), -1 skips an image.  ``counts``: the host copy of
+        ``post['count']`` when the caller has it already; every count must be final (the split path has run).  The
+        counts are checked here; the labels are the plan's own (its NMS writes class indices below ``num_classes``) and
+        are trusted: they stay on the device, and reading them back to check would be the detour this class removes."""
+        N, M = int(post['N']), int(post['max_per_img'])
+        idx = self.next_positions(N) if img_index is None else _host_index(img_index, N)
+        counts = (post['count'].cpu() if counts is None else counts).numpy().astype(np.int64).reshape(-1)
+        if counts.shape[0] != N or (counts < 0).any() or (counts > M).any():
+            raise ValueError(f'counts must be {N} values in [0, {M}] (run the split path first), got {counts.tolist()}')
+        if M > _lib.RESULTS_MAX_PER_IMG:
+            raise NotImplementedError(f'max_per_img={M}: yv4_results_append holds at most {_lib.RESULTS_MAX_PER_IMG} '
+                                      'rows per image')
+        total = int(counts[idx >= 0].sum())
+        self._reserve(total)
+        dets, labels, count = post['dets'], post['labels'], post['count']
+        assert dets.dtype == torch.float32 and labels.dtype == torch.int32 and count.dtype == torch.int32
+        assert dets.is_contiguous() and labels.is_contiguous() and tuple(dets.shape) == (N, M, 5)
+        from .yolocsp_head import _upload
+        idx_dev = _upload(torch.from_numpy(idx), self.device)
+        check(_lib.lib().yv4_results_append(dets.data_ptr(), labels.data_ptr(), count.data_ptr(), idx_dev.data_ptr(), N, M,
+                                            self.num_classes, self.D, self.capacity, self.dets.data_ptr(),
+                                            self.labels.data_ptr(), self.img_index.data_ptr(), stream_ptr()),
+              'yv4_results_append')
+        self.D += total
+        self.num_images += N
+        return total
+
+    def append_lists(self, results, img_index=None):
+        """Images in the reference's form (per image a per-class list of (n, 5) arrays: what ``aug_test`` returns):
+        one ``flatten_results``, one upload."""
+        n = len(results)
+        idx = self.next_positions(n) if img_index is None else _host_index(img_index, n)
+        if n and len(results[0]) != self.num_classes:
+            raise ValueError(f'results hold {len(results[0])} class lists, the table {self.num_classes}')
+        dets, labels, local = flatten_results(results)
+        pos = idx[local]
+        keep = pos >= 0
+        if not keep.all():
+            dets, labels, pos = dets[keep], labels[keep], pos[keep]
+        rows = int(dets.shape[0])
+        self._reserve(rows)
+        if rows:
+            from .yolocsp_head import _upload
+            lo, hi = self.D, self.D + rows
+            self.dets[lo:hi].copy_(_upload(torch.from_numpy(np.ascontiguousarray(dets)), self.device))
+            self.labels[lo:hi].copy_(_upload(torch.from_numpy(np.ascontiguousarray(labels)), self.device))
+            self.img_index[lo:hi].copy_(_upload(torch.from_numpy(np.ascontiguousarray(pos)), self.device))
+        self.D += rows
+        self.num_images += n
+        return rows
+
+    def tensors(self):
+        return self.dets[:self.D], self.labels[:self.D], self.img_index[:self.D]
+
+
+class CocoBBoxDataset:
+    """The ``.dataset`` a validation loader carries: the annotation file and ``evaluate``.  It loads no images (the
+    loader yields them).  ``accepts_flat``: ``evaluate`` takes the flat GPU table as well as the list form, which is
+    what makes an evaluation hook choose the flat test loop.  ``classes`` selects the categories by name as
+    ``CocoDataset.load_annotations`` does (``datasets/coco.py:57-77``)."""
+
+    accepts_flat = True
+
+    def __init__(self, ann_file, classes=None):
+        self.coco = ann_file if isinstance(ann_file, CocoGt) else CocoGt(ann_file)
+        self.CLASSES = tuple(classes) if classes is not None else tuple(c['name'] for c in self.coco.cats.values())
+        self.cat_ids = self.coco.get_cat_ids(cat_names=self.CLASSES)
+        self.img_ids = self.coco.get_img_ids()
+
+    def __len__(self):
+        return len(self.img_ids)
+
+    def evaluate(self, results, metric='bbox', logger=None, **kwargs):
+        """``CocoDataset.evaluate`` for ``metric='bbox'`` (``datasets/coco.py:451-643``) through ``evaluate_bbox``;
+        ``results``: the per-image lists or the flat tuple, ``img_index`` being positions in ``img_ids``."""
+        return evaluate_bbox(results, self.coco, cat_ids=self.cat_ids, img_ids=self.img_ids, logger=logger, metric=metric,
+                             **kwargs)

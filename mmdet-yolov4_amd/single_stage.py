@@ -20,7 +20,7 @@ from .bricks import HipModule, plan_cache_get, plan_cache_put
 from .deferred import DeferredLogVars, read_back_later  # noqa: F401
 from .plan import Plan
 from .registry import DETECTORS, build_backbone, build_head, build_neck
-from .yolocsp_head import collect_results, set_scale_factors
+from .yolocsp_head import collect_results, final_counts, set_scale_factors
 
 
 def bbox2result(bboxes, labels, num_classes):
@@ -177,12 +177,18 @@ class SingleStageDetector(HipModule):
     def forward_dummy(self, img):
         return self.bbox_head(self.extract_feat(img))
 
-    def simple_test(self, img, img_metas, rescale=False):
+    def simple_test(self, img, img_metas, rescale=False, results=None, img_index=None):
+        """``results``: a ``results.DeviceResults``.  The batch is then appended to it on the device, at the dataset
+        positions ``img_index`` (default: the table's next N), and the table is returned: only the (N,) counts are
+        read back, which decide the split path as they do for the list form."""
         self._check_eval()
         N, _, H, W = img.shape
         plan = self.compile(N, H, W, device=img.device, rescale=rescale, graph=True)
         set_scale_factors(plan.post, img_metas, rescale)
         plan.run(img)
+        if results is not None:
+            results.append(plan.post, img_index, counts=final_counts(plan.post))
+            return results
         bbox_list = collect_results(plan.post, with_nms=True, head=self.bbox_head)
         return [bbox2result(d, l, self.bbox_head.num_classes) for d, l in bbox_list]
 

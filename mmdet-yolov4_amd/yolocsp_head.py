@@ -608,10 +608,7 @@ def collect_results(post, with_nms=True, head=None):
             score, cid = cls.max(dim=-1)
             out.append((torch.cat((post['boxes'][n], score[:, None]), dim=-1), cid))
         return out
-    counts = post['count'].cpu()
-    if bool((counts < 0).any()):
-        _run_split_path(post, counts)
-        counts = post['count'].cpu()
+    counts = final_counts(post)
     out = []
     for n in range(N):
         k = int(counts[n])
@@ -622,6 +619,16 @@ def collect_results(post, with_nms=True, head=None):
         else:
             out.append((post['dets'][n, :k].clone(), post['labels'][n, :k].to(torch.int64)))
     return out
+
+
+def final_counts(post):
+    """The host copy of ``post['count']`` once every image's NMS is final: a negative count asks for the split path,
+    which rewrites ``post['dets'] / ['labels'] / ['count']`` in place."""
+    counts = post['count'].cpu()
+    if bool((counts < 0).any()):
+        _run_split_path(post, counts)
+        counts = post['count'].cpu()
+    return counts
 
 
 def _run_split_path(post, counts):

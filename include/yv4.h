@@ -931,6 +931,60 @@ int yv4_coco_accumulate(const float* det, const uint32_t* order, const int32_t* 
                         const int32_t* max_dets, int M, int T, int A, const double* rec_thrs, int R, void* work,
                         double* precision, double* recall, double* scores, void* stream);
 
+/* ---- VOC-style mAP from the flat result table (csrc/map_flat.hip; additive within ABI 8) ------------------------------
+ * The two ends the list path of eval_map leaves to the host: ordering the detections and accumulating tp / fp into
+ * recall, precision and AP.  Between them run yv4_bbox_overlaps_batched and yv4_tpfp_batched, unchanged.  N images x C
+ * classes give P = C * N problems, class-major: problem p = class * N + image, so a class is one contiguous slice of
+ * every table.  All pointers but `stream` are device pointers.  The definition is restated in
+ * mmdet-yolov4_amd/map_eval.py; every floating-point value is one IEEE operation of it, counts are integers, and two
+ * runs give identical bytes.
+ *
+ * yv4_map_rank: two stable sorts of the flat table, by (class, descending score) and then by problem.
+ *   det (total_det, 5) float32 x1 y1 x2 y2 score, labels / img_index (total_det) int64 in the caller's order.  A row
+ *     whose label is outside [0, C) or whose image index is outside [0, N) takes no part.  Dv = the rows that do.
+ *     Equal scores (+0 and -0 are equal) keep the caller's order, in both orders below.  Scores are expected finite.
+ *   gt_off (P+1) int64: the problems' ground-truth offsets (input).
+ *   det4 (total_det, 4) float32, 16-byte aligned: the boxes gathered problem-major, inside a problem in visiting
+ *     order (descending score); det_off (P+1) int64 with det_off[P] = Dv.  Rows at and beyond Dv hold the boxes that
+ *     take no part.
+ *   order, rank (total_det) int32: the tables yv4_tpfp_batched reads.  The boxes already sit in visiting order, so
+ *     both hold a position's rank inside its problem.
+ *   iou_off (P+1) int64: exclusive sums of num_det * num_gt per problem.
+ *   cls_order (total_det) int32: the per-class global order.  Class c owns [det_off[c*N], det_off[(c+1)*N]); entry j
+ *     of that slice is the problem-major position (the column of yv4_tpfp_batched's tp / fp) of the class's j-th
+ *     detection by descending score.
+ *   info (C + 2) int64, for ONE read-back: [0] = iou_off[P] (sizes the IoU buffer), [1] = Dv, [2 + c] = the
+ *     detections of class c.
+ *   work: yv4_map_rank_work(total_det) bytes, 8-byte aligned.  total_det == 0 is legal: det_off, iou_off and info are
+ *     zeroed and nothing else is touched. */
+size_t yv4_map_rank_work(int64_t total_det);
+int yv4_map_rank(const float* det, const int64_t* labels, const int64_t* img_index, int64_t total_det, int N, int C,
+                 const int64_t* gt_off, void* work, float* det4, int64_t* det_off, int32_t* order, int32_t* rank,
+                 int64_t* iou_off, int32_t* cls_order, int64_t* info, void* stream);
+/* yv4_map_accumulate: mean_ap.py:353-396 and average_precision (:12-58) per (threshold t, class c, area range k).
+ *   tp, fp (num_thrs, num_ranges, total_det) bytes as yv4_tpfp_batched wrote them for total_det = Dv columns;
+ *   cls_order, det_off: from yv4_map_rank; num_gts (C, num_ranges) int64: the class's regular gts per area range.
+ *   Over the class's detections in cls_order: integer cumulative ctp / cfp (a class must hold fewer than 2^24
+ *   detections; the caller checks info), recall = float32(ctp) / max(num_gts, float32 eps) in float64, precision =
+ *   float32(ctp) / max(float32(ctp) + float32(cfp), float32 eps) in float32.
+ *   YV4_MAP_AP_AREA: mrec = [0, recall, 1], mpre = [0, precision, 0] in float64, mpre's suffix maximum, and the sum
+ *     of (mrec[i+1] - mrec[i]) * mpre[i+1] over the i with mrec[i+1] != mrec[i], added in ascending i into a single
+ *     float64 accumulator, rounded to float32.
+ *   YV4_MAP_AP_11POINTS: for the levels j * 0.1 (float64), j = 0 .. 10, the maximum precision among the positions with
+ *     recall >= level (0 if none), added in that order in float32, divided by 11 in float32.
+ *   ap (num_thrs, C, num_ranges) float32; last_recall float64 / last_precision float32, both (num_thrs, C,
+ *     num_ranges): the curves' last points, 0 for a class without detections; num_dets (C) int64.
+ *   recall (float64) / precision (float32), both (num_thrs, num_ranges, total_det) or both null: the full curves,
+ *     class c's in columns [det_off[c*N], det_off[(c+1)*N]) in cls_order.
+ *   work: yv4_map_accumulate_work(total_det, num_thrs, num_ranges) bytes, 4-byte aligned. */
+#define YV4_MAP_AP_AREA 0
+#define YV4_MAP_AP_11POINTS 1
+size_t yv4_map_accumulate_work(int64_t total_det, int num_thrs, int num_ranges);
+int yv4_map_accumulate(const uint8_t* tp, const uint8_t* fp, const int32_t* cls_order, const int64_t* det_off,
+                       const int64_t* num_gts, int64_t total_det, int N, int C, int num_thrs, int num_ranges, int mode,
+                       void* work, float* ap, double* last_recall, float* last_precision, double* recall,
+                       float* precision, int64_t* num_dets, void* stream);
+
 /* ---- the flat result table of a test loop (csrc/results.hip; additive within ABI 8) ------------------------------------
  * yv4_results_append: append one batch's post-processing output to the flat table yv4_coco_rank takes, in the order
  * of the reference's _det2json (mmdet/datasets/coco.py:179-199): image, then class, then the row order NMS left.

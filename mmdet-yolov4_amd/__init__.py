@@ -28,8 +28,9 @@ from . import tta  # noqa: F401  (YOLOv3 test-time augmentation)
 from .apis import inference_detector, single_gpu_test, multi_gpu_test
 from .eval_utils import (coco_test_annotation, evaluate_fast_bbox, EVAL_BREAKDOWN, EVAL_IOU_CALCULATOR, EVAL_MATCHER, FlexibleStatisticsEval, IOU2DCoCo,
                          MatcherCoCo, ScaleBreakdown, average_precision, eval_map_flexible, iou_coco, match_coco)
-from .map_eval import (bbox_overlaps, eval_map, evaluate_map, print_map_summary, tpfp_default, tpfp_imagenet)  # noqa: F401
+from .map_eval import (MapGt, bbox_overlaps, eval_map, evaluate_map, print_map_summary, tpfp_default,  # noqa: F401
+                       tpfp_imagenet)
 from .coco_eval import COCOeval, CocoGt, evaluate_bbox, flatten_results  # noqa: F401
-from .results import CocoBBoxDataset, DeviceResults  # noqa: F401
+from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith('_')]

@@ -28,6 +28,7 @@ ACT_NONE, ACT_MISH, ACT_LEAKY, ACT_SWISH = 0, 1, 2, 3
 NMS_IOU_DIV, NMS_IOU_MUL = 0, 1
 OVERLAPS_IOU, OVERLAPS_IOF = 0, 1                                           # YV4_OVERLAPS_*
 TPFP_DEFAULT, TPFP_IMAGENET = 0, 1                                          # YV4_TPFP_*
+MAP_AP_AREA, MAP_AP_11POINTS = 0, 1                                         # YV4_MAP_AP_*
 SOFT_NMS_NAIVE, SOFT_NMS_LINEAR, SOFT_NMS_GAUSSIAN = 0, 1, 2                # YV4_SOFT_NMS_*
 SOFT_NMS_METHODS = {'naive': SOFT_NMS_NAIVE, 'linear': SOFT_NMS_LINEAR, 'gaussian': SOFT_NMS_GAUSSIAN}
 FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL, FLIP_DIAGONAL = 0, 1, 2, 3     # YV4_FLIP_*
@@ -260,6 +261,11 @@ SIGNATURES = {
     'yv4_tpfp_work': (_sz, [_i, _i64, _i64, _i]),
     'yv4_tpfp_batched': (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _i, _vp, _i,
                                    _vp, _vp, _vp, _vp]),
+    'yv4_map_rank_work': (_sz, [_i64]),
+    'yv4_map_rank': (C.c_int, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'yv4_map_accumulate_work': (_sz, [_i64, _i, _i]),
+    'yv4_map_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp]),
     'yv4_coco_rank_work': (_sz, [_i64]),
     'yv4_coco_rank': (C.c_int, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'yv4_coco_match': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp,
@@ -287,6 +293,8 @@ V3_AUGMENT_SYMBOLS = frozenset(('yv4_v3_augment_u8',))
 LOSS_EX_SYMBOLS = frozenset(('yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'))
 #: the VOC-style mAP entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_map_eval()
 MAP_EVAL_SYMBOLS = frozenset(('yv4_bbox_overlaps_batched', 'yv4_tpfp_work', 'yv4_tpfp_batched'))
+#: the flat-table ends of the VOC-style mAP (additive within ABI 8, bound like FP8_SYMBOLS); has_map_flat()
+MAP_FLAT_SYMBOLS = frozenset(('yv4_map_rank_work', 'yv4_map_rank', 'yv4_map_accumulate_work', 'yv4_map_accumulate'))
 #: the COCO bbox evaluation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_coco_eval()
 COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_match', 'yv4_coco_accumulate_work',
                                'yv4_coco_accumulate'))
@@ -335,7 +343,7 @@ def lib():
                 continue
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
                     or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
-                    or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS) \
+                    or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -392,6 +400,12 @@ def has_map_eval():
     """The loaded library exports the VOC-style mAP entry points (``yv4_bbox_overlaps_batched`` / ``yv4_tpfp_batched``)."""
     h = lib()
     return all(hasattr(h, n) for n in MAP_EVAL_SYMBOLS)
+
+
+def has_map_flat():
+    """The loaded library exports the flat-table mAP entry points (``yv4_map_rank`` / ``yv4_map_accumulate``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in MAP_FLAT_SYMBOLS)
 
 
 def has_coco_eval():

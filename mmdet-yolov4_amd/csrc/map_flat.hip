@@ -1,0 +1,400 @@
+// VOC-style mAP from the flat result table (dets (D, 5), labels (D), img_index (D)): the two ends that map_eval.hip's
+// overlaps / tpfp kernels leave to the host in the list path, on the device.
+//   yv4_map_rank        two stable sorts of the flat table -- by (class, descending score), then by problem
+//                       (class * N + image) -- give the boxes gathered problem-major in visiting order, the problems'
+//                       offset tables, the order / rank tables yv4_tpfp_batched reads and the per-class global order
+//   yv4_map_accumulate  per (threshold, class, area range): integer cumulative tp / fp in the per-class order, recall
+//                       (float64), precision (float32) and the AP of mean_ap.py:12-58 ('area' or '11points')
+// Every floating-point value is ONE IEEE operation of the definition (mmdet-yolov4_amd/map_eval.py), in its order
+// (compiled with -ffp-contract=off); counts are integers; the float64 sum of 'area' is a single accumulator in rank
+// order.  No float atomics: two runs give identical bytes.
+#include <cfloat>
+
+#include "radix_sort.h"
+#include "yv4_common.h"
+
+namespace yv4 {
+namespace {
+
+constexpr int kMfLanes = 64;
+constexpr int kMfWaves = 4;
+constexpr int kMfThreads = kMfLanes * kMfWaves;      // one chunk of a class's list
+constexpr int kMfPoints = 11;                        // recall levels of the '11points' AP
+
+// float32 score -> a 32-bit key that ascends as the score DEscends; -0 and +0 share a key
+__device__ __forceinline__ uint32_t mf_desc_key(float s) {
+  const uint32_t b = __float_as_uint(s + 0.f);
+  const uint32_t u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return ~u;
+}
+
+// ---- ordering ------------------------------------------------------------------------------------------------------
+// sort A: (class, descending score) from the flat order; a detection outside every problem gets class C (to the end)
+__global__ __launch_bounds__(256) void mf_keys_class_kernel(const float* __restrict__ det, const int64_t* __restrict__ labels,
+                                                            const int64_t* __restrict__ img, int64_t D, int N, int C,
+                                                            uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= D) return;
+  const int64_t lab = labels[d], im = img[d];
+  const bool part = lab >= 0 && lab < C && im >= 0 && im < N;
+  keys[d] = ((uint64_t)(uint32_t)(part ? (int)lab : C) << 32) | mf_desc_key(det[5 * d + 4]);
+  vals[d] = (uint32_t)d;
+}
+
+// sort B: the problem alone, from the class order: inside a problem the class order (descending score, ties in flat
+// order) survives, which is the visiting order
+__global__ __launch_bounds__(256) void mf_keys_problem_kernel(const uint64_t* __restrict__ keys_a,
+                                                              const uint32_t* __restrict__ vals_a,
+                                                              const int64_t* __restrict__ img, int64_t D, int N, int C,
+                                                              uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= D) return;
+  const uint32_t cls = (uint32_t)(keys_a[j] >> 32);
+  keys[j] = cls >= (uint32_t)C ? (uint32_t)C * (uint32_t)N : cls * (uint32_t)N + (uint32_t)img[vals_a[j]];
+  vals[j] = (uint32_t)j;
+}
+
+// off[q] = first sorted position whose problem is >= q, q = 0 .. P
+__global__ __launch_bounds__(256) void mf_offsets_kernel(const uint32_t* __restrict__ keys, int64_t n, int P,
+                                                         int64_t* __restrict__ off) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q > P) return;
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < (uint32_t)q) lo = mid + 1; else hi = mid;
+  }
+  off[q] = lo;
+}
+
+// position s of the problem-major order: its box, its rank inside the problem (order == rank: the boxes are gathered in
+// visiting order), and where the class order finds it
+__global__ __launch_bounds__(256) void mf_gather_kernel(const float* __restrict__ det, const uint32_t* __restrict__ vals_a,
+                                                        const uint32_t* __restrict__ vals_b,
+                                                        const uint32_t* __restrict__ keys_b,
+                                                        const int64_t* __restrict__ det_off, int64_t D, int P,
+                                                        float* __restrict__ det4, int32_t* __restrict__ order,
+                                                        int32_t* __restrict__ rank, int32_t* __restrict__ cls_order) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= D) return;
+  const uint32_t j = vals_b[s];
+  const float* b = det + 5 * (int64_t)vals_a[j];
+  reinterpret_cast<float4*>(det4)[s] = make_float4(b[0], b[1], b[2], b[3]);
+  const uint32_t p = keys_b[s];
+  const int32_t r = p < (uint32_t)P ? (int32_t)(s - det_off[p]) : 0;
+  order[s] = r;
+  rank[s] = r;
+  cls_order[j] = (int32_t)s;
+}
+
+// iou_off = exclusive sums of nd * ng over the P problems (and the total at [P] and info[0]): a thread sums its
+// contiguous piece, thread 0 scans the 1 024 piece sums, the thread walks its piece again
+__global__ __launch_bounds__(1024) void mf_pairs_kernel(const int64_t* __restrict__ det_off, const int64_t* __restrict__ gt_off,
+                                                       int P, int64_t* __restrict__ iou_off, int64_t* __restrict__ info) {
+  __shared__ int64_t part[1024];
+  const int t = threadIdx.x;
+  const int64_t piece = ((int64_t)P + 1023) / 1024;
+  const int64_t lo = t * piece < P ? t * piece : P;
+  const int64_t hi = lo + piece < P ? lo + piece : P;
+  int64_t su = 0;
+  for (int64_t p = lo; p < hi; ++p) su += (det_off[p + 1] - det_off[p]) * (gt_off[p + 1] - gt_off[p]);
+  part[t] = su;
+  __syncthreads();
+  if (t == 0) {
+    int64_t run = 0;
+    for (int i = 0; i < 1024; ++i) { const int64_t v = part[i]; part[i] = run; run += v; }
+    iou_off[P] = run;
+    info[0] = run;
+    info[1] = det_off[P];
+  }
+  __syncthreads();
+  int64_t run = part[t];
+  for (int64_t p = lo; p < hi; ++p) {
+    iou_off[p] = run;
+    run += (det_off[p + 1] - det_off[p]) * (gt_off[p + 1] - gt_off[p]);
+  }
+}
+
+__global__ __launch_bounds__(256) void mf_class_counts_kernel(const int64_t* __restrict__ det_off, int N, int C,
+                                                              int64_t* __restrict__ info) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) info[2 + c] = det_off[((int64_t)c + 1) * N] - det_off[(int64_t)c * N];
+}
+
+// ---- accumulation: one workgroup of four waves per (threshold, class, area range) ------------------------------------
+// The class's list is walked in chunks of 256 positions (thread = position inside the chunk), three times:
+//   A  forwards   inclusive integer counts (ballots inside a wave, the waves' totals through LDS, the chunks' through a
+//                 running sum every thread keeps) -> precision, recall, the curves on request
+//   B  backwards  precision's suffix maximum (shuffles inside a wave, the waves above through LDS, the chunks above
+//                 through a carried maximum), in place in `scratch`
+//   C  forwards   the counts again; 'area': a term at every position where recall changes, added in rank order into one
+//                 float64 accumulator that every thread carries identically; '11points': the suffix maximum at the
+//                 first position that reaches each level
+__global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
+    const uint8_t* __restrict__ tp, const uint8_t* __restrict__ fp, const int32_t* __restrict__ cls_order,
+    const int64_t* __restrict__ det_off, const int64_t* __restrict__ num_gts, int64_t D, int N, int C, int K, int mode,
+    float* __restrict__ scratch, float* __restrict__ ap, double* __restrict__ last_recall,
+    float* __restrict__ last_precision, double* __restrict__ recall, float* __restrict__ precision,
+    int64_t* __restrict__ num_dets) {
+  __shared__ int s_ct[kMfWaves], s_cf[kMfWaves];
+  __shared__ float s_wmax[kMfWaves];
+  __shared__ unsigned long long s_mask[kMfWaves];
+  __shared__ double s_term[kMfThreads];
+  __shared__ float s_sel[kMfPoints];
+  const int tid = threadIdx.x, lane = tid & (kMfLanes - 1), w = tid >> 6;
+  int id = blockIdx.x;                                    // (t * C + c) * K + k: the index of ap / last_recall
+  const int k = id % K; id /= K;
+  const int c = id % C;
+  const int t = id / C;
+  int64_t base = det_off[(int64_t)c * N];
+  int64_t n = det_off[((int64_t)c + 1) * N] - base;
+  if (base < 0 || base > D) { base = 0; n = 0; }          // (never with the tables yv4_map_rank wrote)
+  if (n > D - base) n = D - base;
+  if (n < 0) n = 0;
+  if (t == 0 && k == 0 && tid == 0) num_dets[c] = n;
+  if (n == 0) {                                           // no curve: both AP forms are 0
+    if (tid == 0) { ap[blockIdx.x] = 0.f; last_recall[blockIdx.x] = 0.0; last_precision[blockIdx.x] = 0.f; }
+    return;
+  }
+  const int64_t row = ((int64_t)t * K + k) * D;
+  const int64_t ng = num_gts[(int64_t)c * K + k];
+  const double den = ng >= 1 ? (double)ng : (double)FLT_EPSILON;          // np.maximum(int64 num_gts, float32 eps)
+  const unsigned long long le = ~0ull >> (63 - lane);     // lanes <= mine
+  const int64_t nchunks = (n + kMfThreads - 1) / kMfThreads;
+  float* mine = scratch + row + base;
+
+  // ---- A
+  int64_t run_tp = 0, run_fp = 0;
+  for (int64_t ch = 0; ch < nchunks; ++ch) {
+    const int64_t pos = ch * kMfThreads + tid;
+    const bool in = pos < n;
+    bool ftp = false, ffp = false;
+    if (in) {
+      const int64_t col = cls_order[base + pos];
+      if (col >= 0 && col < D) { ftp = tp[row + col] != 0; ffp = fp[row + col] != 0; }
+    }
+    const unsigned long long bt = __ballot(ftp), bf = __ballot(ffp);
+    if (lane == 0) { s_ct[w] = __popcll(bt); s_cf[w] = __popcll(bf); }
+    __syncthreads();
+    int pre_t = 0, pre_f = 0, tot_t = 0, tot_f = 0;
+#pragma unroll
+    for (int v = 0; v < kMfWaves; ++v) {
+      const int a = s_ct[v], b = s_cf[v];
+      if (v < w) { pre_t += a; pre_f += b; }
+      tot_t += a;
+      tot_f += b;
+    }
+    if (in) {
+      const float ctp = (float)(run_tp + pre_t + __popcll(bt & le));      // exact: below 2^24 (the host checks)
+      const float cfp = (float)(run_fp + pre_f + __popcll(bf & le));
+      const float both = ctp + cfp;
+      const float p = ctp / (both >= FLT_EPSILON ? both : FLT_EPSILON);
+      const double r = (double)ctp / den;
+      mine[pos] = p;
+      if (recall) { recall[row + base + pos] = r; precision[row + base + pos] = p; }
+      if (pos == n - 1) { last_recall[blockIdx.x] = r; last_precision[blockIdx.x] = p; }
+    }
+    run_tp += tot_t;
+    run_fp += tot_f;
+    __syncthreads();
+  }
+  const int64_t total_tp = run_tp;
+
+  // ---- B (the pad mpre[n + 1] = 0 starts the maximum)
+  float carry = 0.f;
+  for (int64_t ch = nchunks - 1; ch >= 0; --ch) {
+    const int64_t pos = ch * kMfThreads + tid;
+    const bool in = pos < n;
+    float v = in ? mine[pos] : 0.f;
+#pragma unroll
+    for (int o = 1; o < kMfLanes; o <<= 1) {
+      const float u = __shfl_down(v, o);
+      if (lane + o < kMfLanes) v = fmaxf(v, u);
+    }
+    if (lane == 0) s_wmax[w] = v;
+    __syncthreads();
+    float above = carry, all = carry;
+#pragma unroll
+    for (int x = 0; x < kMfWaves; ++x) {
+      const float m = s_wmax[x];
+      if (x > w) above = fmaxf(above, m);
+      all = fmaxf(all, m);
+    }
+    v = fmaxf(v, above);
+    if (in) mine[pos] = v;
+    carry = all;
+    __syncthreads();
+  }
+
+  // ---- C
+  if (tid < kMfPoints) s_sel[tid] = 0.f;
+  __syncthreads();
+  run_tp = 0;
+  double acc = 0.0;
+  for (int64_t ch = 0; ch < nchunks; ++ch) {
+    const int64_t pos = ch * kMfThreads + tid;
+    const bool in = pos < n;
+    bool ftp = false;
+    if (in) {
+      const int64_t col = cls_order[base + pos];
+      if (col >= 0 && col < D) ftp = tp[row + col] != 0;
+    }
+    const unsigned long long bt = __ballot(ftp);
+    if (lane == 0) s_ct[w] = __popcll(bt);
+    __syncthreads();
+    int pre_t = 0, tot_t = 0;
+#pragma unroll
+    for (int v = 0; v < kMfWaves; ++v) {
+      const int a = s_ct[v];
+      if (v < w) pre_t += a;
+      tot_t += a;
+    }
+    const int64_t ctp = run_tp + pre_t + __popcll(bt & le);
+    const double r = (double)(float)ctp / den;
+    const double r_prev = pos == 0 ? 0.0 : (double)(float)(ctp - (ftp ? 1 : 0)) / den;      // mrec[0] = 0
+    const float sm = in ? mine[pos] : 0.f;
+    if (mode == YV4_MAP_AP_AREA) {
+      const bool step = in && r != r_prev;
+      s_term[tid] = step ? (r - r_prev) * (double)sm : 0.0;
+      const unsigned long long m = __ballot(step);
+      if (lane == 0) s_mask[w] = m;
+      __syncthreads();
+#pragma unroll
+      for (int v = 0; v < kMfWaves; ++v) {
+        unsigned long long mm = s_mask[v];
+        while (mm) {
+          acc += s_term[v * kMfLanes + (__ffsll(mm) - 1)];
+          mm &= mm - 1;
+        }
+      }
+    } else {
+      if (in) {
+        for (int j = 0; j < kMfPoints; ++j) {
+          const double thr = (double)j * 0.1;             // np.arange(0, 1 + 1e-3, 0.1)[j]
+          if (r >= thr && (pos == 0 || r_prev < thr)) s_sel[j] = sm;     // the first position with recall >= thr
+        }
+      }
+      __syncthreads();
+    }
+    run_tp += tot_t;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float out;
+    if (mode == YV4_MAP_AP_AREA) {
+      const double r_last = (double)(float)total_tp / den;
+      if (1.0 != r_last) acc += (1.0 - r_last) * 0.0;     // the closing step to mrec[n + 1] = 1 meets mpre[n + 1] = 0
+      out = (float)acc;
+    } else {
+      out = 0.f;
+      for (int j = 0; j < kMfPoints; ++j) out += s_sel[j];
+      out = out / 11.f;
+    }
+    ap[blockIdx.x] = out;
+  }
+}
+
+static inline int mf_class_bits(int C) { return C < 65535 ? 48 : 64; }      // the key's high word holds 0 .. C
+static inline int mf_problem_bits(int64_t P) { return P < 65536 ? 16 : 32; }  // the key holds 0 .. P
+static inline size_t mf_hist_bytes(int64_t n) { return rs_hist_bytes(n + kRsTile); }
+
+struct MfRankLayout {
+  size_t ka0, ka1, va0, va1, kb0, kb1, vb0, vb1, hist;
+  Carve carve;
+  explicit MfRankLayout(int64_t D) {
+    const size_t n = (size_t)(D > 0 ? D : 1);
+    ka0 = carve.take(8 * n);
+    ka1 = carve.take(8 * n);
+    va0 = carve.take(4 * n);
+    va1 = carve.take(4 * n);
+    kb0 = carve.take(4 * n);
+    kb1 = carve.take(4 * n);
+    vb0 = carve.take(4 * n);
+    vb1 = carve.take(4 * n);
+    hist = carve.take(mf_hist_bytes((int64_t)n));
+  }
+};
+
+}  // namespace
+}  // namespace yv4
+
+using namespace yv4;
+
+extern "C" size_t yv4_map_rank_work(int64_t total_det) {
+  if (total_det < 0) return 0;
+  return MfRankLayout(total_det).carve.off;
+}
+
+extern "C" int yv4_map_rank(const float* det, const int64_t* labels, const int64_t* img_index, int64_t total_det, int N,
+                            int C, const int64_t* gt_off, void* work, float* det4, int64_t* det_off, int32_t* order,
+                            int32_t* rank, int64_t* iou_off, int32_t* cls_order, int64_t* info, void* stream) {
+  YV4_REQUIRE(N > 0 && C > 0 && (int64_t)N * C < 0x7fffffff, "map_rank: N x C problems must be positive and fit 31 bits");
+  YV4_REQUIRE(gt_off && det_off && iou_off && info, "map_rank: bad problem table");
+  YV4_REQUIRE(total_det >= 0 && total_det < 0x7f7f7f7f, "map_rank: more than 2^31 detections");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int P = N * C;
+  const int64_t D = total_det;
+  if (D == 0) {
+    if (hipMemsetAsync(det_off, 0, sizeof(int64_t) * ((size_t)P + 1), s) != hipSuccess ||
+        hipMemsetAsync(iou_off, 0, sizeof(int64_t) * ((size_t)P + 1), s) != hipSuccess ||
+        hipMemsetAsync(info, 0, sizeof(int64_t) * ((size_t)C + 2), s) != hipSuccess) {
+      set_error("map_rank: memset failed");
+      return YV4_E_LAUNCH;
+    }
+    return YV4_OK;
+  }
+  YV4_REQUIRE(det && labels && img_index && work && det4 && order && rank && cls_order, "map_rank: null pointer");
+  YV4_REQUIRE(((uintptr_t)work & 7) == 0, "map_rank: work must be 8-byte aligned");
+  YV4_REQUIRE(((uintptr_t)det4 & 15) == 0, "map_rank: det4 must be 16-byte aligned");
+  const MfRankLayout L(D);
+  char* w = reinterpret_cast<char*>(work);
+  uint64_t* ka0 = reinterpret_cast<uint64_t*>(w + L.ka0);
+  uint64_t* ka1 = reinterpret_cast<uint64_t*>(w + L.ka1);
+  uint32_t* va0 = reinterpret_cast<uint32_t*>(w + L.va0);
+  uint32_t* va1 = reinterpret_cast<uint32_t*>(w + L.va1);
+  uint32_t* kb0 = reinterpret_cast<uint32_t*>(w + L.kb0);
+  uint32_t* kb1 = reinterpret_cast<uint32_t*>(w + L.kb1);
+  uint32_t* vb0 = reinterpret_cast<uint32_t*>(w + L.vb0);
+  uint32_t* vb1 = reinterpret_cast<uint32_t*>(w + L.vb1);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(w + L.hist);
+  const unsigned blocks = (unsigned)((D + 255) / 256);
+  hipLaunchKernelGGL(mf_keys_class_kernel, dim3(blocks), dim3(256), 0, s, det, labels, img_index, D, N, C, ka0, va0);
+  // the first pass only reads its input, so both sorts run "in place": the results land in (ka0, va0) and (kb0, vb0)
+  int rc = rs_sort<uint64_t, uint32_t, true>(ka0, ka0, ka1, va0, va0, va1, D, mf_class_bits(C), hist, s, "map_rank: radix sort");
+  if (rc != YV4_OK) return rc;
+  hipLaunchKernelGGL(mf_keys_problem_kernel, dim3(blocks), dim3(256), 0, s, ka0, va0, img_index, D, N, C, kb0, vb0);
+  rc = rs_sort<uint32_t, uint32_t, true>(kb0, kb0, kb1, vb0, vb0, vb1, D, mf_problem_bits(P), hist, s, "map_rank: radix sort");
+  if (rc != YV4_OK) return rc;
+  hipLaunchKernelGGL(mf_offsets_kernel, dim3((unsigned)(P / 256 + 1)), dim3(256), 0, s, kb0, D, P, det_off);
+  hipLaunchKernelGGL(mf_gather_kernel, dim3(blocks), dim3(256), 0, s, det, va0, vb0, kb0, det_off, D, P, det4, order, rank,
+                     cls_order);
+  hipLaunchKernelGGL(mf_pairs_kernel, dim3(1), dim3(1024), 0, s, det_off, gt_off, P, iou_off, info);
+  hipLaunchKernelGGL(mf_class_counts_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, det_off, N, C, info);
+  YV4_CHECK_LAUNCH("map_rank");
+  return YV4_OK;
+}
+
+extern "C" size_t yv4_map_accumulate_work(int64_t total_det, int num_thrs, int num_ranges) {
+  if (total_det < 0 || num_thrs <= 0 || num_ranges <= 0) return 0;
+  return align256(4 * (size_t)num_thrs * (size_t)num_ranges * (size_t)(total_det > 0 ? total_det : 1));
+}
+
+extern "C" int yv4_map_accumulate(const uint8_t* tp, const uint8_t* fp, const int32_t* cls_order, const int64_t* det_off,
+                                  const int64_t* num_gts, int64_t total_det, int N, int C, int num_thrs, int num_ranges,
+                                  int mode, void* work, float* ap, double* last_recall, float* last_precision, double* recall,
+                                  float* precision, int64_t* num_dets, void* stream) {
+  YV4_REQUIRE(N > 0 && C > 0 && (int64_t)N * C < 0x7fffffff, "map_accumulate: N x C problems must be positive and fit 31 bits");
+  YV4_REQUIRE(num_thrs > 0 && num_ranges > 0 && (int64_t)num_thrs * C * num_ranges < 0x7fffffff,
+              "map_accumulate: thresholds x classes x area ranges must be positive and fit 31 bits");
+  YV4_REQUIRE(mode == YV4_MAP_AP_AREA || mode == YV4_MAP_AP_11POINTS, "map_accumulate: mode must be YV4_MAP_AP_AREA or _11POINTS");
+  YV4_REQUIRE(total_det >= 0 && total_det < 0x7f7f7f7f, "map_accumulate: more than 2^31 detections");
+  YV4_REQUIRE(det_off && num_gts && ap && last_recall && last_precision && num_dets && work, "map_accumulate: null pointer");
+  YV4_REQUIRE(total_det == 0 || (tp && fp && cls_order), "map_accumulate: null detection pointer");
+  YV4_REQUIRE((recall == nullptr) == (precision == nullptr), "map_accumulate: the curves come as a pair");
+  YV4_REQUIRE(((uintptr_t)work & 3) == 0, "map_accumulate: work must be 4-byte aligned");
+  hipLaunchKernelGGL(mf_accumulate_kernel, dim3((unsigned)((int64_t)num_thrs * C * num_ranges)), dim3(kMfThreads), 0,
+                     reinterpret_cast<hipStream_t>(stream), tp, fp, cls_order, det_off, num_gts, total_det, N, C, num_ranges,
+                     mode, reinterpret_cast<float*>(work), ap, last_recall, last_precision, recall, precision, num_dets);
+  YV4_CHECK_LAUNCH("map_accumulate");
+  return YV4_OK;
+}

@@ -1,6 +1,6 @@
 // The library's stable LSD radix sort (rs_sort) and the carving of the workspaces it sorts in, shared by the hard and
-// soft NMS split paths (nms_split.hip, soft_nms.hip), the top-k slot tables of test-time augmentation (tta.hip) and the
-// COCO evaluation (coco_eval.hip).  Kernels live in an unnamed namespace: each translation unit that includes this
+// soft NMS split paths (nms_split.hip, soft_nms.hip), the top-k slot tables of test-time augmentation (tta.hip), the
+// COCO evaluation (coco_eval.hip) and the flat-table mAP (map_flat.hip).  Kernels live in an unnamed namespace: each translation unit that includes this
 // header gets its own copies.
 #pragma once
 #include "yv4_common.h"

@@ -27,6 +27,28 @@ Boxes.  Boxes are float32, which is what the reference's dataset loaders produce
 to float32 first; the reference would have computed their areas and (in ``tpfp_imagenet``) thresholds in float64.  This
 is a stated deviation.  Boxes are expected to be finite.
 
+The flat form.  ``eval_map`` / ``evaluate_map`` also take ``(dets (D, 5), labels (D,), img_index (D,))`` as numpy arrays
+or GPU tensors -- a test loop's table before ``bbox2result`` (``results.DeviceResults``); GPU tensors never visit the
+host.  Then the two host ends move to the device too (csrc/map_flat.hip): ``yv4_map_rank`` orders the table, and after
+the same overlaps and tpfp calls ``yv4_map_accumulate`` forms recall / precision / AP; ``MapGt`` keeps the ground-truth
+tables of a dataset between calls.  Definition, where it is more than the list path's:
+
+* A detection's problem is ``label * N + img_index``; one with a label outside ``[0, C)`` or an image index outside
+  ``[0, N)`` takes no part.
+* Ties -- the stated difference from the list path.  The visiting order inside a problem and the per-class order are
+  descending score, STABLE: equal scores (``+0`` and ``-0`` are equal) keep the order of the flat table.  The list path
+  orders them as the host's ``np.argsort`` happens to.  The two paths agree whenever no two detections of a class share
+  a score; scores are expected finite.
+* Accumulation per (class, threshold, area range): integer cumulative tp / fp (the float32 sums of the list path are
+  exact below 2**24 detections per class; more raises here too), ``recall = float32(ctp) / max(num_gts, float32 eps)`` in
+  float64, ``precision = float32(ctp) / max(float32(ctp + cfp), float32 eps)`` in float32, and ``average_precision`` on
+  those dtypes.  ``'area'`` sums ``(mrec[i+1] - mrec[i]) * mpre[i+1]`` over the positions where recall changes into ONE
+  float64 accumulator in rank order (``np.cumsum(terms)[-1]``; ``np.sum`` adds pairwise, which can differ in the last
+  bit of the float64 sum before it is rounded to float32); ``'11points'`` is eleven float32 adds and one division.
+* By default ``eval_results[c]['recall']`` / ``['precision']`` hold the curve's last point only (all that the summary
+  table and ``evaluate_map`` read); ``curves=True`` downloads the full arrays.
+* A foreign ``tpfp_fn`` has no device form: with flat input it raises.
+
 ``eval_recalls`` (``recall.py``, ``metric='recall'``) is not built: it scores RPN proposal lists, which no detector of
 this package produces.
 """
@@ -38,6 +60,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .coco_eval import _is_flat
 from .eval_utils import _dev, _offsets, average_precision
 from .ops import stream_ptr
 
@@ -89,6 +112,29 @@ def bbox_overlaps_batched(boxes1, boxes2, off1, off2, mode='iou', eps=1e-6, dev_
     return iou, iou_off
 
 
+def _gt_tables(annotations, C):
+    """(gt (G, 4) float32, gt_ignore (G,) uint8, ng (C * N,) int64): every image's regular and ignored gts keyed by
+    problem, then one stable sort (regular before ignored, each in the annotation's order)."""
+    N = len(annotations)
+    boxes, key, ign = [np.zeros((0, 4), np.float32)], [np.zeros(0, np.int64)], [np.zeros(0, bool)]
+    for i, a in enumerate(annotations):
+        parts = [(a['bboxes'], a['labels'], False)]
+        if a.get('labels_ignore', None) is not None:
+            parts.append((a['bboxes_ignore'], a['labels_ignore'], True))
+        for b, lab, flag in parts:
+            lab = np.asarray(lab).reshape(-1)
+            if len(lab):
+                boxes.append(_boxes(b)[:, :4])
+                key.append(lab.astype(np.int64) * N + i)
+                ign.append(np.full(len(lab), flag))
+    boxes, key, ign = np.concatenate(boxes), np.concatenate(key), np.concatenate(ign)
+    keep = (key >= 0) & (key < C * N)                        # labels outside [0, C) belong to no problem
+    boxes, key, ign = boxes[keep], key[keep], ign[keep]
+    by = np.lexsort((ign, key))                              # stable: ties keep the gathering order
+    return (np.ascontiguousarray(boxes[by], dtype=np.float32).reshape(-1, 4), ign[by].astype(np.uint8),
+            np.bincount(key, minlength=C * N).astype(np.int64))
+
+
 class MapTables:
     """The (image, class) problems of a dataset as flat host tables, class-major: problem ``c * num_imgs + i``.
 
@@ -106,27 +152,8 @@ class MapTables:
         dets = [d for d in dets if len(d)]
         self.det = (np.concatenate(dets).astype(np.float32, copy=False).reshape(-1, 5) if dets
                     else np.zeros((0, 5), np.float32))
-        # gts: every image's regular and ignored gts keyed by problem, then one stable sort (regular before ignored,
-        # each in the annotation's order)
-        boxes, key, ign = [np.zeros((0, 4), np.float32)], [np.zeros(0, np.int64)], [np.zeros(0, bool)]
-        for i, a in enumerate(annotations):
-            parts = [(a['bboxes'], a['labels'], False)]
-            if a.get('labels_ignore', None) is not None:
-                parts.append((a['bboxes_ignore'], a['labels_ignore'], True))
-            for b, lab, flag in parts:
-                lab = np.asarray(lab).reshape(-1)
-                if len(lab):
-                    boxes.append(_boxes(b)[:, :4])
-                    key.append(lab.astype(np.int64) * N + i)
-                    ign.append(np.full(len(lab), flag))
-        boxes, key, ign = np.concatenate(boxes), np.concatenate(key), np.concatenate(ign)
-        keep = (key >= 0) & (key < C * N)                        # labels outside [0, C) belong to no problem
-        boxes, key, ign = boxes[keep], key[keep], ign[keep]
-        by = np.lexsort((ign, key))                              # stable: ties keep the gathering order
-        self.gt = np.ascontiguousarray(boxes[by], dtype=np.float32).reshape(-1, 4)
-        self.gt_ignore = ign[by].astype(np.uint8)
-        self.ng = ng = np.bincount(key, minlength=C * N).astype(np.int64)
-        self.det_off, self.gt_off = _offsets(nd), _offsets(ng)
+        self.gt, self.gt_ignore, self.ng = _gt_tables(annotations, C)
+        self.det_off, self.gt_off = _offsets(nd), _offsets(self.ng)
         self.order = self.rank = self.cls_order = None
 
     def class_slice(self, c):
@@ -250,6 +277,21 @@ def _num_gts(tab, area):
     return out
 
 
+def _mean_ap(eval_results, scale_ranges):
+    """mean_ap.py:385-396: the mean over the classes that have gts (per scale range)."""
+    if scale_ranges is not None:
+        all_ap = np.vstack([r['ap'] for r in eval_results])
+        all_num_gts = np.vstack([r['num_gts'] for r in eval_results])
+        mean_ap = []
+        for k in range(all_ap.shape[1]):
+            has = all_num_gts[:, k] > 0
+            mean_ap.append(all_ap[has, k].mean() if np.any(has) else 0.0)
+    else:
+        aps = [r['ap'] for r in eval_results if r['num_gts'] > 0]
+        mean_ap = np.array(aps).mean().item() if aps else 0.0
+    return mean_ap
+
+
 def accumulate(tab, tp, fp, num_gts, scale_ranges, dataset):
     """mean_ap.py:353-396 for one threshold: tp / fp (K, D) flags -> (mean_ap, eval_results)."""
     mode = 'area' if dataset != 'voc07' else '11points'
@@ -270,17 +312,7 @@ def accumulate(tab, tp, fp, num_gts, scale_ranges, dataset):
             recalls, precisions, n = recalls[0, :], precisions[0, :], n.item()
         ap = average_precision(recalls, precisions, mode)
         eval_results.append({'num_gts': n, 'num_dets': num_dets, 'recall': recalls, 'precision': precisions, 'ap': ap})
-    if scale_ranges is not None:
-        all_ap = np.vstack([r['ap'] for r in eval_results])
-        all_num_gts = np.vstack([r['num_gts'] for r in eval_results])
-        mean_ap = []
-        for k in range(all_ap.shape[1]):
-            has = all_num_gts[:, k] > 0
-            mean_ap.append(all_ap[has, k].mean() if np.any(has) else 0.0)
-    else:
-        aps = [r['ap'] for r in eval_results if r['num_gts'] > 0]
-        mean_ap = np.array(aps).mean().item() if aps else 0.0
-    return mean_ap, eval_results
+    return _mean_ap(eval_results, scale_ranges), eval_results
 
 
 def _custom_tpfp_all(tab, tpfp_fn, thrs, area_ranges, K):
@@ -298,14 +330,213 @@ def _custom_tpfp_all(tab, tpfp_fn, thrs, area_ranges, K):
     return tp, fp
 
 
-def eval_map(det_results, annotations, scale_ranges=None, iou_thr=0.5, dataset=None, logger=None, tpfp_fn=None, nproc=4):
+# ---- the flat form: ordering and accumulation on the device too (csrc/map_flat.hip) ------------------------------------
+class MapGt:
+    """The ground-truth side of ``MapTables``, built once per dataset: class-major gts (problem ``c * num_imgs + i``),
+    a problem's ignored gts behind its regular ones, ``gt_off``.  The imagenet rule's ``gt - 1`` boxes and ratios are
+    today's numpy expressions on the host; the device copies are cached per device; ``num_gts(area)`` is today's
+    ``_num_gts`` arithmetic.  ``annotations``: what the dataset's ``get_ann_info`` returns per image."""
+
+    def __init__(self, annotations, num_classes):
+        self.annotations = annotations
+        self.num_imgs, self.num_classes = len(annotations), int(num_classes)
+        if self.num_imgs <= 0 or self.num_classes <= 0:
+            raise ValueError('MapGt needs at least one image and one class')
+        if self.num_imgs * self.num_classes >= 2 ** 31 - 1:
+            raise ValueError(f'{self.num_imgs} images x {self.num_classes} classes: the problem index does not fit 31 bits')
+        self.gt, self.gt_ignore, self.ng = _gt_tables(annotations, self.num_classes)
+        self.gt_off = _offsets(self.ng)
+        self._host_imagenet = None
+        self._num_gts = {}
+        self._device = {}
+
+    def imagenet_tables(self):
+        """(gt - 1, w*h / ((w+10)*(h+10))) as ``tpfp_batched`` forms them."""
+        if self._host_imagenet is None:
+            w, h = self.gt[:, 2] - self.gt[:, 0], self.gt[:, 3] - self.gt[:, 1]
+            with np.errstate(all='ignore'):
+                self._host_imagenet = (self.gt - np.float32(1), (w * h) / ((w + 10.0) * (h + 10.0)))
+        return self._host_imagenet
+
+    def device(self, dev, imagenet=False):
+        """The device copies: gt, ign, gt_off, and gt_m1 / ratio once the imagenet rule asked for them."""
+        d = self._device.setdefault((dev.type, dev.index), {})
+        if 'gt' not in d:
+            d.update(gt=_dev(self.gt, np.float32, dev), ign=_dev(self.gt_ignore, np.uint8, dev),
+                     gt_off=_dev(self.gt_off, np.int64, dev))
+        if imagenet and 'gt_m1' not in d:
+            gt_m1, ratio = self.imagenet_tables()
+            d.update(gt_m1=_dev(gt_m1, np.float32, dev), ratio=_dev(ratio, np.float32, dev))
+        return d
+
+    def num_gts(self, area):
+        """(C, K) per area table, kept: the tables do not change."""
+        key = None if area is None else area.tobytes()
+        if key not in self._num_gts:
+            self._num_gts[key] = _num_gts(self, area)
+        return self._num_gts[key]
+
+
+def _device_flat():
+    dev = _device()
+    if not _lib.has_map_flat():
+        raise RuntimeError('the loaded libyv4_hip.so has no yv4_map_rank / yv4_map_accumulate; rebuild it')
+    return dev
+
+
+def _flat_to_device(flat, dev):
+    dets, labels, img_index = flat
+
+    def put(x, np_dtype, t_dtype):
+        if isinstance(x, torch.Tensor):
+            return x.to(dev, t_dtype).contiguous()
+        return _dev(np.asarray(x), np_dtype, dev)
+    dets = put(dets, np.float32, torch.float32).reshape(-1, 5)
+    labels, img_index = put(labels, np.int64, torch.int64).reshape(-1), put(img_index, np.int64, torch.int64).reshape(-1)
+    if labels.numel() != dets.shape[0] or img_index.numel() != dets.shape[0]:
+        raise ValueError(f'flat results: {dets.shape[0]} detections, {labels.numel()} labels, {img_index.numel()} image indices')
+    return dets, labels, img_index
+
+
+def map_flat_device(flat, gt, mode, iou_thrs, area_ranges=None, ap_mode='area', curves=False, phases=None):
+    """The whole flat pipeline for every threshold and area range: ``yv4_map_rank``, one read-back (the pair total and
+    the class counts), ``yv4_bbox_overlaps_batched``, ``yv4_tpfp_batched``, ``yv4_map_accumulate``, one download.
+    ``flat``: ``(dets (D, 5), labels (D,), img_index (D,))``, numpy arrays or GPU tensors (those never visit the host);
+    ``gt``: a ``MapGt``.  Returns host arrays: ap (T, C, K) float32, last_recall float64 / last_precision float32
+    (T, C, K), num_dets (C,), num_gts (C, K) and, with ``curves``, recall float64 / precision float32 (T, K, Dv) whose
+    columns ``[cls_off[c], cls_off[c + 1])`` are class c's curve.  ``phases``: an optional dict that receives seconds
+    per phase (each closed by a synchronise)."""
+    import time
+    dev = _device_flat()
+
+    def tick():
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    marks = [tick()] if phases is not None else None
+    thrs = np.ascontiguousarray(iou_thrs, dtype=np.float32).reshape(-1)
+    area = _area_table(area_ranges)
+    T, K = len(thrs), 1 if area is None else len(area)
+    N, C = gt.num_imgs, gt.num_classes
+    P, G = N * C, len(gt.gt)
+    imagenet = mode == _lib.TPFP_IMAGENET
+    g = gt.device(dev, imagenet)
+    num_gts = gt.num_gts(area)
+    dets, labels, img_index = _flat_to_device(flat, dev)
+    D = int(dets.shape[0])
+    t_thr = _dev(thrs, np.float32, dev)
+    t_area = None if area is None else _dev(area, np.float32, dev)
+    t_ngts = _dev(num_gts, np.int64, dev)
+    if phases is not None:
+        marks.append(tick())
+    lib = _lib.lib()
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()     # noqa: E731
+    i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)            # noqa: E731
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)            # noqa: E731
+    det4 = torch.empty((max(D, 1), 4), dtype=torch.float32, device=dev)
+    det_off, iou_off, info = i64(P + 1), i64(P + 1), i64(C + 2)
+    order, rank, cls_order = i32(max(D, 1)), i32(max(D, 1)), i32(max(D, 1))
+    work = torch.empty(max(int(lib.yv4_map_rank_work(D)), 8), dtype=torch.uint8, device=dev)
+    check(lib.yv4_map_rank(ptr(dets), ptr(labels), ptr(img_index), D, N, C, g['gt_off'].data_ptr(), work.data_ptr(),
+                           det4.data_ptr(), det_off.data_ptr(), order.data_ptr(), rank.data_ptr(), iou_off.data_ptr(),
+                           cls_order.data_ptr(), info.data_ptr(), stream_ptr()), 'yv4_map_rank')
+    info_h = info.cpu().numpy()                                 # the one read-back between the device calls
+    pairs, Dv, counts = int(info_h[0]), int(info_h[1]), info_h[2:]
+    if phases is not None:
+        marks.append(tick())
+    for c in np.flatnonzero(counts >= 2 ** 24):
+        raise ValueError(f'class {c} has {counts[c]} detections: the float32 cumulative sums of the reference are '
+                         'exact only below 2**24')
+    iou = torch.empty(max(pairs, 1), dtype=torch.float32, device=dev)
+    if pairs:
+        check(lib.yv4_bbox_overlaps_batched(det4.data_ptr(), (g['gt_m1'] if imagenet else g['gt']).data_ptr(),
+                                            det_off.data_ptr(), g['gt_off'].data_ptr(), iou_off.data_ptr(), P, pairs,
+                                            _lib.OVERLAPS_IOU, float(np.float32(1e-6)), iou.data_ptr(), stream_ptr()),
+              'yv4_bbox_overlaps_batched')
+    else:
+        iou.zero_()
+    tp = torch.empty((T, K, Dv), dtype=torch.uint8, device=dev)
+    fp = torch.empty((T, K, Dv), dtype=torch.uint8, device=dev)
+    if Dv:
+        work = torch.empty(max(int(lib.yv4_tpfp_work(mode, Dv, G, T)), 4), dtype=torch.uint8, device=dev)
+        check(lib.yv4_tpfp_batched(mode, det4.data_ptr(), ptr(g['gt']), ptr(g['ign']), ptr(g.get('ratio')),
+                                   order.data_ptr() if imagenet else None, None if imagenet else rank.data_ptr(),
+                                   det_off.data_ptr(), g['gt_off'].data_ptr(), iou_off.data_ptr(), P, Dv, G, iou.data_ptr(),
+                                   t_thr.data_ptr(), T, ptr(t_area), K, work.data_ptr(), tp.data_ptr(), fp.data_ptr(),
+                                   stream_ptr()), 'yv4_tpfp_batched')
+    if phases is not None:
+        marks.append(tick())
+    ap = torch.empty((T, C, K), dtype=torch.float32, device=dev)
+    last_r = torch.empty((T, C, K), dtype=torch.float64, device=dev)
+    last_p = torch.empty((T, C, K), dtype=torch.float32, device=dev)
+    num_dets = i64(C)
+    rec = torch.empty((T, K, Dv), dtype=torch.float64, device=dev) if curves else None
+    prec = torch.empty((T, K, Dv), dtype=torch.float32, device=dev) if curves else None
+    work = torch.empty(max(int(lib.yv4_map_accumulate_work(Dv, T, K)), 4), dtype=torch.uint8, device=dev)
+    check(lib.yv4_map_accumulate(ptr(tp), ptr(fp), cls_order.data_ptr(), det_off.data_ptr(), t_ngts.data_ptr(), Dv, N, C, T,
+                                 K, _lib.MAP_AP_11POINTS if ap_mode == '11points' else _lib.MAP_AP_AREA, work.data_ptr(),
+                                 ap.data_ptr(), last_r.data_ptr(), last_p.data_ptr(), ptr(rec), ptr(prec),
+                                 num_dets.data_ptr(), stream_ptr()), 'yv4_map_accumulate')
+    if phases is not None:
+        marks.append(tick())
+    out = dict(ap=ap.cpu().numpy(), last_recall=last_r.cpu().numpy(), last_precision=last_p.cpu().numpy(),
+               num_dets=num_dets.cpu().numpy(), num_gts=num_gts, cls_off=_offsets(counts), total_det=Dv, pairs=pairs)
+    if curves:
+        out.update(recall=rec.cpu().numpy(), precision=prec.cpu().numpy())
+    if phases is not None:
+        marks.append(tick())
+        phases.update({k: b - a for k, a, b in zip(('upload', 'rank', 'tpfp', 'accumulate', 'download'), marks, marks[1:])})
+    return out
+
+
+def _flat_eval_results(out, t, scale_ranges, curves):
+    """One threshold of ``map_flat_device`` in ``accumulate``'s structure.  Without ``curves`` recall / precision hold
+    the curve's last point only (nothing for a class without detections)."""
+    eval_results = []
+    for c in range(out['ap'].shape[1]):
+        n = out['num_gts'][c].copy()
+        num_dets = int(out['num_dets'][c])
+        if curves:
+            sl = slice(int(out['cls_off'][c]), int(out['cls_off'][c + 1]))
+            recalls, precisions = out['recall'][t][:, sl].copy(), out['precision'][t][:, sl].copy()
+        else:
+            recalls = out['last_recall'][t, c][:, np.newaxis][:, :min(num_dets, 1)].copy()
+            precisions = out['last_precision'][t, c][:, np.newaxis][:, :min(num_dets, 1)].copy()
+        ap = out['ap'][t, c].copy()
+        if scale_ranges is None:
+            recalls, precisions, n, ap = recalls[0, :], precisions[0, :], n.item(), ap[0]
+        eval_results.append({'num_gts': n, 'num_dets': num_dets, 'recall': recalls, 'precision': precisions, 'ap': ap})
+    return _mean_ap(eval_results, scale_ranges), eval_results
+
+
+def _as_map_gt(annotations, dataset, num_classes):
+    if isinstance(annotations, MapGt):
+        return annotations
+    if num_classes is None and isinstance(dataset, (list, tuple)):
+        num_classes = len(dataset)
+    if num_classes is None:
+        raise ValueError('flat results carry no class count: pass a MapGt, num_classes, or the class names as dataset')
+    return MapGt(annotations, num_classes)
+
+
+def eval_map(det_results, annotations, scale_ranges=None, iou_thr=0.5, dataset=None, logger=None, tpfp_fn=None, nproc=4,
+             curves=False, num_classes=None):
     """mean_ap.py:267: ``(mean_ap, eval_results)``; ``eval_results[c]`` holds num_gts / num_dets / recall / precision /
     ap of class c.  ``iou_thr`` may also be a list or tuple: the batched entry, which returns one ``(mean_ap,
     eval_results)`` per threshold from one overlaps call and one tpfp call over the whole dataset.  ``nproc`` is
     accepted and unused.  ``tpfp_fn=None`` selects the ImageNet rule for ``dataset in ('det', 'vid')`` and the default
     rule otherwise; this module's ``tpfp_default`` / ``tpfp_imagenet`` select their rule; any other callable is called
-    per (image, class) on the host."""
-    assert len(det_results) == len(annotations)
+    per (image, class) on the host.
+
+    ``det_results`` may also be the flat form ``(dets (D, 5), labels (D,), img_index (D,))`` of numpy arrays or GPU
+    tensors (see the module docstring): ordering and accumulation then run on the device as well.  ``annotations`` may
+    be a ``MapGt`` (with per-image lists, ``num_classes`` or the class names as ``dataset`` give the class count);
+    ``curves=True`` downloads the full recall / precision arrays instead of their last points; only the two rules of
+    this module are available."""
+    flat = _is_flat(det_results)
+    if not flat:
+        if isinstance(annotations, MapGt):
+            annotations = annotations.annotations
+        assert len(det_results) == len(annotations)
     many = isinstance(iou_thr, (list, tuple, np.ndarray))
     thrs = list(iou_thr) if many else [iou_thr]
     area_ranges = [(rg[0] ** 2, rg[1] ** 2) for rg in scale_ranges] if scale_ranges is not None else None
@@ -313,6 +544,21 @@ def eval_map(det_results, annotations, scale_ranges=None, iou_thr=0.5, dataset=N
         tpfp_fn = tpfp_imagenet if dataset in ['det', 'vid'] else tpfp_default
     if not callable(tpfp_fn):
         raise ValueError(f'tpfp_fn has to be a function or None, but got {tpfp_fn}')
+    if flat:
+        if tpfp_fn is not tpfp_default and tpfp_fn is not tpfp_imagenet:
+            raise ValueError('flat results are scored on the device, which knows tpfp_default and tpfp_imagenet only; '
+                             f'for {tpfp_fn!r} pass the per-image lists')
+        out = map_flat_device(det_results, _as_map_gt(annotations, dataset, num_classes),
+                              _lib.TPFP_IMAGENET if tpfp_fn is tpfp_imagenet else _lib.TPFP_DEFAULT, thrs, area_ranges,
+                              '11points' if dataset == 'voc07' else 'area', curves)
+        res = []
+        for t, thr in enumerate(thrs):
+            mean_ap, eval_results = _flat_eval_results(out, t, scale_ranges, curves)
+            if many and logger != 'silent':
+                _log(f'\n{"-" * 15}iou_thr: {thr}{"-" * 15}', logger)
+            print_map_summary(mean_ap, eval_results, dataset, area_ranges, logger=logger)
+            res.append((mean_ap, eval_results))
+        return res if many else res[0]
     area = _area_table(area_ranges)
     K = 1 if area is None else len(area)
     if tpfp_fn is tpfp_default or tpfp_fn is tpfp_imagenet:
@@ -333,10 +579,11 @@ def eval_map(det_results, annotations, scale_ranges=None, iou_thr=0.5, dataset=N
     return out if many else out[0]
 
 
-def evaluate_map(results, annotations, classes=None, iou_thr=0.5, scale_ranges=None, logger=None, metric='mAP'):
+def evaluate_map(results, annotations, classes=None, iou_thr=0.5, scale_ranges=None, logger=None, metric='mAP',
+                 num_classes=None):
     """``dataset.evaluate(results, metric='mAP')`` (datasets/custom.py:309-325): ``AP50``-style keys (rounded to three
     places) plus ``mAP``, their mean, from ONE device pass over all thresholds.  ``annotations``: what the dataset's
-    ``get_ann_info`` returns per image."""
+    ``get_ann_info`` returns per image, or a ``MapGt``.  ``results``: the per-image lists or the flat tuple."""
     if not isinstance(metric, str):
         assert len(metric) == 1
         metric = metric[0]
@@ -350,7 +597,7 @@ def evaluate_map(results, annotations, classes=None, iou_thr=0.5, scale_ranges=N
     eval_results = OrderedDict()
     mean_aps = []
     for thr, (mean_ap, _) in zip(iou_thrs, eval_map(results, annotations, scale_ranges=scale_ranges, iou_thr=iou_thrs,
-                                                    dataset=classes, logger=logger)):
+                                                    dataset=classes, logger=logger, num_classes=num_classes)):
         mean_aps.append(mean_ap)
         eval_results[f'AP{int(thr * 100):02d}'] = round(mean_ap, 3)
     eval_results['mAP'] = sum(mean_aps) / len(mean_aps)

@@ -14,6 +14,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .coco_eval import CocoGt, evaluate_bbox, flatten_results
+from .map_eval import MapGt, evaluate_map
 from .ops import stream_ptr
 
 
@@ -139,3 +140,32 @@ class CocoBBoxDataset:
         ``results``: the per-image lists or the flat tuple, ``img_index`` being positions in ``img_ids``."""
         return evaluate_bbox(results, self.coco, cat_ids=self.cat_ids, img_ids=self.img_ids, logger=logger, metric=metric,
                              **kwargs)
+
+
+class CustomBBoxDataset:
+    """The ``.dataset`` of a validation loader that scores ``metric='mAP'``, as ``CustomDataset.evaluate`` and
+    ``VOCDataset.evaluate`` do by default (``datasets/custom.py:280-337``).  ``annotations``: per image the dict that
+    ``get_ann_info`` returns (``bboxes`` (n, 4), ``labels`` (n,), optionally ``bboxes_ignore`` / ``labels_ignore``);
+    ``classes``: the class names.  It loads no images.  ``accepts_flat``: ``evaluate`` takes the flat GPU table as well
+    as the list form; the ground-truth tables are built once (``MapGt``) and their device copies kept."""
+
+    # the flat loop plus device scoring against the list loop plus list scoring: DESIGN 18's table
+    accepts_flat = True
+
+    def __init__(self, annotations, classes):
+        self.CLASSES = tuple(classes)
+        self.annotations = list(annotations)
+        self.map_gt = MapGt(self.annotations, len(self.CLASSES))
+
+    def __len__(self):
+        return len(self.annotations)
+
+    def get_ann_info(self, idx):
+        return self.annotations[idx]
+
+    def evaluate(self, results, metric='mAP', logger=None, iou_thr=0.5, scale_ranges=None):
+        """``evaluate_map``: ``AP50``-style keys and ``mAP``; ``results``: the per-image lists or the flat tuple,
+        ``img_index`` being positions in ``annotations``.  Unknown metrics raise ``KeyError``; ``'recall'`` raises what
+        ``evaluate_map`` raises."""
+        return evaluate_map(results, self.map_gt, classes=list(self.CLASSES), iou_thr=iou_thr, scale_ranges=scale_ranges,
+                            logger=logger, metric=metric)

@@ -7,7 +7,12 @@ Phases of the package (host clock around a device synchronise, shapes warmed by 
 runs with min / max): host table build, host sorts, upload, the two device calls, download, host accumulation.
 Beside it, on --ref-images images of the same dataset and labelled as CPU numbers: the package's numpy restatement
 (tests/_map_ref.py) on one core, and -- where the reference checkout exists -- the imported reference with nproc=4,
-called once per threshold as datasets/custom.py does.  Prints ONE JSON line."""
+called once per threshold as datasets/custom.py does.
+The flat legs (``flat``) score the same dataset from the flat table ``(dets, labels, img_index)`` -- ordering and
+accumulation on the device too (csrc/map_flat.hip) -- as numpy arrays and as GPU tensors, each with the ground-truth
+tables built per call and with a cached ``MapGt``: gt_build, upload (the tables, the thresholds, a numpy table), rank
+(``yv4_map_rank`` and its one read-back), tpfp (overlaps + tpfp), accumulate, download, results (the per-class dicts and
+mean_ap on the host).  The list leg and the flat legs alternate run by run.  Prints ONE JSON line."""
 import argparse
 import json
 import os
@@ -50,10 +55,41 @@ def stats(xs):
     return dict(median_ms=float(np.median(xs)) * 1e3, min_ms=float(np.min(xs)) * 1e3, max_ms=float(np.max(xs)) * 1e3)
 
 
-def gpu_phases(dets, annos, reps):
+FLAT_LEGS = ('numpy', 'numpy_cached_gt', 'gpu', 'gpu_cached_gt')
+FLAT_PHASES = ('gt_build', 'upload', 'rank', 'tpfp', 'accumulate', 'download', 'results', 'total')
+
+
+def flat_leg(ME, _lib, flat, annos, classes, cached_gt, rec):
+    ph = {}
+    t0 = time.perf_counter()
+    gt = cached_gt if cached_gt is not None else ME.MapGt(annos, classes)
+    t1 = time.perf_counter()
+    out = ME.map_flat_device(flat, gt, _lib.TPFP_DEFAULT, THRS, None, 'area', False, phases=ph)
+    t2 = time.perf_counter()
+    res = [ME._flat_eval_results(out, t, None, False) for t in range(len(THRS))]
+    t3 = time.perf_counter()
+    if rec is not None:
+        for k, v in dict(ph, gt_build=t1 - t0, results=t3 - t2, total=t3 - t0).items():
+            rec[k].append(v)
+    return [m for m, _ in res]
+
+
+def gpu_phases(dets, annos, reps, classes):
+    import torch
     from mmdet_yolov4_amd import _lib, map_eval as ME
+    from mmdet_yolov4_amd.coco_eval import flatten_results
     rec = {k: [] for k in ('table_build', 'sorts', 'upload', 'launch', 'download', 'accumulate', 'total')}
+    t0 = time.perf_counter()
+    flat_np = flatten_results(dets)
+    flatten_s = time.perf_counter() - t0
+    flat_gpu = tuple(torch.from_numpy(a).cuda() for a in flat_np)
+    gt_cached = ME.MapGt(annos, classes)
+    frec = {leg: {k: [] for k in FLAT_PHASES} for leg in FLAT_LEGS}
+    fmaps = {}
     for r in range(reps + 1):                                     # run 0 warms the shapes
+        for leg in FLAT_LEGS:                                     # alternating with the list leg below
+            fmaps[leg] = flat_leg(ME, _lib, flat_gpu if leg.startswith('gpu') else flat_np, annos, classes,
+                                  gt_cached if leg.endswith('cached_gt') else None, frec[leg] if r else None)
         ph = {}
         t0 = time.perf_counter()
         tab = ME.MapTables(dets, annos)
@@ -70,8 +106,14 @@ def gpu_phases(dets, annos, reps):
                 rec[k].append(v)
             for k in ('upload', 'launch', 'download'):
                 rec[k].append(ph[k])
-    return {k: stats(v) for k, v in rec.items()}, [m for m, _ in res], int(len(tab.det)), int(len(tab.gt)), int(
-        (tab.nd * tab.ng).sum())
+    maps = [m for m, _ in res]
+    flat = dict(flatten_results_ms=flatten_s * 1e3,
+                max_abs_diff_to_list={leg: float(np.abs(np.array(fmaps[leg]) - np.array(maps)).max()) for leg in FLAT_LEGS},
+                note='the list path orders equal scores as np.argsort does, the flat path keeps the table order')
+    for leg in FLAT_LEGS:
+        flat[leg] = {k: stats(v) for k, v in frec[leg].items()}
+    return {k: stats(v) for k, v in rec.items()}, maps, int(len(tab.det)), int(len(tab.gt)), int(
+        (tab.nd * tab.ng).sum()), flat
 
 
 def cpu_columns(dets, annos, ref_images):
@@ -109,8 +151,8 @@ def main():
     out = dict(metric='eval_map, ten IoU thresholds, seconds per dataset', images=a.images, classes=a.classes,
                problems=a.images * a.classes, thresholds=len(THRS), data='synthetic')
     if not a.cpu_only:
-        phases, maps, D, G, pairs = gpu_phases(dets, annos, a.reps)
-        out.update(phases=phases, detections=D, gts=G, pairs=pairs, mean_aps=maps, reps=a.reps,
+        phases, maps, D, G, pairs, flat = gpu_phases(dets, annos, a.reps, a.classes)
+        out.update(phases=phases, flat=flat, detections=D, gts=G, pairs=pairs, mean_aps=maps, reps=a.reps,
                    value=phases['total']['median_ms'] * 1e-3, unit='s')
     out['cpu'] = cpu_columns(dets, annos, min(a.ref_images, a.images))
     print(json.dumps(out))

@@ -7,7 +7,10 @@ a few hundred images at batch 32; the head is calibrated like bench.py's (about 
 Usage (GPU box):  python tools/val_loop_bench.py [--images 320] [--batch 32] [--size 416] [--passes 7] [--dtype fp16]
 Both loops run in the same process on the same plans, alternating, after one warming pass of each; per pass the host
 clock around work that ends in a device synchronise: the loop, the scoring, and their sum.  Median with min / max over
-the passes.  The two forms must give the same metrics, or the tool fails.  Prints ONE JSON line."""
+the passes.  The two forms must give the same metrics, or the tool fails.  ``--metric mAP`` scores with a
+``CustomBBoxDataset`` (``evaluate_map``) over the same ground truth instead; its two forms order equal scores differently
+(map_eval.py), and 16-bit scores tie, so there the tool reports whether the metrics agree instead of failing.
+Prints ONE JSON line."""
 import argparse
 import json
 import os
@@ -50,6 +53,7 @@ def main():
     ap.add_argument('--passes', type=int, default=7)
     ap.add_argument('--candidates', type=float, default=2000.0)
     ap.add_argument('--dtype', choices=('fp16', 'bf16'), default='fp16')
+    ap.add_argument('--metric', choices=('bbox', 'mAP'), default='bbox')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('val_loop_bench measures on the GPU; none is visible')
@@ -67,6 +71,15 @@ def main():
     metas = [dict(scale_factor=np.ones(4, np.float32))] * a.batch
     loader = [dict(img=[img], img_metas=[metas[:img.shape[0]]]) for img in batches]
     gt = ground_truth(np.random.default_rng(1), a.images, a.size)
+    if a.metric == 'mAP':
+        xywh = gt.ann_box.astype(np.float32)
+        xyxy = np.concatenate([xywh[:, :2], xywh[:, :2] + xywh[:, 2:]], 1)
+        annos = []
+        for i in range(a.images):
+            mine, crowd = gt.ann_img == i, gt.ann_crowd != 0
+            annos.append(dict(bboxes=xyxy[mine & ~crowd], labels=gt.ann_cat[mine & ~crowd] - 1,
+                              bboxes_ignore=xyxy[mine & crowd], labels_ignore=gt.ann_cat[mine & crowd] - 1))
+        ds = pkg.CustomBBoxDataset(annos, [str(c) for c in range(80)])
 
     def run(flat):
         torch.cuda.synchronize()
@@ -74,7 +87,7 @@ def main():
         res = pkg.single_gpu_test(det, loader, flat=flat)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        out = pkg.evaluate_bbox(res, gt, logger='silent')
+        out = ds.evaluate(res, logger='silent') if a.metric == 'mAP' else pkg.evaluate_bbox(res, gt, logger='silent')
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         rows = int(res[0].shape[0]) if flat else int(sum(len(c) for r in res for c in r))
@@ -82,7 +95,7 @@ def main():
 
     forms = (('list', False), ('flat', True))
     warm = {name: run(flat) for name, flat in forms}
-    if warm['list'][1] != warm['flat'][1] or warm['list'][2] != warm['flat'][2]:
+    if (a.metric == 'bbox' and warm['list'][1] != warm['flat'][1]) or warm['list'][2] != warm['flat'][2]:
         raise SystemExit(f"the two result forms disagree: {warm['list'][1:]} != {warm['flat'][1:]}")
     rec = {name: [] for name, _ in forms}
     for _ in range(a.passes):
@@ -90,7 +103,10 @@ def main():
             rec[name].append(run(flat)[0])
     line = dict(tool='val_loop_bench', model='yolov4s', size=a.size, dtype=a.dtype, images=a.images, batch=a.batch,
                 passes=a.passes, candidates_per_image=round(per_img, 1), rows=warm['flat'][2],
-                bbox_mAP=warm['flat'][1].get('bbox_mAP'))
+                metric=a.metric, bbox_mAP=warm['flat'][1].get('bbox_mAP'), mAP=warm['flat'][1].get('mAP'),
+                metrics_equal=warm['list'][1] == warm['flat'][1])
+    if a.metric == 'mAP':
+        line['list_mAP'] = warm['list'][1].get('mAP')
     for name, _ in forms:
         t = np.asarray(rec[name])
         line[name] = dict(loop=stats(t[:, 0]), scoring=stats(t[:, 1]), total=stats(t[:, 2]))

@@ -1187,6 +1187,92 @@ typedef struct yv4_v3aug_image {
 int yv4_v3_augment_u8(const yv4_v3aug_image* imgs, int N, float* out_nchw, int Hmax, int Wmax, const float* mean3,
                       const float* std3, int to_rgb, void* stream);
 
+/* ---- baseline JPEG decoding (csrc/jpeg_host.cpp, csrc/jpeg.hip; additive within ABI 8) -----------------------------
+ * A hybrid decoder with the quantised coefficients as the seam: the host parses the file and runs the Huffman decode
+ * (yv4_jpeg_parse / yv4_jpeg_entropy_decode make no HIP call and work without a GPU); the device dequantises, runs
+ * libjpeg's "islow" integer IDCT, the fancy chroma upsampling and the integer YCbCr conversion, and writes interleaved
+ * 8-bit pixels (yv4_jpeg_reconstruct, a whole batch of images of different sizes and samplings in one call).  The
+ * arithmetic is libjpeg-turbo's default decode (JDCT_ISLOW, do_fancy_upsampling), so the pixels equal what cv2.imdecode,
+ * turbojpeg and Pillow return, bit for bit.  EXIF orientation is not applied.
+ *
+ * Accepted: 8-bit SOF0 / SOF1 Huffman files with one interleaved scan; 1 component, or 3 components (YCbCr) with luma
+ * sampling 1x1, 2x1 or 2x2 and chroma 1x1 (4:4:4, 4:2:2, 4:2:0); 8-bit quantisation tables.  Progressive, arithmetic,
+ * lossless, 12-bit, 4-component / CMYK, RGB-tagged, 16-bit-table, otherwise-sampled and multi-scan files return
+ * YV4_E_UNSUPPORTED; malformed input (truncation, a code in no table, a coefficient index past 63, a missing table,
+ * zero dimensions, more entropy-coded data than the header's MCUs) returns YV4_E_INVALID.  yv4_last_error names the
+ * reason.  Every read is bounds-checked against len: no input makes the host half read or write outside its buffers.
+ *
+ * yv4_jpeg_info (filled by the host half):
+ *   width, height, ncomp    image size in pixels; 1 or 3 components
+ *   hs, vs                  sampling factors per component (a single component counts as 1x1, as libjpeg treats it)
+ *   tq, td, ta              quantisation / DC Huffman / AC Huffman table selectors per component
+ *   restart_interval        MCUs between RSTn markers, 0: none
+ *   mcus_x, mcus_y          MCU grid; an MCU is (8 * hs[0]) x (8 * vs[0]) pixels
+ *   blocks_w, blocks_h      8x8 blocks per component on the MCU-padded grid
+ *   ncoef                   coefficients of the image: 64 * sum(blocks_w * blocks_h)
+ *   scan_offset             byte offset of the entropy-coded data
+ *   quant                   the four quantisation tables in natural (row-major) order; zero where not defined
+ * Coefficient layout: int16, natural order, 64 per block; each component is its own plane of blocks, block-row-major
+ * over the MCU-padded grid, component 0 first. */
+typedef struct yv4_jpeg_info {
+  int32_t width, height, ncomp;
+  int32_t hs[3], vs[3];
+  int32_t tq[3], td[3], ta[3];
+  int32_t restart_interval;
+  int32_t mcus_x, mcus_y;
+  int32_t blocks_w[3], blocks_h[3];
+  int32_t reserved;
+  int64_t ncoef;
+  int64_t scan_offset;
+  uint16_t quant[4][64];
+} yv4_jpeg_info;
+
+/* Parse the markers up to and including SOS into info.  Returns YV4_OK, YV4_E_UNSUPPORTED or YV4_E_INVALID. */
+int yv4_jpeg_parse(const uint8_t* data, size_t len, yv4_jpeg_info* info);
+
+/* Parse, then Huffman-decode the scan into coef (HOST memory, capacity coef_capacity int16 elements; pinned memory is
+ * what an upload wants).  The first info->ncoef elements are zero-filled by the call and then written; YV4_E_CAPACITY
+ * when coef_capacity < info->ncoef (info is filled, nothing is written to coef).  On YV4_E_INVALID the coefficients
+ * decoded so far stay in the buffer. */
+int yv4_jpeg_entropy_decode(const uint8_t* data, size_t len, yv4_jpeg_info* info, int16_t* coef, int64_t coef_capacity);
+
+/* One image of a reconstruct call.  yv4_jpeg_layout fills a dense table; the caller may then place the outputs
+ * elsewhere (out_off, out_pitch).
+ *   coef_off                first coefficient of the image in the batch's coefficient buffer (int16 elements, % 64 == 0)
+ *   plane_off               byte offset of each component's 8-bit plane (blocks_w * 8 wide, blocks_h * 8 high) in the
+ *                           workspace (% 8 == 0)
+ *   out_off, out_pitch      byte offset of the image's first pixel in the output buffer and its row pitch (>= 3 * width)
+ *   unit_base, tile_base    work units of the images before this one: ceil(blocks / 32) IDCT units and
+ *                           ceil(width / 256) * ceil(height / 4) pixel tiles per image
+ *   width .. blocks_h       as in yv4_jpeg_info */
+typedef struct yv4_jpeg_image {
+  int64_t coef_off;
+  int64_t plane_off[3];
+  int64_t out_off;
+  int64_t unit_base, tile_base;
+  int32_t out_pitch;
+  int32_t width, height, ncomp;
+  int32_t hs, vs;
+  int32_t tq[3];
+  int32_t blocks_w[3], blocks_h[3];
+  int32_t reserved;
+} yv4_jpeg_image;
+
+/* Host only: the dense table of N parsed images -- coefficients back to back, planes 256-byte aligned in the
+ * workspace, outputs at pitch 3 * width and 256-byte aligned offsets.  totals[0..2]: coefficient elements, workspace
+ * bytes, output bytes of the batch. */
+int yv4_jpeg_layout(const yv4_jpeg_info* infos, int N, yv4_jpeg_image* table, int64_t* totals);
+
+/* Coefficients -> pixels for N images in two launches on `stream`.  table: the HOST table, validated here against
+ * coef_elems / work_bytes / out_bytes (YV4_E_INVALID before any launch); table_dev: the same N entries in DEVICE memory,
+ * which the kernels trust.  coef (N images' int16 coefficients), quant ((N, 4, 64) uint16, image n's yv4_jpeg_info.quant),
+ * work and out are DEVICE memory; coef and quant 16-byte, work 8-byte aligned.  Pixels are interleaved (h, w, 3): B, G, R
+ * (what cv2 and mmcv.imread return), or R, G, B with rgb != 0; one component is written three times.  Bytes of out that
+ * are no pixel of an image are not touched. */
+int yv4_jpeg_reconstruct(const yv4_jpeg_image* table, const yv4_jpeg_image* table_dev, int N, const int16_t* coef,
+                         int64_t coef_elems, const uint16_t* quant, uint8_t* work, int64_t work_bytes, uint8_t* out,
+                         int64_t out_bytes, int rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

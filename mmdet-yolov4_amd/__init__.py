@@ -7,7 +7,7 @@ come from ``lib/libyv4_hip.so`` (C-ABI: ``include/yv4.h``); there is no CPU fall
 """
 from . import _lib
 from .registry import (ACTIVATION_LAYERS, ANCHOR_GENERATORS, BACKBONES, BBOX_CODERS, DETECTORS, HEADS, LOSSES,
-                       MODELS, NECKS, Config, ConfigDict, Registry, build_anchor_generator, build_backbone,
+                       MODELS, NECKS, PIPELINES, Config, ConfigDict, Registry, build_anchor_generator, build_backbone,
                        build_bbox_coder, build_detector, build_from_cfg, build_head, build_neck)
 from .bricks import Mish, build_activation_layer, build_norm_layer, wrap_fp16_model
 from .ops import (MishFunction, batched_nms, get_nms_iou_form, mish_backward, mish_forward, multiclass_nms, nms,
@@ -22,6 +22,7 @@ from .single_stage import SingleStageDetector, bbox2result
 from .yolov3 import Darknet, DetectionBlock, ResBlock, YOLOBBoxCoder, YOLOV3, YOLOV3Head, YOLOV3Neck
 from .plan import Plan
 from .preprocess import FusedTestPipeline
+from .image_io import LoadImageFromFile, imdecode, imread
 from .augment import FusedTrainPipeline
 from .augment_v3 import FusedV3TrainPipeline, build_train_pipeline
 from . import tta  # noqa: F401  (YOLOv3 test-time augmentation)

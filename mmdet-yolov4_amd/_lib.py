@@ -147,6 +147,23 @@ class PackDesc(C.Structure):
                     'first_block', 'nblocks', 'rows_per_block')]
 
 
+class JpegInfo(C.Structure):
+    """``yv4_jpeg_info``: what the host half of the JPEG decoder reads from a file's headers."""
+    _fields_ = [(n, C.c_int32) for n in ('width', 'height', 'ncomp')] + \
+               [(n, C.c_int32 * 3) for n in ('hs', 'vs', 'tq', 'td', 'ta')] + \
+               [(n, C.c_int32) for n in ('restart_interval', 'mcus_x', 'mcus_y')] + \
+               [('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('reserved', C.c_int32),
+                ('ncoef', C.c_int64), ('scan_offset', C.c_int64), ('quant', (C.c_uint16 * 64) * 4)]
+
+
+class JpegImage(C.Structure):
+    """``yv4_jpeg_image``: one image of a ``yv4_jpeg_reconstruct`` call."""
+    _fields_ = [('coef_off', C.c_int64), ('plane_off', C.c_int64 * 3), ('out_off', C.c_int64),
+                ('unit_base', C.c_int64), ('tile_base', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('out_pitch', 'width', 'height', 'ncomp', 'hs', 'vs')] + \
+               [('tq', C.c_int32 * 3), ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('reserved', C.c_int32)]
+
+
 _vp, _i, _i64, _f, _sz, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 
 #: every exported symbol: name -> (restype, argtypes).  tests/test_abi.py checks
@@ -274,6 +291,10 @@ SIGNATURES = {
     'yv4_coco_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp,
                                       _vp, _vp]),
     'yv4_results_append': (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp]),
+    'yv4_jpeg_parse': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo)]),
+    'yv4_jpeg_entropy_decode': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo), _vp, _i64]),
+    'yv4_jpeg_layout': (C.c_int, [C.POINTER(JpegInfo), _i, C.POINTER(JpegImage), C.POINTER(C.c_int64)]),
+    'yv4_jpeg_reconstruct': (C.c_int, [C.POINTER(JpegImage), _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -300,6 +321,8 @@ COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_
                                'yv4_coco_accumulate'))
 #: the flat result table of a test loop (additive within ABI 8, bound like FP8_SYMBOLS); has_results_append()
 RESULTS_SYMBOLS = frozenset(('yv4_results_append',))
+#: the baseline JPEG decoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg()
+JPEG_SYMBOLS = frozenset(('yv4_jpeg_parse', 'yv4_jpeg_entropy_decode', 'yv4_jpeg_layout', 'yv4_jpeg_reconstruct'))
 #: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
 RESULTS_MAX_PER_IMG = 4096
 
@@ -343,7 +366,8 @@ def lib():
                 continue
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
                     or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
-                    or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS) \
+                    or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
+                    or name in JPEG_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -418,6 +442,12 @@ def has_results_append():
     """The loaded library exports ``yv4_results_append`` (the flat result table of a test loop)."""
     h = lib()
     return all(hasattr(h, n) for n in RESULTS_SYMBOLS)
+
+
+def has_jpeg():
+    """The loaded library exports the baseline JPEG decoder (``yv4_jpeg_parse`` .. ``yv4_jpeg_reconstruct``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in JPEG_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

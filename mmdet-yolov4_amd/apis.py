@@ -1,24 +1,31 @@
-"""``inference_detector`` under the reference's name (``mmdet/apis/inference.py:88-158``), for loaded images.
+"""``inference_detector`` under the reference's name (``mmdet/apis/inference.py:88-158``).
 
 The reference composes ``cfg.data.test.pipeline`` per image on the CPU (mmcv / OpenCV), collates, scatters and calls
 ``model(return_loss=False, rescale=True, **data)``.  Here the same pipeline block drives ``FusedTestPipeline`` (one
 launch per image, parity unpinned -- see ``preprocess.py``) and the detector's fused ``simple_test``.  Image files are
-not read: the build has no image decoder (the reference reads them with ``mmcv.imread``)."""
+read by ``image_io.imread`` (the reference reads them with ``mmcv.imread``): baseline JPEG, decoded on the GPU to the
+bytes libjpeg-turbo gives; EXIF orientation is not applied."""
+import os
+
 import numpy as np
 import torch
+
+from .image_io import imread
 
 from .preprocess import FusedTestPipeline
 
 
 def inference_detector(model, imgs, test_pipeline=None):
-    """``imgs``: an (h, w, 3) uint8 array (BGR, as ``mmcv.imread`` returns) or a list / tuple of them.  Returns the
-    per-image result (a list of per-class (k, 5) arrays) or, for a list, the list of them -- like the reference.
-    ``test_pipeline`` defaults to ``model.cfg.data.test.pipeline``."""
+    """``imgs``: an (h, w, 3) uint8 array (BGR, as ``mmcv.imread`` returns), a (h, w, 3) ``torch.uint8`` tensor on the
+    model's device, a file name (``str`` / ``os.PathLike``: a baseline JPEG, decoded on the GPU) or a list / tuple of
+    them, mixed freely.  Returns the per-image result (a list of per-class (k, 5) arrays) or, for a list, the list of
+    them -- like the reference.  ``test_pipeline`` defaults to ``model.cfg.data.test.pipeline``."""
     is_batch = isinstance(imgs, (list, tuple))
     if not is_batch:
         imgs = [imgs]
-    if any(not isinstance(i, np.ndarray) for i in imgs):
-        raise NotImplementedError('inference_detector takes loaded images (numpy arrays): no image decoder in this build')
+    for i in imgs:
+        if not isinstance(i, (np.ndarray, torch.Tensor, str, os.PathLike)):
+            raise TypeError(f'inference_detector takes arrays, uint8 tensors and file names, not {type(i).__name__}')
     if test_pipeline is None:
         cfg = getattr(model, 'cfg', None)
         if cfg is None:
@@ -26,7 +33,12 @@ def inference_detector(model, imgs, test_pipeline=None):
         test_pipeline = cfg.data.test.pipeline
     device = next(model.parameters()).device
     pipe = test_pipeline if callable(test_pipeline) else FusedTestPipeline.from_config(test_pipeline, device=device)
-    batch, metas = pipe(list(imgs))
+    imgs = list(imgs)
+    files = [k for k, i in enumerate(imgs) if isinstance(i, (str, os.PathLike))]
+    if files:       # the files of the call are one decode batch
+        for k, img in zip(files, imread([imgs[k] for k in files], device=device)):
+            imgs[k] = img
+    batch, metas = pipe(imgs)
     with torch.no_grad():
         if isinstance(batch, list):      # test-time augmentation: one batch per augmentation (N images each)
             results = model.aug_test(batch, metas, rescale=True)

@@ -1,0 +1,222 @@
+"""Image files onto the GPU: ``imread`` / ``imdecode`` for baseline JPEG, and the ``LoadImageFromFile`` transform.
+
+The decoder is a hybrid (``include/yv4.h``, "baseline JPEG decoding"): the host parses the file and runs the Huffman
+decode (``yv4_jpeg_parse`` / ``yv4_jpeg_entropy_decode``, sequential by nature, one thread per image), the device does
+everything from the quantised coefficients to interleaved pixels (``yv4_jpeg_reconstruct``: dequantisation, libjpeg's
+"islow" integer IDCT, fancy chroma upsampling, integer YCbCr conversion).  A batch is one reconstruct call; its
+coefficients, quantisation tables and per-image table go up through one pinned staging buffer.
+
+The pixels equal libjpeg-turbo's default decode bit for bit, which is what ``cv2.imdecode``, turbojpeg and Pillow -- every
+backend of ``mmcv.imfrombytes`` -- return.  **One known difference**: EXIF orientation is not applied
+(``cv2.imdecode(IMREAD_COLOR)`` rotates by it; turbojpeg and Pillow do not either).
+
+Accepted: 8-bit baseline (SOF0 / SOF1 Huffman) files, grayscale or YCbCr in 4:4:4, 4:2:2 or 4:2:0.  Progressive,
+arithmetic-coded, 12-bit, lossless, CMYK and multi-scan files and every other format raise ``NotImplementedError``.
+"""
+import ctypes as C
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import JpegImage, JpegInfo, check
+from .ops import stream_ptr
+from .registry import PIPELINES
+
+#: the host entropy decodes of a batch run on at most this many threads (never sized from the machine's CPU count)
+MAX_DECODE_THREADS = 16
+
+_MAGIC = ((b'\x89PNG\r\n\x1a\n', 'PNG'), (b'GIF87a', 'GIF'), (b'GIF89a', 'GIF'), (b'BM', 'BMP'), (b'II*\x00', 'TIFF'),
+          (b'MM\x00*', 'TIFF'), (b'\x00\x00\x00\x0cjP  ', 'JPEG 2000'), (b'\xff\x4f\xff\x51', 'JPEG 2000'),
+          (b'P5', 'PNM'), (b'P6', 'PNM'))
+
+
+def image_format(buf):
+    """The format of an encoded image by its magic bytes: ``'JPEG'``, ``'PNG'``, ... or ``'unknown'``."""
+    head = bytes(buf[:16])
+    if head[:2] == b'\xff\xd8':
+        return 'JPEG'
+    if head[:4] == b'RIFF' and head[8:12] == b'WEBP':
+        return 'WebP'
+    for magic, name in _MAGIC:
+        if head.startswith(magic):
+            return name
+    return 'unknown'
+
+
+def _raise(status, what):
+    msg = _lib.lib().yv4_last_error().decode('utf-8', 'replace')      # thread-local: read on the thread that made the call
+    if status == -2:
+        raise NotImplementedError(f'{what}: {msg}')
+    if status == -1:
+        raise ValueError(f'{what}: {msg}')
+    raise _lib.Yv4Error(f'{what} failed with status {status}: {msg}')
+
+
+def _as_bytes(buf):
+    if isinstance(buf, np.ndarray):
+        buf = buf.tobytes()
+    if not isinstance(buf, (bytes, bytearray, memoryview)):
+        raise TypeError(f'an encoded image is a bytes object, not {type(buf).__name__}')
+    buf = bytes(buf)
+    fmt = image_format(buf)
+    if fmt != 'JPEG':
+        raise NotImplementedError(f'{fmt} images are not built: the decoder reads baseline JPEG only')
+    return buf
+
+
+def jpeg_parse(buf):
+    """The host half's header parse -> ``JpegInfo`` (``yv4_jpeg_info``).  Needs no GPU."""
+    info = JpegInfo()
+    st = _lib.lib().yv4_jpeg_parse(buf, len(buf), C.byref(info))
+    if st != 0:
+        _raise(st, 'yv4_jpeg_parse')
+    return info
+
+
+def jpeg_entropy_decode(buf):
+    """The host half on its own -> ``(JpegInfo, int16 coefficient array)``.  Needs no GPU."""
+    info = jpeg_parse(buf)
+    coef = np.empty(int(info.ncoef), np.int16)
+    st = _lib.lib().yv4_jpeg_entropy_decode(buf, len(buf), C.byref(info), coef.ctypes.data, coef.size)
+    if st != 0:
+        _raise(st, 'yv4_jpeg_entropy_decode')
+    return info, coef
+
+
+def _align(n, a=256):
+    return (n + a - 1) // a * a
+
+
+def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None):
+    """The batch decode behind ``imdecode``: ``bufs`` (a list of JPEG byte strings) -> ``(out, table)``, ``out`` the flat
+    ``torch.uint8`` device buffer and ``table`` the ``JpegImage`` array saying where each image lies in it.  With ``out``
+    and ``placement`` (``(byte offset, row pitch)`` per image) the pixels go into the caller's buffer instead -- rows of
+    a larger canvas, say; the library checks every image against the buffer's size before the launch."""
+    if not torch.cuda.is_available():
+        raise RuntimeError('the JPEG decoder reconstructs the pixels on the GPU through libyv4_hip.so (there is no CPU '
+                           'fallback)')
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    L = _lib.lib()
+    N = len(bufs)
+    infos = (JpegInfo * N)()
+    for n, b in enumerate(bufs):
+        st = L.yv4_jpeg_parse(b, len(b), C.byref(infos[n]))
+        if st != 0:
+            _raise(st, f'imdecode: image {n}')
+    table = (JpegImage * N)()
+    totals = (C.c_int64 * 3)()
+    check(L.yv4_jpeg_layout(infos, N, table, totals), 'yv4_jpeg_layout')
+    ncoef, work_bytes, out_bytes = (int(t) for t in totals)
+    if placement is not None:
+        if out is None or out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != 'cuda':
+            raise ValueError('placement needs out=: a contiguous torch.uint8 tensor on the GPU')
+        out_bytes = out.numel()
+        for n, (off, pitch) in enumerate(placement):
+            table[n].out_off, table[n].out_pitch = int(off), int(pitch)
+
+    # one pinned staging buffer: [per-image table | quantisation tables (N, 4, 64) uint16 | coefficients int16]
+    quant_off = _align(C.sizeof(table))
+    coef_off = quant_off + _align(N * 4 * 64 * 2)
+    stage = torch.empty(coef_off + 2 * ncoef, dtype=torch.uint8, pin_memory=True)
+    base = stage.data_ptr()
+    C.memmove(base, table, C.sizeof(table))
+    for n in range(N):
+        C.memmove(base + quant_off + n * 512, infos[n].quant, 512)
+
+    def entropy(n):
+        info = JpegInfo()
+        st = L.yv4_jpeg_entropy_decode(bufs[n], len(bufs[n]), C.byref(info), base + coef_off + 2 * int(table[n].coef_off),
+                                       int(infos[n].ncoef))
+        if st != 0:
+            _raise(st, f'imdecode: image {n}')
+
+    if N == 1:
+        entropy(0)
+    else:
+        with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, N)) as pool:      # ctypes releases the GIL
+            list(pool.map(entropy, range(N)))
+
+    with torch.cuda.device(dev):
+        up = stage.to(dev, non_blocking=True)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        if placement is None:
+            out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+        check(L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, up.data_ptr() + coef_off, ncoef, up.data_ptr() + quant_off,
+                                     work.data_ptr(), work_bytes, out.data_ptr(), out_bytes,
+                                     int(channel_order == 'rgb'), stream_ptr()), 'yv4_jpeg_reconstruct')
+    return out, table
+
+
+def imdecode(buffers, channel_order='bgr', device=None):
+    """``buffers``: the bytes of one JPEG file or a list of them -> a ``torch.uint8`` (h, w, 3) tensor on ``device``
+    (default: the current GPU), or a list of them.  ``channel_order``: ``'bgr'`` (what ``mmcv.imread`` returns) or
+    ``'rgb'``; a grayscale file gives its plane three times, like ``flag='color'``.  A list is decoded as one batch:
+    the entropy decodes on a thread pool, then one upload and one reconstruct call.  EXIF orientation is not applied."""
+    if channel_order not in ('bgr', 'rgb'):
+        raise ValueError(f"channel_order {channel_order!r} is not 'bgr' or 'rgb'")
+    single = not isinstance(buffers, (list, tuple))
+    bufs = [_as_bytes(b) for b in ([buffers] if single else buffers)]
+    if not bufs:
+        return []
+    out, table = decode_into(bufs, channel_order, device)
+    imgs = []
+    for t in table:
+        h, w, off = int(t.height), int(t.width), int(t.out_off)
+        imgs.append(out[off:off + h * w * 3].view(h, w, 3))
+    return imgs[0] if single else imgs
+
+
+def imread(paths, channel_order='bgr', device=None):
+    """``paths``: a file name (``str`` / ``os.PathLike``) or a list of them -> what ``imdecode`` returns for their bytes."""
+    single = not isinstance(paths, (list, tuple))
+    bufs = []
+    for p in ([paths] if single else paths):
+        with open(os.fspath(p), 'rb') as f:
+            bufs.append(f.read())
+    return imdecode(bufs[0] if single else bufs, channel_order=channel_order, device=device)
+
+
+@PIPELINES.register_module()
+class LoadImageFromFile:
+    """``LoadImageFromFile`` of the reference's pipelines (``mmdet/datasets/pipelines/loading.py:12-86``): reads
+    ``img_prefix`` / ``img_info['filename']`` and fills ``filename``, ``ori_filename``, ``img``, ``img_shape``,
+    ``ori_shape`` and ``img_fields``.  ``img`` is a (h, w, 3) BGR tensor on the GPU -- ``torch.uint8``, or
+    ``torch.float32`` with ``to_float32``.  ``im_decode_backend`` is accepted and ignored: every backend the reference
+    offers for JPEG runs libjpeg-turbo's default decode, which is what ``imread`` computes.  EXIF orientation is not
+    applied (the reference's cv2 backend applies it)."""
+
+    def __init__(self, to_float32=False, color_type='color', file_client_args=dict(backend='disk'), im_decode_backend=None,
+                 device=None):
+        if color_type != 'color':
+            raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' only)")
+        if dict(file_client_args) != dict(backend='disk'):
+            raise NotImplementedError(f'LoadImageFromFile(file_client_args={dict(file_client_args)!r}) is not built '
+                                      "(dict(backend='disk') only)")
+        self.to_float32 = to_float32
+        self.color_type = color_type
+        self.file_client_args = dict(file_client_args)
+        self.im_decode_backend = im_decode_backend
+        self.device = device
+
+    def __call__(self, results):
+        if results['img_prefix'] is not None:
+            filename = os.path.join(results['img_prefix'], results['img_info']['filename'])
+        else:
+            filename = results['img_info']['filename']
+        img = imread(filename, device=self.device)
+        if self.to_float32:
+            img = img.float()
+        results['filename'] = filename
+        results['ori_filename'] = results['img_info']['filename']
+        results['img'] = img
+        results['img_shape'] = tuple(img.shape)
+        results['ori_shape'] = tuple(img.shape)
+        results['img_fields'] = ['img']
+        return results
+
+    def __repr__(self):
+        return (f'{self.__class__.__name__}(to_float32={self.to_float32}, color_type={self.color_type!r}, '
+                f'file_client_args={self.file_client_args})')

@@ -32,7 +32,9 @@ def rescale_size(h, w, scale):
 
 class FusedTestPipeline:
     """``FusedTestPipeline(img_scale=(640, 640), size_divisor=32, mean=..., std=..., to_rgb=True)(images)`` ->
-    ``(batch (N, 3, H, W) fp32 on the GPU, img_metas)``.  ``pad_before_normalize``: the order of ``Pad`` and
+    ``(batch (N, 3, H, W) fp32 on the GPU, img_metas)``.  ``images``: (h, w, 3) uint8 numpy arrays, which are uploaded,
+    or ``torch.uint8`` tensors already on the pipeline's device (``image_io.imread``), which are not; mixed freely.
+    ``pad_before_normalize``: the order of ``Pad`` and
     ``Normalize`` in the config (the YOLOv4 configs pad first, so the border carries ``(0 - mean) / std``)."""
 
     def __init__(self, img_scale=(640, 640), size_divisor=32, mean=(114, 114, 114), std=(255, 255, 255), to_rgb=True,
@@ -127,7 +129,12 @@ class FusedTestPipeline:
         dev = torch.device(self.device) if self.device is not None else torch.device('cuda', torch.cuda.current_device())
         geo = []
         for img in images:
-            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            if isinstance(img, torch.Tensor):      # decoded on the device already (image_io.imread): no upload
+                if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+                    raise ValueError('FusedTestPipeline takes (h, w, 3) uint8 images')
+                if img.device.type != dev.type or (dev.index is not None and img.device.index != dev.index):
+                    raise ValueError(f'FusedTestPipeline on {dev} takes uint8 tensors of that device, not of {img.device}')
+            elif img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
                 raise ValueError('FusedTestPipeline takes (h, w, 3) uint8 images')
             h, w = img.shape[:2]
             nh, nw = rescale_size(h, w, img_scale)
@@ -152,7 +159,10 @@ class FusedTestPipeline:
             else:
                 check(L.yv4_letterbox_u8(*args, stream_ptr()), 'yv4_letterbox_u8')
         for i, (img, (h, w, nh, nw, hp, wp)) in enumerate(zip(images, geo)):
-            src = torch.from_numpy(np.ascontiguousarray(img)).to(dev, non_blocking=True)
+            if isinstance(img, torch.Tensor):
+                src = img.contiguous()
+            else:
+                src = torch.from_numpy(np.ascontiguousarray(img)).to(dev, non_blocking=True)
             keep.append(src)
             slot = batch[i]
             if (hp, wp) == (H, W):

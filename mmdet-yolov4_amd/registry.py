@@ -174,6 +174,7 @@ BBOX_SAMPLERS = Registry('bbox_sampler')
 ACTIVATION_LAYERS = Registry('activation layer')
 NORM_LAYERS = Registry('norm layer')
 HOOKS = Registry('hook')
+PIPELINES = Registry('pipeline')      # mmdet/datasets/builder.py:13
 
 
 def build_backbone(cfg):

@@ -1,0 +1,208 @@
+"""Phases of the hybrid JPEG decode on 32 images of 480x640, 4:2:0, quality 90 (the shape of a COCO file).
+
+    python tools/jpeg_bench.py [--images 32] [--repeats 5]
+
+Prints, per phase, the median over ``--repeats`` windows (and the spread):
+  * host parse + entropy decode per image on one thread and on 16 threads (files/s),
+  * the upload of the pinned staging buffer (table + quantisation tables + coefficients),
+  * the two device kernels of ``yv4_jpeg_reconstruct`` by HIP events over a window of back-to-back calls on resident
+    buffers, and the bytes/s they achieve against the measured HBM copy rate of the MI355X (6.29 TB/s): bytes are what
+    the algorithm moves -- coefficients read (2 B), planes written and read (1 B + 1 B), pixels written (3 B),
+  * ``imdecode`` of the batch end to end (host clock around a device synchronise),
+  * Pillow's (libjpeg-turbo's) decode of the same files on one thread, as the reference, where Pillow is importable.
+The images are made with Pillow; without it the tool says so and exits.  There is no pass mark.  Needs the GPU: a
+measurement path that finds none fails.
+"""
+import argparse
+import ctypes as C
+import io
+import json
+import os
+import statistics
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_BYTES_PER_S = 6.29e12      # measured float4 copy rate of the MI355X (8.0e12 is the specification)
+THREADS = 16
+
+
+def make_images(n, h=480, w=640):
+    from PIL import Image
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[0:h, 0:w]
+    out = []
+    for i in range(n):      # smooth structure plus texture: ~120 KB per file at quality 90, a detailed photograph
+        base = np.stack([127 + 100 * np.sin(xx / (23.0 + i) + c) * np.cos(yy / (31.0 + 2 * i) - c) for c in range(3)], -1)
+        img = np.clip(base + rng.normal(0, 12, (h, w, 3)), 0, 255).astype(np.uint8)
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, 'JPEG', quality=90, subsampling=2)
+        out.append(buf.getvalue())
+    return out
+
+
+def windows(fn, repeats):
+    """median and (min, max) of ``fn()`` -- seconds per window -- after one warm-up window"""
+    fn()
+    t = [fn() for _ in range(repeats)]
+    return statistics.median(t), min(t), max(t)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--images', type=int, default=32)
+    ap.add_argument('--repeats', type=int, default=5)
+    args = ap.parse_args()
+    try:
+        import PIL  # noqa: F401
+    except ImportError:
+        print('jpeg_bench: Pillow is not importable here, so the input images cannot be made; nothing measured')
+        return 0
+    import torch
+    import mmdet_yolov4_amd as pkg
+    from mmdet_yolov4_amd import image_io
+    from mmdet_yolov4_amd._lib import JpegImage, JpegInfo
+    from mmdet_yolov4_amd.ops import stream_ptr
+    if not torch.cuda.is_available():
+        raise SystemExit('jpeg_bench: no GPU')
+    dev = torch.device('cuda:0')
+    L = pkg._lib.lib()
+    bufs = make_images(args.images)
+    N = len(bufs)
+    file_bytes = sum(len(b) for b in bufs)
+    res = dict(images=N, height=480, width=640, sampling='4:2:0', quality=90, mean_file_bytes=file_bytes // N)
+
+    # ---- host half ------------------------------------------------------------------------------------------------
+    infos = (JpegInfo * N)()
+    for n, b in enumerate(bufs):
+        assert L.yv4_jpeg_parse(b, len(b), C.byref(infos[n])) == 0
+    table = (JpegImage * N)()
+    totals = (C.c_int64 * 3)()
+    assert L.yv4_jpeg_layout(infos, N, table, totals) == 0
+    ncoef, work_bytes, out_bytes = (int(t) for t in totals)
+    quant_off = image_io._align(C.sizeof(table))
+    coef_off = quant_off + image_io._align(N * 512)
+    stage = torch.empty(coef_off + 2 * ncoef, dtype=torch.uint8, pin_memory=True)
+    base = stage.data_ptr()
+    C.memmove(base, table, C.sizeof(table))
+    for n in range(N):
+        C.memmove(base + quant_off + n * 512, infos[n].quant, 512)
+
+    def host(n):
+        info = JpegInfo()
+        assert L.yv4_jpeg_parse(bufs[n], len(bufs[n]), C.byref(info)) == 0
+        st = L.yv4_jpeg_entropy_decode(bufs[n], len(bufs[n]), C.byref(info), base + coef_off + 2 * int(table[n].coef_off),
+                                       int(info.ncoef))
+        assert st == 0
+
+    rounds = 8
+
+    def one_thread():
+        t0 = time.perf_counter()
+        for _ in range(rounds):
+            for n in range(N):
+                host(n)
+        return time.perf_counter() - t0
+
+    pool = ThreadPoolExecutor(max_workers=THREADS)
+
+    def many_threads():      # one pass per batch, as imdecode runs it: no two threads share an image's coefficients
+        t0 = time.perf_counter()
+        for _ in range(rounds):
+            list(pool.map(host, range(N)))
+        return time.perf_counter() - t0
+
+    for name, fn in (('host_1_thread', one_thread), (f'host_{THREADS}_threads', many_threads)):
+        med, lo, hi = windows(fn, args.repeats)
+        res[name + '_files_per_s'] = round(N * rounds / med, 1)
+        res[name + '_spread'] = [round(N * rounds / hi, 1), round(N * rounds / lo, 1)]
+        print(f'{name:>22}: {N * rounds / med:9.1f} files/s   ({1e3 * med / (N * rounds):.3f} ms per file; '
+              f'windows {N * rounds / hi:.0f} .. {N * rounds / lo:.0f} files/s)')
+    pool.shutdown()
+
+    # ---- upload ---------------------------------------------------------------------------------------------------
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    up = torch.empty(stage.numel(), dtype=torch.uint8, device=dev)
+    copies = 20
+
+    def upload():
+        ev0.record()
+        for _ in range(copies):
+            up.copy_(stage, non_blocking=True)
+        ev1.record()
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) * 1e-3
+
+    med, lo, hi = windows(upload, args.repeats)
+    res['upload_ms'] = round(1e3 * med / copies, 4)
+    res['upload_gb_per_s'] = round(stage.numel() * copies / med / 1e9, 2)
+    print(f'{"upload":>22}: {1e3 * med / copies:9.4f} ms for {stage.numel() / 1e6:.2f} MB   ({res["upload_gb_per_s"]} GB/s; '
+          f'windows {1e3 * lo / copies:.4f} .. {1e3 * hi / copies:.4f} ms)')
+
+    # ---- device kernels -------------------------------------------------------------------------------------------
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+    calls = 200
+    pixels = sum(int(t.width) * int(t.height) for t in table)
+    moved = 4 * ncoef + 3 * pixels
+
+    def kernels():
+        ev0.record()
+        for _ in range(calls):
+            st = L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, up.data_ptr() + coef_off, ncoef, up.data_ptr() + quant_off,
+                                        work.data_ptr(), work_bytes, out.data_ptr(), out_bytes, 0, stream_ptr())
+            assert st == 0
+        ev1.record()
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) * 1e-3
+
+    med, lo, hi = windows(kernels, args.repeats)
+    res['device_ms'] = round(1e3 * med / calls, 4)
+    res['device_files_per_s'] = round(N * calls / med, 1)
+    res['device_bytes_per_s'] = round(moved * calls / med, 0)
+    res['device_share_of_hbm'] = round(moved * calls / med / HBM_BYTES_PER_S, 4)
+    print(f'{"device kernels":>22}: {1e3 * med / calls:9.4f} ms per batch of {N}   ({N * calls / med:.0f} files/s; '
+          f'{moved / 1e6:.2f} MB moved -> {moved * calls / med / 1e9:.1f} GB/s = {100 * moved * calls / med / HBM_BYTES_PER_S:.1f} % '
+          f'of the {HBM_BYTES_PER_S / 1e12:.2f} TB/s HBM copy rate; windows {1e3 * lo / calls:.4f} .. {1e3 * hi / calls:.4f} ms)')
+
+    # ---- end to end -----------------------------------------------------------------------------------------------
+    def end_to_end():
+        t0 = time.perf_counter()
+        for _ in range(4):
+            pkg.imdecode(bufs, device=dev)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    med, lo, hi = windows(end_to_end, args.repeats)
+    res['imdecode_files_per_s'] = round(4 * N / med, 1)
+    print(f'{"imdecode(batch)":>22}: {4 * N / med:9.1f} files/s   ({1e3 * med / 4:.2f} ms per batch of {N}; '
+          f'windows {4 * N / hi:.0f} .. {4 * N / lo:.0f} files/s)')
+
+    # the decode is only worth timing if it is right
+    from PIL import Image
+    got = pkg.imdecode(bufs, channel_order='rgb', device=dev)
+    for b, g in zip(bufs, got):
+        assert np.array_equal(g.cpu().numpy(), np.asarray(Image.open(io.BytesIO(b)))), 'decode differs from Pillow'
+
+    def pillow():
+        t0 = time.perf_counter()
+        for _ in range(rounds):
+            for b in bufs:
+                np.asarray(Image.open(io.BytesIO(b)))
+        return time.perf_counter() - t0
+
+    med, lo, hi = windows(pillow, args.repeats)
+    res['pillow_1_thread_files_per_s'] = round(N * rounds / med, 1)
+    print(f'{"Pillow, 1 thread":>22}: {N * rounds / med:9.1f} files/s   ({1e3 * med / (N * rounds):.3f} ms per file; '
+          f'windows {N * rounds / hi:.0f} .. {N * rounds / lo:.0f} files/s)   [bytes equal to imdecode: yes]')
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -1273,6 +1273,105 @@ int yv4_jpeg_reconstruct(const yv4_jpeg_image* table, const yv4_jpeg_image* tabl
                          int64_t coef_elems, const uint16_t* quant, uint8_t* work, int64_t work_bytes, uint8_t* out,
                          int64_t out_bytes, int rgb, void* stream);
 
+/* ---- the Huffman scan on the device (csrc/jpeg_entropy_core.h, csrc/jpeg_entropy_host.cpp, csrc/jpeg_entropy.hip;
+ * additive within ABI 8) --------------------------------------------------------------------------------------------
+ * The other side of the coefficient seam: the same files yv4_jpeg_entropy_decode accepts, the same coefficients, decoded
+ * by a kernel from the file's bytes.  The unit of parallelism is the SEGMENT: a run of whole MCUs whose bytes start on
+ * a byte boundary in the initial state (DC predictors zero, first block of an MCU).  A file with a restart interval
+ * has one segment per interval, any other file is one segment.  Segments are independent: one lane decodes one segment,
+ * a workgroup is one wave of 64 lanes over up to 64 consecutive segments of ONE image, with that image's Huffman
+ * tables in LDS.  yv4_jpeg_reconstruct, yv4_jpeg_layout and yv4_jpeg_image are unchanged.
+ *
+ * A batch is described by four tables, each built on the host and copied to the device:
+ *   yv4_jpeg_scan      one per image: where its file lies in the batch's bytes, where its coefficients go, its MCU grid,
+ *                      its slice of the segment table and of the packed Huffman tables
+ *   yv4_jpeg_segment   byte range WITHIN THE FILE [begin, end), first MCU and MCU count.  bit_off and pred (a bit offset
+ *                      into the first byte and carried-in DC predictors) are there for entry points inside a segment,
+ *                      which nothing produces yet: they must be zero
+ *   yv4_jpeg_wg        one per workgroup: image, first segment (within the image) and count (1 .. 64)
+ *   yv4_jpeg_huff      one packed Huffman table: the 9-bit lookahead (code length << 8 | symbol, 0: a longer code), the
+ *                      largest code and the value offset of each length 10 .. 16 (-1: no code of that length), the values
+ * A lane that meets an error stores its code into the image's status word (atomic max, so the outcome is the same on
+ * every run) and stops; the other segments go on.  YV4_JPEG_ERR_TRAILING: at least 8 real bits are left after a
+ * segment's last MCU -- data where a restart marker is due or, behind the last segment, more entropy-coded data than
+ * the header's MCUs. */
+#define YV4_JPEG_MAX_HUFF 6            /* tables one image can reference: 3 DC + 3 AC */
+#define YV4_JPEG_WG_SEGMENTS 64        /* segments per workgroup */
+#define YV4_JPEG_ERR_OVERRUN 1         /* a block whose decode reached past the end of its segment's bytes */
+#define YV4_JPEG_ERR_CODE 2            /* a code that is in no table */
+#define YV4_JPEG_ERR_DC_CATEGORY 3     /* a DC magnitude category above 11 */
+#define YV4_JPEG_ERR_INDEX 4           /* a coefficient index past 63 */
+#define YV4_JPEG_ERR_TRAILING 5        /* data where a restart marker or the end of the scan is due */
+
+typedef struct yv4_jpeg_huff {
+  uint16_t look[512];
+  int32_t maxcode[8];       /* [l - 10] for code lengths 10 .. 16; [7] unused */
+  int32_t valoff[8];
+  uint8_t vals[256];
+} yv4_jpeg_huff;
+
+typedef struct yv4_jpeg_scan {
+  int64_t data_off, data_len;      /* the file in the batch's bytes */
+  int64_t coef_off, ncoef;         /* the image's coefficients in the batch's buffer (int16 elements) */
+  int64_t seg_base;                /* its first entry in the segment table */
+  int32_t nseg;
+  int32_t ncomp, mcus_x, mcus_y;
+  int32_t hs, vs;                  /* luma sampling; chroma is 1x1 */
+  int32_t td[3], ta[3];            /* per component: index of its DC / AC table among the image's packed tables */
+  int32_t huff_base, nhuff;        /* its first packed table and their number (1 .. YV4_JPEG_MAX_HUFF) */
+} yv4_jpeg_scan;
+
+typedef struct yv4_jpeg_segment {
+  int64_t begin, end;
+  int32_t first_mcu, mcu_count;
+  int32_t bit_off;
+  int32_t reserved;
+  int16_t pred[4];
+} yv4_jpeg_segment;
+
+typedef struct yv4_jpeg_wg {
+  int32_t image, first_seg, count, reserved;
+} yv4_jpeg_wg;
+
+/* Host only, no HIP call: parse the headers (as yv4_jpeg_parse: the same YV4_E_UNSUPPORTED / YV4_E_INVALID), pack the
+ * Huffman tables the scan references into huff (room for YV4_JPEG_MAX_HUFF) and walk the entropy-coded bytes once for
+ * markers into the segment table segs (room for seg_capacity).  The rules are the host decoder's at a restart: RSTn in
+ * order modulo 8, 0xFF fill bytes before a marker allowed, ceil(MCUs / interval) - 1 markers; a marker that is missing
+ * or out of order, and an RSTn behind the last segment, are YV4_E_INVALID.  scan comes back with data_off, coef_off,
+ * seg_base and huff_base zero for the caller to place, and scan->nseg = restart_interval ? ceil(MCUs / interval) : 1
+ * is set before the capacity check (YV4_E_CAPACITY: nothing is written to segs). */
+int yv4_jpeg_scan_prepare(const uint8_t* data, size_t len, yv4_jpeg_info* info, yv4_jpeg_scan* scan, yv4_jpeg_huff* huff,
+                          yv4_jpeg_segment* segs, int64_t seg_capacity);
+
+/* Host only: the workgroup table of N placed images -- image n's segments in runs of YV4_JPEG_WG_SEGMENTS, images in
+ * order.  *count is the number of workgroups; with wgs NULL only the count is made, else YV4_E_CAPACITY if it exceeds
+ * wg_capacity. */
+int yv4_jpeg_entropy_workgroups(const yv4_jpeg_scan* scans, int N, yv4_jpeg_wg* wgs, int64_t wg_capacity, int64_t* count);
+
+/* Host only: the decode the kernel runs, over the same tables, on the CPU.  Validates like
+ * yv4_jpeg_entropy_decode_device, zero-fills the batch's coefficient range and status[0 .. N), decodes every segment and
+ * leaves the largest YV4_JPEG_ERR_* code of each image (0: none) in status.  All pointers are HOST memory. */
+int yv4_jpeg_entropy_decode_segments(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_wg* wgs,
+                                     int N, int64_t nseg, int64_t nwg, const uint8_t* bytes, int64_t bytes_len,
+                                     const yv4_jpeg_huff* huff, int64_t nhuff, int16_t* coef, int64_t coef_elems,
+                                     int32_t* status);
+
+/* The Huffman decode of N images in one launch on `stream`.  scans / segs / wgs: the HOST tables, validated here against
+ * nseg, nwg, bytes_len, nhuff and coef_elems (every offset and count, the MCU ranges, the workgroup runs; YV4_E_INVALID
+ * before any launch); scans_dev / segs_dev / wgs_dev: the same entries in DEVICE memory (8-byte aligned), which the
+ * kernel trusts.  bytes (the files), huff (4-byte aligned), coef and status (N int32) are DEVICE memory.  The call
+ * zero-fills the batch's coefficient range and status on the stream, then launches; afterwards status[n] is 0 or
+ * image n's largest YV4_JPEG_ERR_* code, and coef feeds yv4_jpeg_reconstruct as the host decoder's output does.  No
+ * read leaves a segment's bytes and no store an image's coefficient range, whatever the bytes hold. */
+int yv4_jpeg_entropy_decode_device(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_wg* wgs,
+                                   const yv4_jpeg_scan* scans_dev, const yv4_jpeg_segment* segs_dev,
+                                   const yv4_jpeg_wg* wgs_dev, int N, int64_t nseg, int64_t nwg, const uint8_t* bytes,
+                                   int64_t bytes_len, const yv4_jpeg_huff* huff, int64_t nhuff, int16_t* coef,
+                                   int64_t coef_elems, int32_t* status, void* stream);
+
+/* The reason behind a YV4_JPEG_ERR_* code, as static text. */
+const char* yv4_jpeg_entropy_strerror(int code);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,7 @@ from .single_stage import SingleStageDetector, bbox2result
 from .yolov3 import Darknet, DetectionBlock, ResBlock, YOLOBBoxCoder, YOLOV3, YOLOV3Head, YOLOV3Neck
 from .plan import Plan
 from .preprocess import FusedTestPipeline
-from .image_io import LoadImageFromFile, imdecode, imread
+from .image_io import LoadImageFromFile, imdecode, imread, set_default_entropy
 from .augment import FusedTrainPipeline
 from .augment_v3 import FusedV3TrainPipeline, build_train_pipeline
 from . import tta  # noqa: F401  (YOLOv3 test-time augmentation)

@@ -164,6 +164,32 @@ class JpegImage(C.Structure):
                [('tq', C.c_int32 * 3), ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('reserved', C.c_int32)]
 
 
+class JpegHuff(C.Structure):
+    """``yv4_jpeg_huff``: one Huffman table in the form the scan decode reads."""
+    _fields_ = [('look', C.c_uint16 * 512), ('maxcode', C.c_int32 * 8), ('valoff', C.c_int32 * 8), ('vals', C.c_uint8 * 256)]
+
+
+class JpegScan(C.Structure):
+    """``yv4_jpeg_scan``: one image of a ``yv4_jpeg_entropy_decode_device`` call."""
+    _fields_ = [(n, C.c_int64) for n in ('data_off', 'data_len', 'coef_off', 'ncoef', 'seg_base')] + \
+               [(n, C.c_int32) for n in ('nseg', 'ncomp', 'mcus_x', 'mcus_y', 'hs', 'vs')] + \
+               [('td', C.c_int32 * 3), ('ta', C.c_int32 * 3), ('huff_base', C.c_int32), ('nhuff', C.c_int32)]
+
+
+class JpegSegment(C.Structure):
+    """``yv4_jpeg_segment``: a run of whole MCUs that decodes on its own."""
+    _fields_ = [('begin', C.c_int64), ('end', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('first_mcu', 'mcu_count', 'bit_off', 'reserved')] + [('pred', C.c_int16 * 4)]
+
+
+class JpegWg(C.Structure):
+    """``yv4_jpeg_wg``: the segments one workgroup of the scan decode serves."""
+    _fields_ = [(n, C.c_int32) for n in ('image', 'first_seg', 'count', 'reserved')]
+
+
+#: ``YV4_JPEG_MAX_HUFF`` / ``YV4_JPEG_WG_SEGMENTS`` (include/yv4.h)
+JPEG_MAX_HUFF, JPEG_WG_SEGMENTS = 6, 64
+
 _vp, _i, _i64, _f, _sz, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 
 #: every exported symbol: name -> (restype, argtypes).  tests/test_abi.py checks
@@ -295,6 +321,12 @@ SIGNATURES = {
     'yv4_jpeg_entropy_decode': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo), _vp, _i64]),
     'yv4_jpeg_layout': (C.c_int, [C.POINTER(JpegInfo), _i, C.POINTER(JpegImage), C.POINTER(C.c_int64)]),
     'yv4_jpeg_reconstruct': (C.c_int, [C.POINTER(JpegImage), _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
+    'yv4_jpeg_scan_prepare': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo), _vp, _vp, _vp, _i64]),
+    'yv4_jpeg_entropy_workgroups': (C.c_int, [_vp, _i, _vp, _i64, C.POINTER(C.c_int64)]),
+    'yv4_jpeg_entropy_decode_segments': (C.c_int, [_vp, _vp, _vp, _i, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    'yv4_jpeg_entropy_decode_device': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i64, _vp, _i64, _vp,
+                                                 _i64, _vp, _vp]),
+    'yv4_jpeg_entropy_strerror': (C.c_char_p, [_i]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -323,6 +355,9 @@ COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_
 RESULTS_SYMBOLS = frozenset(('yv4_results_append',))
 #: the baseline JPEG decoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg()
 JPEG_SYMBOLS = frozenset(('yv4_jpeg_parse', 'yv4_jpeg_entropy_decode', 'yv4_jpeg_layout', 'yv4_jpeg_reconstruct'))
+#: the Huffman scan decode on the device (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_entropy()
+JPEG_ENTROPY_SYMBOLS = frozenset(('yv4_jpeg_scan_prepare', 'yv4_jpeg_entropy_workgroups', 'yv4_jpeg_entropy_decode_segments',
+                                  'yv4_jpeg_entropy_decode_device', 'yv4_jpeg_entropy_strerror'))
 #: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
 RESULTS_MAX_PER_IMG = 4096
 
@@ -367,7 +402,7 @@ def lib():
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
                     or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
                     or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
-                    or name in JPEG_SYMBOLS) \
+                    or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -448,6 +483,13 @@ def has_jpeg():
     """The loaded library exports the baseline JPEG decoder (``yv4_jpeg_parse`` .. ``yv4_jpeg_reconstruct``)."""
     h = lib()
     return all(hasattr(h, n) for n in JPEG_SYMBOLS)
+
+
+def has_jpeg_entropy():
+    """The loaded library exports the Huffman scan decode on the device (``yv4_jpeg_scan_prepare`` ..
+    ``yv4_jpeg_entropy_decode_device``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in JPEG_ENTROPY_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

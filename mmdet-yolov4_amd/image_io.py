@@ -4,7 +4,9 @@ The decoder is a hybrid (``include/yv4.h``, "baseline JPEG decoding"): the host 
 decode (``yv4_jpeg_parse`` / ``yv4_jpeg_entropy_decode``, sequential by nature, one thread per image), the device does
 everything from the quantised coefficients to interleaved pixels (``yv4_jpeg_reconstruct``: dequantisation, libjpeg's
 "islow" integer IDCT, fancy chroma upsampling, integer YCbCr conversion).  A batch is one reconstruct call; its
-coefficients, quantisation tables and per-image table go up through one pinned staging buffer.
+coefficients, quantisation tables and per-image table go up through one pinned staging buffer.  With ``entropy='device'``
+the Huffman decode runs on the device as well (``yv4_jpeg_scan_prepare`` / ``yv4_jpeg_entropy_decode_device``, one lane per
+restart segment): the files and their segment tables go up instead of the coefficients, and the host only parses.
 
 The pixels equal libjpeg-turbo's default decode bit for bit, which is what ``cv2.imdecode``, turbojpeg and Pillow -- every
 backend of ``mmcv.imfrombytes`` -- return.  **One known difference**: EXIF orientation is not applied
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import JpegImage, JpegInfo, check
+from ._lib import JpegHuff, JpegImage, JpegInfo, JpegScan, JpegSegment, JpegWg, check
 from .ops import stream_ptr
 from .registry import PIPELINES
 
@@ -90,22 +92,154 @@ def _align(n, a=256):
     return (n + a - 1) // a * a
 
 
-def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None):
+#: where the Huffman scan of a file is decoded when a call does not say: ``'host'`` (``yv4_jpeg_entropy_decode`` on a
+#: thread pool) or ``'device'`` (``yv4_jpeg_entropy_decode_device``).  ``set_default_entropy`` changes it.
+DEFAULT_ENTROPY = 'host'
+
+
+def set_default_entropy(mode):
+    """Sets the module's default for ``entropy=`` (``'host'`` or ``'device'``) and returns the previous one."""
+    global DEFAULT_ENTROPY
+    if mode not in ('host', 'device'):
+        raise ValueError(f"entropy {mode!r} is not 'host' or 'device'")
+    prev, DEFAULT_ENTROPY = DEFAULT_ENTROPY, mode
+    return prev
+
+
+def _entropy_mode(entropy):
+    mode = DEFAULT_ENTROPY if entropy is None else entropy
+    if mode not in ('host', 'device'):
+        raise ValueError(f"entropy {mode!r} is not 'host' or 'device'")
+    return mode
+
+
+class ScanTables:
+    """The host tables of a device Huffman decode (``include/yv4.h``, "the Huffman scan on the device") for a list of
+    files: ``infos``, ``scans`` (one per image, placed: files back to back at 4-byte aligned offsets, segments and packed
+    tables dense, ``coef_off`` as given), ``segs``, ``wgs``, ``huff``; ``nseg``, ``nwg``, ``nhuff``, ``nbytes``.  Needs
+    no GPU.  A refused or malformed file raises as ``jpeg_parse`` does, naming the image."""
+
+    def __init__(self, bufs, coef_offs=None, what='jpeg_scan_tables'):
+        L = _lib.lib()
+        N = len(bufs)
+        self.bufs = bufs
+        self.infos = (JpegInfo * N)()
+        for n, b in enumerate(bufs):
+            st = L.yv4_jpeg_parse(b, len(b), C.byref(self.infos[n]))
+            if st != 0:
+                _raise(st, f'{what}: image {n}')
+        counts = [-(-f.mcus_x * f.mcus_y // f.restart_interval) if f.restart_interval else 1 for f in self.infos]
+        self.nseg = sum(counts)
+        self.scans = (JpegScan * N)()
+        self.segs = (JpegSegment * self.nseg)()
+        self.huff = (JpegHuff * (_lib.JPEG_MAX_HUFF * N))()
+        seg = nhuff = off = coef = 0
+        info = JpegInfo()
+        for n, b in enumerate(bufs):
+            sc = self.scans[n]
+            st = L.yv4_jpeg_scan_prepare(b, len(b), C.byref(info), C.addressof(sc),
+                                         C.addressof(self.huff) + nhuff * C.sizeof(JpegHuff),
+                                         C.addressof(self.segs) + seg * C.sizeof(JpegSegment), counts[n])
+            if st != 0:
+                _raise(st, f'{what}: image {n}')
+            sc.data_off, sc.seg_base, sc.huff_base = off, seg, nhuff
+            sc.coef_off = coef if coef_offs is None else int(coef_offs[n])
+            off += _align(len(b), 4)
+            seg += sc.nseg
+            nhuff += sc.nhuff
+            coef += int(sc.ncoef)
+        self.nhuff, self.nbytes, self.ncoef = nhuff, off, coef
+        count = C.c_int64()
+        scans = C.addressof(self.scans)
+        check(L.yv4_jpeg_entropy_workgroups(scans, N, None, 0, C.byref(count)), 'yv4_jpeg_entropy_workgroups')
+        self.nwg = int(count.value)
+        self.wgs = (JpegWg * self.nwg)()
+        check(L.yv4_jpeg_entropy_workgroups(scans, N, C.addressof(self.wgs), self.nwg, C.byref(count)),
+              'yv4_jpeg_entropy_workgroups')
+
+    def sections(self):
+        """``(ctypes object or None, byte count)`` of each table in upload order: scans, segs, wgs, huff, file bytes."""
+        return ((self.scans, C.sizeof(self.scans)), (self.segs, C.sizeof(self.segs)), (self.wgs, C.sizeof(self.wgs)),
+                (self.huff, self.nhuff * C.sizeof(JpegHuff)), (None, self.nbytes))
+
+    def write_bytes(self, base):
+        """The files to host address ``base`` at their ``data_off``."""
+        for sc, b in zip(self.scans, self.bufs):
+            C.memmove(base + int(sc.data_off), b, len(b))
+
+
+def jpeg_entropy_decode_segments(bufs):
+    """The device decode's tables and core run on the CPU (``yv4_jpeg_entropy_decode_segments``) -> ``(ScanTables, int16
+    coefficients of the batch, int32 status per image)``.  Needs no GPU."""
+    t = ScanTables(bufs)
+    data = np.zeros(max(t.nbytes, 1), np.uint8)
+    t.write_bytes(data.ctypes.data)
+    coef = np.empty(t.ncoef, np.int16)
+    status = np.empty(len(bufs), np.int32)
+    check(_lib.lib().yv4_jpeg_entropy_decode_segments(
+        C.addressof(t.scans), C.addressof(t.segs), C.addressof(t.wgs), len(bufs), t.nseg, t.nwg, data.ctypes.data, t.nbytes,
+        C.addressof(t.huff), t.nhuff, coef.ctypes.data, coef.size, status.ctypes.data), 'yv4_jpeg_entropy_decode_segments')
+    return t, coef, status
+
+
+def jpeg_entropy_decode_device(bufs, device=None, coef=None, status=None, tables=None):
+    """The device Huffman decode on its own -> ``(ScanTables, int16 coefficient tensor, int32 status tensor)`` on the GPU,
+    nothing read back.  ``coef`` / ``status``: the caller's tensors to decode into (``tables.ncoef`` / ``len(bufs)``
+    elements, views into larger buffers say); ``tables``: a ``ScanTables`` of ``bufs`` made before."""
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    t = ScanTables(bufs) if tables is None else tables
+    offs, end = [], 0
+    for _, size in t.sections():
+        offs.append(end)
+        end += _align(size)
+    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
+    for (obj, size), off in zip(t.sections(), offs):
+        if obj is not None:
+            C.memmove(stage.data_ptr() + off, obj, size)
+    t.write_bytes(stage.data_ptr() + offs[4])
+    with torch.cuda.device(dev):
+        up = stage.to(dev, non_blocking=True)
+        coef = torch.empty(t.ncoef, dtype=torch.int16, device=dev) if coef is None else coef
+        status = torch.empty(len(bufs), dtype=torch.int32, device=dev) if status is None else status
+        d = [up.data_ptr() + o for o in offs]
+        check(_lib.lib().yv4_jpeg_entropy_decode_device(
+            C.addressof(t.scans), C.addressof(t.segs), C.addressof(t.wgs), d[0], d[1], d[2], len(bufs), t.nseg, t.nwg, d[4],
+            t.nbytes, d[3], t.nhuff, coef.data_ptr(), coef.numel(), status.data_ptr(), stream_ptr()),
+            'yv4_jpeg_entropy_decode_device')
+    return t, coef, status
+
+
+def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None, entropy=None):
     """The batch decode behind ``imdecode``: ``bufs`` (a list of JPEG byte strings) -> ``(out, table)``, ``out`` the flat
     ``torch.uint8`` device buffer and ``table`` the ``JpegImage`` array saying where each image lies in it.  With ``out``
     and ``placement`` (``(byte offset, row pitch)`` per image) the pixels go into the caller's buffer instead -- rows of
-    a larger canvas, say; the library checks every image against the buffer's size before the launch."""
+    a larger canvas, say; the library checks every image against the buffer's size before the launch.
+
+    ``entropy``: ``'host'`` decodes the Huffman scans on a thread pool and uploads coefficients; ``'device'`` uploads the
+    files and their segment tables and decodes them in one launch (``yv4_jpeg_entropy_decode_device``), the coefficients
+    never leaving device memory; ``None``: ``DEFAULT_ENTROPY``.  Both give the same pixels.  With ``'device'`` the scan's
+    errors are known only after the batch: one read-back of a status word per image, then ``ValueError`` naming the first
+    bad image -- by then the batch's pixels have been written (a caller's ``out`` included)."""
     if not torch.cuda.is_available():
         raise RuntimeError('the JPEG decoder reconstructs the pixels on the GPU through libyv4_hip.so (there is no CPU '
                            'fallback)')
+    mode = _entropy_mode(entropy)
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     L = _lib.lib()
     N = len(bufs)
-    infos = (JpegInfo * N)()
-    for n, b in enumerate(bufs):
-        st = L.yv4_jpeg_parse(b, len(b), C.byref(infos[n]))
-        if st != 0:
-            _raise(st, f'imdecode: image {n}')
+    scan = None
+    if mode == 'device':
+        if not _lib.has_jpeg_entropy():
+            raise RuntimeError("entropy='device' needs yv4_jpeg_entropy_decode_device, which the loaded libyv4_hip.so "
+                               'does not export (there is no fallback): rebuild it')
+        scan = ScanTables(bufs, what='imdecode')
+        infos = scan.infos
+    else:
+        infos = (JpegInfo * N)()
+        for n, b in enumerate(bufs):
+            st = L.yv4_jpeg_parse(b, len(b), C.byref(infos[n]))
+            if st != 0:
+                _raise(st, f'imdecode: image {n}')
     table = (JpegImage * N)()
     totals = (C.c_int64 * 3)()
     check(L.yv4_jpeg_layout(infos, N, table, totals), 'yv4_jpeg_layout')
@@ -117,51 +251,81 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
         for n, (off, pitch) in enumerate(placement):
             table[n].out_off, table[n].out_pitch = int(off), int(pitch)
 
-    # one pinned staging buffer: [per-image table | quantisation tables (N, 4, 64) uint16 | coefficients int16]
+    # one pinned staging buffer: [per-image table | quantisation tables (N, 4, 64) uint16 | ...
     quant_off = _align(C.sizeof(table))
     coef_off = quant_off + _align(N * 4 * 64 * 2)
-    stage = torch.empty(coef_off + 2 * ncoef, dtype=torch.uint8, pin_memory=True)
+    if scan is None:      # ... coefficients int16]
+        stage = torch.empty(coef_off + 2 * ncoef, dtype=torch.uint8, pin_memory=True)
+    else:                 # ... scans | segments | workgroups | packed Huffman tables | the files]: no coefficients
+        offs, end = [], coef_off
+        for _, size in scan.sections():
+            offs.append(end)
+            end += _align(size)
+        stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
     base = stage.data_ptr()
     C.memmove(base, table, C.sizeof(table))
     for n in range(N):
         C.memmove(base + quant_off + n * 512, infos[n].quant, 512)
 
-    def entropy(n):
+    def entropy_host(n):
         info = JpegInfo()
         st = L.yv4_jpeg_entropy_decode(bufs[n], len(bufs[n]), C.byref(info), base + coef_off + 2 * int(table[n].coef_off),
                                        int(infos[n].ncoef))
         if st != 0:
             _raise(st, f'imdecode: image {n}')
 
-    if N == 1:
-        entropy(0)
+    if scan is not None:
+        for (obj, size), off in zip(scan.sections(), offs):
+            if obj is not None:
+                C.memmove(base + off, obj, size)
+        scan.write_bytes(base + offs[4])
+    elif N == 1:
+        entropy_host(0)
     else:
         with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, N)) as pool:      # ctypes releases the GIL
-            list(pool.map(entropy, range(N)))
+            list(pool.map(entropy_host, range(N)))
 
+    status = None
     with torch.cuda.device(dev):
         up = stage.to(dev, non_blocking=True)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
         if placement is None:
             out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
-        check(L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, up.data_ptr() + coef_off, ncoef, up.data_ptr() + quant_off,
+        if scan is None:
+            coef_ptr = up.data_ptr() + coef_off
+        else:
+            coef = torch.empty(ncoef, dtype=torch.int16, device=dev)
+            status = torch.empty(N, dtype=torch.int32, device=dev)
+            d = [up.data_ptr() + o for o in offs]
+            check(L.yv4_jpeg_entropy_decode_device(
+                C.addressof(scan.scans), C.addressof(scan.segs), C.addressof(scan.wgs), d[0], d[1], d[2], N, scan.nseg,
+                scan.nwg, d[4], scan.nbytes, d[3], scan.nhuff, coef.data_ptr(), ncoef, status.data_ptr(), stream_ptr()),
+                'yv4_jpeg_entropy_decode_device')
+            coef_ptr = coef.data_ptr()
+        check(L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, coef_ptr, ncoef, up.data_ptr() + quant_off,
                                      work.data_ptr(), work_bytes, out.data_ptr(), out_bytes,
                                      int(channel_order == 'rgb'), stream_ptr()), 'yv4_jpeg_reconstruct')
+    if status is not None:
+        for n, code in enumerate(status.cpu().tolist()):      # the batch's one read-back
+            if code:
+                raise ValueError(f'imdecode: image {n}: jpeg: ' + L.yv4_jpeg_entropy_strerror(code).decode())
     return out, table
 
 
-def imdecode(buffers, channel_order='bgr', device=None):
+def imdecode(buffers, channel_order='bgr', device=None, entropy=None):
     """``buffers``: the bytes of one JPEG file or a list of them -> a ``torch.uint8`` (h, w, 3) tensor on ``device``
     (default: the current GPU), or a list of them.  ``channel_order``: ``'bgr'`` (what ``mmcv.imread`` returns) or
     ``'rgb'``; a grayscale file gives its plane three times, like ``flag='color'``.  A list is decoded as one batch:
-    the entropy decodes on a thread pool, then one upload and one reconstruct call.  EXIF orientation is not applied."""
+    the entropy decodes on a thread pool, then one upload and one reconstruct call -- or, with ``entropy='device'``, the
+    files go up and a kernel decodes their scans (``decode_into``; ``None``: ``DEFAULT_ENTROPY``, which starts as
+    ``'host'``).  EXIF orientation is not applied."""
     if channel_order not in ('bgr', 'rgb'):
         raise ValueError(f"channel_order {channel_order!r} is not 'bgr' or 'rgb'")
     single = not isinstance(buffers, (list, tuple))
     bufs = [_as_bytes(b) for b in ([buffers] if single else buffers)]
     if not bufs:
         return []
-    out, table = decode_into(bufs, channel_order, device)
+    out, table = decode_into(bufs, channel_order, device, entropy=entropy)
     imgs = []
     for t in table:
         h, w, off = int(t.height), int(t.width), int(t.out_off)
@@ -169,14 +333,14 @@ def imdecode(buffers, channel_order='bgr', device=None):
     return imgs[0] if single else imgs
 
 
-def imread(paths, channel_order='bgr', device=None):
+def imread(paths, channel_order='bgr', device=None, entropy=None):
     """``paths``: a file name (``str`` / ``os.PathLike``) or a list of them -> what ``imdecode`` returns for their bytes."""
     single = not isinstance(paths, (list, tuple))
     bufs = []
     for p in ([paths] if single else paths):
         with open(os.fspath(p), 'rb') as f:
             bufs.append(f.read())
-    return imdecode(bufs[0] if single else bufs, channel_order=channel_order, device=device)
+    return imdecode(bufs[0] if single else bufs, channel_order=channel_order, device=device, entropy=entropy)
 
 
 @PIPELINES.register_module()
@@ -186,10 +350,10 @@ class LoadImageFromFile:
     ``ori_shape`` and ``img_fields``.  ``img`` is a (h, w, 3) BGR tensor on the GPU -- ``torch.uint8``, or
     ``torch.float32`` with ``to_float32``.  ``im_decode_backend`` is accepted and ignored: every backend the reference
     offers for JPEG runs libjpeg-turbo's default decode, which is what ``imread`` computes.  EXIF orientation is not
-    applied (the reference's cv2 backend applies it)."""
+    applied (the reference's cv2 backend applies it).  ``entropy``: where the Huffman scan is decoded (``imdecode``)."""
 
     def __init__(self, to_float32=False, color_type='color', file_client_args=dict(backend='disk'), im_decode_backend=None,
-                 device=None):
+                 device=None, entropy=None):
         if color_type != 'color':
             raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' only)")
         if dict(file_client_args) != dict(backend='disk'):
@@ -200,13 +364,14 @@ class LoadImageFromFile:
         self.file_client_args = dict(file_client_args)
         self.im_decode_backend = im_decode_backend
         self.device = device
+        self.entropy = None if entropy is None else _entropy_mode(entropy)
 
     def __call__(self, results):
         if results['img_prefix'] is not None:
             filename = os.path.join(results['img_prefix'], results['img_info']['filename'])
         else:
             filename = results['img_info']['filename']
-        img = imread(filename, device=self.device)
+        img = imread(filename, device=self.device, entropy=self.entropy)
         if self.to_float32:
             img = img.float()
         results['filename'] = filename

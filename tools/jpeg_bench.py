@@ -1,6 +1,6 @@
 """Phases of the hybrid JPEG decode on 32 images of 480x640, 4:2:0, quality 90 (the shape of a COCO file).
 
-    python tools/jpeg_bench.py [--images 32] [--repeats 5]
+    python tools/jpeg_bench.py [--images 32] [--repeats 5] [--device-batches 32,256] [--json PATH]
 
 Prints, per phase, the median over ``--repeats`` windows (and the spread):
   * host parse + entropy decode per image on one thread and on 16 threads (files/s),
@@ -9,7 +9,13 @@ Prints, per phase, the median over ``--repeats`` windows (and the spread):
     buffers, and the bytes/s they achieve against the measured HBM copy rate of the MI355X (6.29 TB/s): bytes are what
     the algorithm moves -- coefficients read (2 B), planes written and read (1 B + 1 B), pixels written (3 B),
   * ``imdecode`` of the batch end to end (host clock around a device synchronise),
-  * Pillow's (libjpeg-turbo's) decode of the same files on one thread, as the reference, where Pillow is importable.
+  * Pillow's (libjpeg-turbo's) decode of the same files on one thread, as the reference, where Pillow is importable,
+  * with ``--device-batches``, per batch size B (the image set repeated to B files) and for the same files re-encoded with
+    ``restart_marker_rows=1`` (30 segments per file instead of one): the host side of the device Huffman decode
+    (``ScanTables``: parse, segment table, packed tables; one thread), the staging bytes and their upload, HIP events
+    around ``yv4_jpeg_entropy_decode_device`` alone and around it plus ``yv4_jpeg_reconstruct`` on resident buffers, and
+    ``imdecode`` end to end with ``entropy='device'`` against ``entropy='host'`` on 16 and on 2 threads (2 is one rank's
+    share when eight ranks split 16 CPUs).  ``--json`` writes everything measured to a file.
 The images are made with Pillow; without it the tool says so and exits.  There is no pass mark.  Needs the GPU: a
 measurement path that finds none fails.
 """
@@ -32,7 +38,7 @@ HBM_BYTES_PER_S = 6.29e12      # measured float4 copy rate of the MI355X (8.0e12
 THREADS = 16
 
 
-def make_images(n, h=480, w=640):
+def make_images(n, h=480, w=640, **kw):
     from PIL import Image
     rng = np.random.default_rng(0)
     yy, xx = np.mgrid[0:h, 0:w]
@@ -41,7 +47,7 @@ def make_images(n, h=480, w=640):
         base = np.stack([127 + 100 * np.sin(xx / (23.0 + i) + c) * np.cos(yy / (31.0 + 2 * i) - c) for c in range(3)], -1)
         img = np.clip(base + rng.normal(0, 12, (h, w, 3)), 0, 255).astype(np.uint8)
         buf = io.BytesIO()
-        Image.fromarray(img).save(buf, 'JPEG', quality=90, subsampling=2)
+        Image.fromarray(img).save(buf, 'JPEG', quality=90, subsampling=2, **kw)
         out.append(buf.getvalue())
     return out
 
@@ -57,6 +63,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=32)
     ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--device-batches', default='', help='comma-separated batch sizes for the device Huffman decode phases')
+    ap.add_argument('--json', default='', help='write the results to this file as well')
     args = ap.parse_args()
     try:
         import PIL  # noqa: F401
@@ -200,8 +208,148 @@ def main():
     res['pillow_1_thread_files_per_s'] = round(N * rounds / med, 1)
     print(f'{"Pillow, 1 thread":>22}: {N * rounds / med:9.1f} files/s   ({1e3 * med / (N * rounds):.3f} ms per file; '
           f'windows {N * rounds / hi:.0f} .. {N * rounds / lo:.0f} files/s)   [bytes equal to imdecode: yes]')
+    if args.device_batches:
+        sizes = [int(b) for b in args.device_batches.split(',')]
+        restart = make_images(min(N, 32), restart_marker_rows=1)
+        res['device_entropy'] = [device_phases(kind, src, B, args.repeats, dev)
+                                 for kind, src in (('plain', bufs), ('restart_rows_1', restart)) for B in sizes]
     print(json.dumps(res))
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
     return 0
+
+
+def device_phases(kind, src, B, repeats, dev):
+    """The phases of the device Huffman decode for the first ``B`` files of ``src`` repeated."""
+    import torch
+    import mmdet_yolov4_amd as pkg
+    from mmdet_yolov4_amd import image_io
+    from mmdet_yolov4_amd._lib import JpegImage
+    from mmdet_yolov4_amd.ops import stream_ptr
+    L = pkg._lib.lib()
+    bufs = [src[i % len(src)] for i in range(B)]
+    r = dict(files=kind, batch=B)
+    print(f'--- device Huffman decode: {kind}, batch of {B} ---')
+
+    def prepare():
+        t0 = time.perf_counter()
+        image_io.ScanTables(bufs)
+        return time.perf_counter() - t0
+
+    med, lo, hi = windows(prepare, repeats)
+    r['prepare_1_thread_files_per_s'] = round(B / med, 1)
+    t = image_io.ScanTables(bufs)
+    r['segments'], r['workgroups'] = t.nseg, t.nwg
+    print(f'{"prepare, 1 thread":>22}: {B / med:9.1f} files/s   ({1e6 * med / B:.1f} us per file; {t.nseg} segments in {t.nwg} '
+          f'workgroups)')
+
+    table = (JpegImage * B)()
+    totals = (C.c_int64 * 3)()
+    assert L.yv4_jpeg_layout(t.infos, B, table, totals) == 0
+    ncoef, work_bytes, out_bytes = (int(v) for v in totals)
+    sections = ((table, C.sizeof(table)), (None, B * 512)) + tuple(t.sections())
+    offs, end = [], 0
+    for _, size in sections:
+        offs.append(end)
+        end += image_io._align(size)
+    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
+    for (obj, size), off in zip(sections, offs):
+        if obj is not None:
+            C.memmove(stage.data_ptr() + off, obj, size)
+    for n in range(B):
+        C.memmove(stage.data_ptr() + offs[1] + n * 512, t.infos[n].quant, 512)
+    t.write_bytes(stage.data_ptr() + offs[6])
+    r['staging_bytes'], r['host_path_staging_bytes'] = end, offs[2] + 2 * ncoef
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    up = torch.empty(end, dtype=torch.uint8, device=dev)
+    copies = 20
+
+    def upload():
+        ev0.record()
+        for _ in range(copies):
+            up.copy_(stage, non_blocking=True)
+        ev1.record()
+        ev1.synchronize()
+        return ev0.elapsed_time(ev1) * 1e-3
+
+    med, lo, hi = windows(upload, repeats)
+    r['upload_ms'] = round(1e3 * med / copies, 4)
+    print(f'{"upload":>22}: {1e3 * med / copies:9.4f} ms for {end / 1e6:.2f} MB (the host path stages {r["host_path_staging_bytes"] / 1e6:.2f} MB)')
+
+    coef = torch.empty(ncoef, dtype=torch.int16, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+    d = [up.data_ptr() + o for o in offs]
+    calls = 3
+
+    def entropy():
+        st = L.yv4_jpeg_entropy_decode_device(C.addressof(t.scans), C.addressof(t.segs), C.addressof(t.wgs), d[2], d[3], d[4], B,
+                                              t.nseg, t.nwg, d[6], t.nbytes, d[5], t.nhuff, coef.data_ptr(), ncoef,
+                                              status.data_ptr(), stream_ptr())
+        assert st == 0
+
+    def reconstruct():
+        st = L.yv4_jpeg_reconstruct(table, d[0], B, coef.data_ptr(), ncoef, d[1], work.data_ptr(), work_bytes, out.data_ptr(),
+                                    out_bytes, 0, stream_ptr())
+        assert st == 0
+
+    def timed(*steps):
+        def window():
+            ev0.record()
+            for _ in range(calls):
+                for step in steps:
+                    step()
+            ev1.record()
+            ev1.synchronize()
+            return ev0.elapsed_time(ev1) * 1e-3
+        return window
+
+    for name, fn in (('entropy', timed(entropy)), ('entropy_reconstruct', timed(entropy, reconstruct))):
+        med, lo, hi = windows(fn, repeats)
+        r[name + '_ms'] = round(1e3 * med / calls, 4)
+        r[name + '_spread_ms'] = [round(1e3 * lo / calls, 4), round(1e3 * hi / calls, 4)]
+        print(f'{name:>22}: {1e3 * med / calls:9.4f} ms per batch of {B}   ({B * calls / med:.0f} files/s; windows '
+              f'{1e3 * lo / calls:.4f} .. {1e3 * hi / calls:.4f} ms)')
+    assert not status.cpu().any()
+    symbols = None
+    if kind == 'plain':      # the single-lane symbol rate: coded symbols of the slowest file over the batch's time
+        per_file = []
+        for b in src[:len(src)]:
+            c = image_io.jpeg_entropy_decode(b)[1].reshape(-1, 64)
+            # per block: one DC symbol, one symbol per nonzero AC coefficient, ZRLs not counted, one EOB unless it ends at 63
+            per_file.append(int(c.shape[0] + (c[:, 1:] != 0).sum() + (c[:, 63] == 0).sum()))
+        symbols = max(per_file)
+        r['symbols_of_largest_file'] = symbols
+        r['ns_per_symbol_one_lane'] = round(1e6 * r['entropy_ms'] / symbols, 2)
+        print(f'{"one lane":>22}: {symbols} symbols in the largest file -> at most {r["ns_per_symbol_one_lane"]} ns per symbol')
+
+    def end_to_end(mode):
+        def window():
+            t0 = time.perf_counter()
+            for _ in range(2):
+                pkg.imdecode(bufs, device=dev, entropy=mode)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / 2
+        return window
+
+    keep = image_io.MAX_DECODE_THREADS
+    for name, mode, threads in (('imdecode_device', 'device', keep), ('imdecode_host_16_threads', 'host', 16),
+                                ('imdecode_host_2_threads', 'host', 2)):
+        image_io.MAX_DECODE_THREADS = threads
+        try:
+            med, lo, hi = windows(end_to_end(mode), repeats)
+        finally:
+            image_io.MAX_DECODE_THREADS = keep
+        r[name + '_ms'] = round(1e3 * med, 3)
+        r[name + '_files_per_s'] = round(B / med, 1)
+        print(f'{name:>26}: {1e3 * med:9.3f} ms per batch of {B}   ({B / med:.0f} files/s; windows {1e3 * lo:.3f} .. {1e3 * hi:.3f} ms)')
+    a = pkg.imdecode(bufs[:len(src)], device=dev, entropy='device')
+    b = pkg.imdecode(bufs[:len(src)], device=dev, entropy='host')
+    assert all(torch.equal(x, y) for x, y in zip(a, b)), 'the device path differs from the host path'
+    return r
 
 
 if __name__ == '__main__':

@@ -1,5 +1,6 @@
-"""Writes the JPEG byte strings of tests/golden/jpeg.npz as files: ``python tools/jpeg_fixtures_dump.py DIR``
-(the input of tools/jpeg_sanitize.cpp, the stand-alone sanitizer run of the decoder's host half)."""
+"""Writes the JPEG byte strings of tests/golden/jpeg.npz and tests/golden/jpeg_entropy.npz as files:
+``python tools/jpeg_fixtures_dump.py DIR`` (the input of tools/jpeg_sanitize.cpp and tools/jpeg_entropy_sanitize.cpp, the
+stand-alone sanitizer runs of the decoder's host code)."""
 import os
 import sys
 
@@ -10,12 +11,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main(out):
     os.makedirs(out, exist_ok=True)
-    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'jpeg.npz'))
-    names = list(g['names']) + list(g['refused'])
-    for n in names:
-        with open(os.path.join(out, f'{n}.jpg'), 'wb') as f:
-            f.write(g['jpg_' + n].tobytes())
-    print(f'{len(names)} files -> {out}')
+    count = 0
+    for fixture, lists in (('jpeg.npz', ('names', 'refused')), ('jpeg_entropy.npz', ('names', 'damaged'))):
+        g = np.load(os.path.join(ROOT, 'tests', 'golden', fixture))
+        for n in (n for key in lists for n in g[key]):
+            with open(os.path.join(out, f'{n}.jpg'), 'wb') as f:
+                f.write(g['jpg_' + n].tobytes())
+            count += 1
+    print(f'{count} files -> {out}')
 
 
 if __name__ == '__main__':

@@ -1286,8 +1286,8 @@ int yv4_jpeg_reconstruct(const yv4_jpeg_image* table, const yv4_jpeg_image* tabl
  *   yv4_jpeg_scan      one per image: where its file lies in the batch's bytes, where its coefficients go, its MCU grid,
  *                      its slice of the segment table and of the packed Huffman tables
  *   yv4_jpeg_segment   byte range WITHIN THE FILE [begin, end), first MCU and MCU count.  bit_off and pred (a bit offset
- *                      into the first byte and carried-in DC predictors) are there for entry points inside a segment,
- *                      which nothing produces yet: they must be zero
+ *                      into the first byte and carried-in DC predictors) were meant for entry points inside a segment;
+ *                      those live in yv4_jpeg_entry instead ("self-synchronising chunks" below): they must be zero
  *   yv4_jpeg_wg        one per workgroup: image, first segment (within the image) and count (1 .. 64)
  *   yv4_jpeg_huff      one packed Huffman table: the 9-bit lookahead (code length << 8 | symbol, 0: a longer code), the
  *                      largest code and the value offset of each length 10 .. 16 (-1: no code of that length), the values
@@ -1371,6 +1371,98 @@ int yv4_jpeg_entropy_decode_device(const yv4_jpeg_scan* scans, const yv4_jpeg_se
 
 /* The reason behind a YV4_JPEG_ERR_* code, as static text. */
 const char* yv4_jpeg_entropy_strerror(int code);
+
+/* ---- self-synchronising chunks: many lanes per segment (additive within ABI 8) ------------------------------------------
+ * A file without restart markers is one segment, hence one lane above.  Here every segment's bytes [begin, end) are cut
+ * into CHUNKS of chunk_bytes raw bytes (stuffed bytes included; an empty segment is one empty chunk) and one lane
+ * decodes one chunk.  A coded symbol -- a Huffman code and its magnitude bits -- belongs to the chunk in which its first
+ * bit lies.  The decoder state at a symbol boundary is one word:
+ *     (bit position in the file: byte * 8 + bit) << 16 | block index within the MCU << 8 | zigzag index k
+ * with k = 0 for "a DC symbol is next"; the position's byte is never the 0x00 of a stuffed 0xFF00 pair.
+ *   1. sync     Chunk 0 of a segment starts in the true state, every other chunk from a guess (its first bit, block 0,
+ *               k = 0).  A lane decodes, storing nothing, up to the first symbol that starts at or behind its chunk's
+ *               end and records that exit state, the blocks it completed and per component the sum of the DC
+ *               differences modulo 2^16.  In each of max_rounds further rounds a chunk whose predecessor's exit differs
+ *               from the entry it was decoded from is decoded again from that exit.  Errors met on the way say only
+ *               that the entry was wrong.
+ *   2. proof    A segment's chain is accepted only if, for every chunk c > 0, the exit of chunk c - 1 EQUALS the entry
+ *               chunk c was last decoded from.  Chunk 0's entry is true, so by induction an accepted chain is the
+ *               sequential decode.  Exclusive sums over the chain give each chunk's first block ordinal and DC
+ *               predictors; the entry's block index must be that ordinal modulo the blocks per MCU, the segment's
+ *               total mcu_count times the blocks per MCU, and the last chunk must end on a block boundary with fewer
+ *               than 8 real bits left.
+ *   3. decode   One lane per chunk decodes again from its proven entry and stores DC and nonzero AC terms into the
+ *               zero-filled planes.  A block that straddles a chunk's end is finished by the next lane.
+ * An image with any chain not accepted, any check failed or any error inside an accepted chain is UNDECIDED: its word
+ * in `undecided` is nonzero, its coefficients are unspecified, and the caller decodes it again with the one lane per
+ * segment decode above, which alone decides status codes.  The chunk decode never raises status.
+ *
+ * chunk_bytes: YV4_JPEG_MIN_CHUNK_BYTES .. YV4_JPEG_MAX_CHUNK_BYTES.  The reader's look-back is one byte and is guarded
+ * by the segment's begin, so it sets no floor; 4 keeps a chunk no smaller than the longest symbol (31 bits) in all but
+ * stuffed bytes.  max_rounds: 0 .. YV4_JPEG_MAX_ROUNDS (0: only single-chunk segments are ever accepted).
+ *
+ * yv4_jpeg_segment.bit_off / pred stay zero: entry points live in yv4_jpeg_entry. */
+#define YV4_JPEG_MIN_CHUNK_BYTES 4
+#define YV4_JPEG_MAX_CHUNK_BYTES (1 << 20)
+#define YV4_JPEG_MAX_ROUNDS 4096
+#define YV4_JPEG_WG_CHUNKS 64          /* chunks per workgroup */
+
+typedef struct yv4_jpeg_chunk {
+  int32_t image;
+  int32_t seg;             /* its segment, counted within the batch's segment table */
+  int32_t index, count;    /* its place among the segment's chunks, and their number */
+} yv4_jpeg_chunk;
+
+typedef struct yv4_jpeg_entry {   /* written by the decode: what one chunk was decoded from and what it left */
+  uint64_t entry;          /* the state (above) its last pass started from */
+  uint64_t exit[2];        /* the state at the first symbol behind the chunk, or all ones after an error; round r
+                              writes exit[r & 1], and exit[max_rounds & 1] is the final one */
+  int32_t nblk;            /* blocks completed in the chunk */
+  int32_t first_block;     /* ordinal, within the segment, of the block the entry lies in; -1: the chunk is not proven */
+  uint16_t dc[3];          /* per component, the sum of the DC differences decoded in the chunk, modulo 2^16 */
+  uint16_t tail;           /* 1: fewer than 8 real bits are left behind the exit */
+  int16_t pred[3];         /* the DC predictors at the entry */
+  int16_t reserved;
+} yv4_jpeg_entry;
+
+/* Host only, no HIP call: the chunk table of N placed images (scans / segs as yv4_jpeg_scan_prepare made and the caller
+ * placed them).  chunks: every chunk of the batch, images, segments and chunks in order; seg_first (nseg + 1 entries):
+ * each segment's first chunk, then the chunk count; wgs: runs of up to YV4_JPEG_WG_CHUNKS consecutive chunks of one
+ * image (first_seg holds the run's first CHUNK, counted within the batch).  *nchunk / *nwg are the counts; with chunks
+ * NULL only they are made, else YV4_E_CAPACITY if they exceed chunk_capacity / wg_capacity.  YV4_E_INVALID for a
+ * chunk_bytes out of range, a segment with end < begin or more than 2^31 - 1 chunks. */
+int yv4_jpeg_chunks_build(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, int N, int64_t nseg,
+                          int32_t chunk_bytes, yv4_jpeg_chunk* chunks, int64_t chunk_capacity, int32_t* seg_first,
+                          yv4_jpeg_wg* wgs, int64_t wg_capacity, int64_t* nchunk, int64_t* nwg);
+
+/* Host only: the whole method on the CPU over the same tables with the same core, then the one lane per segment decode
+ * of every undecided image (its coefficient range zero-filled again first).  All pointers are HOST memory.  Validates
+ * like yv4_jpeg_entropy_decode_device_sync.  entries (nchunk): the records as the chunk decode left them; undecided
+ * (N int32): nonzero where the image took the second decode; status (N int32): the final YV4_JPEG_ERR_* code of each
+ * image, equal to yv4_jpeg_entropy_decode_segments'; *rounds (may be NULL): the last round in which any chunk was
+ * decoded again. */
+int yv4_jpeg_entropy_decode_sync(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_chunk* chunks,
+                                 const int32_t* seg_first, const yv4_jpeg_wg* wgs, int N, int64_t nseg, int64_t nchunk,
+                                 int64_t nwg, const uint8_t* bytes, int64_t bytes_len, const yv4_jpeg_huff* huff,
+                                 int64_t nhuff, int32_t chunk_bytes, int32_t max_rounds, yv4_jpeg_entry* entries,
+                                 int16_t* coef, int64_t coef_elems, int32_t* status, int32_t* undecided, int32_t* rounds);
+
+/* The chunk decode of N images on `stream`: 1 + max_rounds sync launches (one wave per yv4_jpeg_wg run, the image's
+ * tables in LDS), one launch for the sums and checks (one workgroup per segment), one for the storing decode.  No lane
+ * waits on another workgroup; a round is a launch.  The HOST tables are validated before any launch (YV4_E_INVALID);
+ * the *_dev copies (8-byte aligned; seg_first_dev 4-byte) are trusted.  entries_dev: nchunk records of DEVICE scratch.
+ * The call zero-fills the batch's coefficient range, status and undecided (N int32 each, DEVICE).  Afterwards
+ * undecided[n] != 0 names the images to decode again with yv4_jpeg_entropy_decode_device; status stays zero.  No read
+ * leaves a segment's bytes and no store an image's coefficient range, whatever the bytes hold. */
+int yv4_jpeg_entropy_decode_device_sync(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs,
+                                        const yv4_jpeg_chunk* chunks, const int32_t* seg_first, const yv4_jpeg_wg* wgs,
+                                        const yv4_jpeg_scan* scans_dev, const yv4_jpeg_segment* segs_dev,
+                                        const yv4_jpeg_chunk* chunks_dev, const int32_t* seg_first_dev,
+                                        const yv4_jpeg_wg* wgs_dev, int N, int64_t nseg, int64_t nchunk, int64_t nwg,
+                                        const uint8_t* bytes, int64_t bytes_len, const yv4_jpeg_huff* huff, int64_t nhuff,
+                                        int32_t chunk_bytes, int32_t max_rounds, yv4_jpeg_entry* entries_dev,
+                                        int16_t* coef, int64_t coef_elems, int32_t* status, int32_t* undecided,
+                                        void* stream);
 
 #ifdef __cplusplus
 }

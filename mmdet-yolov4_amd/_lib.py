@@ -187,6 +187,17 @@ class JpegWg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('image', 'first_seg', 'count', 'reserved')]
 
 
+class JpegChunk(C.Structure):
+    """``yv4_jpeg_chunk``: one chunk of a segment's bytes, the unit of the self-synchronising scan decode."""
+    _fields_ = [(n, C.c_int32) for n in ('image', 'seg', 'index', 'count')]
+
+
+class JpegEntry(C.Structure):
+    """``yv4_jpeg_entry``: the state a chunk was decoded from and what the pass left."""
+    _fields_ = [('entry', C.c_uint64), ('exit', C.c_uint64 * 2), ('nblk', C.c_int32), ('first_block', C.c_int32),
+                ('dc', C.c_uint16 * 3), ('tail', C.c_uint16), ('pred', C.c_int16 * 3), ('reserved', C.c_int16)]
+
+
 #: ``YV4_JPEG_MAX_HUFF`` / ``YV4_JPEG_WG_SEGMENTS`` (include/yv4.h)
 JPEG_MAX_HUFF, JPEG_WG_SEGMENTS = 6, 64
 
@@ -327,6 +338,13 @@ SIGNATURES = {
     'yv4_jpeg_entropy_decode_device': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp, _i64, _vp, _i64, _vp,
                                                  _i64, _vp, _vp]),
     'yv4_jpeg_entropy_strerror': (C.c_char_p, [_i]),
+    'yv4_jpeg_chunks_build': (C.c_int, [_vp, _vp, _i, _i64, C.c_int32, _vp, _i64, _vp, _vp, _i64, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_int64)]),
+    'yv4_jpeg_entropy_decode_sync': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _vp, _i64, _vp, _i64,
+                                               C.c_int32, C.c_int32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'yv4_jpeg_entropy_decode_device_sync': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64,
+                                                      _vp, _i64, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp, _vp,
+                                                      _vp]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -358,6 +376,11 @@ JPEG_SYMBOLS = frozenset(('yv4_jpeg_parse', 'yv4_jpeg_entropy_decode', 'yv4_jpeg
 #: the Huffman scan decode on the device (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_entropy()
 JPEG_ENTROPY_SYMBOLS = frozenset(('yv4_jpeg_scan_prepare', 'yv4_jpeg_entropy_workgroups', 'yv4_jpeg_entropy_decode_segments',
                                   'yv4_jpeg_entropy_decode_device', 'yv4_jpeg_entropy_strerror'))
+#: the self-synchronising chunk decode of the Huffman scan (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_sync()
+JPEG_SYNC_SYMBOLS = frozenset(('yv4_jpeg_chunks_build', 'yv4_jpeg_entropy_decode_sync',
+                               'yv4_jpeg_entropy_decode_device_sync'))
+#: ``YV4_JPEG_MIN_CHUNK_BYTES`` / ``YV4_JPEG_MAX_CHUNK_BYTES`` / ``YV4_JPEG_MAX_ROUNDS`` (include/yv4.h)
+JPEG_MIN_CHUNK_BYTES, JPEG_MAX_CHUNK_BYTES, JPEG_MAX_ROUNDS = 4, 1 << 20, 4096
 #: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
 RESULTS_MAX_PER_IMG = 4096
 
@@ -402,7 +425,7 @@ def lib():
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
                     or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
                     or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
-                    or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS) \
+                    or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -490,6 +513,13 @@ def has_jpeg_entropy():
     ``yv4_jpeg_entropy_decode_device``)."""
     h = lib()
     return all(hasattr(h, n) for n in JPEG_ENTROPY_SYMBOLS)
+
+
+def has_jpeg_sync():
+    """The loaded library exports the self-synchronising chunk decode (``yv4_jpeg_chunks_build`` ..
+    ``yv4_jpeg_entropy_decode_device_sync``)."""
+    h = lib()
+    return has_jpeg_entropy() and all(hasattr(h, n) for n in JPEG_SYNC_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

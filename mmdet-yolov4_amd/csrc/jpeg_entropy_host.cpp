@@ -1,7 +1,8 @@
 // Host side of the device Huffman decode (include/yv4.h, "the Huffman scan on the device"): the segment table, the
 // packed Huffman tables and the workgroup table of a batch, their validation, and the CPU run of the shared decode
-// (jpeg_entropy_core.h).  No HIP call: plain C++, usable without a GPU, and compiled on its own with sanitizers by
-// tools/jpeg_entropy_sanitize.cpp.
+// (jpeg_entropy_core.h); and the same for the chunk decode: the chunk tables, their validation and the whole method on
+// the CPU (yv4_jpeg_chunks_build, yv4_jpeg_entropy_decode_sync).  No HIP call: plain C++, usable without a GPU, and
+// compiled on its own with sanitizers by tools/jpeg_entropy_sanitize.cpp and tools/jpeg_entropy_sync_sanitize.cpp.
 //
 // The bytes are untrusted.  yv4_jpeg_parse has checked every header segment's length against the file before the
 // table pass below walks the same segments; the marker walk reads below len only.
@@ -187,7 +188,8 @@ extern "C" int yv4_jpeg_entropy_workgroups(const yv4_jpeg_scan* scans, int N, yv
 int yv4::jpeg_entropy_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_wg* wgs, int N,
                                int64_t nseg, int64_t nwg, int64_t bytes_len, int64_t nhuff, int64_t coef_elems,
                                int64_t* coef_lo, int64_t* coef_hi) {
-  REQUIRE(N > 0 && nseg > 0 && nwg > 0 && bytes_len > 0 && nhuff > 0 && coef_elems > 0,
+  // wgs == nullptr: the caller has a workgroup table of another kind (the chunk decode), which it checks itself
+  REQUIRE(N > 0 && nseg > 0 && (nwg > 0 || !wgs) && bytes_len > 0 && nhuff > 0 && coef_elems > 0,
           "jpeg_entropy: empty batch, table or buffer");
   REQUIRE(nseg < (1ll << 31) && nwg < (1ll << 31), "jpeg_entropy: the batch is too large for one launch");
   int64_t seg = 0, wg = 0, lo = coef_elems, hi = 0;
@@ -223,7 +225,7 @@ int yv4::jpeg_entropy_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segmen
       mcu += g.mcu_count;
     }
     REQUIRE(mcu == total, "jpeg_entropy: image %d: its segments hold %lld of %lld MCUs", n, (long long)mcu, (long long)total);
-    for (int32_t first = 0; first < c.nseg; first += YV4_JPEG_WG_SEGMENTS, ++wg) {
+    for (int32_t first = 0; wgs && first < c.nseg; first += YV4_JPEG_WG_SEGMENTS, ++wg) {
       REQUIRE(wg < nwg, "jpeg_entropy: image %d: the workgroup table ends early", n);
       const int32_t left = c.nseg - first;
       REQUIRE(wgs[wg].image == n && wgs[wg].first_seg == first &&
@@ -234,7 +236,7 @@ int yv4::jpeg_entropy_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segmen
     if (c.coef_off < lo) lo = c.coef_off;
     if (c.coef_off + c.ncoef > hi) hi = c.coef_off + c.ncoef;
   }
-  REQUIRE(seg == nseg && wg == nwg, "jpeg_entropy: %lld segments and %lld workgroups for tables of %lld and %lld",
+  REQUIRE(seg == nseg && (wg == nwg || !wgs), "jpeg_entropy: %lld segments and %lld workgroups for tables of %lld and %lld",
           (long long)seg, (long long)wg, (long long)nseg, (long long)nwg);
   *coef_lo = lo; *coef_hi = hi;
   return YV4_OK;
@@ -256,6 +258,182 @@ extern "C" int yv4_jpeg_entropy_decode_segments(const yv4_jpeg_scan* scans, cons
       const int e = yv4::jpeg::decode_segment(c, segs[c.seg_base + wgs[w].first_seg + l], bytes + c.data_off,
                                               huff + c.huff_base, kZigzag, coef + c.coef_off);
       if (e > status[wgs[w].image]) status[wgs[w].image] = e;
+    }
+  }
+  return YV4_OK;
+}
+
+// ---- self-synchronising chunks (include/yv4.h) ----------------------------------------------------------------------------
+
+namespace {
+int64_t chunks_of(const yv4_jpeg_segment& g, int32_t chunk_bytes) {
+  const int64_t n = ceil_div64(g.end - g.begin, chunk_bytes);
+  return n < 1 ? 1 : n;
+}
+}  // namespace
+
+extern "C" int yv4_jpeg_chunks_build(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, int N, int64_t nseg,
+                                     int32_t chunk_bytes, yv4_jpeg_chunk* chunks, int64_t chunk_capacity,
+                                     int32_t* seg_first, yv4_jpeg_wg* wgs, int64_t wg_capacity, int64_t* nchunk,
+                                     int64_t* nwg) {
+  REQUIRE(scans && segs && nchunk && nwg && N > 0 && nseg > 0, "jpeg_chunks_build: null pointer or no image");
+  REQUIRE(chunk_bytes >= YV4_JPEG_MIN_CHUNK_BYTES && chunk_bytes <= YV4_JPEG_MAX_CHUNK_BYTES,
+          "jpeg_chunks_build: chunk_bytes %d is not in %d .. %d", chunk_bytes, YV4_JPEG_MIN_CHUNK_BYTES,
+          YV4_JPEG_MAX_CHUNK_BYTES);
+  REQUIRE(!chunks || (seg_first && wgs), "jpeg_chunks_build: chunks without seg_first and wgs");
+  int64_t nc = 0, nw = 0, seg = 0;
+  for (int n = 0; n < N; ++n) {
+    const yv4_jpeg_scan& c = scans[n];
+    REQUIRE(c.nseg >= 1 && c.seg_base == seg && c.nseg <= nseg - seg, "jpeg_chunks_build: image %d: seg_base / nseg", n);
+    const int64_t image_first = nc;
+    for (int32_t s = 0; s < c.nseg; ++s, ++seg) {
+      const yv4_jpeg_segment& g = segs[seg];
+      REQUIRE(g.begin >= 0 && g.begin <= g.end, "jpeg_chunks_build: image %d: segment %d has end < begin", n, s);
+      const int64_t cnt = chunks_of(g, chunk_bytes);
+      REQUIRE(nc + cnt < (1ll << 31), "jpeg_chunks_build: the batch has 2^31 chunks or more");
+      if (chunks) {
+        if (nc + cnt > chunk_capacity) {
+          ::yv4::set_error("jpeg_chunks_build: more than %lld chunks", (long long)chunk_capacity);
+          return YV4_E_CAPACITY;
+        }
+        seg_first[seg] = (int32_t)nc;
+        for (int64_t i = 0; i < cnt; ++i) {
+          yv4_jpeg_chunk& k = chunks[nc + i];
+          k.image = n; k.seg = (int32_t)seg; k.index = (int32_t)i; k.count = (int32_t)cnt;
+        }
+      }
+      nc += cnt;
+    }
+    for (int64_t first = image_first; first < nc; first += YV4_JPEG_WG_CHUNKS, ++nw) {
+      if (!chunks) continue;
+      if (nw >= wg_capacity) {
+        ::yv4::set_error("jpeg_chunks_build: more than %lld workgroups", (long long)wg_capacity);
+        return YV4_E_CAPACITY;
+      }
+      const int64_t left = nc - first;
+      wgs[nw].image = n; wgs[nw].first_seg = (int32_t)first;
+      wgs[nw].count = (int32_t)(left < YV4_JPEG_WG_CHUNKS ? left : YV4_JPEG_WG_CHUNKS);
+      wgs[nw].reserved = 0;
+    }
+  }
+  REQUIRE(seg == nseg, "jpeg_chunks_build: %lld segments for a table of %lld", (long long)seg, (long long)nseg);
+  if (chunks) seg_first[nseg] = (int32_t)nc;
+  *nchunk = nc; *nwg = nw;
+  return YV4_OK;
+}
+
+namespace yv4 {
+// Everything the chunk decode indexes with, on the host copies: the scans and segments as the segment decode checks
+// them, then every entry of the chunk, seg_first and workgroup tables against what yv4_jpeg_chunks_build makes.
+int jpeg_sync_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_chunk* chunks,
+                       const int32_t* seg_first, const yv4_jpeg_wg* wgs, int N, int64_t nseg, int64_t nchunk, int64_t nwg,
+                       int64_t bytes_len, int64_t nhuff, int32_t chunk_bytes, int32_t max_rounds, int64_t coef_elems,
+                       int64_t* coef_lo, int64_t* coef_hi) {
+  REQUIRE(chunk_bytes >= YV4_JPEG_MIN_CHUNK_BYTES && chunk_bytes <= YV4_JPEG_MAX_CHUNK_BYTES,
+          "jpeg_entropy_sync: chunk_bytes %d is not in %d .. %d", chunk_bytes, YV4_JPEG_MIN_CHUNK_BYTES,
+          YV4_JPEG_MAX_CHUNK_BYTES);
+  REQUIRE(max_rounds >= 0 && max_rounds <= YV4_JPEG_MAX_ROUNDS, "jpeg_entropy_sync: max_rounds %d is not in 0 .. %d",
+          max_rounds, YV4_JPEG_MAX_ROUNDS);
+  REQUIRE(nchunk > 0 && nwg > 0 && nchunk < (1ll << 31) && nwg < (1ll << 31), "jpeg_entropy_sync: empty or oversized chunk table");
+  const int st = jpeg_entropy_validate(scans, segs, nullptr, N, nseg, 0, bytes_len, nhuff, coef_elems, coef_lo, coef_hi);
+  if (st != YV4_OK) return st;
+  int64_t nc = 0, nw = 0;
+  for (int n = 0; n < N; ++n) {
+    const yv4_jpeg_scan& c = scans[n];
+    const int64_t image_first = nc;
+    for (int32_t s = 0; s < c.nseg; ++s) {
+      const int64_t seg = c.seg_base + s;
+      const int64_t cnt = chunks_of(segs[seg], chunk_bytes);
+      REQUIRE(cnt <= nchunk - nc, "jpeg_entropy_sync: image %d: the chunk table ends early", n);
+      REQUIRE(seg_first[seg] == nc, "jpeg_entropy_sync: image %d: seg_first of segment %d", n, s);
+      for (int64_t i = 0; i < cnt; ++i) {
+        const yv4_jpeg_chunk& k = chunks[nc + i];
+        REQUIRE(k.image == n && k.seg == seg && k.index == i && k.count == cnt,
+                "jpeg_entropy_sync: chunk %lld is not chunk %lld of segment %d of image %d", (long long)(nc + i),
+                (long long)i, s, n);
+      }
+      nc += cnt;
+    }
+    for (int64_t first = image_first; first < nc; first += YV4_JPEG_WG_CHUNKS, ++nw) {
+      REQUIRE(nw < nwg, "jpeg_entropy_sync: image %d: the workgroup table ends early", n);
+      const int64_t left = nc - first;
+      REQUIRE(wgs[nw].image == n && wgs[nw].first_seg == first &&
+                  wgs[nw].count == (left < YV4_JPEG_WG_CHUNKS ? left : YV4_JPEG_WG_CHUNKS),
+              "jpeg_entropy_sync: workgroup %lld is not the next run of image %d", (long long)nw, n);
+    }
+  }
+  REQUIRE(nc == nchunk && nw == nwg && seg_first[nseg] == nchunk,
+          "jpeg_entropy_sync: %lld chunks and %lld workgroups for tables of %lld and %lld", (long long)nc, (long long)nw,
+          (long long)nchunk, (long long)nwg);
+  return YV4_OK;
+}
+}  // namespace yv4
+
+extern "C" int yv4_jpeg_entropy_decode_sync(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs,
+                                            const yv4_jpeg_chunk* chunks, const int32_t* seg_first, const yv4_jpeg_wg* wgs,
+                                            int N, int64_t nseg, int64_t nchunk, int64_t nwg, const uint8_t* bytes,
+                                            int64_t bytes_len, const yv4_jpeg_huff* huff, int64_t nhuff,
+                                            int32_t chunk_bytes, int32_t max_rounds, yv4_jpeg_entry* entries,
+                                            int16_t* coef, int64_t coef_elems, int32_t* status, int32_t* undecided,
+                                            int32_t* rounds) {
+  REQUIRE(scans && segs && chunks && seg_first && wgs && bytes && huff && entries && coef && status && undecided,
+          "jpeg_entropy_decode_sync: null pointer");
+  int64_t lo, hi;
+  const int st = yv4::jpeg_sync_validate(scans, segs, chunks, seg_first, wgs, N, nseg, nchunk, nwg, bytes_len, nhuff,
+                                         chunk_bytes, max_rounds, coef_elems, &lo, &hi);
+  if (st != YV4_OK) return st;
+  memset(coef + lo, 0, (size_t)(hi - lo) * sizeof(int16_t));
+  memset(status, 0, (size_t)N * sizeof(int32_t));
+  memset(undecided, 0, (size_t)N * sizeof(int32_t));
+  using namespace yv4::jpeg;
+  // 1. sync: the kernel's mapping, workgroup w, lane l, one pass over the table per round.  The exit word a round reads
+  // is the one the round before wrote, so the order of the lanes within a round does not matter here either.
+  int32_t last_change = 0;
+  for (int r = 0; r <= max_rounds; ++r)
+    for (int64_t w = 0; w < nwg; ++w) {
+      const yv4_jpeg_scan& c = scans[wgs[w].image];
+      for (int l = 0; l < wgs[w].count; ++l) {
+        const int64_t g = (int64_t)wgs[w].first_seg + l;
+        const yv4_jpeg_chunk& k = chunks[g];
+        const uint64_t prev = r > 0 && k.index > 0 ? entries[g - 1].exit[(r + 1) & 1] : kChunkInvalid;
+        const uint64_t before = r > 0 ? entries[g].entry : 0;
+        sync_chunk(c, segs[k.seg], bytes + c.data_off, huff + c.huff_base, kZigzag, k, chunk_bytes, r, prev, &entries[g]);
+        if (r > 0 && entries[g].entry != before) last_change = r;
+      }
+    }
+  if (rounds) *rounds = last_change;
+  // 2. the exclusive sums over each segment's chunks, and the checks
+  const int fin = max_rounds & 1;
+  for (int64_t s = 0; s < nseg; ++s) {
+    int64_t first = 0;
+    uint32_t dcs[3] = {0, 0, 0};
+    for (int64_t g = seg_first[s]; g < seg_first[s + 1]; ++g) {
+      const yv4_jpeg_chunk& k = chunks[g];
+      const uint64_t prev = k.index > 0 ? entries[g - 1].exit[fin] : kChunkInvalid;
+      if (!check_chunk(scans[k.image], segs[s], k, fin, prev, first, dcs, &entries[g])) undecided[k.image] = 1;
+      first += entries[g].nblk;
+      for (int j = 0; j < 3; ++j) dcs[j] += entries[g].dc[j];
+    }
+  }
+  // 3. the storing decode of the decided images
+  for (int64_t g = 0; g < nchunk; ++g) {
+    const yv4_jpeg_chunk& k = chunks[g];
+    if (undecided[k.image]) continue;
+    const yv4_jpeg_scan& c = scans[k.image];
+    ChunkPass p;
+    const int e = decode_chunk<true>(c, segs[k.seg], bytes + c.data_off, huff + c.huff_base, kZigzag, k.index, k.count,
+                                     chunk_bytes, entries[g].entry, entries[g].first_block, entries[g].pred,
+                                     coef + c.coef_off, &p);
+    if (e || p.exit != entries[g].exit[fin] || p.nblk != entries[g].nblk) undecided[k.image] = 2;
+  }
+  // 4. what is not proven goes to the one lane per segment decode, which decides the status
+  for (int n = 0; n < N; ++n) {
+    if (!undecided[n]) continue;
+    const yv4_jpeg_scan& c = scans[n];
+    memset(coef + c.coef_off, 0, (size_t)c.ncoef * sizeof(int16_t));
+    for (int32_t s = 0; s < c.nseg; ++s) {
+      const int e = decode_segment(c, segs[c.seg_base + s], bytes + c.data_off, huff + c.huff_base, kZigzag, coef + c.coef_off);
+      if (e > status[n]) status[n] = e;
     }
   }
   return YV4_OK;

@@ -7,6 +7,9 @@ everything from the quantised coefficients to interleaved pixels (``yv4_jpeg_rec
 coefficients, quantisation tables and per-image table go up through one pinned staging buffer.  With ``entropy='device'``
 the Huffman decode runs on the device as well (``yv4_jpeg_scan_prepare`` / ``yv4_jpeg_entropy_decode_device``, one lane per
 restart segment): the files and their segment tables go up instead of the coefficients, and the host only parses.
+``entropy='device_sync'`` cuts every segment into chunks that many lanes decode at once from self-synchronised entry
+points (``yv4_jpeg_entropy_decode_device_sync``), which is what gives a file without restart markers more than one lane;
+whatever that path cannot prove goes through the ``'device'`` kernel again.
 
 The pixels equal libjpeg-turbo's default decode bit for bit, which is what ``cv2.imdecode``, turbojpeg and Pillow -- every
 backend of ``mmcv.imfrombytes`` -- return.  **One known difference**: EXIF orientation is not applied
@@ -23,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import JpegHuff, JpegImage, JpegInfo, JpegScan, JpegSegment, JpegWg, check
+from ._lib import JpegChunk, JpegEntry, JpegHuff, JpegImage, JpegInfo, JpegScan, JpegSegment, JpegWg, check
 from .ops import stream_ptr
 from .registry import PIPELINES
 
@@ -93,24 +96,43 @@ def _align(n, a=256):
 
 
 #: where the Huffman scan of a file is decoded when a call does not say: ``'host'`` (``yv4_jpeg_entropy_decode`` on a
-#: thread pool) or ``'device'`` (``yv4_jpeg_entropy_decode_device``).  ``set_default_entropy`` changes it.
+#: thread pool), ``'device'`` (``yv4_jpeg_entropy_decode_device``, one lane per restart segment) or ``'device_sync'``
+#: (``yv4_jpeg_entropy_decode_device_sync``, one lane per chunk of a segment).  ``set_default_entropy`` changes it.
 DEFAULT_ENTROPY = 'host'
+ENTROPY_MODES = ('host', 'device', 'device_sync')
+
+#: ``entropy='device_sync'``: the raw bytes of a segment one lane decodes, and the synchronisation rounds after the
+#: first pass, when a call does not say (DESIGN 19.2 has the sweep they come from)
+DEFAULT_CHUNK_BYTES = 64
+DEFAULT_MAX_ROUNDS = 48
 
 
 def set_default_entropy(mode):
-    """Sets the module's default for ``entropy=`` (``'host'`` or ``'device'``) and returns the previous one."""
+    """Sets the module's default for ``entropy=`` (``'host'``, ``'device'`` or ``'device_sync'``) and returns the
+    previous one."""
     global DEFAULT_ENTROPY
-    if mode not in ('host', 'device'):
-        raise ValueError(f"entropy {mode!r} is not 'host' or 'device'")
+    if mode not in ENTROPY_MODES:
+        raise ValueError(f"entropy {mode!r} is not 'host', 'device' or 'device_sync'")
     prev, DEFAULT_ENTROPY = DEFAULT_ENTROPY, mode
     return prev
 
 
 def _entropy_mode(entropy):
     mode = DEFAULT_ENTROPY if entropy is None else entropy
-    if mode not in ('host', 'device'):
-        raise ValueError(f"entropy {mode!r} is not 'host' or 'device'")
+    if mode not in ENTROPY_MODES:
+        raise ValueError(f"entropy {mode!r} is not 'host', 'device' or 'device_sync'")
     return mode
+
+
+def _sync_params(chunk_bytes, max_rounds):
+    """The validated ``(chunk_bytes, max_rounds)`` of a ``'device_sync'`` decode; ``None``: the module's defaults."""
+    cb = DEFAULT_CHUNK_BYTES if chunk_bytes is None else chunk_bytes
+    mr = DEFAULT_MAX_ROUNDS if max_rounds is None else max_rounds
+    for name, v, lo, hi in (('chunk_bytes', cb, _lib.JPEG_MIN_CHUNK_BYTES, _lib.JPEG_MAX_CHUNK_BYTES),
+                            ('max_rounds', mr, 0, _lib.JPEG_MAX_ROUNDS)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f'{name} {v!r} is not an integer in {lo} .. {hi}')
+    return int(cb), int(mr)
 
 
 class ScanTables:
@@ -168,6 +190,105 @@ class ScanTables:
             C.memmove(base + int(sc.data_off), b, len(b))
 
 
+class ChunkTables:
+    """The chunk tables of a ``'device_sync'`` decode (``include/yv4.h``, "self-synchronising chunks") over a
+    ``ScanTables``: ``chunks``, ``seg_first``, ``wgs``; ``nchunk``, ``nwg``, ``chunk_bytes``.  Needs no GPU."""
+
+    def __init__(self, scan, chunk_bytes):
+        L = _lib.lib()
+        self.scan, self.chunk_bytes = scan, chunk_bytes
+        nchunk, nwg = C.c_int64(), C.c_int64()
+        args = (C.addressof(scan.scans), C.addressof(scan.segs), len(scan.bufs), scan.nseg, chunk_bytes)
+        check(L.yv4_jpeg_chunks_build(*args, None, 0, None, None, 0, C.byref(nchunk), C.byref(nwg)), 'yv4_jpeg_chunks_build')
+        self.nchunk, self.nwg = int(nchunk.value), int(nwg.value)
+        self.chunks = (JpegChunk * self.nchunk)()
+        self.seg_first = (C.c_int32 * (scan.nseg + 1))()
+        self.wgs = (JpegWg * self.nwg)()
+        check(L.yv4_jpeg_chunks_build(*args, C.addressof(self.chunks), self.nchunk, C.addressof(self.seg_first),
+                                      C.addressof(self.wgs), self.nwg, C.byref(nchunk), C.byref(nwg)),
+              'yv4_jpeg_chunks_build')
+
+    def sections(self):
+        """``(ctypes object, byte count)`` of each table in upload order: chunks, seg_first, wgs."""
+        return ((self.chunks, C.sizeof(self.chunks)), (self.seg_first, C.sizeof(self.seg_first)),
+                (self.wgs, C.sizeof(self.wgs)))
+
+
+def _one_chunk_each(scan, chunk_bytes):
+    """Every segment of the batch is at most one chunk long: chunks would add no lane."""
+    return all(g.end - g.begin <= chunk_bytes for g in scan.segs)
+
+
+def jpeg_entropy_decode_sync(bufs, chunk_bytes=None, max_rounds=None):
+    """The whole ``'device_sync'`` method on the CPU (``yv4_jpeg_entropy_decode_sync``: the core the kernels run, then the
+    one lane per segment decode of the undecided images) -> ``(ScanTables, ChunkTables, JpegEntry array, int16
+    coefficients, int32 status per image, int32 undecided per image, last round that changed an entry)``.  Needs no
+    GPU."""
+    chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
+    t = ScanTables(bufs)
+    ch = ChunkTables(t, chunk_bytes)
+    data = np.zeros(max(t.nbytes, 1), np.uint8)
+    t.write_bytes(data.ctypes.data)
+    coef = np.empty(t.ncoef, np.int16)
+    status = np.empty(len(bufs), np.int32)
+    undecided = np.empty(len(bufs), np.int32)
+    entries = (JpegEntry * ch.nchunk)()
+    rounds = C.c_int32()
+    check(_lib.lib().yv4_jpeg_entropy_decode_sync(
+        C.addressof(t.scans), C.addressof(t.segs), C.addressof(ch.chunks), C.addressof(ch.seg_first), C.addressof(ch.wgs),
+        len(bufs), t.nseg, ch.nchunk, ch.nwg, data.ctypes.data, t.nbytes, C.addressof(t.huff), t.nhuff, chunk_bytes,
+        max_rounds, C.addressof(entries), coef.ctypes.data, coef.size, status.ctypes.data, undecided.ctypes.data,
+        C.addressof(rounds)), 'yv4_jpeg_entropy_decode_sync')
+    return t, ch, entries, coef, status, undecided, int(rounds.value)
+
+
+def _upload_plan(sections, start=0):
+    offs, end = [], start
+    for _, size in sections:
+        offs.append(end)
+        end += _align(size)
+    return offs, end
+
+
+def _launch_sync(L, scan, ch, d, N, max_rounds, entries, coef, ncoef, status, undecided):
+    """``yv4_jpeg_entropy_decode_device_sync`` over uploaded tables: ``d`` holds the device addresses of scans, segs, the
+    segment workgroups (unused here), huff, the files, chunks, seg_first and the chunk workgroups."""
+    check(L.yv4_jpeg_entropy_decode_device_sync(
+        C.addressof(scan.scans), C.addressof(scan.segs), C.addressof(ch.chunks), C.addressof(ch.seg_first),
+        C.addressof(ch.wgs), d[0], d[1], d[5], d[6], d[7], N, scan.nseg, ch.nchunk, ch.nwg, d[4], scan.nbytes, d[3],
+        scan.nhuff, ch.chunk_bytes, max_rounds, entries.data_ptr(), coef.data_ptr(), ncoef, status.data_ptr(),
+        undecided.data_ptr(), stream_ptr()), 'yv4_jpeg_entropy_decode_device_sync')
+
+
+def jpeg_entropy_decode_device_sync(bufs, chunk_bytes=None, max_rounds=None, device=None, coef=None, status=None,
+                                    undecided=None, tables=None):
+    """The chunk kernels on their own, without the second decode of undecided images -> ``(ScanTables, ChunkTables, int16
+    coefficient tensor, int32 status tensor, int32 undecided tensor)`` on the GPU, nothing read back.  ``coef`` /
+    ``status`` / ``undecided``: the caller's tensors to decode into, as in ``jpeg_entropy_decode_device``."""
+    chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
+    if not _lib.has_jpeg_sync():
+        raise RuntimeError('yv4_jpeg_entropy_decode_device_sync is not exported by the loaded libyv4_hip.so: rebuild it')
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    t = ScanTables(bufs) if tables is None else tables
+    ch = ChunkTables(t, chunk_bytes)
+    sections = t.sections() + ch.sections()
+    offs, end = _upload_plan(sections)
+    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
+    for (obj, size), off in zip(sections, offs):
+        if obj is not None:
+            C.memmove(stage.data_ptr() + off, obj, size)
+    t.write_bytes(stage.data_ptr() + offs[4])
+    with torch.cuda.device(dev):
+        up = stage.to(dev, non_blocking=True)
+        coef = torch.empty(t.ncoef, dtype=torch.int16, device=dev) if coef is None else coef
+        status = torch.empty(len(bufs), dtype=torch.int32, device=dev) if status is None else status
+        undecided = torch.empty(len(bufs), dtype=torch.int32, device=dev) if undecided is None else undecided
+        entries = torch.empty(ch.nchunk * C.sizeof(JpegEntry), dtype=torch.uint8, device=dev)
+        _launch_sync(_lib.lib(), t, ch, [up.data_ptr() + o for o in offs], len(bufs), max_rounds, entries, coef,
+                     coef.numel(), status, undecided)
+    return t, ch, coef, status, undecided
+
+
 def jpeg_entropy_decode_segments(bufs):
     """The device decode's tables and core run on the CPU (``yv4_jpeg_entropy_decode_segments``) -> ``(ScanTables, int16
     coefficients of the batch, int32 status per image)``.  Needs no GPU."""
@@ -209,7 +330,8 @@ def jpeg_entropy_decode_device(bufs, device=None, coef=None, status=None, tables
     return t, coef, status
 
 
-def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None, entropy=None):
+def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None, entropy=None, chunk_bytes=None,
+                max_rounds=None):
     """The batch decode behind ``imdecode``: ``bufs`` (a list of JPEG byte strings) -> ``(out, table)``, ``out`` the flat
     ``torch.uint8`` device buffer and ``table`` the ``JpegImage`` array saying where each image lies in it.  With ``out``
     and ``placement`` (``(byte offset, row pitch)`` per image) the pixels go into the caller's buffer instead -- rows of
@@ -217,23 +339,35 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
 
     ``entropy``: ``'host'`` decodes the Huffman scans on a thread pool and uploads coefficients; ``'device'`` uploads the
     files and their segment tables and decodes them in one launch (``yv4_jpeg_entropy_decode_device``), the coefficients
-    never leaving device memory; ``None``: ``DEFAULT_ENTROPY``.  Both give the same pixels.  With ``'device'`` the scan's
+    never leaving device memory; ``'device_sync'`` does the same with one lane per ``chunk_bytes`` raw bytes of a segment,
+    entered through at most ``max_rounds`` synchronisation rounds (``None``: ``DEFAULT_CHUNK_BYTES`` /
+    ``DEFAULT_MAX_ROUNDS``); ``None``: ``DEFAULT_ENTROPY``.  All give the same pixels.  With the device modes the scan's
     errors are known only after the batch: one read-back of a status word per image, then ``ValueError`` naming the first
-    bad image -- by then the batch's pixels have been written (a caller's ``out`` included)."""
+    bad image -- by then the batch's pixels have been written (a caller's ``out`` included).  ``'device_sync'`` reads a
+    second word per image in that read-back: the images its chunks could not prove, damaged ones among them, are then
+    decoded by the ``'device'`` kernel, which decides their status, and the batch is reconstructed again.  A batch whose
+    segments are all at most one chunk long takes the ``'device'`` path directly."""
     if not torch.cuda.is_available():
         raise RuntimeError('the JPEG decoder reconstructs the pixels on the GPU through libyv4_hip.so (there is no CPU '
                            'fallback)')
     mode = _entropy_mode(entropy)
+    if mode == 'device_sync' or chunk_bytes is not None or max_rounds is not None:
+        chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     L = _lib.lib()
     N = len(bufs)
-    scan = None
-    if mode == 'device':
+    scan = chunks = None
+    if mode != 'host':
         if not _lib.has_jpeg_entropy():
             raise RuntimeError("entropy='device' needs yv4_jpeg_entropy_decode_device, which the loaded libyv4_hip.so "
                                'does not export (there is no fallback): rebuild it')
+        if mode == 'device_sync' and not _lib.has_jpeg_sync():
+            raise RuntimeError("entropy='device_sync' needs yv4_jpeg_entropy_decode_device_sync, which the loaded "
+                               'libyv4_hip.so does not export (there is no fallback): rebuild it')
         scan = ScanTables(bufs, what='imdecode')
         infos = scan.infos
+        if mode == 'device_sync' and not _one_chunk_each(scan, chunk_bytes):
+            chunks = ChunkTables(scan, chunk_bytes)
     else:
         infos = (JpegInfo * N)()
         for n, b in enumerate(bufs):
@@ -256,11 +390,9 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
     coef_off = quant_off + _align(N * 4 * 64 * 2)
     if scan is None:      # ... coefficients int16]
         stage = torch.empty(coef_off + 2 * ncoef, dtype=torch.uint8, pin_memory=True)
-    else:                 # ... scans | segments | workgroups | packed Huffman tables | the files]: no coefficients
-        offs, end = [], coef_off
-        for _, size in scan.sections():
-            offs.append(end)
-            end += _align(size)
+    else:                 # ... scans | segments | workgroups | packed Huffman tables | the files | chunk tables]: no coefficients
+        sections = scan.sections() + (chunks.sections() if chunks is not None else ())
+        offs, end = _upload_plan(sections, coef_off)
         stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
     base = stage.data_ptr()
     C.memmove(base, table, C.sizeof(table))
@@ -275,7 +407,7 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
             _raise(st, f'imdecode: image {n}')
 
     if scan is not None:
-        for (obj, size), off in zip(scan.sections(), offs):
+        for (obj, size), off in zip(sections, offs):
             if obj is not None:
                 C.memmove(base + off, obj, size)
         scan.write_bytes(base + offs[4])
@@ -285,7 +417,12 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
         with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, N)) as pool:      # ctypes releases the GIL
             list(pool.map(entropy_host, range(N)))
 
-    status = None
+    def reconstruct(coef_ptr):
+        check(L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, coef_ptr, ncoef, up.data_ptr() + quant_off,
+                                     work.data_ptr(), work_bytes, out.data_ptr(), out_bytes,
+                                     int(channel_order == 'rgb'), stream_ptr()), 'yv4_jpeg_reconstruct')
+
+    status = undecided = None
     with torch.cuda.device(dev):
         up = stage.to(dev, non_blocking=True)
         work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
@@ -295,37 +432,59 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
             coef_ptr = up.data_ptr() + coef_off
         else:
             coef = torch.empty(ncoef, dtype=torch.int16, device=dev)
-            status = torch.empty(N, dtype=torch.int32, device=dev)
+            flags = torch.empty(2 * N, dtype=torch.int32, device=dev)      # status | undecided: one read-back
+            status = flags[:N]
             d = [up.data_ptr() + o for o in offs]
-            check(L.yv4_jpeg_entropy_decode_device(
-                C.addressof(scan.scans), C.addressof(scan.segs), C.addressof(scan.wgs), d[0], d[1], d[2], N, scan.nseg,
-                scan.nwg, d[4], scan.nbytes, d[3], scan.nhuff, coef.data_ptr(), ncoef, status.data_ptr(), stream_ptr()),
-                'yv4_jpeg_entropy_decode_device')
+            if chunks is None:
+                check(L.yv4_jpeg_entropy_decode_device(
+                    C.addressof(scan.scans), C.addressof(scan.segs), C.addressof(scan.wgs), d[0], d[1], d[2], N, scan.nseg,
+                    scan.nwg, d[4], scan.nbytes, d[3], scan.nhuff, coef.data_ptr(), ncoef, status.data_ptr(),
+                    stream_ptr()), 'yv4_jpeg_entropy_decode_device')
+            else:
+                undecided = flags[N:]
+                entries = torch.empty(chunks.nchunk * C.sizeof(JpegEntry), dtype=torch.uint8, device=dev)
+                _launch_sync(L, scan, chunks, d, N, max_rounds, entries, coef, ncoef, status, undecided)
             coef_ptr = coef.data_ptr()
-        check(L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, coef_ptr, ncoef, up.data_ptr() + quant_off,
-                                     work.data_ptr(), work_bytes, out.data_ptr(), out_bytes,
-                                     int(channel_order == 'rgb'), stream_ptr()), 'yv4_jpeg_reconstruct')
-    if status is not None:
-        for n, code in enumerate(status.cpu().tolist()):      # the batch's one read-back
-            if code:
-                raise ValueError(f'imdecode: image {n}: jpeg: ' + L.yv4_jpeg_entropy_strerror(code).decode())
+        reconstruct(coef_ptr)
+        if status is not None:
+            codes = (flags if undecided is not None else status).cpu().tolist()      # the batch's one read-back
+            again = [n for n in range(N) if codes[N + n]] if undecided is not None else []
+            if again:
+                # what the chunks did not prove: the one lane per segment kernel, a run of neighbouring images a launch
+                # (it zero-fills from its first image's coefficients to its last's), then the pixels once more
+                runs = [[again[0]]]
+                for n in again[1:]:
+                    if n == runs[-1][-1] + 1:
+                        runs[-1].append(n)
+                    else:
+                        runs.append([n])
+                for run in runs:
+                    a, b = run[0], run[-1] + 1
+                    sub = ScanTables(bufs[a:b], coef_offs=[int(scan.scans[n].coef_off) for n in run], what='imdecode')
+                    jpeg_entropy_decode_device(bufs[a:b], dev, coef=coef, status=status[a:b], tables=sub)
+                reconstruct(coef_ptr)
+                codes = status.cpu().tolist()
+            for n, code in enumerate(codes[:N]):
+                if code:
+                    raise ValueError(f'imdecode: image {n}: jpeg: ' + L.yv4_jpeg_entropy_strerror(code).decode())
     return out, table
 
 
-def imdecode(buffers, channel_order='bgr', device=None, entropy=None):
+def imdecode(buffers, channel_order='bgr', device=None, entropy=None, chunk_bytes=None, max_rounds=None):
     """``buffers``: the bytes of one JPEG file or a list of them -> a ``torch.uint8`` (h, w, 3) tensor on ``device``
     (default: the current GPU), or a list of them.  ``channel_order``: ``'bgr'`` (what ``mmcv.imread`` returns) or
     ``'rgb'``; a grayscale file gives its plane three times, like ``flag='color'``.  A list is decoded as one batch:
     the entropy decodes on a thread pool, then one upload and one reconstruct call -- or, with ``entropy='device'``, the
-    files go up and a kernel decodes their scans (``decode_into``; ``None``: ``DEFAULT_ENTROPY``, which starts as
-    ``'host'``).  EXIF orientation is not applied."""
+    files go up and a kernel decodes their scans, one lane per restart segment, or with ``entropy='device_sync'`` one lane
+    per ``chunk_bytes`` of a segment after at most ``max_rounds`` synchronisation rounds (``decode_into``; ``None``:
+    ``DEFAULT_ENTROPY``, which starts as ``'host'``).  EXIF orientation is not applied."""
     if channel_order not in ('bgr', 'rgb'):
         raise ValueError(f"channel_order {channel_order!r} is not 'bgr' or 'rgb'")
     single = not isinstance(buffers, (list, tuple))
     bufs = [_as_bytes(b) for b in ([buffers] if single else buffers)]
     if not bufs:
         return []
-    out, table = decode_into(bufs, channel_order, device, entropy=entropy)
+    out, table = decode_into(bufs, channel_order, device, entropy=entropy, chunk_bytes=chunk_bytes, max_rounds=max_rounds)
     imgs = []
     for t in table:
         h, w, off = int(t.height), int(t.width), int(t.out_off)
@@ -333,14 +492,15 @@ def imdecode(buffers, channel_order='bgr', device=None, entropy=None):
     return imgs[0] if single else imgs
 
 
-def imread(paths, channel_order='bgr', device=None, entropy=None):
+def imread(paths, channel_order='bgr', device=None, entropy=None, chunk_bytes=None, max_rounds=None):
     """``paths``: a file name (``str`` / ``os.PathLike``) or a list of them -> what ``imdecode`` returns for their bytes."""
     single = not isinstance(paths, (list, tuple))
     bufs = []
     for p in ([paths] if single else paths):
         with open(os.fspath(p), 'rb') as f:
             bufs.append(f.read())
-    return imdecode(bufs[0] if single else bufs, channel_order=channel_order, device=device, entropy=entropy)
+    return imdecode(bufs[0] if single else bufs, channel_order=channel_order, device=device, entropy=entropy,
+                    chunk_bytes=chunk_bytes, max_rounds=max_rounds)
 
 
 @PIPELINES.register_module()
@@ -350,10 +510,11 @@ class LoadImageFromFile:
     ``ori_shape`` and ``img_fields``.  ``img`` is a (h, w, 3) BGR tensor on the GPU -- ``torch.uint8``, or
     ``torch.float32`` with ``to_float32``.  ``im_decode_backend`` is accepted and ignored: every backend the reference
     offers for JPEG runs libjpeg-turbo's default decode, which is what ``imread`` computes.  EXIF orientation is not
-    applied (the reference's cv2 backend applies it).  ``entropy``: where the Huffman scan is decoded (``imdecode``)."""
+    applied (the reference's cv2 backend applies it).  ``entropy``, ``chunk_bytes``, ``max_rounds``: where and how the
+    Huffman scan is decoded (``imdecode``)."""
 
     def __init__(self, to_float32=False, color_type='color', file_client_args=dict(backend='disk'), im_decode_backend=None,
-                 device=None, entropy=None):
+                 device=None, entropy=None, chunk_bytes=None, max_rounds=None):
         if color_type != 'color':
             raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' only)")
         if dict(file_client_args) != dict(backend='disk'):
@@ -365,13 +526,17 @@ class LoadImageFromFile:
         self.im_decode_backend = im_decode_backend
         self.device = device
         self.entropy = None if entropy is None else _entropy_mode(entropy)
+        self.chunk_bytes = self.max_rounds = None
+        if chunk_bytes is not None or max_rounds is not None:
+            self.chunk_bytes, self.max_rounds = _sync_params(chunk_bytes, max_rounds)
 
     def __call__(self, results):
         if results['img_prefix'] is not None:
             filename = os.path.join(results['img_prefix'], results['img_info']['filename'])
         else:
             filename = results['img_info']['filename']
-        img = imread(filename, device=self.device, entropy=self.entropy)
+        img = imread(filename, device=self.device, entropy=self.entropy, chunk_bytes=self.chunk_bytes,
+                     max_rounds=self.max_rounds)
         if self.to_float32:
             img = img.float()
         results['filename'] = filename

@@ -1,6 +1,7 @@
 """Phases of the hybrid JPEG decode on 32 images of 480x640, 4:2:0, quality 90 (the shape of a COCO file).
 
     python tools/jpeg_bench.py [--images 32] [--repeats 5] [--device-batches 32,256] [--json PATH]
+                               [--entropy device_sync [--chunk-bytes 64,256,1024] [--max-rounds 8]]
 
 Prints, per phase, the median over ``--repeats`` windows (and the spread):
   * host parse + entropy decode per image on one thread and on 16 threads (files/s),
@@ -16,6 +17,11 @@ Prints, per phase, the median over ``--repeats`` windows (and the spread):
     around ``yv4_jpeg_entropy_decode_device`` alone and around it plus ``yv4_jpeg_reconstruct`` on resident buffers, and
     ``imdecode`` end to end with ``entropy='device'`` against ``entropy='host'`` on 16 and on 2 threads (2 is one rank's
     share when eight ranks split 16 CPUs).  ``--json`` writes everything measured to a file.
+  * with ``--entropy device_sync`` on top of that, in the same process and per ``--chunk-bytes`` value: the chunk and
+    workgroup counts, the rounds the batch's chains need to close (from the CPU run of the same core), HIP events around
+    ``yv4_jpeg_entropy_decode_device_sync`` alone at ``--max-rounds`` and at 0 rounds (one pass, the sums and nothing
+    stored: every multi-chunk image is undecided), the images left undecided, and ``imdecode(entropy='device_sync')`` end
+    to end -- next to the one lane per segment kernel and the host paths measured just before.
 The images are made with Pillow; without it the tool says so and exits.  There is no pass mark.  Needs the GPU: a
 measurement path that finds none fails.
 """
@@ -65,6 +71,10 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--device-batches', default='', help='comma-separated batch sizes for the device Huffman decode phases')
     ap.add_argument('--json', default='', help='write the results to this file as well')
+    ap.add_argument('--entropy', default='device', choices=('device', 'device_sync'),
+                    help="device_sync: measure the chunk decode as well, per --chunk-bytes value")
+    ap.add_argument('--chunk-bytes', default='', help='comma-separated chunk sizes (default: the module default)')
+    ap.add_argument('--max-rounds', type=int, default=None, help='synchronisation rounds (default: the module default)')
     args = ap.parse_args()
     try:
         import PIL  # noqa: F401
@@ -213,6 +223,13 @@ def main():
         restart = make_images(min(N, 32), restart_marker_rows=1)
         res['device_entropy'] = [device_phases(kind, src, B, args.repeats, dev)
                                  for kind, src in (('plain', bufs), ('restart_rows_1', restart)) for B in sizes]
+        if args.entropy == 'device_sync':
+            chunk_sizes = [int(c) for c in args.chunk_bytes.split(',')] if args.chunk_bytes else [image_io.DEFAULT_CHUNK_BYTES]
+            rounds_max = image_io.DEFAULT_MAX_ROUNDS if args.max_rounds is None else args.max_rounds
+            res['max_rounds'] = rounds_max
+            for r, (kind, src) in zip(res['device_entropy'], [(k, s) for k, s in (('plain', bufs), ('restart_rows_1', restart))
+                                                              for _ in sizes]):
+                r['device_sync'] = [sync_phases(kind, src, r['batch'], args.repeats, dev, cb, rounds_max) for cb in chunk_sizes]
     print(json.dumps(res))
     if args.json:
         with open(args.json, 'w') as f:
@@ -349,6 +366,87 @@ def device_phases(kind, src, B, repeats, dev):
     a = pkg.imdecode(bufs[:len(src)], device=dev, entropy='device')
     b = pkg.imdecode(bufs[:len(src)], device=dev, entropy='host')
     assert all(torch.equal(x, y) for x, y in zip(a, b)), 'the device path differs from the host path'
+    return r
+
+
+_ROUNDS = {}      # (files, chunk size, count) -> rounds each image's chains need to close
+
+
+def sync_phases(kind, src, B, repeats, dev, chunk_bytes, max_rounds):
+    """The chunk decode (``entropy='device_sync'``) of the first ``B`` files of ``src`` repeated, at one chunk size."""
+    import torch
+    import mmdet_yolov4_amd as pkg
+    from mmdet_yolov4_amd import image_io
+    from mmdet_yolov4_amd._lib import JpegEntry
+    bufs = [src[i % len(src)] for i in range(B)]
+    r = dict(chunk_bytes=chunk_bytes, max_rounds=max_rounds)
+    print(f'--- chunk decode: {kind}, batch of {B}, chunks of {chunk_bytes} bytes, {max_rounds} rounds ---')
+    # rounds to convergence: the CPU run of the same core over the distinct files (a repeated file needs the same)
+    key = (kind, chunk_bytes, min(B, len(src)))
+    if key not in _ROUNDS:
+        _ROUNDS[key] = [image_io.jpeg_entropy_decode_sync([b], chunk_bytes, pkg._lib.JPEG_MAX_ROUNDS)[6] for b in src[:key[2]]]
+    per_image = _ROUNDS[key]
+    r['rounds_to_convergence'] = max(per_image)
+    r['rounds_per_image_median'], r['rounds_per_image_max'] = int(statistics.median(per_image)), max(per_image)
+    t = image_io.ScanTables(bufs)
+    ch = image_io.ChunkTables(t, chunk_bytes)
+    r['chunks'], r['workgroups'] = ch.nchunk, ch.nwg
+    sections = t.sections() + ch.sections()
+    offs, end = image_io._upload_plan(sections)
+    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
+    for (obj, size), off in zip(sections, offs):
+        if obj is not None:
+            C.memmove(stage.data_ptr() + off, obj, size)
+    t.write_bytes(stage.data_ptr() + offs[4])
+    up = stage.to(dev)
+    r['staging_bytes'] = end
+    coef = torch.empty(t.ncoef, dtype=torch.int16, device=dev)
+    flags = torch.empty(2 * B, dtype=torch.int32, device=dev)
+    entries = torch.empty(ch.nchunk * C.sizeof(JpegEntry), dtype=torch.uint8, device=dev)
+    d = [up.data_ptr() + o for o in offs]
+    L = pkg._lib.lib()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    calls = 3
+
+    def kernels(rounds):
+        def window():
+            ev0.record()
+            for _ in range(calls):
+                image_io._launch_sync(L, t, ch, d, B, rounds, entries, coef, t.ncoef, flags[:B], flags[B:])
+            ev1.record()
+            ev1.synchronize()
+            return ev0.elapsed_time(ev1) * 1e-3
+        return window
+
+    for name, rounds in (('kernels', max_rounds), ('kernels_0_rounds', 0)):
+        med, lo, hi = windows(kernels(rounds), repeats)
+        r[name + '_ms'] = round(1e3 * med / calls, 4)
+        r[name + '_spread_ms'] = [round(1e3 * lo / calls, 4), round(1e3 * hi / calls, 4)]
+        print(f'{name:>22}: {1e3 * med / calls:9.4f} ms per batch of {B}   (windows {1e3 * lo / calls:.4f} .. {1e3 * hi / calls:.4f} ms)')
+        if rounds == max_rounds:
+            codes = flags.cpu().numpy()
+            assert not codes[:B].any()
+            r['undecided_images'] = int((codes[B:] != 0).sum())
+            r['undecided_share'] = round(r['undecided_images'] / B, 4)
+    print(f'{"chains":>22}: {ch.nchunk} chunks in {ch.nwg} workgroups; closed after {r["rounds_to_convergence"]} rounds (per image: '
+          f'median {r["rounds_per_image_median"]}, max {r["rounds_per_image_max"]}); {r["undecided_images"]} of {B} images '
+          f'undecided at {max_rounds} rounds')
+
+    def end_to_end():
+        t0 = time.perf_counter()
+        for _ in range(2):
+            pkg.imdecode(bufs, device=dev, entropy='device_sync', chunk_bytes=chunk_bytes, max_rounds=max_rounds)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / 2
+
+    med, lo, hi = windows(end_to_end, repeats)
+    r['imdecode_device_sync_ms'] = round(1e3 * med, 3)
+    r['imdecode_device_sync_files_per_s'] = round(B / med, 1)
+    print(f'{"imdecode_device_sync":>26}: {1e3 * med:9.3f} ms per batch of {B}   ({B / med:.0f} files/s; windows {1e3 * lo:.3f} .. '
+          f'{1e3 * hi:.3f} ms)')
+    a = pkg.imdecode(bufs[:len(src)], device=dev, entropy='device_sync', chunk_bytes=chunk_bytes, max_rounds=max_rounds)
+    b = pkg.imdecode(bufs[:len(src)], device=dev, entropy='host')
+    assert all(torch.equal(x, y) for x, y in zip(a, b)), 'the chunk decode differs from the host path'
     return r
 
 

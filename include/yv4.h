@@ -985,6 +985,49 @@ int yv4_map_accumulate(const uint8_t* tp, const uint8_t* fp, const int32_t* cls_
                        void* work, float* ap, double* last_recall, float* last_precision, double* recall,
                        float* precision, int64_t* num_dets, void* stream);
 
+/* ---- metric='fast-bbox' from the flat result table (csrc/flex_eval.hip; additive within ABI 8) -----------------------
+ * mean_ap_flexible.py's eval_map_flexible with IOU2DCoCo, MatcherCoCo and the 'All' + ScaleBreakdown groups
+ * (datasets/coco.py:464-496), scored from the flat table without a visit to the host.  The definition, restated in
+ * mmdet-yolov4_amd/eval_utils.py:
+ *   Input: dets (D, 5) float32, labels (D) int64, img_index (D) int64; the ground truth class-major with B breakdown
+ *     rows gt_bkd (B, G) (row 0 'All', then one per scale range; an ignored gt is 0 in every row).
+ *   Problems: N images x C classes give P = C * N problems, p = c * N + i, as in yv4_map_rank.  Matching problem
+ *     q = p * B + b shares problem p's IoU block and ignores the gts with gt_bkd[b] == 0.
+ *   Order: yv4_map_rank's two stable orders; equal scores keep the table's order (the list path's ties follow numpy's
+ *     argsort()[::-1]: the one stated difference).
+ *   Per class c, breakdown b, threshold t, over the class's detections in cls_order (a detection sits in problem p at
+ *     local position d): mg_own = matched[q(p, b)][t][d], mg_last = matched[q(p, B-1)][t][d];
+ *     tp = (shared_tp ? mg_last : mg_own) > -1 (shared_tp restates the reference, whose breakdowns share one tp array);
+ *     in = mg_own > -1 ? gt_bkd[b][gt_off[p] + mg_own] : (b == 0 || lo_b <= area < hi_b), area = (x2-x1)*(y2-y1) with
+ *     each float32 operation rounded on its own and the bounds rounded to float32 once on the host.  A problem without
+ *     ground truth matches nothing.
+ *   With k the running count of `in` and ctp the running count of `in & tp` (integers): precision = double(ctp) /
+ *     double(k), recall = double(ctp) / double(num_gt) (/ 1e-7 when num_gt == 0), both over the `in` positions only.
+ *     AP: precision's suffix maximum, then the sum of (recall_m - recall_prev) * envelope_m over the positions where
+ *     recall changes (recall_prev starts at 0), added in rank order into a single float64 accumulator, rounded to
+ *     float32.  (numpy adds pairwise: the definition's one freedom.)
+ *   No float atomics: two runs give identical bytes.  All pointers but `stream` are device pointers.
+ *
+ * yv4_flex_tables: the Q = P * B problem tables yv4_match_coco_batched reads, from yv4_map_rank's det_off / iou_off
+ *   (both P+1): q_det_off[p*B + b] = B * det_off[p] + b * nd[p], q_det_off[Q] = B * det_off[P]; q_iou_off[q] =
+ *   iou_off[p], q_iou_off[Q] = iou_off[P].  Both outputs hold Q+1 int64.  The gt-side tables (q_gt_off and the ignore /
+ *   crowd flags per (problem, breakdown)) are static per dataset and come from the host.
+ * yv4_flex_accumulate: the rule above, one workgroup per (class, breakdown, threshold).
+ *   matched: yv4_match_coco_batched's output for the Q problems (B * total_det * num_thrs int32); det4, cls_order,
+ *     det_off: from yv4_map_rank, total_det = its Dv; gt_off (P+1) int64; gt_bkd (num_bkd, total_gt) bytes;
+ *     num_gt (C, num_bkd) int64; area_bounds (num_bkd - 1, 2) float32 (lo, hi), may be null when num_bkd == 1.
+ *   A class must hold fewer than 2^24 detections (the caller checks yv4_map_rank's info).
+ *   num_det int64, recall float64 (the last recall, 0 when num_det == 0), ap float32: each (C, num_bkd, num_thrs).
+ *   work: yv4_flex_accumulate_work(total_det, num_thrs, num_bkd) bytes, 8-byte aligned.  total_det == 0 is legal and
+ *     gives zeros. */
+int yv4_flex_tables(const int64_t* det_off, const int64_t* iou_off, int P, int B, int64_t* q_det_off,
+                    int64_t* q_iou_off, void* stream);
+size_t yv4_flex_accumulate_work(int64_t total_det, int num_thrs, int num_bkd);
+int yv4_flex_accumulate(const int32_t* matched, const float* det4, const int32_t* cls_order, const int64_t* det_off,
+                        const int64_t* gt_off, const uint8_t* gt_bkd, const int64_t* num_gt, const float* area_bounds,
+                        int64_t total_det, int64_t total_gt, int N, int C, int num_bkd, int num_thrs, int shared_tp,
+                        void* work, int64_t* num_det, double* recall, float* ap, void* stream);
+
 /* ---- the flat result table of a test loop (csrc/results.hip; additive within ABI 8) ------------------------------------
  * yv4_results_append: append one batch's post-processing output to the flat table yv4_coco_rank takes, in the order
  * of the reference's _det2json (mmdet/datasets/coco.py:179-199): image, then class, then the row order NMS left.

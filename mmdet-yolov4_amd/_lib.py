@@ -320,6 +320,10 @@ SIGNATURES = {
     'yv4_map_accumulate_work': (_sz, [_i64, _i, _i]),
     'yv4_map_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp]),
+    'yv4_flex_tables': (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'yv4_flex_accumulate_work': (_sz, [_i64, _i, _i]),
+    'yv4_flex_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp,
+                                      _vp, _vp]),
     'yv4_coco_rank_work': (_sz, [_i64]),
     'yv4_coco_rank': (C.c_int, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'yv4_coco_match': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _i, _vp, _i, _vp, _i64, _vp, _vp,
@@ -366,6 +370,8 @@ LOSS_EX_SYMBOLS = frozenset(('yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'))
 MAP_EVAL_SYMBOLS = frozenset(('yv4_bbox_overlaps_batched', 'yv4_tpfp_work', 'yv4_tpfp_batched'))
 #: the flat-table ends of the VOC-style mAP (additive within ABI 8, bound like FP8_SYMBOLS); has_map_flat()
 MAP_FLAT_SYMBOLS = frozenset(('yv4_map_rank_work', 'yv4_map_rank', 'yv4_map_accumulate_work', 'yv4_map_accumulate'))
+#: metric='fast-bbox' from the flat table (additive within ABI 8, bound like FP8_SYMBOLS); has_flex_flat()
+FLEX_FLAT_SYMBOLS = frozenset(('yv4_flex_tables', 'yv4_flex_accumulate_work', 'yv4_flex_accumulate'))
 #: the COCO bbox evaluation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_coco_eval()
 COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_match', 'yv4_coco_accumulate_work',
                                'yv4_coco_accumulate'))
@@ -425,6 +431,7 @@ def lib():
             if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
                     or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
                     or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
+                    or name in FLEX_FLAT_SYMBOLS
                     or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
@@ -488,6 +495,12 @@ def has_map_flat():
     """The loaded library exports the flat-table mAP entry points (``yv4_map_rank`` / ``yv4_map_accumulate``)."""
     h = lib()
     return all(hasattr(h, n) for n in MAP_FLAT_SYMBOLS)
+
+
+def has_flex_flat():
+    """The loaded library exports the flat-table fast-bbox entry points (``yv4_flex_tables`` / ``yv4_flex_accumulate``)."""
+    h = lib()
+    return has_map_flat() and all(hasattr(h, n) for n in FLEX_FLAT_SYMBOLS)
 
 
 def has_coco_eval():

@@ -12,6 +12,33 @@ problem of the dataset into one table and evaluates it with ONE ``yv4_iou_coco_b
 ``yv4_match_coco_batched`` launch (all breakdowns and thresholds in parallel).  Sorting by score keeps
 numpy's ``argsort()[::-1]`` on the host so that exact score ties order as in the reference.  There is no
 CPU implementation of the two ops in this package.
+
+The flat path.  ``statistics_eval`` / ``eval_map_flexible`` / ``evaluate_fast_bbox`` also take the flat table of a test
+loop in place of the per-image lists, and a ``FlexGt`` in place of ``annotations``; the whole evaluation then runs on the
+device (``flex_flat_device``; csrc/flex_eval.hip with csrc/map_flat.hip's ``yv4_map_rank`` and the two batched ops
+above).  Its definition (stated in include/yv4.h, restated here):
+
+* Input: ``dets (D, 5) float32``, ``labels (D,) int64``, ``img_index (D,) int64``, numpy arrays or GPU tensors; the
+  ground truth as a ``FlexGt``.
+* Problems: N images x C classes give P = C * N problems, class-major (``p = c * N + i``), exactly as in ``map_flat``.
+  B breakdown rows: row 0 is ``'All'``, then one per ``ScaleBreakdown`` range.  Matching problem ``q = p * B + b`` shares
+  problem p's IoU block.
+* Order: ``yv4_map_rank``'s two stable orders.  Score ties keep the table's order -- the one stated difference from the
+  list path, whose ties follow ``argsort()[::-1]``.
+* Per class c, breakdown b, threshold t, over the class's detections in ``cls_order`` (a detection sits in problem p at
+  local position d): ``mg_own = matched[q(p, b)][t][d]``, ``mg_last = matched[q(p, B-1)][t][d]``,
+  ``tp = (mg_last if shared_tp else mg_own) > -1``; ``in = gt_bkd[b][gt_off[p] + mg_own]`` when ``mg_own > -1``, else the
+  detection's own breakdown flag (row 0 always true, row b >= 1 is ``lo <= area < hi`` with
+  ``area = (x2-x1)*(y2-y1)``, each float32 operation rounded on its own, the bounds rounded to float32 once on the
+  host).  A problem with no ground truth matches nothing (the list path's ``ious is None`` branch).
+* With ``k`` the running count of ``in`` and ``ctp`` the running count of ``in & tp`` (integers):
+  ``precision = double(ctp) / double(k)``, ``recall = double(ctp) / double(num_gt)`` (``/ 1e-7`` when ``num_gt == 0``).
+  The AP is taken over the compacted list (the ``in`` positions only): precision's suffix maximum, the sum of
+  ``(recall_m - recall_prev) * envelope_m`` over the positions where recall changes (``recall_prev`` starts at 0), added
+  in rank order into a single float64 accumulator, then rounded to float32.  (``np.sum`` adds pairwise: the definition's
+  one freedom.)
+* Outputs, each ``(C, B, T)``: ``num_det`` int64, the last recall float64 (0 when ``num_det == 0``), ``mAP`` float32.
+  No float atomics: two runs give identical bytes.
 """
 from collections import OrderedDict
 
@@ -20,6 +47,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .coco_eval import _is_flat
 from .ops import stream_ptr
 from .registry import Registry, build_from_cfg
 
@@ -210,6 +238,186 @@ class ScaleBreakdown(NoBreakdown):
         return flags
 
 
+class FlexGt:
+    """The ground-truth side of the flat path, built once per dataset from the ``gt_bboxes`` / ``gt_labels`` /
+    ``gt_attrs`` dicts ``eval_map_flexible`` takes per image (``coco_test_annotation``).  ``scale_ranges``: the
+    ``ScaleBreakdown`` argument, name -> (min_side, max_side) (or a list of such pairs); B = 1 + their number.
+
+    Holds the class-major gts (problem ``c * num_imgs + i``; a gt whose label is outside [0, C) takes no part) as
+    ``gt (G, 4)``, ``gt_off (P + 1)``, ``crowd (G)``; ``gt_bkd (B, G)``: ``NoBreakdown`` / ``ScaleBreakdown.breakdown_flags``
+    with ``ignore`` applied (``attrs['area']`` where given, else the box product); ``num_gt (C, B)``; ``bounds (B - 1, 2)``
+    float32, the squared sides the device compares a detection's area with; and the matching kernel's static tables for
+    the Q = P * B problems ``q = p * B + b``: ``q_gt_off (Q + 1)``, ``q_ignore`` / ``q_crowd (B * G)``.  Device copies are
+    kept per device."""
+
+    def __init__(self, annotations, num_classes, scale_ranges=None):
+        self.annotations = annotations
+        self.num_imgs, self.num_classes = len(annotations), int(num_classes)
+        pairs = list(scale_ranges.items()) if isinstance(scale_ranges, dict) else list(scale_ranges or [])
+        self.names = ['All'] + [str(k) for k, _ in pairs]
+        self.area_ranges = [(lo * lo, hi * hi) for _, (lo, hi) in pairs]
+        N, C, B = self.num_imgs, self.num_classes, len(self.names)
+        if N <= 0 or C <= 0:
+            raise ValueError('FlexGt needs at least one image and one class')
+        if N * C * B >= 2 ** 31 - 1:
+            raise ValueError(f'{N} images x {C} classes x {B} breakdowns: the problem index does not fit 31 bits')
+        self.num_bkd = B
+        self.bounds = np.array(self.area_ranges, dtype=np.float32).reshape(-1, 2)
+        boxes, labels, imgs, crowd, flags = [np.zeros((0, 4), np.float32)], [], [], [], [np.zeros((B, 0), bool)]
+        for i, anno in enumerate(annotations):
+            gtb = np.asarray(anno['gt_bboxes'], dtype=np.float32).reshape(-1, 4)
+            attrs = anno.get('gt_attrs') or {}
+            n = len(gtb)
+            if 'area' in attrs:
+                area = np.asarray(attrs['area'])
+            else:
+                wh = gtb[:, 2:] - gtb[:, :2]
+                area = wh[:, 0] * wh[:, 1]
+            rows = np.ones((B, n), dtype=bool)
+            for b, (lo, hi) in enumerate(self.area_ranges):
+                rows[1 + b] = (area >= lo) & (area < hi)
+            if 'ignore' in attrs:
+                rows[:, np.asarray(attrs['ignore'], dtype=bool)] = False
+            boxes.append(gtb)
+            labels.append(np.asarray(anno['gt_labels'], dtype=np.int64).reshape(-1))
+            imgs.append(np.full(n, i, np.int64))
+            crowd.append(np.asarray(attrs['iscrowd'], dtype=bool) if 'iscrowd' in attrs else np.zeros(n, dtype=bool))
+            flags.append(rows)
+        boxes, flags = np.concatenate(boxes), np.concatenate(flags, axis=1)
+        labels, imgs, crowd = (np.concatenate(x) if x else np.zeros(0, t) for x, t in
+                               ((labels, np.int64), (imgs, np.int64), (crowd, bool)))
+        if not (len(boxes) == len(labels) == len(crowd) == flags.shape[1]):
+            raise ValueError('FlexGt: gt_bboxes, gt_labels and gt_attrs disagree in length')
+        keep = np.flatnonzero((labels >= 0) & (labels < C))
+        prob = labels[keep] * N + imgs[keep]
+        sel = keep[np.argsort(prob, kind='stable')]          # class-major, the image's own gt order inside a problem
+        P = N * C
+        ng = np.bincount(prob, minlength=P).astype(np.int64)
+        self.gt = np.ascontiguousarray(boxes[sel])
+        self.crowd = crowd[sel].astype(np.uint8)
+        self.gt_bkd = np.ascontiguousarray(flags[:, sel]).astype(np.uint8)
+        self.gt_off = _offsets(ng)
+        G = len(sel)
+        cls_of = labels[sel]
+        self.num_gt = np.stack([np.bincount(cls_of[self.gt_bkd[b] != 0], minlength=C) for b in range(B)],
+                               axis=1).astype(np.int64)
+        # the Q-side: problem p's gts once per breakdown, row b of its (B, ng) block at B * gt_off[p] + b * ng[p]
+        self.q_gt_off = (B * np.repeat(self.gt_off[:-1], B) + np.tile(np.arange(B), P) * np.repeat(ng, B))
+        self.q_gt_off = np.append(self.q_gt_off, B * G).astype(np.int64)
+        pg = np.repeat(np.arange(P), ng)
+        idx = (B * self.gt_off[pg] + (np.arange(G) - self.gt_off[pg]))[None, :] + np.arange(B)[:, None] * ng[pg][None, :]
+        self.q_ignore, self.q_crowd = np.zeros(B * G, np.uint8), np.zeros(B * G, np.uint8)
+        self.q_ignore[idx] = self.gt_bkd == 0
+        self.q_crowd[idx] = self.crowd[None, :]
+        self._device = {}
+
+    def same_breakdown(self, names, area_ranges):
+        return list(names) == self.names and [tuple(r) for r in area_ranges] == [tuple(r) for r in self.area_ranges]
+
+    def device(self, dev):
+        d = self._device.setdefault((dev.type, dev.index), {})
+        if not d:
+            pad = lambda a: a if len(a) else np.zeros((1,) + a.shape[1:], a.dtype)      # noqa: E731
+            d.update(gt=_dev(pad(self.gt), np.float32, dev), crowd=_dev(pad(self.crowd), np.uint8, dev),
+                     gt_off=_dev(self.gt_off, np.int64, dev), gt_bkd=_dev(pad(self.gt_bkd.reshape(-1)), np.uint8, dev),
+                     num_gt=_dev(self.num_gt, np.int64, dev), bounds=_dev(pad(self.bounds.reshape(-1)), np.float32, dev),
+                     q_gt_off=_dev(self.q_gt_off, np.int64, dev), q_ignore=_dev(pad(self.q_ignore), np.uint8, dev),
+                     q_crowd=_dev(pad(self.q_crowd), np.uint8, dev))
+        return d
+
+
+def _flat_to_device(flat, dev):
+    dets, labels, img_index = flat
+
+    def put(x, np_dtype, t_dtype):
+        if isinstance(x, torch.Tensor):
+            return x.to(dev, t_dtype).contiguous()
+        return _dev(np.asarray(x), np_dtype, dev)
+    dets = put(dets, np.float32, torch.float32).reshape(-1, 5)
+    labels, img_index = put(labels, np.int64, torch.int64).reshape(-1), put(img_index, np.int64, torch.int64).reshape(-1)
+    if labels.numel() != dets.shape[0] or img_index.numel() != dets.shape[0]:
+        raise ValueError(f'flat results: {dets.shape[0]} detections, {labels.numel()} labels, {img_index.numel()} image indices')
+    return dets, labels, img_index
+
+
+def flex_flat_device(flat, gt, iou_thrs, shared_tp=True, phases=None):
+    """The flat path of the module docstring on the device: ``yv4_map_rank``, one read-back (the pair total and the class
+    counts), ``yv4_iou_coco_batched``, ``yv4_flex_tables``, ``yv4_match_coco_batched`` over the Q = P * B problems,
+    ``yv4_flex_accumulate``, one download.  ``flat``: numpy arrays or GPU tensors (those never visit the host); ``gt``: a
+    ``FlexGt``.  Returns host arrays shaped (C, B, T): ``num_det`` int64, ``recall`` float64, ``mAP`` float32.
+    ``phases``: an optional dict that receives seconds per phase (each closed by a synchronise)."""
+    import time
+    dev = _device()
+    if not _lib.has_flex_flat():
+        raise RuntimeError('the loaded libyv4_hip.so has no yv4_flex_tables / yv4_flex_accumulate; rebuild it')
+
+    def tick():
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    marks = [tick()] if phases is not None else None
+    thrs = np.ascontiguousarray(iou_thrs, dtype=np.float32).reshape(-1)
+    N, C, B, T = gt.num_imgs, gt.num_classes, gt.num_bkd, len(thrs)
+    if T == 0:
+        raise ValueError('flat results need at least one IoU threshold')
+    P, G = N * C, len(gt.gt)
+    g = gt.device(dev)
+    dets, labels, img_index = _flat_to_device(flat, dev)
+    D = int(dets.shape[0])
+    t_thr = _dev(thrs, np.float32, dev)
+    if phases is not None:
+        marks.append(tick())
+    lib = _lib.lib()
+    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()     # noqa: E731
+    i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)            # noqa: E731
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)            # noqa: E731
+    det4 = torch.empty((max(D, 1), 4), dtype=torch.float32, device=dev)
+    det_off, iou_off, info = i64(P + 1), i64(P + 1), i64(C + 2)
+    order, rank, cls_order = i32(max(D, 1)), i32(max(D, 1)), i32(max(D, 1))
+    work = torch.empty(max(int(lib.yv4_map_rank_work(D)), 8), dtype=torch.uint8, device=dev)
+    check(lib.yv4_map_rank(ptr(dets), ptr(labels), ptr(img_index), D, N, C, g['gt_off'].data_ptr(), work.data_ptr(),
+                           det4.data_ptr(), det_off.data_ptr(), order.data_ptr(), rank.data_ptr(), iou_off.data_ptr(),
+                           cls_order.data_ptr(), info.data_ptr(), stream_ptr()), 'yv4_map_rank')
+    info_h = info.cpu().numpy()                                 # the one read-back between the device calls
+    pairs, Dv, counts = int(info_h[0]), int(info_h[1]), info_h[2:]
+    if phases is not None:
+        marks.append(tick())
+    for c in np.flatnonzero(counts >= 2 ** 24):
+        raise ValueError(f'class {c} has {counts[c]} detections: the cumulative counts are kept exact only below 2**24')
+    iou = torch.empty(max(pairs, 1), dtype=torch.float32, device=dev)
+    if pairs:
+        check(lib.yv4_iou_coco_batched(det4.data_ptr(), g['gt'].data_ptr(), g['crowd'].data_ptr(), det_off.data_ptr(),
+                                       g['gt_off'].data_ptr(), iou_off.data_ptr(), P, pairs, iou.data_ptr(), stream_ptr()),
+              'yv4_iou_coco_batched')
+    matched = i32(max(B * Dv * T, 1))
+    if Dv:
+        Q = P * B
+        q_det_off, q_iou_off = i64(Q + 1), i64(Q + 1)
+        check(lib.yv4_flex_tables(det_off.data_ptr(), iou_off.data_ptr(), P, B, q_det_off.data_ptr(), q_iou_off.data_ptr(),
+                                  stream_ptr()), 'yv4_flex_tables')
+        work = torch.empty(max(B * G * T, 1), dtype=torch.uint8, device=dev)
+        check(lib.yv4_match_coco_batched(iou.data_ptr(), q_det_off.data_ptr(), g['q_gt_off'].data_ptr(), q_iou_off.data_ptr(),
+                                         t_thr.data_ptr(), T, g['q_ignore'].data_ptr(), g['q_crowd'].data_ptr(), Q,
+                                         work.data_ptr(), matched.data_ptr(), stream_ptr()), 'yv4_match_coco_batched')
+    if phases is not None:
+        marks.append(tick())
+    num_det = torch.empty((C, B, T), dtype=torch.int64, device=dev)
+    recall = torch.empty((C, B, T), dtype=torch.float64, device=dev)
+    ap = torch.empty((C, B, T), dtype=torch.float32, device=dev)
+    work = torch.empty(max(int(lib.yv4_flex_accumulate_work(Dv, T, B)), 8), dtype=torch.uint8, device=dev)
+    check(lib.yv4_flex_accumulate(matched.data_ptr(), det4.data_ptr(), cls_order.data_ptr(), det_off.data_ptr(),
+                                  g['gt_off'].data_ptr(), g['gt_bkd'].data_ptr(), g['num_gt'].data_ptr(),
+                                  g['bounds'].data_ptr(), Dv, G, N, C, B, T, 1 if shared_tp else 0, work.data_ptr(),
+                                  num_det.data_ptr(), recall.data_ptr(), ap.data_ptr(), stream_ptr()), 'yv4_flex_accumulate')
+    if phases is not None:
+        marks.append(tick())
+    out = dict(num_det=num_det.cpu().numpy(), recall=recall.cpu().numpy(), mAP=ap.cpu().numpy(), num_gt=gt.num_gt,
+               total_det=Dv, pairs=pairs)
+    if phases is not None:
+        marks.append(tick())
+        phases.update({k: b - a for k, a, b in zip(('upload', 'rank', 'match', 'accumulate', 'download'), marks, marks[1:])})
+    return out
+
+
 class FlexibleStatisticsEval(object):
     """mean_ap_flexible.py:99-276.  ``nproc`` is accepted and ignored: the per-problem work the reference
     spreads over a process pool is one batched GPU launch here.  A custom ``iou_calculator`` / ``matcher``
@@ -218,10 +426,15 @@ class FlexibleStatisticsEval(object):
     ``shared_tp`` (default True = the reference's behaviour): statistics_single fills one ``cls_tp`` array
     in place per breakdown (:172,191-192) and appends that same object every time (:199-202), so all
     breakdowns of an (image, class) problem carry the true-positive flags of the LAST breakdown's matching.
-    ``shared_tp=False`` gives every breakdown the flags of its own matching."""
+    ``shared_tp=False`` gives every breakdown the flags of its own matching.
+
+    ``statistics_eval`` also takes the flat table ``(dets (D, 5), labels (D,), img_index (D,))`` in place of the
+    per-image lists and a ``FlexGt`` in place of ``annotations``: the module docstring's flat path, which knows exactly
+    ``IOU2DCoCo``, ``MatcherCoCo`` and ``ScaleBreakdown`` entries with ``apply_to=None``."""
 
     def __init__(self, classes, iou_thrs, breakdown, iou_calculator, matcher, nproc, shared_tp=True):
         self.shared_tp = shared_tp
+        self._breakdown_cfg = list(breakdown)
         self.classes = classes
         self.iou_thrs = iou_thrs
         self.breakdown = [NoBreakdown(classes)]
@@ -292,8 +505,70 @@ class FlexibleStatisticsEval(object):
                     np.empty((0, len(thrs), len(boxes)), np.int32)
         return out
 
+    # ---- the flat path ----------------------------------------------------------------------------------------------
+    def _flat_breakdown(self):
+        """(names, area_ranges) of the breakdown rows when the flat path knows this configuration."""
+        if type(self.iou_calculator) is not IOU2DCoCo:
+            raise NotImplementedError(f'flat results are scored on the device, which knows IOU2DCoCo only; for the '
+                                      f'iou_calculator {type(self.iou_calculator).__name__} pass the per-image lists')
+        if type(self.matcher) is not MatcherCoCo:
+            raise NotImplementedError(f'flat results are scored on the device, which knows MatcherCoCo only; for the '
+                                      f'matcher {type(self.matcher).__name__} pass the per-image lists')
+        names, ranges = ['All'], []
+        for cfg, f in zip(self._breakdown_cfg, self.breakdown[1:]):
+            if type(f) is not ScaleBreakdown:
+                raise NotImplementedError(f'flat results are scored on the device, which knows ScaleBreakdown only; for '
+                                          f'the breakdown {type(f).__name__} pass the per-image lists')
+            if cfg.get('apply_to') is not None:
+                raise NotImplementedError(f'flat results are scored on the device, which knows ScaleBreakdown with '
+                                          f'apply_to=None only; for apply_to={cfg["apply_to"]!r} pass the per-image lists')
+            names += [str(n) for n in f.names]
+            ranges += list(f.area_ranges)
+        return names, ranges
+
+    def _flat_gt(self, annotations):
+        """The ``FlexGt`` the flat path scores against: the one given (checked against this configuration) or one built
+        from the per-image dicts."""
+        names, ranges = self._flat_breakdown()
+        if isinstance(annotations, FlexGt):
+            gt = annotations
+            if not gt.same_breakdown(names, ranges):
+                raise ValueError(f'the FlexGt was built for the breakdowns {gt.names} with areas {gt.area_ranges}, the '
+                                 f'evaluation asks for {names} with {ranges}')
+        else:
+            if self.classes is None:
+                raise ValueError('flat results carry no class count: pass a FlexGt or the class names')
+            _device()                                           # refuse before the tables are built
+            gt = FlexGt(annotations, len(self.classes),
+                        [kv for cfg in self._breakdown_cfg for kv in cfg['scale_ranges'].items()])
+        if self.classes is not None and len(self.classes) != gt.num_classes:
+            raise ValueError(f'{len(self.classes)} class names, the FlexGt holds {gt.num_classes} classes')
+        return gt
+
+    def _flat_list(self, out, gt):
+        """``flex_flat_device``'s tables as the list path's (key, value) pairs: class, breakdown, threshold."""
+        results = []
+        for c in range(gt.num_classes):
+            cls_name = self.classes[c] if self.classes is not None else c
+            for b, bkd in enumerate(gt.names):
+                num_gt = int(gt.num_gt[c, b])
+                for t, iou_thr in enumerate(self.iou_thrs):
+                    results.append((dict(class_name=cls_name, breakdown=bkd, iou_threshold=iou_thr),
+                                    dict(num_det=int(out['num_det'][c, b, t]), num_gt=num_gt,
+                                         recall=out['recall'][c, b, t], mAP=out['mAP'][c, b, t])))
+        return results
+
+    def _flat_eval(self, flat, annotations):
+        gt = self._flat_gt(annotations)
+        return self._flat_list(flex_flat_device(flat, gt, self.iou_thrs, self.shared_tp), gt)
+
     def statistics_eval(self, det_results, annotations):
-        """mean_ap_flexible.py:119-208 (per problem) and :225-260 (accumulate over the dataset)."""
+        """mean_ap_flexible.py:119-208 (per problem) and :225-260 (accumulate over the dataset); the flat tuple goes to
+        the device whole."""
+        if _is_flat(det_results):
+            return self._flat_eval(det_results, annotations)
+        if isinstance(annotations, FlexGt):
+            annotations = annotations.annotations
         nt = len(self.iou_thrs)
         probs = self._problems(det_results, annotations)
         batched = type(self.iou_calculator) is IOU2DCoCo and type(self.matcher) is MatcherCoCo
@@ -345,8 +620,10 @@ class FlexibleStatisticsEval(object):
 def eval_map_flexible(det_results, annotations, iou_thrs=[0.5], breakdown=[], iou_calculator=dict(type='IOU2DCoCo'),
                       matcher=dict(type='MatcherCoCo'), classes=None, logger=None,
                       report_config=[('map', lambda x: x['breakdown'] == 'All')], nproc=None):
-    """mean_ap_flexible.py:279-302."""
-    assert len(det_results) == len(annotations)
+    """mean_ap_flexible.py:279-302.  ``det_results`` may be the flat tuple and ``annotations`` a ``FlexGt`` (the module
+    docstring's flat path)."""
+    if not _is_flat(det_results):
+        assert len(det_results) == len(annotations.annotations if isinstance(annotations, FlexGt) else annotations)
     fse = FlexibleStatisticsEval(classes, iou_thrs, breakdown, iou_calculator, matcher, nproc or 0)
     return fse.report(fse.statistics_eval(det_results, annotations), report_config)
 
@@ -370,12 +647,18 @@ def coco_test_annotation(ann_info, cat_ids, cat2label):
                               area=np.array(area, dtype=np.float32)))
 
 
+#: the three object scales of ``metric='fast-bbox'`` (datasets/coco.py:476-479)
+FAST_BBOX_SCALE_RANGES = OrderedDict(Scale_S=(0, 32), Scale_M=(32, 96), Scale_L=(96, 10000))
+
+
 def evaluate_fast_bbox(results, annotations, classes, logger=None):
     """``dataset.evaluate(results, metric='fast-bbox')`` (datasets/coco.py:464-496): the ten COCO IoU thresholds, the
-    three object-scale breakdowns, and the six-number report ``map, map50, map75, s_map, m_map, l_map``."""
+    three object-scale breakdowns, and the six-number report ``map, map50, map75, s_map, m_map, l_map``.  ``results``: the
+    per-image lists or the flat tuple; ``annotations``: the per-image dicts or a ``FlexGt`` built with
+    ``FAST_BBOX_SCALE_RANGES``."""
     return eval_map_flexible(
         results, annotations, iou_thrs=[0.5 + 0.05 * x for x in range(10)],
-        breakdown=[dict(type='ScaleBreakdown', scale_ranges=dict(Scale_S=(0, 32), Scale_M=(32, 96), Scale_L=(96, 10000)))],
+        breakdown=[dict(type='ScaleBreakdown', scale_ranges=dict(FAST_BBOX_SCALE_RANGES))],
         report_config=[('map', lambda x: x['breakdown'] == 'All'),
                        ('map50', lambda x: x['iou_threshold'] == 0.5 and x['breakdown'] == 'All'),
                        ('map75', lambda x: x['iou_threshold'] == 0.75 and x['breakdown'] == 'All'),

@@ -14,6 +14,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .coco_eval import CocoGt, evaluate_bbox, flatten_results
+from .eval_utils import FAST_BBOX_SCALE_RANGES, FlexGt, coco_test_annotation, evaluate_fast_bbox
 from .map_eval import MapGt, evaluate_map
 from .ops import stream_ptr
 
@@ -131,13 +132,37 @@ class CocoBBoxDataset:
         self.CLASSES = tuple(classes) if classes is not None else tuple(c['name'] for c in self.coco.cats.values())
         self.cat_ids = self.coco.get_cat_ids(cat_names=self.CLASSES)
         self.img_ids = self.coco.get_img_ids()
+        self._flex_gt = None
 
     def __len__(self):
         return len(self.img_ids)
 
+    def flex_gt(self):
+        """The ground truth of ``metric='fast-bbox'``: per image of ``img_ids`` what ``CocoDataset.get_ann_info_test``
+        returns (``coco_test_annotation``; a box of an unlisted category keeps label -1, which no class owns), as one
+        ``FlexGt`` with the metric's three scale ranges.  Built on first use and kept."""
+        if self._flex_gt is None:
+            per_img = {i: [] for i in self.img_ids}
+            for ann in self.coco.dataset.get('annotations', []):
+                if ann['image_id'] in per_img:
+                    per_img[ann['image_id']].append(ann)
+            cat2label = {c['id']: -1 for c in self.coco.cats.values()}
+            cat2label.update({cat_id: i for i, cat_id in enumerate(self.cat_ids)})
+            annotations = [coco_test_annotation(per_img[i], self.cat_ids, cat2label) for i in self.img_ids]
+            self._flex_gt = FlexGt(annotations, len(self.CLASSES), FAST_BBOX_SCALE_RANGES)
+        return self._flex_gt
+
     def evaluate(self, results, metric='bbox', logger=None, **kwargs):
-        """``CocoDataset.evaluate`` for ``metric='bbox'`` (``datasets/coco.py:451-643``) through ``evaluate_bbox``;
+        """``CocoDataset.evaluate`` (``datasets/coco.py:451-643``): ``metric='bbox'`` through ``evaluate_bbox``,
+        ``metric='fast-bbox'`` (alone, as in the reference) through ``evaluate_fast_bbox`` against ``flex_gt()``;
         ``results``: the per-image lists or the flat tuple, ``img_index`` being positions in ``img_ids``."""
+        metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
+        if 'fast-bbox' in metrics:
+            assert len(metrics) == 1, 'fast-bbox evaluation can only be used alone!'
+            if kwargs:                # (the reference ignores them: its thresholds, ranges and report are fixed)
+                raise TypeError(f"metric='fast-bbox' takes no further arguments (its thresholds, scale ranges and report "
+                                f'are fixed), got {sorted(kwargs)}')
+            return evaluate_fast_bbox(results, self.flex_gt(), self.CLASSES, logger=logger)
         return evaluate_bbox(results, self.coco, cat_ids=self.cat_ids, img_ids=self.img_ids, logger=logger, metric=metric,
                              **kwargs)
 

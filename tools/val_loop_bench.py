@@ -10,6 +10,8 @@ clock around work that ends in a device synchronise: the loop, the scoring, and 
 the passes.  The two forms must give the same metrics, or the tool fails.  ``--metric mAP`` scores with a
 ``CustomBBoxDataset`` (``evaluate_map``) over the same ground truth instead; its two forms order equal scores differently
 (map_eval.py), and 16-bit scores tie, so there the tool reports whether the metrics agree instead of failing.
+``--metric fast-bbox`` scores with ``CocoBBoxDataset.evaluate(metric='fast-bbox')`` (``evaluate_fast_bbox``; its ``FlexGt`` is
+built once, before the passes); the same holds for its ties, and the largest difference of the six report numbers is given.
 Prints ONE JSON line."""
 import argparse
 import json
@@ -53,7 +55,7 @@ def main():
     ap.add_argument('--passes', type=int, default=7)
     ap.add_argument('--candidates', type=float, default=2000.0)
     ap.add_argument('--dtype', choices=('fp16', 'bf16'), default='fp16')
-    ap.add_argument('--metric', choices=('bbox', 'mAP'), default='bbox')
+    ap.add_argument('--metric', choices=('bbox', 'mAP', 'fast-bbox'), default='bbox')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('val_loop_bench measures on the GPU; none is visible')
@@ -81,13 +83,24 @@ def main():
                               bboxes_ignore=xyxy[mine & crowd], labels_ignore=gt.ann_cat[mine & crowd] - 1))
         ds = pkg.CustomBBoxDataset(annos, [str(c) for c in range(80)])
 
+    if a.metric == 'fast-bbox':
+        ds = pkg.CocoBBoxDataset(gt)
+        ds.flex_gt()
+
+    def score(res):
+        if a.metric == 'mAP':
+            return ds.evaluate(res, logger='silent')
+        if a.metric == 'fast-bbox':
+            return {k: float(v) for k, v in ds.evaluate(res, metric='fast-bbox', logger='silent').items()}
+        return pkg.evaluate_bbox(res, gt, logger='silent')
+
     def run(flat):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         res = pkg.single_gpu_test(det, loader, flat=flat)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        out = ds.evaluate(res, logger='silent') if a.metric == 'mAP' else pkg.evaluate_bbox(res, gt, logger='silent')
+        out = score(res)
         torch.cuda.synchronize()
         t2 = time.perf_counter()
         rows = int(res[0].shape[0]) if flat else int(sum(len(c) for r in res for c in r))
@@ -107,6 +120,9 @@ def main():
                 metrics_equal=warm['list'][1] == warm['flat'][1])
     if a.metric == 'mAP':
         line['list_mAP'] = warm['list'][1].get('mAP')
+    if a.metric == 'fast-bbox':
+        line['report'] = dict(list=warm['list'][1], flat=warm['flat'][1])
+        line['max_abs_diff'] = max(abs(warm['list'][1][k] - warm['flat'][1][k]) for k in warm['flat'][1])
     for name, _ in forms:
         t = np.asarray(rec[name])
         line[name] = dict(loop=stats(t[:, 0]), scoring=stats(t[:, 1]), total=stats(t[:, 2]))

@@ -1236,7 +1236,8 @@ int yv4_v3_augment_u8(const yv4_v3aug_image* imgs, int N, float* out_nchw, int H
  * libjpeg's "islow" integer IDCT, the fancy chroma upsampling and the integer YCbCr conversion, and writes interleaved
  * 8-bit pixels (yv4_jpeg_reconstruct, a whole batch of images of different sizes and samplings in one call).  The
  * arithmetic is libjpeg-turbo's default decode (JDCT_ISLOW, do_fancy_upsampling), so the pixels equal what cv2.imdecode,
- * turbojpeg and Pillow return, bit for bit.  EXIF orientation is not applied.
+ * turbojpeg and Pillow return, bit for bit.  EXIF orientation is read by the parse (yv4_jpeg_info.orientation) and
+ * applied by the pixel stage only where the caller asks for it (yv4_jpeg_layout_oriented); yv4_jpeg_layout never does.
  *
  * Accepted: 8-bit SOF0 / SOF1 Huffman files with one interleaved scan; 1 component, or 3 components (YCbCr) with luma
  * sampling 1x1, 2x1 or 2x2 and chroma 1x1 (4:4:4, 4:2:2, 4:2:0); 8-bit quantisation tables.  Progressive, arithmetic,
@@ -1253,6 +1254,9 @@ int yv4_v3_augment_u8(const yv4_v3aug_image* imgs, int N, float* out_nchw, int H
  *   mcus_x, mcus_y          MCU grid; an MCU is (8 * hs[0]) x (8 * vs[0]) pixels
  *   blocks_w, blocks_h      8x8 blocks per component on the MCU-padded grid
  *   ncoef                   coefficients of the image: 64 * sum(blocks_w * blocks_h)
+ *   orientation             EXIF tag 0x0112 of the first APP1 segment that begins "Exif\0\0": 1 .. 8 when IFD0 holds it as
+ *                           one SHORT, 0 otherwise (no such segment, a short or inconsistent one, an offset outside it,
+ *                           another type, count or value) -- never an error
  *   scan_offset             byte offset of the entropy-coded data
  *   quant                   the four quantisation tables in natural (row-major) order; zero where not defined
  * Coefficient layout: int16, natural order, 64 per block; each component is its own plane of blocks, block-row-major
@@ -1264,7 +1268,7 @@ typedef struct yv4_jpeg_info {
   int32_t restart_interval;
   int32_t mcus_x, mcus_y;
   int32_t blocks_w[3], blocks_h[3];
-  int32_t reserved;
+  int32_t orientation;
   int64_t ncoef;
   int64_t scan_offset;
   uint16_t quant[4][64];
@@ -1286,8 +1290,16 @@ int yv4_jpeg_entropy_decode(const uint8_t* data, size_t len, yv4_jpeg_info* info
  *                           workspace (% 8 == 0)
  *   out_off, out_pitch      byte offset of the image's first pixel in the output buffer and its row pitch (>= 3 * width)
  *   unit_base, tile_base    work units of the images before this one: ceil(blocks / 32) IDCT units and
- *                           ceil(width / 256) * ceil(height / 4) pixel tiles per image
- *   width .. blocks_h       as in yv4_jpeg_info */
+ *                           ceil(width / 256) * ceil(height / 4) pixel tiles per image (none for an image with
+ *                           orientation 2 .. 8: those are written by a launch of their own)
+ *   width .. blocks_h       as in yv4_jpeg_info: the DECODED picture D, height x width
+ *   orientation             the EXIF orientation to apply, 0 or 1: none.  The output O is width x height for 2 .. 4 and
+ *                           height x width (height pixels a row, width rows) for 5 .. 8, and out_pitch counts against O's
+ *                           row.  With h = height, w = width:
+ *                             2  O[y,x] = D[y, w-1-x]        5  O[y,x] = D[x, y]
+ *                             3  O[y,x] = D[h-1-y, w-1-x]    6  O[y,x] = D[h-1-x, y]
+ *                             4  O[y,x] = D[h-1-y, x]        7  O[y,x] = D[h-1-x, w-1-y]
+ *                                                            8  O[y,x] = D[x, w-1-y] */
 typedef struct yv4_jpeg_image {
   int64_t coef_off;
   int64_t plane_off[3];
@@ -1298,7 +1310,7 @@ typedef struct yv4_jpeg_image {
   int32_t hs, vs;
   int32_t tq[3];
   int32_t blocks_w[3], blocks_h[3];
-  int32_t reserved;
+  int32_t orientation;
 } yv4_jpeg_image;
 
 /* Host only: the dense table of N parsed images -- coefficients back to back, planes 256-byte aligned in the
@@ -1306,7 +1318,12 @@ typedef struct yv4_jpeg_image {
  * bytes, output bytes of the batch. */
 int yv4_jpeg_layout(const yv4_jpeg_info* infos, int N, yv4_jpeg_image* table, int64_t* totals);
 
-/* Coefficients -> pixels for N images in two launches on `stream`.  table: the HOST table, validated here against
+/* yv4_jpeg_layout with EXIF orientation: where apply != 0, image n's yv4_jpeg_info.orientation goes into the table and
+ * its output is laid out as the oriented picture (pitch 3 * height for 5 .. 8).  apply == 0 is yv4_jpeg_layout. */
+int yv4_jpeg_layout_oriented(const yv4_jpeg_info* infos, int N, int apply, yv4_jpeg_image* table, int64_t* totals);
+
+/* Coefficients -> pixels for N images in two launches on `stream`, and one more for every image whose orientation is
+ * 2 .. 8 (32 x 32 pixel tiles turned through LDS).  table: the HOST table, validated here against
  * coef_elems / work_bytes / out_bytes (YV4_E_INVALID before any launch); table_dev: the same N entries in DEVICE memory,
  * which the kernels trust.  coef (N images' int16 coefficients), quant ((N, 4, 64) uint16, image n's yv4_jpeg_info.quant),
  * work and out are DEVICE memory; coef and quant 16-byte, work 8-byte aligned.  Pixels are interleaved (h, w, 3): B, G, R

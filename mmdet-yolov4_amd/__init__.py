@@ -6,7 +6,7 @@ Importing the package registers ``DarknetCSP``, ``YOLOV4Neck``/``YOLOV5Neck``,
 come from ``lib/libyv4_hip.so`` (C-ABI: ``include/yv4.h``); there is no CPU fallback.
 """
 from . import _lib
-from .registry import (ACTIVATION_LAYERS, ANCHOR_GENERATORS, BACKBONES, BBOX_CODERS, DETECTORS, HEADS, LOSSES,
+from .registry import (ACTIVATION_LAYERS, ANCHOR_GENERATORS, BACKBONES, BBOX_CODERS, DATASETS, DETECTORS, HEADS, LOSSES,
                        MODELS, NECKS, PIPELINES, Config, ConfigDict, Registry, build_anchor_generator, build_backbone,
                        build_bbox_coder, build_detector, build_from_cfg, build_head, build_neck)
 from .bricks import Mish, build_activation_layer, build_norm_layer, wrap_fp16_model
@@ -33,5 +33,7 @@ from .map_eval import (MapGt, bbox_overlaps, eval_map, evaluate_map, print_map_s
                        tpfp_imagenet)
 from .coco_eval import COCOeval, CocoGt, evaluate_bbox, flatten_results  # noqa: F401
 from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: F401
+from .datasets import (CocoDataset, DistributedGroupSampler, GroupSampler, TrainLoader, build_dataset,  # noqa: F401
+                       build_train_loader)
 
 __all__ = [n for n in dir() if not n.startswith('_')]

@@ -152,7 +152,7 @@ class JpegInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('width', 'height', 'ncomp')] + \
                [(n, C.c_int32 * 3) for n in ('hs', 'vs', 'tq', 'td', 'ta')] + \
                [(n, C.c_int32) for n in ('restart_interval', 'mcus_x', 'mcus_y')] + \
-               [('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('reserved', C.c_int32),
+               [('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('orientation', C.c_int32),
                 ('ncoef', C.c_int64), ('scan_offset', C.c_int64), ('quant', (C.c_uint16 * 64) * 4)]
 
 
@@ -161,7 +161,7 @@ class JpegImage(C.Structure):
     _fields_ = [('coef_off', C.c_int64), ('plane_off', C.c_int64 * 3), ('out_off', C.c_int64),
                 ('unit_base', C.c_int64), ('tile_base', C.c_int64)] + \
                [(n, C.c_int32) for n in ('out_pitch', 'width', 'height', 'ncomp', 'hs', 'vs')] + \
-               [('tq', C.c_int32 * 3), ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('reserved', C.c_int32)]
+               [('tq', C.c_int32 * 3), ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('orientation', C.c_int32)]
 
 
 class JpegHuff(C.Structure):
@@ -335,6 +335,7 @@ SIGNATURES = {
     'yv4_jpeg_parse': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo)]),
     'yv4_jpeg_entropy_decode': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo), _vp, _i64]),
     'yv4_jpeg_layout': (C.c_int, [C.POINTER(JpegInfo), _i, C.POINTER(JpegImage), C.POINTER(C.c_int64)]),
+    'yv4_jpeg_layout_oriented': (C.c_int, [C.POINTER(JpegInfo), _i, _i, C.POINTER(JpegImage), C.POINTER(C.c_int64)]),
     'yv4_jpeg_reconstruct': (C.c_int, [C.POINTER(JpegImage), _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
     'yv4_jpeg_scan_prepare': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo), _vp, _vp, _vp, _i64]),
     'yv4_jpeg_entropy_workgroups': (C.c_int, [_vp, _i, _vp, _i64, C.POINTER(C.c_int64)]),
@@ -379,6 +380,8 @@ COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_
 RESULTS_SYMBOLS = frozenset(('yv4_results_append',))
 #: the baseline JPEG decoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg()
 JPEG_SYMBOLS = frozenset(('yv4_jpeg_parse', 'yv4_jpeg_entropy_decode', 'yv4_jpeg_layout', 'yv4_jpeg_reconstruct'))
+#: EXIF orientation in the JPEG decoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_orientation()
+JPEG_ORIENT_SYMBOLS = frozenset(('yv4_jpeg_layout_oriented',))
 #: the Huffman scan decode on the device (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_entropy()
 JPEG_ENTROPY_SYMBOLS = frozenset(('yv4_jpeg_scan_prepare', 'yv4_jpeg_entropy_workgroups', 'yv4_jpeg_entropy_decode_segments',
                                   'yv4_jpeg_entropy_decode_device', 'yv4_jpeg_entropy_strerror'))
@@ -432,7 +435,8 @@ def lib():
                     or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
                     or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
                     or name in FLEX_FLAT_SYMBOLS
-                    or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS) \
+                    or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS
+                    or name in JPEG_ORIENT_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -519,6 +523,13 @@ def has_jpeg():
     """The loaded library exports the baseline JPEG decoder (``yv4_jpeg_parse`` .. ``yv4_jpeg_reconstruct``)."""
     h = lib()
     return all(hasattr(h, n) for n in JPEG_SYMBOLS)
+
+
+def has_jpeg_orientation():
+    """The loaded library exports ``yv4_jpeg_layout_oriented``: its parse reads the EXIF orientation and its pixel stage
+    applies it."""
+    h = lib()
+    return all(hasattr(h, n) for n in JPEG_ORIENT_SYMBOLS)
 
 
 def has_jpeg_entropy():

@@ -21,6 +21,12 @@
 // filters need (4 of each component in 4:2:2, 8 in 4:2:0) and writes 12 bytes as three words where the address allows,
 // byte by byte otherwise (a row's tail, a pitch that breaks the alignment).
 // A workgroup finds its image by binary search over the table's unit_base / tile_base prefix sums.
+// orient_kernel: an image whose EXIF orientation (2 .. 8) is applied has no tile in pixel_kernel and a launch of its
+// own: a 32 x 32 pixel tile of the decoded picture is computed as above (a quad per thread, contiguous reads of the
+// planes) into LDS, one word a pixel, and read back so that consecutive lanes write consecutive pixels of an OUTPUT row
+// -- for 5 .. 8 that is a column of the tile; at a row pitch of 33 words the 32 lanes of a half-wave read 32 distinct
+// banks (ds_read_b32: bank = word % 32 within a half-wave), and so do the quad writes.  A batch without such an image
+// launches the two kernels above and nothing else.
 #include "yv4_common.h"
 
 namespace yv4 {
@@ -213,6 +219,102 @@ __global__ __launch_bounds__(256) void jpeg_pixel_kernel(const yv4_jpeg_image* _
   }
 }
 
+// The four pixels x0 .. x0 + 3 (x0 % 4 == 0, x0 < width) of row y of image g -> px, three output bytes each: the arithmetic
+// of jpeg_pixel_kernel, for jpeg_orient_kernel.  It is a second copy on purpose: as a function the compiler schedules it
+// differently, and the kernel every untagged decode runs keeps the machine code it was measured with.
+__device__ __forceinline__ void pixel_quad(const yv4_jpeg_image& g, const uint8_t* __restrict__ work, int x0, int y,
+                                           int rgb, unsigned (&px)[4]) {
+  // planes are 8-byte aligned with a pitch that is a multiple of 8, and x0 one of 4: the word may reach past the image's
+  // width, never past the plane's row
+  const unsigned yw = *reinterpret_cast<const unsigned*>(work + g.plane_off[0] + (int64_t)y * (g.blocks_w[0] * 8) + x0);
+  if (g.ncomp == 1) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) px[k] = ((yw >> (8 * k)) & 255u) * 0x010101u;
+  } else {
+    const int cw = (g.width + g.hs - 1) / g.hs, ch = (g.height + g.vs - 1) / g.vs;      // real chroma samples
+    const int pitch = g.blocks_w[1] * 8;
+    int c4[2][4];                                                                        // Cb, Cr of the four pixels
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const uint8_t* p = work + g.plane_off[1 + c];
+      if (g.hs == 1) {
+        const unsigned w4 = *reinterpret_cast<const unsigned*>(p + (int64_t)y * pitch + x0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c4[c][k] = (int)((w4 >> (8 * k)) & 255u);
+      } else {
+        // the pixels x0 .. x0 + 3 lie over the samples cx0, cx0 + 1 and filter with cx0 - 1 .. cx0 + 2, edges replicated
+        const int cx0 = x0 >> 1;
+        int col[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) col[k] = min(max(cx0 - 1 + k, 0), cw - 1);
+        if (g.vs == 1) {
+          const uint8_t* r = p + (int64_t)y * pitch;
+          const int s0 = r[col[0]], s1 = r[col[1]], s2 = r[col[2]], s3 = r[col[3]];
+          c4[c][0] = (3 * s1 + s0 + 1) >> 2;
+          c4[c][1] = (3 * s1 + s2 + 2) >> 2;
+          c4[c][2] = (3 * s2 + s1 + 1) >> 2;
+          c4[c][3] = (3 * s2 + s3 + 2) >> 2;
+        } else {
+          const int cy = y >> 1;
+          const int cf = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);    // the far row, edge replicated
+          const uint8_t* rn = p + (int64_t)cy * pitch;
+          const uint8_t* rf = p + (int64_t)cf * pitch;
+          int s[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) s[k] = 3 * rn[col[k]] + rf[col[k]];
+          c4[c][0] = (3 * s[1] + s[0] + 8) >> 4;
+          c4[c][1] = (3 * s[1] + s[2] + 7) >> 4;
+          c4[c][2] = (3 * s[2] + s[1] + 8) >> 4;
+          c4[c][3] = (3 * s[2] + s[3] + 7) >> 4;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) px[k] = ycc_pixel((int)((yw >> (8 * k)) & 255u), c4[0][k], c4[1][k], rgb);
+  }
+}
+
+constexpr int kOrientTile = 32, kOrientPitch = kOrientTile + 1;
+
+__global__ __launch_bounds__(256) void jpeg_orient_kernel(const yv4_jpeg_image* __restrict__ table, int n,
+                                                          const uint8_t* __restrict__ work, uint8_t* __restrict__ out,
+                                                          int rgb) {
+  __shared__ unsigned lds[kOrientTile * kOrientPitch];
+  const yv4_jpeg_image g = table[n];
+  const int tiles_x = (g.width + kOrientTile - 1) / kOrientTile;
+  const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
+  const int x_base = tx * kOrientTile, y_base = ty * kOrientTile;      // the tile's corner in the decoded picture D
+  {
+    const int lx = (threadIdx.x & 7) * 4, ly = threadIdx.x >> 3;         // a quad of D per thread: 8 x 32 of them
+    if (x_base + lx < g.width && y_base + ly < g.height) {
+      unsigned px[4];
+      pixel_quad(g, work, x_base + lx, y_base + ly, rgb, px);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) lds[ly * kOrientPitch + lx + k] = px[k];      // columns past the width: never read back
+    }
+  }
+  __syncthreads();
+  const int o = g.orientation;
+  const bool transpose = o >= 5;
+  const bool flip_y = o == 3 || o == 4 || o == 6 || o == 7;      // D's row h-1-a instead of a
+  const bool flip_x = o == 2 || o == 3 || o == 7 || o == 8;      // D's column w-1-b instead of b
+#pragma unroll
+  for (int it = 0; it < kOrientTile * kOrientTile / 256; ++it) {
+    const int fast = threadIdx.x & 31, slow = (threadIdx.x >> 5) + 8 * it;
+    // consecutive lanes walk an output row: D's rows for 5 .. 8 (a column of the tile), D's columns otherwise
+    const int ly = transpose ? fast : slow, lx = transpose ? slow : fast;
+    const int dy = y_base + ly, dx = x_base + lx;
+    if (dy >= g.height || dx >= g.width) continue;
+    const int a = flip_y ? g.height - 1 - dy : dy, b = flip_x ? g.width - 1 - dx : dx;
+    const int oy = transpose ? b : a, ox = transpose ? a : b;
+    const unsigned px = lds[ly * kOrientPitch + lx];
+    uint8_t* q = out + g.out_off + (int64_t)oy * g.out_pitch + 3 * ox;
+    q[0] = (uint8_t)px;
+    q[1] = (uint8_t)(px >> 8);
+    q[2] = (uint8_t)(px >> 16);
+  }
+}
+
 }  // namespace yv4
 
 using namespace yv4;
@@ -247,18 +349,29 @@ extern "C" int yv4_jpeg_reconstruct(const yv4_jpeg_image* table, const yv4_jpeg_
     }
     YV4_REQUIRE(g.coef_off >= 0 && (g.coef_off & 63) == 0 && g.coef_off <= coef_elems - blocks * 64,
                 "jpeg_reconstruct: image %d: its coefficients leave the buffer", n);
-    YV4_REQUIRE(g.out_pitch >= 3 * g.width && g.out_off >= 0 &&
-                    g.out_off <= out_bytes - ((int64_t)(g.height - 1) * g.out_pitch + 3 * g.width),
+    YV4_REQUIRE(g.orientation >= 0 && g.orientation <= 8, "jpeg_reconstruct: image %d: orientation %d", n, g.orientation);
+    const int ow = g.orientation >= 5 ? g.height : g.width, oh = g.orientation >= 5 ? g.width : g.height;      // the output's
+    YV4_REQUIRE(g.out_pitch >= 3 * ow && g.out_off >= 0 &&
+                    g.out_off <= out_bytes - ((int64_t)(oh - 1) * g.out_pitch + 3 * ow),
                 "jpeg_reconstruct: image %d: its pixels leave the output buffer", n);
     YV4_REQUIRE(g.unit_base == units && g.tile_base == tiles, "jpeg_reconstruct: image %d: unit_base / tile_base", n);
     units += (blocks + 31) / 32;
-    tiles += (int64_t)((g.width + 255) / 256) * ((g.height + 3) / 4);
+    if (g.orientation < 2) tiles += (int64_t)((g.width + 255) / 256) * ((g.height + 3) / 4);
   }
   YV4_REQUIRE(units < (1ll << 31) && tiles < (1ll << 31), "jpeg_reconstruct: the batch is too large for one launch");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)units), dim3(256), 0, s, table_dev, N, coef, quant, work);
   YV4_CHECK_LAUNCH("jpeg_idct");
-  hipLaunchKernelGGL(jpeg_pixel_kernel, dim3((unsigned)tiles), dim3(256), 0, s, table_dev, N, work, out, rgb ? 1 : 0);
-  YV4_CHECK_LAUNCH("jpeg_pixel");
+  if (tiles > 0) {      // every image of the batch may be an oriented one
+    hipLaunchKernelGGL(jpeg_pixel_kernel, dim3((unsigned)tiles), dim3(256), 0, s, table_dev, N, work, out, rgb ? 1 : 0);
+    YV4_CHECK_LAUNCH("jpeg_pixel");
+  }
+  for (int n = 0; n < N; ++n) {
+    const yv4_jpeg_image& g = table[n];
+    if (g.orientation < 2) continue;
+    const unsigned grid = (unsigned)((g.width + kOrientTile - 1) / kOrientTile) * (unsigned)((g.height + kOrientTile - 1) / kOrientTile);
+    hipLaunchKernelGGL(jpeg_orient_kernel, dim3(grid), dim3(256), 0, s, table_dev, n, work, out, rgb ? 1 : 0);
+    YV4_CHECK_LAUNCH("jpeg_orient");
+  }
   return YV4_OK;
 }

@@ -73,13 +73,42 @@ int build_huff(Huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) {
 
 int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// EXIF tag 0x0112 of an APP1 payload p[0 .. n): "Exif\0\0", then a TIFF header ("II" / "MM", 42, the offset of IFD0 from
+// the TIFF header) and IFD0 (a count, then 12-byte entries: tag, type, count, value).  1 .. 8 when the tag is there as one
+// SHORT, 0 for everything else.  Offsets count from the TIFF header and every read is checked against n.
+int exif_orientation(const uint8_t* p, size_t n) {
+  if (n < 14 || memcmp(p, "Exif\0\0", 6) != 0) return 0;
+  const uint8_t* t = p + 6;
+  const size_t tn = n - 6;      // >= 8: the TIFF header is there
+  bool le;
+  if (t[0] == 'I' && t[1] == 'I') le = true;
+  else if (t[0] == 'M' && t[1] == 'M') le = false;
+  else return 0;
+  auto u16 = [&](size_t o) { return le ? (unsigned)t[o] | ((unsigned)t[o + 1] << 8) : ((unsigned)t[o] << 8) | t[o + 1]; };
+  auto u32 = [&](size_t o) { return le ? u16(o) | (u16(o + 2) << 16) : (u16(o) << 16) | u16(o + 2); };
+  if (u16(2) != 42) return 0;
+  const size_t ifd = u32(4);
+  if (ifd < 8 || ifd > tn || tn - ifd < 2) return 0;
+  const size_t count = u16(ifd);
+  if ((tn - ifd - 2) / 12 < count) return 0;      // an IFD that says more entries than the segment holds: inconsistent
+  for (size_t i = 0; i < count; ++i) {
+    const size_t e = ifd + 2 + 12 * i;
+    if (u16(e) != 0x0112) continue;
+    if (u16(e + 2) != 3 || u32(e + 4) != 1) return 0;      // SHORT, one value: held in the entry's first two value bytes
+    const unsigned v = u16(e + 8);
+    return v >= 1 && v <= 8 ? (int)v : 0;
+  }
+  return 0;
+}
+
 // Markers up to and including SOS.  On YV4_OK c.pos is the first byte of the entropy-coded data.
 int parse_headers(Cursor& c, yv4_jpeg_info* info, Tables* t) {
   memset(info, 0, sizeof(*info));
   memset(t, 0, sizeof(*t));
   if (!c.have(2) || c.d[0] != 0xFF || c.d[1] != 0xD8) JPEG_FAIL(YV4_E_INVALID, "jpeg: no SOI marker at the start");
   c.pos = 2;
-  bool have_sof = false, adobe = false;
+  bool have_sof = false, adobe = false, exif = false;
+  int orientation = 0;
   int adobe_transform = 0;
   int comp_id[3] = {0, 0, 0};
   for (;;) {      // every turn consumes at least two bytes
@@ -169,6 +198,11 @@ int parse_headers(Cursor& c, yv4_jpeg_info* info, Tables* t) {
     } else if (m == 0xDD) {
       if (left != 2) JPEG_FAIL(YV4_E_INVALID, "jpeg: restart interval segment length");
       info->restart_interval = (int32_t)c.u16();
+    } else if (m == 0xE1) {
+      if (!exif && left >= 6 && memcmp(c.d + c.pos, "Exif\0\0", 6) == 0) {      // the first Exif segment decides
+        exif = true;
+        orientation = exif_orientation(c.d + c.pos, left);
+      }
     } else if (m == 0xEE) {
       if (left >= 12 && memcmp(c.d + c.pos, "Adobe", 5) == 0) {
         adobe = true;
@@ -199,6 +233,7 @@ int parse_headers(Cursor& c, yv4_jpeg_info* info, Tables* t) {
       }
       if (adobe && info->ncomp == 3 && adobe_transform != 1)
         JPEG_FAIL(YV4_E_UNSUPPORTED, "jpeg: Adobe colour transform %d is not built (YCbCr only)", adobe_transform);
+      info->orientation = orientation;
       info->scan_offset = (int64_t)c.pos;
       return YV4_OK;
     } else if (m == 0xC2) {
@@ -382,6 +417,11 @@ extern "C" int yv4_jpeg_entropy_decode(const uint8_t* data, size_t len, yv4_jpeg
 }
 
 extern "C" int yv4_jpeg_layout(const yv4_jpeg_info* infos, int N, yv4_jpeg_image* table, int64_t* totals) {
+  return yv4_jpeg_layout_oriented(infos, N, 0, table, totals);
+}
+
+extern "C" int yv4_jpeg_layout_oriented(const yv4_jpeg_info* infos, int N, int apply, yv4_jpeg_image* table,
+                                        int64_t* totals) {
   if (!infos || !table || !totals || N <= 0) JPEG_FAIL(YV4_E_INVALID, "jpeg_layout: null pointer or no image");
   int64_t coef = 0, work = 0, out = 0, units = 0, tiles = 0;
   for (int n = 0; n < N; ++n) {
@@ -403,13 +443,17 @@ extern "C" int yv4_jpeg_layout(const yv4_jpeg_info* infos, int N, yv4_jpeg_image
       blocks += nb;
     }
     coef += 64 * blocks;
+    if (apply) {
+      if (f.orientation < 0 || f.orientation > 8) JPEG_FAIL(YV4_E_INVALID, "jpeg_layout: image %d: orientation %d", n, f.orientation);
+      g.orientation = f.orientation;
+    }
     g.out_off = out;
-    g.out_pitch = 3 * f.width;
+    g.out_pitch = 3 * (g.orientation >= 5 ? f.height : f.width);      // 5 .. 8: the output's rows are the picture's columns
     out += ((int64_t)3 * f.width * f.height + 255) & ~(int64_t)255;
     g.unit_base = units;
     g.tile_base = tiles;
     units += (blocks + 31) / 32;
-    tiles += (int64_t)((f.width + 255) / 256) * ((f.height + 3) / 4);
+    if (g.orientation < 2) tiles += (int64_t)((f.width + 255) / 256) * ((f.height + 3) / 4);
   }
   totals[0] = coef; totals[1] = work; totals[2] = out;
   return YV4_OK;

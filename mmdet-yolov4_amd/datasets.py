@@ -1,0 +1,526 @@
+"""Training from image files: the COCO dataset in train mode, the group samplers and a loader that decodes and augments
+on the GPU.
+
+``cfg.data.train`` of a reference config (``configs/yolov4/*.py``: ``dict(type='CocoDataset', ann_file=...,
+img_prefix=..., pipeline=train_pipeline)``) goes through ``build_train_loader`` and yields ``train_step`` data dicts:
+
+* ``CocoDataset`` restates ``mmdet/datasets/coco.py`` and ``custom.py`` on ``coco_eval.CocoGt`` (no pycocotools): which
+  images survive, their aspect-ratio groups, each image's boxes, and the random partner draws of the mosaic.
+* ``GroupSampler`` / ``DistributedGroupSampler`` restate ``mmdet/datasets/samplers/group_sampler.py``.
+* ``TrainLoader`` takes the sampler's indices, reads the files on a thread pool, decodes the whole batch with ONE
+  ``image_io.decode_into`` call and hands the device views to the fused pipeline (``build_train_pipeline``).  No pixel
+  crosses back to the host.
+
+What is pinned draw for draw against the reference (tests/golden/coco_train_set.npz): ``CocoDataset._rand_another`` /
+``batch_rand_others`` and both samplers' orders, given the same generator state.  What is this loader's own: the ORDER
+in which the samples of a batch take their draws.  The reference spreads them over its worker processes, each with its
+own ``np.random`` state, so its stream cannot be replayed; here one ``RandomState`` per (seed, epoch, rank) serves, in
+this order per batch: ``batch_rand_others`` for each sample in sample order (mosaic only), a ``_rand_another`` for each
+refused file (``on_unsupported='resample'``), then the pipeline's draws for each sample in sample order.
+"""
+import logging
+import math
+import os
+import re
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import image_io
+from .augment import FusedTrainPipeline
+from .augment_v3 import build_train_pipeline
+from .registry import DATASETS
+from .results import CocoBBoxDataset
+
+#: the files of a batch are read on at most this many threads (never sized from the machine's CPU count)
+MAX_READ_THREADS = 16
+
+COCO_CLASSES = ('person', 'bicycle', 'car', 'motorcycle', 'airplane', 'bus', 'train', 'truck', 'boat', 'traffic light',
+                'fire hydrant', 'stop sign', 'parking meter', 'bench', 'bird', 'cat', 'dog', 'horse', 'sheep', 'cow',
+                'elephant', 'bear', 'zebra', 'giraffe', 'backpack', 'umbrella', 'handbag', 'tie', 'suitcase', 'frisbee',
+                'skis', 'snowboard', 'sports ball', 'kite', 'baseball bat', 'baseball glove', 'skateboard', 'surfboard',
+                'tennis racket', 'bottle', 'wine glass', 'cup', 'fork', 'knife', 'spoon', 'bowl', 'banana', 'apple',
+                'sandwich', 'orange', 'broccoli', 'carrot', 'hot dog', 'pizza', 'donut', 'cake', 'chair', 'couch',
+                'potted plant', 'bed', 'dining table', 'toilet', 'tv', 'laptop', 'mouse', 'remote', 'keyboard',
+                'cell phone', 'microwave', 'oven', 'toaster', 'sink', 'refrigerator', 'book', 'clock', 'vase', 'scissors',
+                'teddy bear', 'hair drier', 'toothbrush')
+
+
+@DATASETS.register_module()
+class CocoDataset(CocoBBoxDataset):
+    """``CocoDataset`` of the reference (``mmdet/datasets/coco.py:19-173`` on ``custom.py:56-191``) for ``bbox`` work:
+    the annotation tables of training, and ``evaluate`` from ``CocoBBoxDataset``.  ``pipeline`` is kept as the config
+    block (``build_train_loader`` builds the fused pipeline from it); ``classes``: a sequence of names, or ``None`` for
+    the 80 COCO names (``coco.py:21-34``; a file of names is not built).  With ``test_mode`` nothing is filtered and no
+    group flag is set (``custom.py:96-102``).  Parity with pycocotools itself is unpinned (it is absent here): ``CocoGt``
+    stands in for its ``COCO`` class -- image, category and annotation ids in file order."""
+
+    CLASSES = COCO_CLASSES
+
+    def __init__(self, ann_file, pipeline=None, classes=None, data_root=None, img_prefix='', test_mode=False,
+                 filter_empty_gt=True):
+        if isinstance(classes, str):
+            raise NotImplementedError('CocoDataset(classes=<file name>) is not built: pass the names')
+        self.data_root, self.img_prefix = data_root, img_prefix
+        if data_root is not None:                                          # custom.py:76-80
+            if isinstance(ann_file, str) and not os.path.isabs(ann_file):
+                ann_file = os.path.join(data_root, ann_file)
+            if not (img_prefix is None or os.path.isabs(img_prefix)):
+                self.img_prefix = os.path.join(data_root, img_prefix)
+        super().__init__(ann_file, classes=self.CLASSES if classes is None else classes)
+        self.ann_file = ann_file
+        self.pipeline = pipeline
+        self.test_mode, self.filter_empty_gt = test_mode, filter_empty_gt
+        self.data_infos = self.load_annotations()
+        if not test_mode:
+            valid_inds = self._filter_imgs()
+            self.data_infos = [self.data_infos[i] for i in valid_inds]
+            self.valid_inds = valid_inds
+            self._set_group_flag()
+
+    def __len__(self):
+        return len(self.data_infos)
+
+    def load_annotations(self):
+        """``coco.py:36-60``: ``data_infos`` in ``get_img_ids()`` order with ``filename = file_name``; each image's
+        annotation records in file order (``COCO.get_ann_ids(img_ids=[i])``); annotation ids must be unique."""
+        self.cat2label = {cat_id: i for i, cat_id in enumerate(self.cat_ids)}
+        self.img_ids = self.coco.get_img_ids()
+        self._img_anns = {i: [] for i in self.img_ids}
+        for ann in self.coco.dataset.get('annotations', []):
+            if ann['image_id'] in self._img_anns:
+                self._img_anns[ann['image_id']].append(ann)
+        data_infos, total_ann_ids = [], []
+        for i in self.img_ids:
+            info = self.coco.imgs[i]
+            info['filename'] = info['file_name']
+            data_infos.append(info)
+            total_ann_ids.extend(a['id'] for a in self._img_anns[i])
+        assert len(set(total_ann_ids)) == len(total_ann_ids), f"Annotation ids in '{self.ann_file}' are not unique!"
+        return data_infos
+
+    def _filter_imgs(self, min_size=32):
+        """``coco.py:92-114``: with ``filter_empty_gt`` only images that hold an annotation of a listed category stay;
+        images whose shorter side is below ``min_size`` go; ``img_ids`` becomes the survivors'."""
+        valid_inds, valid_img_ids = [], []
+        anns = self.coco.dataset.get('annotations', [])
+        ids_with_ann = set(a['image_id'] for a in anns)
+        cat_ids = set(self.cat_ids)
+        ids_in_cat = set(a['image_id'] for a in anns if a['category_id'] in cat_ids) & ids_with_ann
+        for i, img_info in enumerate(self.data_infos):
+            img_id = self.img_ids[i]
+            if self.filter_empty_gt and img_id not in ids_in_cat:
+                continue
+            if min(img_info['width'], img_info['height']) >= min_size:
+                valid_inds.append(i)
+                valid_img_ids.append(img_id)
+        self.img_ids = valid_img_ids
+        return valid_inds
+
+    def _set_group_flag(self):
+        """``custom.py:164-174``: aspect ratio ``width / height > 1`` is group 1, the rest group 0."""
+        self.flag = np.zeros(len(self), dtype=np.uint8)
+        for i in range(len(self)):
+            img_info = self.data_infos[i]
+            if img_info['width'] / img_info['height'] > 1:
+                self.flag[i] = 1
+
+    def get_ann_info(self, idx):
+        """``coco.py:62-75``."""
+        info = self.data_infos[idx]
+        return self._parse_ann_info(info, self._img_anns[info['id']])
+
+    def get_cat_ids(self, idx):
+        """``coco.py:77-90``."""
+        return [ann['category_id'] for ann in self._img_anns[self.data_infos[idx]['id']]]
+
+    def _parse_ann_info(self, img_info, ann_info):
+        """``coco.py:116-173`` without the masks: ``ignore`` records, boxes that do not meet the image, boxes with
+        ``area <= 0 or w < 1 or h < 1`` and boxes of unlisted categories are skipped; crowd boxes go to
+        ``bboxes_ignore``; x y w h becomes x1 y1 x2 y2; float32 boxes, int64 labels, (0, 4) / (0,) when empty."""
+        gt_bboxes, gt_labels, gt_bboxes_ignore = [], [], []
+        for ann in ann_info:
+            if ann.get('ignore', False):
+                continue
+            x1, y1, w, h = ann['bbox']
+            inter_w = max(0, min(x1 + w, img_info['width']) - max(x1, 0))
+            inter_h = max(0, min(y1 + h, img_info['height']) - max(y1, 0))
+            if inter_w * inter_h == 0:
+                continue
+            if ann['area'] <= 0 or w < 1 or h < 1:
+                continue
+            if ann['category_id'] not in self.cat_ids:
+                continue
+            bbox = [x1, y1, x1 + w, y1 + h]
+            if ann.get('iscrowd', False):
+                gt_bboxes_ignore.append(bbox)
+            else:
+                gt_bboxes.append(bbox)
+                gt_labels.append(self.cat2label[ann['category_id']])
+        if gt_bboxes:
+            gt_bboxes = np.array(gt_bboxes, dtype=np.float32)
+            gt_labels = np.array(gt_labels, dtype=np.int64)
+        else:
+            gt_bboxes = np.zeros((0, 4), dtype=np.float32)
+            gt_labels = np.array([], dtype=np.int64)
+        if gt_bboxes_ignore:
+            gt_bboxes_ignore = np.array(gt_bboxes_ignore, dtype=np.float32)
+        else:
+            gt_bboxes_ignore = np.zeros((0, 4), dtype=np.float32)
+        return dict(bboxes=gt_bboxes, labels=gt_labels, bboxes_ignore=gt_bboxes_ignore,
+                    seg_map=img_info['filename'].replace('jpg', 'png'))
+
+    def _rand_another(self, idx, rng=np.random):
+        """``custom.py:176-179``, drawing from ``rng`` (a ``RandomState``; default: the module-level ``np.random``)."""
+        pool = np.where(self.flag == self.flag[idx])[0]
+        return rng.choice(pool)
+
+    def batch_rand_others(self, idx, batch, rng=np.random):
+        """``custom.py:181-191``, draw for draw: ``batch`` other indices of ``idx``'s group -- ``[idx] * batch`` when
+        there is no other, with replacement when there are fewer than ``batch``, without otherwise."""
+        mask = (self.flag == self.flag[idx])
+        mask[idx] = False
+        pool = np.where(mask)[0]
+        if len(pool) == 0:
+            return np.array([idx] * batch)
+        if len(pool) < batch:
+            return rng.choice(pool, size=batch, replace=True)
+        return rng.choice(pool, size=batch, replace=False)
+
+
+class GroupSampler:
+    """``group_sampler.py:10-48``: every group shuffled, padded to a multiple of ``samples_per_gpu`` with
+    ``choice(indice, num_extra)``, then whole batches permuted -- the same three calls on ``rng`` (a ``RandomState``;
+    default: the module-level ``np.random``).  With ``seed``, ``set_epoch(e)`` replaces ``rng`` by
+    ``RandomState([seed, e])`` (the reference's class has no epoch: its order comes from the process's global state)."""
+
+    def __init__(self, dataset, samples_per_gpu=1, rng=None, seed=None):
+        assert hasattr(dataset, 'flag')
+        self.dataset = dataset
+        self.samples_per_gpu = samples_per_gpu
+        self.flag = dataset.flag.astype(np.int64)
+        self.group_sizes = np.bincount(self.flag)
+        self.num_samples = 0
+        for i, size in enumerate(self.group_sizes):
+            self.num_samples += int(np.ceil(size / self.samples_per_gpu)) * self.samples_per_gpu
+        self.seed, self.epoch = seed, 0
+        self.rng = rng if rng is not None else np.random
+        if seed is not None:
+            self.set_epoch(0)
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch
+        if self.seed is not None:
+            self.rng = np.random.RandomState([int(self.seed), int(epoch)])
+
+    def __iter__(self):
+        rng = self.rng
+        indices = []
+        for i, size in enumerate(self.group_sizes):
+            if size == 0:
+                continue
+            indice = np.where(self.flag == i)[0]
+            assert len(indice) == size
+            rng.shuffle(indice)
+            num_extra = int(np.ceil(size / self.samples_per_gpu)) * self.samples_per_gpu - len(indice)
+            indice = np.concatenate([indice, rng.choice(indice, num_extra)])
+            indices.append(indice)
+        indices = np.concatenate(indices)
+        indices = [indices[i * self.samples_per_gpu:(i + 1) * self.samples_per_gpu]
+                   for i in rng.permutation(range(len(indices) // self.samples_per_gpu))]
+        indices = np.concatenate(indices)
+        indices = indices.astype(np.int64).tolist()
+        assert len(indices) == self.num_samples
+        return iter(indices)
+
+    def __len__(self):
+        return self.num_samples
+
+
+class DistributedGroupSampler:
+    """``group_sampler.py:51-148``: one ``torch.Generator`` seeded ``epoch + seed`` permutes every group
+    (``torch.randperm``) and then the whole batches; groups are padded by repetition to a multiple of
+    ``samples_per_gpu * num_replicas``; rank ``r`` takes the ``r``-th contiguous run of ``num_samples``."""
+
+    def __init__(self, dataset, samples_per_gpu=1, num_replicas=1, rank=0, seed=0):
+        self.dataset = dataset
+        self.samples_per_gpu = samples_per_gpu
+        self.num_replicas = num_replicas
+        self.rank = rank
+        self.epoch = 0
+        self.seed = seed if seed is not None else 0
+        assert hasattr(self.dataset, 'flag')
+        self.flag = self.dataset.flag
+        self.group_sizes = np.bincount(self.flag)
+        self.num_samples = 0
+        for i, j in enumerate(self.group_sizes):
+            self.num_samples += int(math.ceil(self.group_sizes[i] * 1.0 / self.samples_per_gpu /
+                                              self.num_replicas)) * self.samples_per_gpu
+        self.total_size = self.num_samples * self.num_replicas
+
+    def __iter__(self):
+        g = torch.Generator()
+        g.manual_seed(self.epoch + self.seed)
+        indices = []
+        for i, size in enumerate(self.group_sizes):
+            if size > 0:
+                indice = np.where(self.flag == i)[0]
+                assert len(indice) == size
+                indice = indice[list(torch.randperm(int(size), generator=g).numpy())].tolist()
+                extra = int(math.ceil(size * 1.0 / self.samples_per_gpu / self.num_replicas)
+                            ) * self.samples_per_gpu * self.num_replicas - len(indice)
+                tmp = indice.copy()
+                for _ in range(extra // size):
+                    indice.extend(tmp)
+                indice.extend(tmp[:extra % size])
+                indices.extend(indice)
+        assert len(indices) == self.total_size
+        indices = [indices[j] for i in list(torch.randperm(len(indices) // self.samples_per_gpu, generator=g))
+                   for j in range(i * self.samples_per_gpu, (i + 1) * self.samples_per_gpu)]
+        offset = self.num_samples * self.rank
+        indices = indices[offset:offset + self.num_samples]
+        assert len(indices) == self.num_samples
+        return iter(indices)
+
+    def __len__(self):
+        return self.num_samples
+
+    def set_epoch(self, epoch):
+        self.epoch = epoch
+
+
+def _read(path):
+    with open(path, 'rb') as f:
+        return f.read()
+
+
+class TrainLoader:
+    """What ``Runner.data_loader`` and the hooks expect of a loader (``hooks.BatchSource``), fed from image files:
+    iterable over ``train_step`` data dicts (``img`` (N, 3, H, W) float32 on the device, ``img_metas``, ``gt_bboxes``,
+    ``gt_labels``), with ``__len__`` (batches an epoch), ``.dataset`` and ``.sampler`` (``samples_per_gpu``,
+    ``set_epoch``).  An iteration is one epoch; the sampler's epoch then advances by one, and ``set_epoch`` (a resume,
+    ``DistSamplerSeedHook``) overrides it.  The same ``(seed, epoch, rank, world)`` gives the same batches bit for bit.
+
+    Per batch: the sampler's indices; for a mosaic pipeline ``dataset.batch_rand_others(idx, 3)`` per sample from the
+    epoch's ``RandomState``; the files read on at most ``MAX_READ_THREADS`` threads; every header through
+    ``jpeg_parse``; ONE ``image_io.decode_into`` of the whole batch in the ``entropy`` mode asked for; the device views
+    into the fused pipeline with the same ``RandomState``.  ``draws`` records the last batch: ``indices``, ``sources``
+    (per sample the dataset indices whose files were decoded, after any resampling) and the pipeline's ``params``.
+
+    ``prefetch=1``: one worker thread reads the next batch's files and does the host half of their decode
+    (``image_io.HostHalf``: the parses, and with ``entropy='host'`` the Huffman decodes) while the caller runs the step.
+    Every HIP and torch call stays on the caller's thread and stream, and every draw on the caller's thread in the
+    order above, so the batches equal ``prefetch=0``'s bit for bit.
+
+    ``on_unsupported``: ``'raise'`` -- a file the decoder refuses (progressive, CMYK, another format ...) raises
+    ``NotImplementedError`` naming the file; ``'resample'`` -- it is replaced by ``dataset._rand_another(idx)``, the
+    rule of the reference's ``__getitem__`` retry (``custom.py:206-211``), logged once per file and counted in
+    ``resampled``.  A damaged scan is a ``ValueError`` either way."""
+
+    def __init__(self, dataset, pipeline, samples_per_gpu, seed=0, rank=0, world=1, device=None, entropy=None, prefetch=0,
+                 on_unsupported='raise', orientation=True):
+        if on_unsupported not in ('raise', 'resample'):
+            raise ValueError(f"on_unsupported {on_unsupported!r} is not 'raise' or 'resample'")
+        if prefetch not in (0, 1):
+            raise ValueError(f'prefetch {prefetch!r} is not 0 or 1')
+        if not 0 <= rank < world:
+            raise ValueError(f'rank {rank} of world {world}')
+        self.dataset, self.pipeline = dataset, pipeline
+        self.mosaic = isinstance(pipeline, FusedTrainPipeline)
+        self.seed, self.rank, self.world = int(seed), int(rank), int(world)
+        self.device = torch.device(device) if device is not None else None
+        self.entropy = image_io._entropy_mode(entropy)
+        self.prefetch, self.on_unsupported, self.orientation = prefetch, on_unsupported, bool(orientation)
+        if world == 1:
+            self.sampler = GroupSampler(dataset, samples_per_gpu, seed=self.seed)
+        else:
+            self.sampler = DistributedGroupSampler(dataset, samples_per_gpu, world, rank, seed=self.seed)
+        self.resampled = 0
+        self._logged = set()
+        self.draws = None
+        #: host seconds of the last epoch by phase (tools/loader_bench.py): index draws, file reads, header parse and
+        #: host half, the decode call, the pipeline call
+        self.times = dict(draws=0.0, read=0.0, host=0.0, decode=0.0, pipeline=0.0)
+        self._readers = ThreadPoolExecutor(max_workers=MAX_READ_THREADS, thread_name_prefix='yv4-read')
+        self._worker = ThreadPoolExecutor(max_workers=1, thread_name_prefix='yv4-prefetch') if prefetch else None
+
+    def __len__(self):
+        return len(self.sampler) // self.sampler.samples_per_gpu
+
+    def set_epoch(self, epoch):
+        self.sampler.set_epoch(epoch)
+
+    def close(self):
+        """Ends the loader's threads (they are idle between batches; an interpreter exit ends them as well)."""
+        self._readers.shutdown(wait=True)
+        if self._worker is not None:
+            self._worker.shutdown(wait=True)
+
+    def _path(self, j):
+        name = self.dataset.data_infos[j]['filename']
+        return os.path.join(self.dataset.img_prefix, name) if self.dataset.img_prefix is not None else name
+
+    # ---- host work of one batch: no HIP call, no torch call, no draw (may run on the worker thread) -----------------------
+    def _host(self, sources):
+        """Reads and parses the files of ``sources`` (a flat list of dataset indices) -> ``(bufs, refused, host,
+        (read seconds, parse seconds))``: ``refused`` maps positions to the decoder's refusal; ``host`` is the batch's
+        ``HostHalf`` when none was."""
+        t0 = time.perf_counter()
+        bufs = list(self._readers.map(_read, [self._path(j) for j in sources]))
+        t1 = time.perf_counter()
+        refused = {}
+        for k, b in enumerate(bufs):
+            try:
+                image_io.jpeg_parse(image_io._as_bytes(b))
+            except NotImplementedError as e:
+                refused[k] = e
+        host = None
+        if not refused:
+            host = self._host_half(bufs, sources)
+        t2 = time.perf_counter()
+        return bufs, refused, host, (t1 - t0, t2 - t1)
+
+    def _named(self, e, sources):
+        """The decoder's ``ValueError`` about "image n" of a batch, naming the file."""
+        m = re.search(r'image (\d+)', str(e))
+        where = self._path(sources[int(m.group(1))]) if m else f'batch of {[self._path(j) for j in sources]}'
+        return ValueError(f'TrainLoader: {where}: {e}')
+
+    def _host_half(self, bufs, sources):
+        try:
+            return image_io.HostHalf(bufs, self.entropy, what='TrainLoader')
+        except ValueError as e:      # a damaged scan found by the host Huffman decode or the segment walk
+            raise self._named(e, sources) from None
+
+    def _settle(self, sources, job, rng):
+        """The refusals of a batch, on the caller's thread: raise, or draw replacements until every file is accepted."""
+        bufs, refused, host, (t_read, t_host) = job
+        self.times['read'] += t_read
+        self.times['host'] += t_host
+        while refused:
+            t0 = time.perf_counter()
+            for k in sorted(refused):
+                path = self._path(sources[k])
+                if self.on_unsupported == 'raise':
+                    raise NotImplementedError(f'TrainLoader: {path}: {refused[k]}')
+                if path not in self._logged:
+                    self._logged.add(path)
+                    logging.getLogger(__name__).warning('TrainLoader: %s is refused (%s): another image of its group is '
+                                                        'drawn in its place', path, refused[k])
+                self.resampled += 1
+                sources[k] = int(self.dataset._rand_another(sources[k], rng))
+                bufs[k] = _read(self._path(sources[k]))
+            again = {}
+            for k in refused:
+                try:
+                    image_io.jpeg_parse(image_io._as_bytes(bufs[k]))
+                except NotImplementedError as e:
+                    again[k] = e
+            refused = again
+            if not refused:
+                host = self._host_half(bufs, sources)
+            self.times['host'] += time.perf_counter() - t0
+        return bufs, host
+
+    def _start(self, indices, rng):
+        """The draws of a batch's sources (caller's thread), then its host work: a future with ``prefetch``."""
+        t0 = time.perf_counter()
+        if self.mosaic:
+            sources = []
+            for idx in indices:
+                sources += [idx] + [int(j) for j in self.dataset.batch_rand_others(idx, 3, rng)]
+        else:
+            sources = list(indices)
+        self.times['draws'] += time.perf_counter() - t0
+        job = self._worker.submit(self._host, list(sources)) if self._worker is not None else self._host(list(sources))
+        return indices, sources, job
+
+    def _finish(self, started, rng):
+        indices, sources, job = started
+        bufs, host = self._settle(sources, job.result() if self._worker is not None else job, rng)
+        dev = self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+        t0 = time.perf_counter()
+        try:
+            out, table = image_io.decode_into(bufs, 'bgr', dev, orientation=self.orientation, host=host)
+        except ValueError as e:      # a damaged scan found by the device decode's status read-back
+            raise self._named(e, sources) from None
+        imgs = []
+        for t in table:
+            (h, w), off = image_io.oriented_size(t), int(t.out_off)
+            imgs.append(out[off:off + h * w * 3].view(h, w, 3))
+        t1 = time.perf_counter()
+        anns = [self.dataset.get_ann_info(j) for j in sources]
+        triples = [(im, a['bboxes'], a['labels']) for im, a in zip(imgs, anns)]
+        if self.mosaic:
+            samples = [tuple(triples[4 * n:4 * n + 4]) for n in range(len(indices))]
+        else:
+            samples = triples
+        res = self.pipeline(samples, rng=rng)
+        t2 = time.perf_counter()
+        self.times['decode'] += t1 - t0
+        self.times['pipeline'] += t2 - t1
+        per = 4 if self.mosaic else 1
+        groups = [sources[per * n:per * n + per] for n in range(len(indices))]
+        self.draws = dict(indices=list(indices), sources=groups, params=res['params'])
+        metas = res.get('img_metas')
+        if metas is None:
+            shape = tuple(res['img'].shape[2:]) + (3,)
+            metas = [dict(img_shape=shape, pad_shape=shape, scale_factor=1.0, flip=False) for _ in indices]
+        for m, g in zip(metas, groups):
+            m['ori_filename'] = self.dataset.data_infos[g[0]]['filename']
+            m['filename'] = self._path(g[0])
+        return dict(img=res['img'], img_metas=metas, gt_bboxes=res['gt_bboxes'], gt_labels=res['gt_labels'])
+
+    def __iter__(self):
+        epoch = self.sampler.epoch
+        rng = np.random.RandomState([self.seed, int(epoch), self.rank, 1])
+        for k in self.times:
+            self.times[k] = 0.0
+        order = list(iter(self.sampler))
+        n = self.sampler.samples_per_gpu
+        batches = [order[i:i + n] for i in range(0, len(order), n)]
+        started = self._start(batches[0], rng) if batches else None
+        for k in range(len(batches)):
+            if self.prefetch:
+                data = self._finish(started, rng)
+                started = self._start(batches[k + 1], rng) if k + 1 < len(batches) else None
+            else:
+                data = self._finish(started if k == 0 else self._start(batches[k], rng), rng)
+            yield data
+        self.sampler.set_epoch(epoch + 1)
+
+
+def build_dataset(cfg, default_args=None):
+    """``mmdet/datasets/builder.py`` ``build_dataset`` for a plain dataset block (the wrappers -- ``RepeatDataset``,
+    ``ConcatDataset``, ``ClassBalancedDataset`` -- are not built)."""
+    from .registry import build_from_cfg
+    if isinstance(cfg, (list, tuple)) or cfg.get('type') in ('RepeatDataset', 'ConcatDataset', 'ClassBalancedDataset'):
+        raise NotImplementedError('dataset wrappers are not built: pass one dataset block')
+    return build_from_cfg(cfg, DATASETS, default_args)
+
+
+def build_train_loader(cfg, samples_per_gpu, seed=0, rank=0, world=1, device=None, entropy=None, prefetch=0,
+                       on_unsupported='raise'):
+    """``cfg``: ``cfg.data.train`` of a reference config, a dataset block with its ``pipeline`` -> ``TrainLoader``.  The
+    pipeline block goes through ``build_train_pipeline`` (the mosaic recipes and the YOLOv3 mstrain recipe).  Its
+    ``LoadImageFromFile`` says how files are read, with the reference's meaning: ``color_type='color'`` (the default)
+    applies the EXIF orientation, ``'color_ignore_orientation'`` does not."""
+    dataset = build_dataset(cfg)
+    if dataset.pipeline is None:
+        raise ValueError('build_train_loader: the dataset block has no pipeline')
+    color_type = 'color'
+    stack = list(dataset.pipeline)
+    while stack:
+        t = stack.pop()
+        if t['type'] == 'LoadImageFromFile':
+            color_type = t.get('color_type', 'color')
+        stack += list(t.get('individual_pipeline', ()))
+    if color_type not in ('color', 'color_ignore_orientation'):
+        raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' and "
+                                  "'color_ignore_orientation' only)")
+    pipeline = build_train_pipeline(dataset.pipeline, device=device)
+    return TrainLoader(dataset, pipeline, samples_per_gpu, seed=seed, rank=rank, world=world, device=device,
+                       entropy=entropy, prefetch=prefetch, on_unsupported=on_unsupported,
+                       orientation=color_type == 'color')

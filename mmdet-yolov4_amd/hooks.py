@@ -109,6 +109,17 @@ class Hook:
         return (runner.iter + 1) % n == 0 if n > 0 else False
 
 
+@HOOKS.register_module()
+class DistSamplerSeedHook(Hook):
+    """mmcv's ``DistSamplerSeedHook`` (``mmcv/runner/hooks/sampler_seed.py``): the loader's sampler learns the epoch
+    before it starts, so that a resumed run shuffles as the uninterrupted one does."""
+
+    def before_epoch(self, runner):
+        sampler = getattr(runner.data_loader, 'sampler', None)
+        if hasattr(sampler, 'set_epoch'):
+            sampler.set_epoch(runner.epoch)
+
+
 # ---- a22 ---------------------------------------------------------------------------------------------
 @HOOKS.register_module()
 class Fp16GradAccumulateOptimizerHook(Hook):

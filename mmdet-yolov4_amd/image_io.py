@@ -12,8 +12,11 @@ points (``yv4_jpeg_entropy_decode_device_sync``), which is what gives a file wit
 whatever that path cannot prove goes through the ``'device'`` kernel again.
 
 The pixels equal libjpeg-turbo's default decode bit for bit, which is what ``cv2.imdecode``, turbojpeg and Pillow -- every
-backend of ``mmcv.imfrombytes`` -- return.  **One known difference**: EXIF orientation is not applied
-(``cv2.imdecode(IMREAD_COLOR)`` rotates by it; turbojpeg and Pillow do not either).
+backend of ``mmcv.imfrombytes`` -- return.  EXIF orientation (``cv2.imdecode(IMREAD_COLOR)`` and
+``mmcv.imread(flag='color')`` rotate by it; turbojpeg and a bare Pillow decode do not) is read by the header parse
+(``JpegInfo.orientation``) and applied by the pixel stage where the caller asks: ``orientation=True`` of ``imdecode`` /
+``imread`` / ``decode_into``, ``apply_orientation=True`` of ``LoadImageFromFile``.  The default is off; the training
+loader (``datasets.TrainLoader``) turns it on for ``color_type='color'``, as the reference's reader does.
 
 Accepted: 8-bit baseline (SOF0 / SOF1 Huffman) files, grayscale or YCbCr in 4:4:4, 4:2:2 or 4:2:0.  Progressive,
 arithmetic-coded, 12-bit, lossless, CMYK and multi-scan files and every other format raise ``NotImplementedError``.
@@ -330,8 +333,55 @@ def jpeg_entropy_decode_device(bufs, device=None, coef=None, status=None, tables
     return t, coef, status
 
 
+class HostHalf:
+    """What the host does for a batch before any GPU call, so that a worker thread can do it ahead of time
+    (``decode_into(host=...)``): the header parses (``infos``), with a device mode the scan and chunk tables, with
+    ``'host'`` the Huffman decodes into ``coef`` (int16, the images back to back as ``yv4_jpeg_layout`` places them).
+    Makes no HIP and no torch call.  A refused or malformed file raises as ``imdecode`` does, naming the image."""
+
+    def __init__(self, bufs, entropy=None, chunk_bytes=None, max_rounds=None, what='imdecode'):
+        self.mode = _entropy_mode(entropy)
+        self.chunk_bytes, self.max_rounds = chunk_bytes, max_rounds
+        if self.mode == 'device_sync' or chunk_bytes is not None or max_rounds is not None:
+            self.chunk_bytes, self.max_rounds = _sync_params(chunk_bytes, max_rounds)
+        L = _lib.lib()
+        N = len(bufs)
+        self.bufs, self.scan, self.chunks, self.coef = bufs, None, None, None
+        if self.mode != 'host':
+            self.scan = ScanTables(bufs, what=what)
+            self.infos = self.scan.infos
+            if self.mode == 'device_sync' and not _one_chunk_each(self.scan, self.chunk_bytes):
+                self.chunks = ChunkTables(self.scan, self.chunk_bytes)
+            return
+        self.infos = (JpegInfo * N)()
+        for n, b in enumerate(bufs):
+            st = L.yv4_jpeg_parse(b, len(b), C.byref(self.infos[n]))
+            if st != 0:
+                _raise(st, f'{what}: image {n}')
+        offs = np.concatenate([[0], np.cumsum([int(f.ncoef) for f in self.infos])])
+        self.coef = np.empty(int(offs[-1]), np.int16)
+
+        def one(n):
+            info = JpegInfo()
+            st = L.yv4_jpeg_entropy_decode(bufs[n], len(bufs[n]), C.byref(info), self.coef.ctypes.data + 2 * int(offs[n]),
+                                           int(self.infos[n].ncoef))
+            if st != 0:
+                _raise(st, f'{what}: image {n}')
+
+        if N == 1:
+            one(0)
+        else:
+            with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, N)) as pool:      # ctypes releases the GIL
+                list(pool.map(one, range(N)))
+
+
+def oriented_size(t):
+    """``(height, width)`` of the picture a ``JpegImage`` entry writes: swapped for orientations 5 to 8."""
+    return (int(t.width), int(t.height)) if t.orientation >= 5 else (int(t.height), int(t.width))
+
+
 def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None, entropy=None, chunk_bytes=None,
-                max_rounds=None):
+                max_rounds=None, orientation=False, host=None):
     """The batch decode behind ``imdecode``: ``bufs`` (a list of JPEG byte strings) -> ``(out, table)``, ``out`` the flat
     ``torch.uint8`` device buffer and ``table`` the ``JpegImage`` array saying where each image lies in it.  With ``out``
     and ``placement`` (``(byte offset, row pitch)`` per image) the pixels go into the caller's buffer instead -- rows of
@@ -346,13 +396,24 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
     bad image -- by then the batch's pixels have been written (a caller's ``out`` included).  ``'device_sync'`` reads a
     second word per image in that read-back: the images its chunks could not prove, damaged ones among them, are then
     decoded by the ``'device'`` kernel, which decides their status, and the batch is reconstructed again.  A batch whose
-    segments are all at most one chunk long takes the ``'device'`` path directly."""
+    segments are all at most one chunk long takes the ``'device'`` path directly.
+
+    ``orientation=True`` applies each file's EXIF orientation in the pixel stage (``yv4_jpeg_layout_oriented``): the table
+    then carries it, ``oriented_size`` gives the picture's size, and a ``placement`` pitch counts against the oriented
+    width -- one that is too narrow raises ``ValueError`` before any launch.  It is the same in every entropy mode.
+    ``host``: a ``HostHalf`` of ``bufs`` made before, on another thread say; its mode and chunk parameters are used."""
     if not torch.cuda.is_available():
         raise RuntimeError('the JPEG decoder reconstructs the pixels on the GPU through libyv4_hip.so (there is no CPU '
                            'fallback)')
-    mode = _entropy_mode(entropy)
-    if mode == 'device_sync' or chunk_bytes is not None or max_rounds is not None:
-        chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
+    if host is not None:
+        mode, chunk_bytes, max_rounds = host.mode, host.chunk_bytes, host.max_rounds
+    else:
+        mode = _entropy_mode(entropy)
+        if mode == 'device_sync' or chunk_bytes is not None or max_rounds is not None:
+            chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
+    if orientation and not _lib.has_jpeg_orientation():
+        raise RuntimeError('orientation=True needs yv4_jpeg_layout_oriented, which the loaded libyv4_hip.so does not export '
+                           '(there is no fallback): rebuild it')
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     L = _lib.lib()
     N = len(bufs)
@@ -364,10 +425,15 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
         if mode == 'device_sync' and not _lib.has_jpeg_sync():
             raise RuntimeError("entropy='device_sync' needs yv4_jpeg_entropy_decode_device_sync, which the loaded "
                                'libyv4_hip.so does not export (there is no fallback): rebuild it')
-        scan = ScanTables(bufs, what='imdecode')
+        if host is not None:
+            scan, chunks = host.scan, host.chunks
+        else:
+            scan = ScanTables(bufs, what='imdecode')
+            if mode == 'device_sync' and not _one_chunk_each(scan, chunk_bytes):
+                chunks = ChunkTables(scan, chunk_bytes)
         infos = scan.infos
-        if mode == 'device_sync' and not _one_chunk_each(scan, chunk_bytes):
-            chunks = ChunkTables(scan, chunk_bytes)
+    elif host is not None:
+        infos = host.infos
     else:
         infos = (JpegInfo * N)()
         for n, b in enumerate(bufs):
@@ -376,7 +442,10 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
                 _raise(st, f'imdecode: image {n}')
     table = (JpegImage * N)()
     totals = (C.c_int64 * 3)()
-    check(L.yv4_jpeg_layout(infos, N, table, totals), 'yv4_jpeg_layout')
+    if orientation:
+        check(L.yv4_jpeg_layout_oriented(infos, N, 1, table, totals), 'yv4_jpeg_layout_oriented')
+    else:
+        check(L.yv4_jpeg_layout(infos, N, table, totals), 'yv4_jpeg_layout')
     ncoef, work_bytes, out_bytes = (int(t) for t in totals)
     if placement is not None:
         if out is None or out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != 'cuda':
@@ -384,6 +453,9 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
         out_bytes = out.numel()
         for n, (off, pitch) in enumerate(placement):
             table[n].out_off, table[n].out_pitch = int(off), int(pitch)
+            if orientation and int(pitch) < 3 * oriented_size(table[n])[1]:      # before the scan decode's launch
+                raise ValueError(f'imdecode: image {n}: pitch {int(pitch)} is narrower than its oriented row of '
+                                 f'{3 * oriented_size(table[n])[1]} bytes')
 
     # one pinned staging buffer: [per-image table | quantisation tables (N, 4, 64) uint16 | ...
     quant_off = _align(C.sizeof(table))
@@ -411,6 +483,8 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
             if obj is not None:
                 C.memmove(base + off, obj, size)
         scan.write_bytes(base + offs[4])
+    elif host is not None:
+        C.memmove(base + coef_off, host.coef.ctypes.data, 2 * ncoef)
     elif N == 1:
         entropy_host(0)
     else:
@@ -470,29 +544,33 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
     return out, table
 
 
-def imdecode(buffers, channel_order='bgr', device=None, entropy=None, chunk_bytes=None, max_rounds=None):
+def imdecode(buffers, channel_order='bgr', device=None, entropy=None, chunk_bytes=None, max_rounds=None,
+             orientation=False):
     """``buffers``: the bytes of one JPEG file or a list of them -> a ``torch.uint8`` (h, w, 3) tensor on ``device``
     (default: the current GPU), or a list of them.  ``channel_order``: ``'bgr'`` (what ``mmcv.imread`` returns) or
     ``'rgb'``; a grayscale file gives its plane three times, like ``flag='color'``.  A list is decoded as one batch:
     the entropy decodes on a thread pool, then one upload and one reconstruct call -- or, with ``entropy='device'``, the
     files go up and a kernel decodes their scans, one lane per restart segment, or with ``entropy='device_sync'`` one lane
     per ``chunk_bytes`` of a segment after at most ``max_rounds`` synchronisation rounds (``decode_into``; ``None``:
-    ``DEFAULT_ENTROPY``, which starts as ``'host'``).  EXIF orientation is not applied."""
+    ``DEFAULT_ENTROPY``, which starts as ``'host'``).  ``orientation=True`` applies the EXIF orientation, as
+    ``mmcv.imread(flag='color')`` does: the tensor is then (w, h, 3) for orientations 5 to 8.  The default leaves it
+    alone."""
     if channel_order not in ('bgr', 'rgb'):
         raise ValueError(f"channel_order {channel_order!r} is not 'bgr' or 'rgb'")
     single = not isinstance(buffers, (list, tuple))
     bufs = [_as_bytes(b) for b in ([buffers] if single else buffers)]
     if not bufs:
         return []
-    out, table = decode_into(bufs, channel_order, device, entropy=entropy, chunk_bytes=chunk_bytes, max_rounds=max_rounds)
+    out, table = decode_into(bufs, channel_order, device, entropy=entropy, chunk_bytes=chunk_bytes, max_rounds=max_rounds,
+                             orientation=orientation)
     imgs = []
     for t in table:
-        h, w, off = int(t.height), int(t.width), int(t.out_off)
+        (h, w), off = oriented_size(t), int(t.out_off)
         imgs.append(out[off:off + h * w * 3].view(h, w, 3))
     return imgs[0] if single else imgs
 
 
-def imread(paths, channel_order='bgr', device=None, entropy=None, chunk_bytes=None, max_rounds=None):
+def imread(paths, channel_order='bgr', device=None, entropy=None, chunk_bytes=None, max_rounds=None, orientation=False):
     """``paths``: a file name (``str`` / ``os.PathLike``) or a list of them -> what ``imdecode`` returns for their bytes."""
     single = not isinstance(paths, (list, tuple))
     bufs = []
@@ -500,7 +578,7 @@ def imread(paths, channel_order='bgr', device=None, entropy=None, chunk_bytes=No
         with open(os.fspath(p), 'rb') as f:
             bufs.append(f.read())
     return imdecode(bufs[0] if single else bufs, channel_order=channel_order, device=device, entropy=entropy,
-                    chunk_bytes=chunk_bytes, max_rounds=max_rounds)
+                    chunk_bytes=chunk_bytes, max_rounds=max_rounds, orientation=orientation)
 
 
 @PIPELINES.register_module()
@@ -509,14 +587,19 @@ class LoadImageFromFile:
     ``img_prefix`` / ``img_info['filename']`` and fills ``filename``, ``ori_filename``, ``img``, ``img_shape``,
     ``ori_shape`` and ``img_fields``.  ``img`` is a (h, w, 3) BGR tensor on the GPU -- ``torch.uint8``, or
     ``torch.float32`` with ``to_float32``.  ``im_decode_backend`` is accepted and ignored: every backend the reference
-    offers for JPEG runs libjpeg-turbo's default decode, which is what ``imread`` computes.  EXIF orientation is not
-    applied (the reference's cv2 backend applies it).  ``entropy``, ``chunk_bytes``, ``max_rounds``: where and how the
+    offers for JPEG runs libjpeg-turbo's default decode, which is what ``imread`` computes.  ``color_type``: ``'color'`` or
+    ``'color_ignore_orientation'``.  EXIF orientation is applied with ``apply_orientation=True`` and never with
+    ``'color_ignore_orientation'``; the default is off (``mmcv.imread(flag='color')`` applies it: the training loader,
+    ``datasets.build_train_loader``, turns it on for ``'color'``).  ``entropy``, ``chunk_bytes``, ``max_rounds``: where and how the
     Huffman scan is decoded (``imdecode``)."""
 
     def __init__(self, to_float32=False, color_type='color', file_client_args=dict(backend='disk'), im_decode_backend=None,
-                 device=None, entropy=None, chunk_bytes=None, max_rounds=None):
-        if color_type != 'color':
-            raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' only)")
+                 device=None, entropy=None, chunk_bytes=None, max_rounds=None, apply_orientation=False):
+        if color_type not in ('color', 'color_ignore_orientation'):
+            raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' and "
+                                      "'color_ignore_orientation' only)")
+        if apply_orientation and color_type == 'color_ignore_orientation':
+            raise ValueError("apply_orientation=True contradicts color_type='color_ignore_orientation'")
         if dict(file_client_args) != dict(backend='disk'):
             raise NotImplementedError(f'LoadImageFromFile(file_client_args={dict(file_client_args)!r}) is not built '
                                       "(dict(backend='disk') only)")
@@ -525,6 +608,7 @@ class LoadImageFromFile:
         self.file_client_args = dict(file_client_args)
         self.im_decode_backend = im_decode_backend
         self.device = device
+        self.apply_orientation = bool(apply_orientation)
         self.entropy = None if entropy is None else _entropy_mode(entropy)
         self.chunk_bytes = self.max_rounds = None
         if chunk_bytes is not None or max_rounds is not None:
@@ -536,7 +620,7 @@ class LoadImageFromFile:
         else:
             filename = results['img_info']['filename']
         img = imread(filename, device=self.device, entropy=self.entropy, chunk_bytes=self.chunk_bytes,
-                     max_rounds=self.max_rounds)
+                     max_rounds=self.max_rounds, orientation=self.apply_orientation)
         if self.to_float32:
             img = img.float()
         results['filename'] = filename

@@ -175,6 +175,7 @@ ACTIVATION_LAYERS = Registry('activation layer')
 NORM_LAYERS = Registry('norm layer')
 HOOKS = Registry('hook')
 PIPELINES = Registry('pipeline')      # mmdet/datasets/builder.py:13
+DATASETS = Registry('dataset')        # mmdet/datasets/builder.py:12
 
 
 def build_backbone(cfg):

@@ -8,7 +8,10 @@
 // For every file given: parse and entropy-decode it as it is, every prefix of it, and every single-byte change
 // (XOR 0xFF, +1 and one set bit) inside the header segments and the first bytes of the scan.  The coefficient buffer
 // is exactly info.ncoef elements on the heap, the input an exact-length heap copy, so AddressSanitizer sees any read
-// or write past either.  Exit status 0: nothing was reported; the counts of each return code are printed.
+// or write past either.  A file that carries an APP1 segment (the EXIF fixtures of tests/golden/jpeg_exif.npz, which
+// jpeg_fixtures_dump.py writes as well) gets one more pass: the same three changes of every byte of every APP1 segment
+// through yv4_jpeg_parse alone, whose orientation must stay within 0 .. 8 and whose other fields must not depend on the
+// segment's payload.  Exit status 0: nothing was reported; the counts of each return code are printed.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
@@ -30,6 +33,55 @@ void set_error(const char* fmt, ...) {      // the library's is in api.hip
 }  // namespace yv4
 
 static long g_count[5];      // OK, INVALID, UNSUPPORTED, (LAUNCH), CAPACITY
+static long g_app1_inputs, g_app1_files, g_orient[9];
+
+// parse only, on an exact-length heap copy -> status; info is filled
+static int parse_copy(const uint8_t* src, size_t len, yv4_jpeg_info* info) {
+  uint8_t* data = (uint8_t*)malloc(len ? len : 1);
+  memcpy(data, src, len);
+  const int st = yv4_jpeg_parse(data, len, info);
+  free(data);
+  if (st == YV4_OK && (info->orientation < 0 || info->orientation > 8)) {
+    fprintf(stderr, "parse returned orientation %d\n", info->orientation);
+    exit(2);
+  }
+  return st;
+}
+
+// every byte of every APP1 payload (after its length field), three changes each, through the parse alone
+static void app1_pass(std::vector<uint8_t>& buf) {
+  yv4_jpeg_info base;
+  if (parse_copy(buf.data(), buf.size(), &base) != YV4_OK) return;
+  ++g_orient[base.orientation];
+  bool any = false;
+  size_t pos = 2;
+  while (pos + 4 <= buf.size() && pos < (size_t)base.scan_offset && buf[pos] == 0xFF) {
+    const unsigned m = buf[pos + 1];
+    const size_t seglen = ((size_t)buf[pos + 2] << 8) | buf[pos + 3];
+    if (seglen < 2 || pos + 2 + seglen > buf.size()) break;
+    if (m == 0xE1) {
+      any = true;
+      for (size_t i = pos + 4; i < pos + 2 + seglen; ++i) {
+        const uint8_t keep = buf[i];
+        const uint8_t variants[3] = {(uint8_t)(keep ^ 0xFF), (uint8_t)(keep + 1), (uint8_t)(keep ^ (1u << (i & 7)))};
+        for (int v = 0; v < 3; ++v) {
+          buf[i] = variants[v];
+          yv4_jpeg_info info;
+          const int st = parse_copy(buf.data(), buf.size(), &info);
+          ++g_app1_inputs;
+          info.orientation = base.orientation;
+          if (st != YV4_OK || memcmp(&info, &base, sizeof(info)) != 0) {
+            fprintf(stderr, "a change inside an APP1 payload (offset %zu) changed more than the orientation\n", i);
+            exit(2);
+          }
+        }
+        buf[i] = keep;
+      }
+    }
+    pos += 2 + seglen;
+  }
+  if (any) ++g_app1_files;
+}
 
 static int run(const uint8_t* src, size_t len) {
   uint8_t* data = (uint8_t*)malloc(len ? len : 1);      // exact length: a read past it is a heap overflow
@@ -37,6 +89,10 @@ static int run(const uint8_t* src, size_t len) {
   yv4_jpeg_info info, info2;
   int st = yv4_jpeg_parse(data, len, &info);
   if (st == YV4_OK) {
+    if (info.orientation < 0 || info.orientation > 8) {
+      fprintf(stderr, "parse returned orientation %d\n", info.orientation);
+      exit(2);
+    }
     if (info.ncoef <= 0 || info.ncoef > (int64_t)64 * 3 * 8192 * 8192) {
       fprintf(stderr, "parse returned OK with ncoef %lld\n", (long long)info.ncoef);
       exit(2);
@@ -100,7 +156,11 @@ int main(int argc, char** argv) {
       }
       buf[i] = keep;
     }
+    app1_pass(buf);
   }
+  printf("APP1: %ld files, %ld changed inputs; orientation of the files as given:", g_app1_files, g_app1_inputs);
+  for (int o = 0; o <= 8; ++o) printf(" %d:%ld", o, g_orient[o]);
+  printf("\n");
   printf("ok %ld  invalid %ld  unsupported %ld  capacity %ld\n", g_count[0], g_count[1], g_count[2], g_count[4]);
   return 0;
 }

@@ -3,7 +3,8 @@
 Small integers are exact in bf16, fp16 and fp32, and so are their products.  While every partial sum is an integer
 below 2**24, every fp32 summation order gives the same exact value, so a correct kernel equals a float64 reference bit
 for bit on any route and at any size; a 16-bit output is rounded once, which ``ref64.to(dtype)`` reproduces.  One
-dropped, duplicated or misplaced product changes the result.
+dropped, duplicated or misplaced product changes the result.  The fused forward epilogue stays exact as well on the
+operands of ``Epilogue`` (scales from {1, 2}, integer shifts, an integer residual, a leaky slope of 0.5).
 
 Tensors here are NHWC: x (N, H, W, Cin), dY / y (N, Ho, Wo, Cout); weights are (Cout, Cin, KH, KW) as torch has
 them, weight gradients (Cout, KH, KW, Cin) as the kernels write them.  The references are sums over taps of shifted
@@ -108,11 +109,110 @@ def fwd_ref(x, w, stride, pad, out_dtype=torch.float64):
     return out
 
 
+ACT_NONE, ACT_LEAKY = 0, 2     # YV4_ACT_NONE, YV4_ACT_LEAKY
+EXACT_SLOPE = 0.5              # a leaky slope that keeps integers exact: one more fractional bit per activation
+
+
+class Epilogue:
+    """Operands of the fused epilogue ``y = act2((act1(conv * s1 + t1) + residual) * s2 + t2)`` that keep it exact in
+    fp32: per-channel s from {1, 2} and t integers in [-3, 3] (seeded, fp32, on ``device``), the activations NONE or
+    LEAKY with slope 0.5.  ``affine1`` False: s1 = 1, t1 = 0 (the entry points always take a first stage);
+    ``two_stage`` False: no second stage at all.  The residual is the caller's (``int_operand``)."""
+
+    def __init__(self, Cout, seed, device, affine1=True, act1=ACT_NONE, two_stage=False, act2=ACT_NONE):
+        g = torch.Generator(device=device).manual_seed(seed)
+
+        def st():
+            s = torch.randint(1, 3, (Cout,), generator=g, device=device).float()
+            t = torch.randint(-3, 4, (Cout,), generator=g, device=device).float()
+            return s, t
+        self.s1, self.t1 = st()
+        self.s2, self.t2 = st()
+        if not affine1:
+            self.s1, self.t1 = torch.ones_like(self.s1), torch.zeros_like(self.t1)
+        assert act1 in (ACT_NONE, ACT_LEAKY) and act2 in (ACT_NONE, ACT_LEAKY)
+        self.act1, self.act2, self.two_stage = act1, act2 if two_stage else ACT_NONE, two_stage
+        self.slope = EXACT_SLOPE
+
+    def bound(self, conv_bound, res_max=0):
+        """Worst-case magnitude after the whole epilogue times 2**(fractional bits): below EXACT_LIMIT, every
+        intermediate and the result are exact in fp32 (a slope of 0.5 adds one fractional bit per activation, an
+        integer affine none)."""
+        b = conv_bound * amax(self.s1) + amax(self.t1)
+        frac = 1 if self.act1 == ACT_LEAKY else 0
+        b += res_max
+        if self.two_stage:
+            b = b * amax(self.s2) + amax(self.t2)
+            frac += 1 if self.act2 == ACT_LEAKY else 0
+        return b * 2 ** frac
+
+    def guard(self, terms, *maxima, res_max=0):
+        """``guard`` for the convolution's partial sums AND for the epilogue's result."""
+        conv_bound = guard(terms, *maxima)
+        return guard(1, self.bound(conv_bound, res_max))
+
+
+def _act64(v, act, slope):
+    return torch.where(v >= 0, v, v * slope) if act == ACT_LEAKY else v
+
+
+def epilogue_ref(conv64, ep, residual=None):
+    """The fused epilogue on a float64 convolution (N, Ho, Wo, Cout), every step in float64."""
+    v = _act64(conv64 * ep.s1.double() + ep.t1.double(), ep.act1, ep.slope)
+    if residual is not None:
+        v = v + residual.double()
+    if ep.two_stage:
+        v = _act64(v * ep.s2.double() + ep.t2.double(), ep.act2, ep.slope)
+    return v
+
+
+def fwd_epilogue_ref(x, w, stride, pad, ep, residual=None):
+    return epilogue_ref(fwd_ref(x, w, stride, pad), ep, residual)
+
+
+REF_SHAPES_CPU = [(2, 7, 5, 3, 4, 3, 1, 1), (2, 9, 8, 5, 6, 3, 2, 1), (1, 6, 7, 4, 3, 1, 2, 0),
+                  (3, 5, 5, 2, 3, 1, 1, 0), (1, 12, 11, 3, 2, 6, 2, 2), (2, 8, 8, 4, 5, 3, 2, 0)]
+
+
+def check_epilogue_ref_cpu():
+    """``fwd_epilogue_ref`` against F.conv2d plus the same expression written out in float64 (NCHW, F.leaky_relu), on
+    the shapes of ``check_refs_cpu``, every combination of stages; the result is exact in fp32 (it survives the round
+    trip) and below the guard's bound."""
+    for i, (N, H, W, Cin, Cout, K, s, p) in enumerate(REF_SHAPES_CPU):
+        x = int_operand((N, H, W, Cin), 1, 'cpu')
+        w = int_operand((Cout, Cin, K, K), 2, 'cpu')
+        Ho, Wo = out_size(H, K, s, p), out_size(W, K, s, p)
+        res = int_operand((N, Ho, Wo, Cout), 3, 'cpu')
+        conv = F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), None, s, p)
+        for affine1 in (False, True):
+            for act1 in (ACT_NONE, ACT_LEAKY):
+                for use_res in (False, True):
+                    for two_stage, act2 in ((False, ACT_NONE), (True, ACT_NONE), (True, ACT_LEAKY)):
+                        ep = Epilogue(Cout, 10 + i, 'cpu', affine1, act1, two_stage, act2)
+                        assert set(ep.s2.tolist()) <= {1.0, 2.0} and ep.t2.abs().max() <= 3
+                        c = lambda t: t.double()[None, :, None, None]
+                        v = conv * c(ep.s1) + c(ep.t1) if affine1 else conv
+                        if act1 == ACT_LEAKY:
+                            v = F.leaky_relu(v, 0.5)
+                        if use_res:
+                            v = v + res.double().permute(0, 3, 1, 2)
+                        if two_stage:
+                            v = v * c(ep.s2) + c(ep.t2)
+                            if act2 == ACT_LEAKY:
+                                v = F.leaky_relu(v, 0.5)
+                        got = fwd_epilogue_ref(x, w, s, p, ep, res if use_res else None)
+                        assert torch.equal(got, v.permute(0, 2, 3, 1))
+                        assert torch.equal(got.float().double(), got)
+                        b = ep.guard(K * K * Cin, amax(x), amax(w), res_max=amax(res) if use_res else 0)
+                        frac = (act1 == ACT_LEAKY) + (two_stage and act2 == ACT_LEAKY)
+                        assert float(got.abs().max()) * 2 ** frac <= b
+                        assert torch.equal(got * 2 ** frac, (got * 2 ** frac).round())
+
+
 def check_refs_cpu():
     """The three references against F.conv2d and torch.nn.grad in float64 on the CPU, at small shapes covering 1x1,
     3x3 and 6x6 windows, stride 1 and 2, even and odd sizes."""
-    for (N, H, W, Cin, Cout, K, s, p) in [(2, 7, 5, 3, 4, 3, 1, 1), (2, 9, 8, 5, 6, 3, 2, 1), (1, 6, 7, 4, 3, 1, 2, 0),
-                                          (3, 5, 5, 2, 3, 1, 1, 0), (1, 12, 11, 3, 2, 6, 2, 2), (2, 8, 8, 4, 5, 3, 2, 0)]:
+    for (N, H, W, Cin, Cout, K, s, p) in REF_SHAPES_CPU:
         x = int_operand((N, H, W, Cin), 1, 'cpu')
         w = int_operand((Cout, Cin, K, K), 2, 'cpu').double()
         Ho, Wo = out_size(H, K, s, p), out_size(W, K, s, p)

@@ -14,6 +14,22 @@ def test_references_match_torch_float64():
     X.check_refs_cpu()
 
 
+def test_epilogue_reference_matches_torch_float64():
+    X.check_epilogue_ref_cpu()
+
+
+def test_epilogue_guard_counts_scales_shifts_residual_and_fractional_bits():
+    """(conv * 2 + 3 + residual) * 2 + 3 with two slope-0.5 activations: the bound is the magnitude times 4."""
+    ep = X.Epilogue(64, 0, 'cpu', True, X.ACT_LEAKY, True, X.ACT_LEAKY)
+    s1, t1, s2, t2 = X.amax(ep.s1), X.amax(ep.t1), X.amax(ep.s2), X.amax(ep.t2)
+    assert (s1, s2) == (2, 2) and t1 <= 3 and t2 <= 3
+    assert ep.bound(1000, res_max=2) == ((1000 * s1 + t1 + 2) * s2 + t2) * 4
+    assert X.Epilogue(64, 0, 'cpu', False).bound(1000) == 1000
+    ep.guard(9 * 512, 2, 2, res_max=2)
+    with pytest.raises(AssertionError, match='not exact'):
+        ep.guard(2 ** 18, 2, 2, res_max=2)          # the convolution alone would pass: 2**20
+
+
 def test_int_operand_values_and_seed():
     a = X.int_operand((3, 5, 7, 11), 4, 'cpu', torch.bfloat16)
     assert set(a.float().unique().tolist()) == {-2.0, -1.0, 1.0, 2.0}

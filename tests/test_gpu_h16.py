@@ -134,7 +134,7 @@ SPLITK_SHAPES = [
     (1, 38, 38, 128, 256, 3, 2, 1),     # stride 2
     (1, 19, 19, 1024, 255, 1, 1, 0),    # head: Cout 255 (slab rows padded to 256)
     (1, 11, 13, 192, 72, 3, 1, 1),      # ragged M, Cout tail inside an 8-channel group
-    (1, 76, 76, 128, 128, 3, 1, 1),     # 182 tiles: two ways
+    (1, 76, 76, 128, 128, 3, 1, 1),     # 182 tiles, 18 slices: four ways
 ]
 
 

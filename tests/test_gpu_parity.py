@@ -219,8 +219,8 @@ def test_conv_wide_f32_refuses_what_it_cannot_address(gpu_device):
         _conv_case(gpu_device, 1, 12, 12, 32, 64, 3, 1, 1, 1, 43, out_extra=3)       # rows that are not 16-byte aligned
 
 
-@pytest.mark.parametrize('tile', [L.TILE_128x128, L.TILE_128x64, L.TILE_64x128, L.TILE_64x64, L.TILE_DMA_64x64, L.TILE_DMA_128x64, L.TILE_DMA_128x128, L.TILE_STEM])
-@pytest.mark.parametrize('shape', [
+TILES_F32 = [L.TILE_128x128, L.TILE_128x64, L.TILE_64x128, L.TILE_64x64, L.TILE_DMA_64x64, L.TILE_DMA_128x64, L.TILE_DMA_128x128, L.TILE_STEM]
+SHAPES = [
     # N, H, W, Cin, Cout, k, stride, pad
     (2, 19, 19, 64, 128, 3, 1, 1),     # uniform-tap path, ragged M (722 rows)
     (1, 16, 20, 32, 255, 1, 1, 0),     # head-like: Cout 255 not a tile multiple
@@ -230,7 +230,11 @@ def test_conv_wide_f32_refuses_what_it_cannot_address(gpu_device):
     (1, 24, 24, 3, 16, 6, 2, 2),       # Focus conv k=6 s=2 p=2
     (1, 9, 37, 3, 16, 3, 1, 1),        # stem, W not a multiple of 32, Cout 16 (v4s)
     (1, 8, 70, 3, 40, 3, 1, 1),        # stem, Cout 40 (v4x): two column tiles
-])
+]
+
+
+@pytest.mark.parametrize('tile', TILES_F32)
+@pytest.mark.parametrize('shape', SHAPES)
 def test_conv_shapes_and_tiles(gpu_device, shape, tile):
     stem_shape = shape[3] == 3 and shape[5:] == (3, 1, 1)
     if tile == L.TILE_STEM and not stem_shape:

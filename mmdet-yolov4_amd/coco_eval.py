@@ -47,7 +47,8 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib
+from . import _eval_common, _lib
+from ._eval_common import _dev, _is_flat, _log, _offsets, _ptr
 from ._lib import check
 from .ops import stream_ptr
 
@@ -58,27 +59,7 @@ METRIC_NAMES = {'mAP': 0, 'mAP_50': 1, 'mAP_75': 2, 'mAP_s': 3, 'mAP_m': 4, 'mAP
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError('coco_eval runs on the GPU through libyv4_hip.so; no GPU is visible '
-                           '(there is no CPU fallback for this path)')
-    if not _lib.has_coco_eval():
-        raise RuntimeError('the loaded libyv4_hip.so has no yv4_coco_rank / yv4_coco_match / yv4_coco_accumulate; rebuild it')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _offsets(counts):
-    off = np.zeros(len(counts) + 1, np.int64)
-    np.cumsum(counts, out=off[1:])
-    return off
-
-
-def _log(msg, logger, level=logging.INFO):
-    if logger is None:
-        print(msg)
-    elif isinstance(logger, logging.Logger):
-        logger.log(level, msg)
-    elif logger != 'silent':
-        logging.getLogger(logger).log(level, msg)
+    return _eval_common._device('coco_eval', _lib.has_coco_eval, 'yv4_coco_rank / yv4_coco_match / yv4_coco_accumulate')
 
 
 class CocoGt:
@@ -147,10 +128,6 @@ def flatten_results(results):
     labels = np.repeat(np.tile(np.arange(C, dtype=np.int64), len(results)), lens.reshape(-1))
     img_index = np.repeat(np.arange(len(results), dtype=np.int64), lens.sum(axis=1))
     return dets, labels, img_index
-
-
-def _is_flat(results):
-    return isinstance(results, tuple) and len(results) == 3 and not isinstance(results[0], (list, tuple))
 
 
 class COCOeval:
@@ -250,24 +227,21 @@ class COCOeval:
         if T == 0 or A == 0 or len(p.maxDets) == 0:
             raise ValueError('params.iouThrs, params.areaRng and params.maxDets must not be empty')
         max_last = int(p.maxDets[-1])
-
-        def up(a, dtype):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
-        dets = dets.to(dev, torch.float32).contiguous() if isinstance(dets, torch.Tensor) else up(dets, np.float32)
-        labels = labels.to(dev) if isinstance(labels, torch.Tensor) else up(labels, np.int64)
-        img_index = img_index.to(dev) if isinstance(img_index, torch.Tensor) else up(img_index, np.int64)
+        dets = dets.to(dev, torch.float32).contiguous() if isinstance(dets, torch.Tensor) else _dev(dets, np.float32, dev)
+        labels = labels.to(dev) if isinstance(labels, torch.Tensor) else _dev(labels, np.int64, dev)
+        img_index = img_index.to(dev) if isinstance(img_index, torch.Tensor) else _dev(img_index, np.int64, dev)
         D = int(dets.shape[0])
         if dets.dim() != 2 or dets.shape[1] != 5 or labels.numel() != D or img_index.numel() != D:
             raise ValueError('flat results: dets (D, 5), labels (D,), img_index (D,)')
-        kmap, imap = up(tab['kmap'], np.int64), up(tab['imap'], np.int64)
+        kmap, imap = _dev(tab['kmap'], np.int64, dev), _dev(tab['imap'], np.int64, dev)
         labels, img_index = labels.reshape(-1).long(), img_index.reshape(-1).long()
         ok = (labels >= 0) & (labels < len(kmap)) & (img_index >= 0) & (img_index < len(imap))
         k = kmap[labels.clamp(0, len(kmap) - 1)]
         i = imap[img_index.clamp(0, len(imap) - 1)]
         prob = torch.where(ok & (k >= 0) & (i >= 0), i * K + k, torch.full_like(k, -1)).to(torch.int32)
-        gt_box, gt_area = up(tab['gt_box'].reshape(-1), np.float64), up(tab['gt_area'], np.float64)
-        gt_flag, gt_off = up(tab['gt_flag'], np.uint8), up(tab['gt_off'], np.int64)
-        t_thr, t_area = up(thrs, np.float64), up(area.reshape(-1), np.float64)
+        gt_box, gt_area = _dev(tab['gt_box'].reshape(-1), np.float64, dev), _dev(tab['gt_area'], np.float64, dev)
+        gt_flag, gt_off = _dev(tab['gt_flag'], np.uint8, dev), _dev(tab['gt_off'], np.int64, dev)
+        t_thr, t_area = _dev(thrs, np.float64, dev), _dev(area.reshape(-1), np.float64, dev)
         t2 = self._tick()
 
         lib = _lib.lib()
@@ -287,10 +261,7 @@ class COCOeval:
         state = torch.zeros(2, dtype=torch.int64, device=dev)
         flags = torch.empty(n1 * A * T, dtype=torch.uint8, device=dev)
         counts = torch.empty(K * A, dtype=torch.int32, device=dev)
-
-        def ptr(t):
-            return t.data_ptr() if t.numel() else None
-        check(lib.yv4_coco_match(ptr(dets), order.data_ptr(), det_off.data_ptr(), ptr(gt_box), ptr(gt_area), ptr(gt_flag),
+        check(lib.yv4_coco_match(_ptr(dets), order.data_ptr(), det_off.data_ptr(), _ptr(gt_box), _ptr(gt_area), _ptr(gt_flag),
                                  gt_off.data_ptr(), P, K, D, max_last, t_thr.data_ptr(), T, t_area.data_ptr(), A,
                                  mwork.data_ptr(), need, state.data_ptr(), flags.data_ptr(), counts.data_ptr(),
                                  stream_ptr()), 'yv4_coco_match')

@@ -8,8 +8,9 @@
 //                        (k, a, m, t) the cumulative tp / fp, precision envelope and the recall-threshold sampling
 // Every floating-point value is ONE IEEE float64 operation of the definition, in its order (compiled with
 // -ffp-contract=off); sums are integers.  Bit-exact against the definition; two runs give identical bytes.
-#include "radix_sort.h"
-#include "yv4_common.h"
+// The score key, the offsets kernel and the sorts' sizing are eval_common.h's; ce_scan_kernel's one-wave backward walk
+// is its own.
+#include "eval_common.h"
 
 namespace yv4 {
 namespace {
@@ -19,23 +20,6 @@ constexpr int kCeIouLds = 2048;      // a problem's IoU block sits in LDS up to 
 constexpr int kCeGtLds = 512;        // ... when its gts' matched bits do too (one bit per gt and lane)
 constexpr int kCeMaxRec = 256;       // recall thresholds held in LDS
 constexpr int kCeMaxM = 16;          // maxDets entries (passed by value)
-
-// float32 score -> a 32-bit key that ascends as the score DEscends.  float32 -> float64 is monotone and injective, so
-// ordering the float32 scores orders COCOeval's float64 ones; -0 and +0 compare equal there and share a key here.
-__device__ __forceinline__ uint32_t ce_desc_key(float s) {
-  const uint32_t b = __float_as_uint(s + 0.f);
-  const uint32_t u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ~u;
-}
-
-__device__ __forceinline__ int64_t ce_lower_bound(const uint64_t* __restrict__ keys, int64_t n, uint64_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 // doubles of workspace a problem needs per (a, t) lane group: the IoU block and 64 lanes' matched bits (0: both in LDS)
 __host__ __device__ __forceinline__ int64_t ce_problem_need(int64_t nd, int64_t ng) {
@@ -52,16 +36,8 @@ __global__ __launch_bounds__(256) void ce_keys1_kernel(const float* __restrict__
   if (d >= D) return;
   const int32_t p = prob[d];
   const uint32_t pp = (p < 0 || p >= P) ? (uint32_t)P : (uint32_t)p;       // outside every problem: sorted to the end
-  keys[d] = ((uint64_t)pp << 32) | ce_desc_key(det[5 * d + 4]);
+  keys[d] = ((uint64_t)pp << 32) | desc_key(det[5 * d + 4]);
   vals[d] = (uint32_t)d;
-}
-
-// off[q] = first sorted position whose key's high word is >= q, q = 0 .. Q
-__global__ __launch_bounds__(256) void ce_offsets_kernel(const uint64_t* __restrict__ keys, int64_t n, int Q,
-                                                         int64_t* __restrict__ off) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > Q) return;
-  off[q] = n > 0 ? ce_lower_bound(keys, n, (uint64_t)(uint32_t)q << 32) : 0;
 }
 
 __global__ __launch_bounds__(256) void ce_sprob_kernel(const uint64_t* __restrict__ keys, int64_t D,
@@ -202,7 +178,7 @@ __global__ __launch_bounds__(256) void ce_keys2_kernel(const float* __restrict__
   const int32_t p = sprob[s];
   uint64_t key = (uint64_t)(uint32_t)K << 32;             // cut by maxDets[-1] or outside every problem: to the end
   if (p < P && s - det_off[p] < max_det)
-    key = ((uint64_t)(uint32_t)(p % K) << 32) | ce_desc_key(det[5 * (int64_t)order[s] + 4]);
+    key = ((uint64_t)(uint32_t)(p % K) << 32) | desc_key(det[5 * (int64_t)order[s] + 4]);
   keys[s] = key;
   vals[s] = (uint32_t)s;
 }
@@ -323,8 +299,31 @@ __global__ __launch_bounds__(kCeLanes) void ce_scan_kernel(const int32_t* __rest
   }
 }
 
-static inline int ce_sort_bits(int q) { return q < 65535 ? 48 : 64; }     // the key's high word holds 0 .. q
-static inline size_t ce_hist_bytes(int64_t n) { return rs_hist_bytes(n + kRsTile); }   // reserves one tile more than rs_sort counts
+// the two workspaces, each read by its *_work function and its entry point
+struct CeRankLayout {       // keys x2 | values | histogram
+  size_t kx, ky, vy, hist;
+  Carve carve;
+  explicit CeRankLayout(int64_t D) {
+    const size_t n = (size_t)D;
+    kx = carve.take(8 * n), ky = carve.take(8 * n);
+    vy = carve.take(4 * n);
+    hist = carve.take(sort_hist_bytes(D));
+  }
+};
+
+struct CeAccumLayout {      // keys x2 | values x2 | histogram | cat_off | rank2 | score2 | flags2
+  size_t kx, ky, vx, vy, hist, cat_off, rank2, score2, flags2;
+  Carve carve;
+  CeAccumLayout(int64_t D, int K, int num_at) {
+    const size_t n = (size_t)(D > 0 ? D : 1);
+    kx = carve.take(8 * n), ky = carve.take(8 * n);
+    vx = carve.take(4 * n), vy = carve.take(4 * n);
+    hist = carve.take(sort_hist_bytes((int64_t)n));
+    cat_off = carve.take(8 * ((size_t)K + 1));
+    rank2 = carve.take(4 * n), score2 = carve.take(4 * n);
+    flags2 = carve.take(n * (size_t)num_at);
+  }
+};
 
 }  // namespace
 }  // namespace yv4
@@ -333,8 +332,7 @@ using namespace yv4;
 
 extern "C" size_t yv4_coco_rank_work(int64_t total_det) {
   if (total_det <= 0) return 256;
-  const size_t D = (size_t)total_det;
-  return 2 * align256(8 * D) + align256(4 * D) + ce_hist_bytes(total_det);    // keys x2 | values | histogram
+  return CeRankLayout(total_det).carve.off;
 }
 
 extern "C" int yv4_coco_rank(const float* det, const int32_t* prob, int64_t total_det, int P, int max_det, int num_at,
@@ -353,17 +351,18 @@ extern "C" int yv4_coco_rank(const float* det, const int32_t* prob, int64_t tota
   YV4_REQUIRE(det && prob && work && order && sprob, "coco_rank: null pointer");
   YV4_REQUIRE(((uintptr_t)work & 7) == 0, "coco_rank: work must be 8-byte aligned");
   const int64_t D = total_det;
+  const CeRankLayout L(D);
   char* w = reinterpret_cast<char*>(work);
-  uint64_t* kx = reinterpret_cast<uint64_t*>(w);
-  uint64_t* ky = reinterpret_cast<uint64_t*>(w + align256(8 * (size_t)D));
-  uint32_t* vy = reinterpret_cast<uint32_t*>(w + 2 * align256(8 * (size_t)D));
-  uint32_t* hist = reinterpret_cast<uint32_t*>(w + 2 * align256(8 * (size_t)D) + align256(4 * (size_t)D));
+  uint64_t* kx = reinterpret_cast<uint64_t*>(w + L.kx);
+  uint64_t* ky = reinterpret_cast<uint64_t*>(w + L.ky);
+  uint32_t* vy = reinterpret_cast<uint32_t*>(w + L.vy);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(w + L.hist);
   const unsigned blocks = (unsigned)((D + 255) / 256);
   hipLaunchKernelGGL(ce_keys1_kernel, dim3(blocks), dim3(256), 0, s, det, prob, D, P, kx, order);
   // the first pass only reads its input, so the keys / values are sorted "in place": the result lands in (kx, order)
-  const int rc = rs_sort<uint64_t, uint32_t, true>(kx, kx, ky, order, order, vy, D, ce_sort_bits(P), hist, s, "coco_rank: radix sort");
+  const int rc = rs_sort<uint64_t, uint32_t, true>(kx, kx, ky, order, order, vy, D, key_bits_hi32(P), hist, s, "coco_rank: radix sort");
   if (rc != YV4_OK) return rc;
-  hipLaunchKernelGGL(ce_offsets_kernel, dim3((unsigned)(P / 256 + 1)), dim3(256), 0, s, kx, D, P, det_off);
+  hipLaunchKernelGGL((offsets_kernel<uint64_t, 32>), dim3((unsigned)(P / 256 + 1)), dim3(256), 0, s, kx, D, P, det_off);
   hipLaunchKernelGGL(ce_sprob_kernel, dim3(blocks), dim3(256), 0, s, kx, D, sprob);
   hipLaunchKernelGGL(ce_need_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, det_off, gt_off, P, max_det,
                      (num_at + kCeLanes - 1) / kCeLanes, reinterpret_cast<unsigned long long*>(match_need));
@@ -401,10 +400,7 @@ extern "C" int yv4_coco_match(const float* det, const uint32_t* order, const int
 
 extern "C" size_t yv4_coco_accumulate_work(int64_t total_det, int K, int num_at) {
   if (total_det < 0 || K <= 0 || num_at <= 0) return 0;
-  const size_t D = (size_t)(total_det > 0 ? total_det : 1);
-  // keys x2 | values x2 | histogram | cat_off | rank2 | score2 | flags2
-  return 2 * align256(8 * D) + 2 * align256(4 * D) + ce_hist_bytes((int64_t)D) + align256(8 * ((size_t)K + 1)) +
-         2 * align256(4 * D) + align256(D * (size_t)num_at);
+  return CeAccumLayout(total_det, K, num_at).carve.off;
 }
 
 extern "C" int yv4_coco_accumulate(const float* det, const uint32_t* order, const int32_t* sprob, const int64_t* det_off,
@@ -425,18 +421,19 @@ extern "C" int yv4_coco_accumulate(const float* det, const uint32_t* order, cons
   YV4_REQUIRE(((uintptr_t)work & 7) == 0, "coco_accumulate: work must be 8-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t D = total_det;
-  const size_t Dn = (size_t)(D > 0 ? D : 1);
+  const int64_t Dn = D > 0 ? D : 1;
   const int AT = A * T;
+  const CeAccumLayout L(D, K, AT);
   char* w = reinterpret_cast<char*>(work);
-  uint64_t* kx = reinterpret_cast<uint64_t*>(w);                        w += align256(8 * Dn);
-  uint64_t* ky = reinterpret_cast<uint64_t*>(w);                        w += align256(8 * Dn);
-  uint32_t* vx = reinterpret_cast<uint32_t*>(w);                        w += align256(4 * Dn);
-  uint32_t* vy = reinterpret_cast<uint32_t*>(w);                        w += align256(4 * Dn);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(w);                      w += ce_hist_bytes((int64_t)Dn);
-  int64_t* cat_off = reinterpret_cast<int64_t*>(w);                     w += align256(8 * ((size_t)K + 1));
-  int32_t* rank2 = reinterpret_cast<int32_t*>(w);                       w += align256(4 * Dn);
-  float* score2 = reinterpret_cast<float*>(w);                          w += align256(4 * Dn);
-  uint8_t* flags2 = reinterpret_cast<uint8_t*>(w);
+  uint64_t* kx = reinterpret_cast<uint64_t*>(w + L.kx);
+  uint64_t* ky = reinterpret_cast<uint64_t*>(w + L.ky);
+  uint32_t* vx = reinterpret_cast<uint32_t*>(w + L.vx);
+  uint32_t* vy = reinterpret_cast<uint32_t*>(w + L.vy);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(w + L.hist);
+  int64_t* cat_off = reinterpret_cast<int64_t*>(w + L.cat_off);
+  int32_t* rank2 = reinterpret_cast<int32_t*>(w + L.rank2);
+  float* score2 = reinterpret_cast<float*>(w + L.score2);
+  uint8_t* flags2 = reinterpret_cast<uint8_t*>(w + L.flags2);
   const int64_t n_pr = (int64_t)T * R * K * A * M, n_rc = (int64_t)T * K * A * M;
   hipLaunchKernelGGL(ce_fill_kernel, dim3((unsigned)((n_pr + 255) / 256 < 4096 ? (n_pr + 255) / 256 : 4096)), dim3(256), 0, s,
                      precision, n_pr, -1.0);
@@ -449,7 +446,7 @@ extern "C" int yv4_coco_accumulate(const float* det, const uint32_t* order, cons
     hipLaunchKernelGGL(ce_keys2_kernel, dim3(blocks), dim3(256), 0, s, det, order, sprob, det_off, D, P, K, max_last, kx, vx);
     const int rc = rs_sort<uint64_t, uint32_t, true>(kx, kx, ky, vx, vx, vy, D, 48, hist, s, "coco_accumulate: radix sort");
     if (rc != YV4_OK) return rc;
-    hipLaunchKernelGGL(ce_offsets_kernel, dim3((unsigned)(K / 256 + 1)), dim3(256), 0, s, kx, D, K, cat_off);
+    hipLaunchKernelGGL((offsets_kernel<uint64_t, 32>), dim3((unsigned)(K / 256 + 1)), dim3(256), 0, s, kx, D, K, cat_off);
     hipLaunchKernelGGL(ce_gather_kernel, dim3(blocks), dim3(256), 0, s, det, order, sprob, det_off, flags, vx, cat_off, K, D,
                        AT, rank2, score2, flags2);
   } else if (hipMemsetAsync(cat_off, 0, sizeof(int64_t) * ((size_t)K + 1), s) != hipSuccess) {
@@ -457,7 +454,7 @@ extern "C" int yv4_coco_accumulate(const float* det, const uint32_t* order, cons
     return YV4_E_LAUNCH;
   }
   hipLaunchKernelGGL(ce_scan_kernel, dim3((unsigned)((int64_t)K * A * M * T)), dim3(kCeLanes), 0, s, rank2, score2, flags2,
-                     cat_off, counts, md, (int64_t)Dn, K, A, M, T, rec_thrs, R, precision, recall, scores);
+                     cat_off, counts, md, Dn, K, A, M, T, rec_thrs, R, precision, recall, scores);
   YV4_CHECK_LAUNCH("coco_accumulate");
   return YV4_OK;
 }

@@ -7,18 +7,11 @@
 // [det_off[p], det_off[p+1]), ground truths [gt_off[p], gt_off[p+1]) and the row-major
 // (num_det x num_gt) IoU block at iou_off[p].
 // Arithmetic is the reference's fp32 expression order (compiled with -ffp-contract=off): bit-exact.
-#include "yv4_common.h"
+// The problem search over an offset table is eval_common.h's find_problem.
+#include "eval_common.h"
 
 namespace yv4 {
-
-__device__ __forceinline__ int find_problem(const int64_t* __restrict__ off, int P, int64_t i) {
-  int lo = 0, hi = P;       // invariant: off[lo] <= i < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+namespace {
 
 __global__ __launch_bounds__(256) void iou_coco_kernel(const float* __restrict__ det, const float* __restrict__ gt,
                                                        const uint8_t* __restrict__ is_crowd,
@@ -29,7 +22,7 @@ __global__ __launch_bounds__(256) void iou_coco_kernel(const float* __restrict__
   const int64_t total = iou_off[P];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int p = find_problem(iou_off, P, i);
+    const int p = find_problem(iou_off, 0, P, i);
     const int64_t ng = gt_off[p + 1] - gt_off[p];
     const int64_t local = i - iou_off[p];
     const int64_t d = det_off[p] + local / ng;
@@ -94,6 +87,7 @@ __global__ __launch_bounds__(64) void match_coco_kernel(const float* __restrict_
   }
 }
 
+}  // namespace
 }  // namespace yv4
 
 using namespace yv4;

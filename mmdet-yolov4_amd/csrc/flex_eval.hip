@@ -7,14 +7,11 @@
 // The definition is stated in include/yv4.h and restated in mmdet-yolov4_amd/eval_utils.py.  Every floating-point value
 // is ONE IEEE operation of it (compiled with -ffp-contract=off), counts are integers, the float64 sum is a single
 // accumulator in rank order.  No float atomics: two runs give identical bytes.
-#include "yv4_common.h"
+// The problem search and the chunk primitives of the walk are eval_common.h's.
+#include "eval_common.h"
 
 namespace yv4 {
 namespace {
-
-constexpr int kFxLanes = 64;
-constexpr int kFxWaves = 4;
-constexpr int kFxThreads = kFxLanes * kFxWaves;      // one chunk of a class's list
 
 __global__ __launch_bounds__(256) void fx_tables_kernel(const int64_t* __restrict__ det_off, const int64_t* __restrict__ iou_off,
                                                         int P, int B, int64_t* __restrict__ q_det_off,
@@ -50,12 +47,7 @@ struct FxArgs {
 __device__ __forceinline__ int fx_flags(const FxArgs& a, int64_t base, int64_t n, int64_t pc, int b, int t, int64_t pos) {
   const int64_t s = a.cls_order[base + pos];
   if (s < base || s >= base + n) return 0;                // (never with the tables yv4_map_rank wrote)
-  int64_t lo = pc, hi = pc + a.N;                         // det_off[lo] <= s < det_off[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a.det_off[mid] <= s) lo = mid; else hi = mid;
-  }
-  const int64_t p = lo, first = a.det_off[p];
+  const int64_t p = find_problem(a.det_off, pc, pc + a.N, s), first = a.det_off[p];
   const int64_t nd = a.det_off[p + 1] - first, d = s - first;
   const int64_t blk = (int64_t)a.B * first * a.T + (int64_t)t * nd + d;      // breakdown 0's entry
   const int32_t mg_own = a.matched[blk + (int64_t)b * nd * a.T];
@@ -77,22 +69,22 @@ __device__ __forceinline__ int fx_flags(const FxArgs& a, int64_t base, int64_t n
 
 // One workgroup of four waves per (class, breakdown, threshold).  The class's list is walked in chunks of 256 positions
 // (thread = position inside the chunk), three times:
-//   A  forwards   inclusive integer counts of `in` and `in & tp` (ballots inside a wave, the waves' totals through LDS,
-//                 the chunks' through a running sum every thread keeps) -> precision at the `in` positions, -1 elsewhere
-//   B  backwards  precision's suffix maximum over the `in` positions (shuffles inside a wave, the waves above through
-//                 LDS, the chunks above through a carried maximum), in place in `scratch`; a position outside the list
-//                 holds -1, below every precision, so a chunk without an `in` position passes the carry through
+//   A  forwards   inclusive integer counts of `in` and `in & tp` (chunk_count2; the chunks' through a running sum every
+//                 thread keeps) -> precision at the `in` positions, -1 elsewhere
+//   B  backwards  precision's suffix maximum over the `in` positions (chunk_suffix_max), in place in `scratch`; a
+//                 position outside the list holds -1, below every precision, so a chunk without an `in` position passes
+//                 the carry through
 //   C  forwards   the `in & tp` counts again: recall changes exactly there, and the recall before it is (count - 1) /
 //                 num_gt whatever lies between; the terms go in rank order into one float64 accumulator that every
 //                 thread carries identically
-__global__ __launch_bounds__(kFxThreads) void fx_accumulate_kernel(FxArgs a, const int64_t* __restrict__ num_gt,
-                                                                   double* __restrict__ scratch, int64_t* __restrict__ num_det,
-                                                                   double* __restrict__ recall, float* __restrict__ ap) {
-  __shared__ int s_in[kFxWaves], s_tp[kFxWaves];
-  __shared__ double s_wmax[kFxWaves];
-  __shared__ unsigned long long s_mask[kFxWaves];
-  __shared__ double s_term[kFxThreads];
-  const int tid = threadIdx.x, lane = tid & (kFxLanes - 1), w = tid >> 6;
+__global__ __launch_bounds__(kEvalThreads) void fx_accumulate_kernel(FxArgs a, const int64_t* __restrict__ num_gt,
+                                                                     double* __restrict__ scratch, int64_t* __restrict__ num_det,
+                                                                     double* __restrict__ recall, float* __restrict__ ap) {
+  __shared__ int s_in[kEvalWaves], s_tp[kEvalWaves];
+  __shared__ double s_wmax[kEvalWaves];
+  __shared__ unsigned long long s_mask[kEvalWaves];
+  __shared__ double s_term[kEvalThreads];
+  const int tid = threadIdx.x;
   int id = blockIdx.x;                                    // (c * B + b) * T + t: the index of the outputs
   const int t = id % a.T; id /= a.T;
   const int b = id % a.B;
@@ -105,34 +97,24 @@ __global__ __launch_bounds__(kFxThreads) void fx_accumulate_kernel(FxArgs a, con
   if (n < 0) n = 0;
   const int64_t ng = num_gt[(int64_t)c * a.B + b];
   const double den = ng >= 1 ? (double)ng : 1e-7;         // max(num_gt, 1e-7)
-  const unsigned long long le = ~0ull >> (63 - lane);     // lanes <= mine
-  const int64_t nchunks = (n + kFxThreads - 1) / kFxThreads;
+  const int64_t nchunks = (n + kEvalThreads - 1) / kEvalThreads;
   double* mine = scratch + ((int64_t)b * a.T + t) * a.D + base;
 
   // ---- A
   int64_t run_in = 0, run_tp = 0;
   for (int64_t ch = 0; ch < nchunks; ++ch) {
-    const int64_t pos = ch * kFxThreads + tid;
+    const int64_t pos = ch * kEvalThreads + tid;
     const int f = pos < n ? fx_flags(a, base, n, pc, b, t, pos) : 0;
     const bool fin = (f & 1) != 0, ftp = f == 3;
-    const unsigned long long bi = __ballot(fin), bt = __ballot(ftp);
-    if (lane == 0) { s_in[w] = __popcll(bi); s_tp[w] = __popcll(bt); }
-    __syncthreads();
-    int pre_i = 0, pre_t = 0, tot_i = 0, tot_t = 0;
-#pragma unroll
-    for (int v = 0; v < kFxWaves; ++v) {
-      const int x = s_in[v], y = s_tp[v];
-      if (v < w) { pre_i += x; pre_t += y; }
-      tot_i += x;
-      tot_t += y;
-    }
+    ChunkCount ci, ct;
+    chunk_count2(fin, ftp, s_in, s_tp, ci, ct);
     if (pos < n) {
-      const int64_t k = run_in + pre_i + __popcll(bi & le);
-      const int64_t ctp = run_tp + pre_t + __popcll(bt & le);
+      const int64_t k = run_in + ci.incl;
+      const int64_t ctp = run_tp + ct.incl;
       mine[pos] = fin ? (double)ctp / (double)k : -1.0;
     }
-    run_in += tot_i;
-    run_tp += tot_t;
+    run_in += ci.total;
+    run_tp += ct.total;
     __syncthreads();
   }
   if (tid == 0) {
@@ -147,25 +129,10 @@ __global__ __launch_bounds__(kFxThreads) void fx_accumulate_kernel(FxArgs a, con
   // ---- B (the pad mpre[n + 1] = 0 starts the maximum)
   double carry = 0.0;
   for (int64_t ch = nchunks - 1; ch >= 0; --ch) {
-    const int64_t pos = ch * kFxThreads + tid;
+    const int64_t pos = ch * kEvalThreads + tid;
     const double own = pos < n ? mine[pos] : -1.0;
-    double v = own;
-#pragma unroll
-    for (int o = 1; o < kFxLanes; o <<= 1) {
-      const double u = __shfl_down(v, o);
-      if (lane + o < kFxLanes) v = fmax(v, u);
-    }
-    if (lane == 0) s_wmax[w] = v;
-    __syncthreads();
-    double above = carry, all = carry;
-#pragma unroll
-    for (int x = 0; x < kFxWaves; ++x) {
-      const double m = s_wmax[x];
-      if (x > w) above = fmax(above, m);
-      all = fmax(all, m);
-    }
-    if (own >= 0.0) mine[pos] = fmax(v, above);
-    carry = all;
+    const double v = chunk_suffix_max(own, carry, s_wmax);
+    if (own >= 0.0) mine[pos] = v;
     __syncthreads();
   }
 
@@ -173,34 +140,17 @@ __global__ __launch_bounds__(kFxThreads) void fx_accumulate_kernel(FxArgs a, con
   run_tp = 0;
   double acc = 0.0;
   for (int64_t ch = 0; ch < nchunks; ++ch) {
-    const int64_t pos = ch * kFxThreads + tid;
+    const int64_t pos = ch * kEvalThreads + tid;
     const bool step = pos < n && fx_flags(a, base, n, pc, b, t, pos) == 3;
-    const unsigned long long bt = __ballot(step);
-    if (lane == 0) { s_tp[w] = __popcll(bt); s_mask[w] = bt; }
-    __syncthreads();
-    int pre_t = 0, tot_t = 0;
-#pragma unroll
-    for (int v = 0; v < kFxWaves; ++v) {
-      const int y = s_tp[v];
-      if (v < w) pre_t += y;
-      tot_t += y;
-    }
+    const ChunkCount ct = chunk_count(step, s_tp);
+    double term = 0.0;
     if (step) {
-      const int64_t ctp = run_tp + pre_t + __popcll(bt & le);
+      const int64_t ctp = run_tp + ct.incl;
       const double r = (double)ctp / den, r_prev = (double)(ctp - 1) / den;      // mrec[0] = 0 = 0 / den
-      s_term[tid] = (r - r_prev) * mine[pos];
+      term = (r - r_prev) * mine[pos];
     }
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < kFxWaves; ++v) {
-      unsigned long long mm = s_mask[v];
-      while (mm) {
-        acc += s_term[v * kFxLanes + (__ffsll(mm) - 1)];
-        mm &= mm - 1;
-      }
-    }
-    run_tp += tot_t;
-    __syncthreads();
+    chunk_ordered_sum(term, step, acc, s_term, s_mask);
+    run_tp += ct.total;
   }
   // the closing step to mrec[n + 1] = 1 meets mpre[n + 1] = 0: it adds a zero
   if (tid == 0) ap[blockIdx.x] = (float)acc;
@@ -257,7 +207,7 @@ extern "C" int yv4_flex_accumulate(const int32_t* matched, const float* det4, co
   a.B = num_bkd;
   a.T = num_thrs;
   a.shared_tp = shared_tp != 0;
-  hipLaunchKernelGGL(fx_accumulate_kernel, dim3((unsigned)((int64_t)C * num_bkd * num_thrs)), dim3(kFxThreads), 0,
+  hipLaunchKernelGGL(fx_accumulate_kernel, dim3((unsigned)((int64_t)C * num_bkd * num_thrs)), dim3(kEvalThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), a, num_gt, reinterpret_cast<double*>(work), num_det, recall, ap);
   YV4_CHECK_LAUNCH("flex_accumulate");
   return YV4_OK;

@@ -6,19 +6,11 @@
 // (image, class) problem of a dataset, every IoU threshold and every area range.  Problem p owns boxes
 // [off1[p], off1[p+1]) / [off2[p], off2[p+1]) and the row-major (n1 x n2) IoU block at iou_off[p].
 // Arithmetic is the reference's fp32 expression order (compiled with -ffp-contract=off): bit-exact.
-#include "yv4_common.h"
+// The problem search over an offset table is eval_common.h's find_problem.
+#include "eval_common.h"
 
 namespace yv4 {
-
-// the last p with off[p] <= i (problems without elements share their offset with the next one and are stepped over)
-__device__ __forceinline__ int map_find_problem(const int64_t* __restrict__ off, int P, int64_t i) {
-  int lo = 0, hi = P;       // invariant: off[lo] <= i < off[hi]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+namespace {
 
 // np.maximum / np.minimum: a NaN in either operand is the result (fmaxf would drop it)
 __device__ __forceinline__ float np_max(float a, float b) { return (a >= b || a != a) ? a : b; }
@@ -38,7 +30,7 @@ __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const float* __restr
   const int64_t total = iou_off[P];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int p = map_find_problem(iou_off, P, i);
+    const int p = find_problem(iou_off, 0, P, i);
     const int64_t n2 = off2[p + 1] - off2[p];
     const int64_t local = i - iou_off[p];
     const float4 a = reinterpret_cast<const float4*>(b1)[off1[p] + local / n2];
@@ -69,7 +61,7 @@ __global__ __launch_bounds__(256) void tpfp_rowmax_kernel(const float* __restric
                                                           int32_t* __restrict__ det_prob, int32_t* __restrict__ winner) {
   const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (d >= D) return;
-  const int p = map_find_problem(det_off, P, d);
+  const int p = find_problem(det_off, 0, P, d);
   const int64_t ng = gt_off[p + 1] - gt_off[p];
   float best = -INFINITY;
   int32_t arg = -1;
@@ -182,6 +174,7 @@ static inline unsigned map_blocks(long long n, int per) {
   return (unsigned)b;
 }
 
+}  // namespace
 }  // namespace yv4
 
 using namespace yv4;

@@ -8,25 +8,15 @@
 // Every floating-point value is ONE IEEE operation of the definition (mmdet-yolov4_amd/map_eval.py), in its order
 // (compiled with -ffp-contract=off); counts are integers; the float64 sum of 'area' is a single accumulator in rank
 // order.  No float atomics: two runs give identical bytes.
+// The score key, the offsets kernel, the sorts' sizing and the chunk primitives of the walk are eval_common.h's.
 #include <cfloat>
 
-#include "radix_sort.h"
-#include "yv4_common.h"
+#include "eval_common.h"
 
 namespace yv4 {
 namespace {
 
-constexpr int kMfLanes = 64;
-constexpr int kMfWaves = 4;
-constexpr int kMfThreads = kMfLanes * kMfWaves;      // one chunk of a class's list
 constexpr int kMfPoints = 11;                        // recall levels of the '11points' AP
-
-// float32 score -> a 32-bit key that ascends as the score DEscends; -0 and +0 share a key
-__device__ __forceinline__ uint32_t mf_desc_key(float s) {
-  const uint32_t b = __float_as_uint(s + 0.f);
-  const uint32_t u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ~u;
-}
 
 // ---- ordering ------------------------------------------------------------------------------------------------------
 // sort A: (class, descending score) from the flat order; a detection outside every problem gets class C (to the end)
@@ -37,7 +27,7 @@ __global__ __launch_bounds__(256) void mf_keys_class_kernel(const float* __restr
   if (d >= D) return;
   const int64_t lab = labels[d], im = img[d];
   const bool part = lab >= 0 && lab < C && im >= 0 && im < N;
-  keys[d] = ((uint64_t)(uint32_t)(part ? (int)lab : C) << 32) | mf_desc_key(det[5 * d + 4]);
+  keys[d] = ((uint64_t)(uint32_t)(part ? (int)lab : C) << 32) | desc_key(det[5 * d + 4]);
   vals[d] = (uint32_t)d;
 }
 
@@ -52,19 +42,6 @@ __global__ __launch_bounds__(256) void mf_keys_problem_kernel(const uint64_t* __
   const uint32_t cls = (uint32_t)(keys_a[j] >> 32);
   keys[j] = cls >= (uint32_t)C ? (uint32_t)C * (uint32_t)N : cls * (uint32_t)N + (uint32_t)img[vals_a[j]];
   vals[j] = (uint32_t)j;
-}
-
-// off[q] = first sorted position whose problem is >= q, q = 0 .. P
-__global__ __launch_bounds__(256) void mf_offsets_kernel(const uint32_t* __restrict__ keys, int64_t n, int P,
-                                                         int64_t* __restrict__ off) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (q > P) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < (uint32_t)q) lo = mid + 1; else hi = mid;
-  }
-  off[q] = lo;
 }
 
 // position s of the problem-major order: its box, its rank inside the problem (order == rank: the boxes are gathered in
@@ -123,25 +100,24 @@ __global__ __launch_bounds__(256) void mf_class_counts_kernel(const int64_t* __r
 
 // ---- accumulation: one workgroup of four waves per (threshold, class, area range) ------------------------------------
 // The class's list is walked in chunks of 256 positions (thread = position inside the chunk), three times:
-//   A  forwards   inclusive integer counts (ballots inside a wave, the waves' totals through LDS, the chunks' through a
-//                 running sum every thread keeps) -> precision, recall, the curves on request
-//   B  backwards  precision's suffix maximum (shuffles inside a wave, the waves above through LDS, the chunks above
-//                 through a carried maximum), in place in `scratch`
+//   A  forwards   inclusive integer counts (chunk_count2; the chunks' through a running sum every thread keeps) ->
+//                 precision, recall, the curves on request
+//   B  backwards  precision's suffix maximum (chunk_suffix_max), in place in `scratch`
 //   C  forwards   the counts again; 'area': a term at every position where recall changes, added in rank order into one
 //                 float64 accumulator that every thread carries identically; '11points': the suffix maximum at the
 //                 first position that reaches each level
-__global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
+__global__ __launch_bounds__(kEvalThreads) void mf_accumulate_kernel(
     const uint8_t* __restrict__ tp, const uint8_t* __restrict__ fp, const int32_t* __restrict__ cls_order,
     const int64_t* __restrict__ det_off, const int64_t* __restrict__ num_gts, int64_t D, int N, int C, int K, int mode,
     float* __restrict__ scratch, float* __restrict__ ap, double* __restrict__ last_recall,
     float* __restrict__ last_precision, double* __restrict__ recall, float* __restrict__ precision,
     int64_t* __restrict__ num_dets) {
-  __shared__ int s_ct[kMfWaves], s_cf[kMfWaves];
-  __shared__ float s_wmax[kMfWaves];
-  __shared__ unsigned long long s_mask[kMfWaves];
-  __shared__ double s_term[kMfThreads];
+  __shared__ int s_ct[kEvalWaves], s_cf[kEvalWaves];
+  __shared__ float s_wmax[kEvalWaves];
+  __shared__ unsigned long long s_mask[kEvalWaves];
+  __shared__ double s_term[kEvalThreads];
   __shared__ float s_sel[kMfPoints];
-  const int tid = threadIdx.x, lane = tid & (kMfLanes - 1), w = tid >> 6;
+  const int tid = threadIdx.x;
   int id = blockIdx.x;                                    // (t * C + c) * K + k: the index of ap / last_recall
   const int k = id % K; id /= K;
   const int c = id % C;
@@ -159,34 +135,24 @@ __global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
   const int64_t row = ((int64_t)t * K + k) * D;
   const int64_t ng = num_gts[(int64_t)c * K + k];
   const double den = ng >= 1 ? (double)ng : (double)FLT_EPSILON;          // np.maximum(int64 num_gts, float32 eps)
-  const unsigned long long le = ~0ull >> (63 - lane);     // lanes <= mine
-  const int64_t nchunks = (n + kMfThreads - 1) / kMfThreads;
+  const int64_t nchunks = (n + kEvalThreads - 1) / kEvalThreads;
   float* mine = scratch + row + base;
 
   // ---- A
   int64_t run_tp = 0, run_fp = 0;
   for (int64_t ch = 0; ch < nchunks; ++ch) {
-    const int64_t pos = ch * kMfThreads + tid;
+    const int64_t pos = ch * kEvalThreads + tid;
     const bool in = pos < n;
     bool ftp = false, ffp = false;
     if (in) {
       const int64_t col = cls_order[base + pos];
       if (col >= 0 && col < D) { ftp = tp[row + col] != 0; ffp = fp[row + col] != 0; }
     }
-    const unsigned long long bt = __ballot(ftp), bf = __ballot(ffp);
-    if (lane == 0) { s_ct[w] = __popcll(bt); s_cf[w] = __popcll(bf); }
-    __syncthreads();
-    int pre_t = 0, pre_f = 0, tot_t = 0, tot_f = 0;
-#pragma unroll
-    for (int v = 0; v < kMfWaves; ++v) {
-      const int a = s_ct[v], b = s_cf[v];
-      if (v < w) { pre_t += a; pre_f += b; }
-      tot_t += a;
-      tot_f += b;
-    }
+    ChunkCount ct, cf;
+    chunk_count2(ftp, ffp, s_ct, s_cf, ct, cf);
     if (in) {
-      const float ctp = (float)(run_tp + pre_t + __popcll(bt & le));      // exact: below 2^24 (the host checks)
-      const float cfp = (float)(run_fp + pre_f + __popcll(bf & le));
+      const float ctp = (float)(run_tp + ct.incl);        // exact: below 2^24 (the host checks)
+      const float cfp = (float)(run_fp + cf.incl);
       const float both = ctp + cfp;
       const float p = ctp / (both >= FLT_EPSILON ? both : FLT_EPSILON);
       const double r = (double)ctp / den;
@@ -194,8 +160,8 @@ __global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
       if (recall) { recall[row + base + pos] = r; precision[row + base + pos] = p; }
       if (pos == n - 1) { last_recall[blockIdx.x] = r; last_precision[blockIdx.x] = p; }
     }
-    run_tp += tot_t;
-    run_fp += tot_f;
+    run_tp += ct.total;
+    run_fp += cf.total;
     __syncthreads();
   }
   const int64_t total_tp = run_tp;
@@ -203,26 +169,10 @@ __global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
   // ---- B (the pad mpre[n + 1] = 0 starts the maximum)
   float carry = 0.f;
   for (int64_t ch = nchunks - 1; ch >= 0; --ch) {
-    const int64_t pos = ch * kMfThreads + tid;
+    const int64_t pos = ch * kEvalThreads + tid;
     const bool in = pos < n;
-    float v = in ? mine[pos] : 0.f;
-#pragma unroll
-    for (int o = 1; o < kMfLanes; o <<= 1) {
-      const float u = __shfl_down(v, o);
-      if (lane + o < kMfLanes) v = fmaxf(v, u);
-    }
-    if (lane == 0) s_wmax[w] = v;
-    __syncthreads();
-    float above = carry, all = carry;
-#pragma unroll
-    for (int x = 0; x < kMfWaves; ++x) {
-      const float m = s_wmax[x];
-      if (x > w) above = fmaxf(above, m);
-      all = fmaxf(all, m);
-    }
-    v = fmaxf(v, above);
+    const float v = chunk_suffix_max(in ? mine[pos] : 0.f, carry, s_wmax);
     if (in) mine[pos] = v;
-    carry = all;
     __syncthreads();
   }
 
@@ -232,41 +182,21 @@ __global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
   run_tp = 0;
   double acc = 0.0;
   for (int64_t ch = 0; ch < nchunks; ++ch) {
-    const int64_t pos = ch * kMfThreads + tid;
+    const int64_t pos = ch * kEvalThreads + tid;
     const bool in = pos < n;
     bool ftp = false;
     if (in) {
       const int64_t col = cls_order[base + pos];
       if (col >= 0 && col < D) ftp = tp[row + col] != 0;
     }
-    const unsigned long long bt = __ballot(ftp);
-    if (lane == 0) s_ct[w] = __popcll(bt);
-    __syncthreads();
-    int pre_t = 0, tot_t = 0;
-#pragma unroll
-    for (int v = 0; v < kMfWaves; ++v) {
-      const int a = s_ct[v];
-      if (v < w) pre_t += a;
-      tot_t += a;
-    }
-    const int64_t ctp = run_tp + pre_t + __popcll(bt & le);
+    const ChunkCount ct = chunk_count(ftp, s_ct);
+    const int64_t ctp = run_tp + ct.incl;
     const double r = (double)(float)ctp / den;
     const double r_prev = pos == 0 ? 0.0 : (double)(float)(ctp - (ftp ? 1 : 0)) / den;      // mrec[0] = 0
     const float sm = in ? mine[pos] : 0.f;
     if (mode == YV4_MAP_AP_AREA) {
       const bool step = in && r != r_prev;
-      s_term[tid] = step ? (r - r_prev) * (double)sm : 0.0;
-      const unsigned long long m = __ballot(step);
-      if (lane == 0) s_mask[w] = m;
-      __syncthreads();
-#pragma unroll
-      for (int v = 0; v < kMfWaves; ++v) {
-        unsigned long long mm = s_mask[v];
-        while (mm) {
-          acc += s_term[v * kMfLanes + (__ffsll(mm) - 1)];
-          mm &= mm - 1;
-        }
-      }
+      chunk_ordered_sum(step ? (r - r_prev) * (double)sm : 0.0, step, acc, s_term, s_mask);
     } else {
       if (in) {
         for (int j = 0; j < kMfPoints; ++j) {
@@ -276,7 +206,7 @@ __global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
       }
       __syncthreads();
     }
-    run_tp += tot_t;
+    run_tp += ct.total;
   }
   __syncthreads();
   if (tid == 0) {
@@ -294,9 +224,7 @@ __global__ __launch_bounds__(kMfThreads) void mf_accumulate_kernel(
   }
 }
 
-static inline int mf_class_bits(int C) { return C < 65535 ? 48 : 64; }      // the key's high word holds 0 .. C
 static inline int mf_problem_bits(int64_t P) { return P < 65536 ? 16 : 32; }  // the key holds 0 .. P
-static inline size_t mf_hist_bytes(int64_t n) { return rs_hist_bytes(n + kRsTile); }
 
 struct MfRankLayout {
   size_t ka0, ka1, va0, va1, kb0, kb1, vb0, vb1, hist;
@@ -311,7 +239,7 @@ struct MfRankLayout {
     kb1 = carve.take(4 * n);
     vb0 = carve.take(4 * n);
     vb1 = carve.take(4 * n);
-    hist = carve.take(mf_hist_bytes((int64_t)n));
+    hist = carve.take(sort_hist_bytes((int64_t)n));
   }
 };
 
@@ -360,12 +288,12 @@ extern "C" int yv4_map_rank(const float* det, const int64_t* labels, const int64
   const unsigned blocks = (unsigned)((D + 255) / 256);
   hipLaunchKernelGGL(mf_keys_class_kernel, dim3(blocks), dim3(256), 0, s, det, labels, img_index, D, N, C, ka0, va0);
   // the first pass only reads its input, so both sorts run "in place": the results land in (ka0, va0) and (kb0, vb0)
-  int rc = rs_sort<uint64_t, uint32_t, true>(ka0, ka0, ka1, va0, va0, va1, D, mf_class_bits(C), hist, s, "map_rank: radix sort");
+  int rc = rs_sort<uint64_t, uint32_t, true>(ka0, ka0, ka1, va0, va0, va1, D, key_bits_hi32(C), hist, s, "map_rank: radix sort");
   if (rc != YV4_OK) return rc;
   hipLaunchKernelGGL(mf_keys_problem_kernel, dim3(blocks), dim3(256), 0, s, ka0, va0, img_index, D, N, C, kb0, vb0);
   rc = rs_sort<uint32_t, uint32_t, true>(kb0, kb0, kb1, vb0, vb0, vb1, D, mf_problem_bits(P), hist, s, "map_rank: radix sort");
   if (rc != YV4_OK) return rc;
-  hipLaunchKernelGGL(mf_offsets_kernel, dim3((unsigned)(P / 256 + 1)), dim3(256), 0, s, kb0, D, P, det_off);
+  hipLaunchKernelGGL((offsets_kernel<uint32_t, 0>), dim3((unsigned)(P / 256 + 1)), dim3(256), 0, s, kb0, D, P, det_off);
   hipLaunchKernelGGL(mf_gather_kernel, dim3(blocks), dim3(256), 0, s, det, va0, vb0, kb0, det_off, D, P, det4, order, rank,
                      cls_order);
   hipLaunchKernelGGL(mf_pairs_kernel, dim3(1), dim3(1024), 0, s, det_off, gt_off, P, iou_off, info);
@@ -392,7 +320,7 @@ extern "C" int yv4_map_accumulate(const uint8_t* tp, const uint8_t* fp, const in
   YV4_REQUIRE(total_det == 0 || (tp && fp && cls_order), "map_accumulate: null detection pointer");
   YV4_REQUIRE((recall == nullptr) == (precision == nullptr), "map_accumulate: the curves come as a pair");
   YV4_REQUIRE(((uintptr_t)work & 3) == 0, "map_accumulate: work must be 4-byte aligned");
-  hipLaunchKernelGGL(mf_accumulate_kernel, dim3((unsigned)((int64_t)num_thrs * C * num_ranges)), dim3(kMfThreads), 0,
+  hipLaunchKernelGGL(mf_accumulate_kernel, dim3((unsigned)((int64_t)num_thrs * C * num_ranges)), dim3(kEvalThreads), 0,
                      reinterpret_cast<hipStream_t>(stream), tp, fp, cls_order, det_off, num_gts, total_det, N, C, num_ranges,
                      mode, reinterpret_cast<float*>(work), ap, last_recall, last_precision, recall, precision, num_dets);
   YV4_CHECK_LAUNCH("map_accumulate");

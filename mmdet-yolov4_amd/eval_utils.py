@@ -45,9 +45,9 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import _lib
+from . import _eval_common, _lib
+from ._eval_common import PhaseTimer, _dev, _flat_to_device, _is_flat, _offsets, rank_flat
 from ._lib import check
-from .coco_eval import _is_flat
 from .ops import stream_ptr
 from .registry import Registry, build_from_cfg
 
@@ -57,20 +57,7 @@ EVAL_MATCHER = Registry('Evaluation Matcher')
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError('eval_utils runs on the GPU through libyv4_hip.so; no GPU is visible '
-                           '(there is no CPU fallback for this path)')
-    return torch.device('cuda', torch.cuda.current_device())
-
-
-def _dev(a, dtype, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev, non_blocking=False)
-
-
-def _offsets(counts):
-    off = np.zeros(len(counts) + 1, np.int64)
-    np.cumsum(counts, out=off[1:])
-    return off
+    return _eval_common._device('eval_utils')
 
 
 def iou_coco_batched(det, gt, is_crowd, det_off, gt_off):
@@ -326,80 +313,42 @@ class FlexGt:
         return d
 
 
-def _flat_to_device(flat, dev):
-    dets, labels, img_index = flat
-
-    def put(x, np_dtype, t_dtype):
-        if isinstance(x, torch.Tensor):
-            return x.to(dev, t_dtype).contiguous()
-        return _dev(np.asarray(x), np_dtype, dev)
-    dets = put(dets, np.float32, torch.float32).reshape(-1, 5)
-    labels, img_index = put(labels, np.int64, torch.int64).reshape(-1), put(img_index, np.int64, torch.int64).reshape(-1)
-    if labels.numel() != dets.shape[0] or img_index.numel() != dets.shape[0]:
-        raise ValueError(f'flat results: {dets.shape[0]} detections, {labels.numel()} labels, {img_index.numel()} image indices')
-    return dets, labels, img_index
-
-
 def flex_flat_device(flat, gt, iou_thrs, shared_tp=True, phases=None):
     """The flat path of the module docstring on the device: ``yv4_map_rank``, one read-back (the pair total and the class
     counts), ``yv4_iou_coco_batched``, ``yv4_flex_tables``, ``yv4_match_coco_batched`` over the Q = P * B problems,
     ``yv4_flex_accumulate``, one download.  ``flat``: numpy arrays or GPU tensors (those never visit the host); ``gt``: a
     ``FlexGt``.  Returns host arrays shaped (C, B, T): ``num_det`` int64, ``recall`` float64, ``mAP`` float32.
     ``phases``: an optional dict that receives seconds per phase (each closed by a synchronise)."""
-    import time
-    dev = _device()
-    if not _lib.has_flex_flat():
-        raise RuntimeError('the loaded libyv4_hip.so has no yv4_flex_tables / yv4_flex_accumulate; rebuild it')
-
-    def tick():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
-    marks = [tick()] if phases is not None else None
+    dev = _eval_common._device('eval_utils', _lib.has_flex_flat, 'yv4_flex_tables / yv4_flex_accumulate')
+    timer = PhaseTimer(phases, dev)
     thrs = np.ascontiguousarray(iou_thrs, dtype=np.float32).reshape(-1)
     N, C, B, T = gt.num_imgs, gt.num_classes, gt.num_bkd, len(thrs)
     if T == 0:
         raise ValueError('flat results need at least one IoU threshold')
     P, G = N * C, len(gt.gt)
     g = gt.device(dev)
-    dets, labels, img_index = _flat_to_device(flat, dev)
-    D = int(dets.shape[0])
+    flat = _flat_to_device(flat, dev)
     t_thr = _dev(thrs, np.float32, dev)
-    if phases is not None:
-        marks.append(tick())
+    timer.mark('upload')
     lib = _lib.lib()
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()     # noqa: E731
-    i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)            # noqa: E731
-    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)            # noqa: E731
-    det4 = torch.empty((max(D, 1), 4), dtype=torch.float32, device=dev)
-    det_off, iou_off, info = i64(P + 1), i64(P + 1), i64(C + 2)
-    order, rank, cls_order = i32(max(D, 1)), i32(max(D, 1)), i32(max(D, 1))
-    work = torch.empty(max(int(lib.yv4_map_rank_work(D)), 8), dtype=torch.uint8, device=dev)
-    check(lib.yv4_map_rank(ptr(dets), ptr(labels), ptr(img_index), D, N, C, g['gt_off'].data_ptr(), work.data_ptr(),
-                           det4.data_ptr(), det_off.data_ptr(), order.data_ptr(), rank.data_ptr(), iou_off.data_ptr(),
-                           cls_order.data_ptr(), info.data_ptr(), stream_ptr()), 'yv4_map_rank')
-    info_h = info.cpu().numpy()                                 # the one read-back between the device calls
-    pairs, Dv, counts = int(info_h[0]), int(info_h[1]), info_h[2:]
-    if phases is not None:
-        marks.append(tick())
-    for c in np.flatnonzero(counts >= 2 ** 24):
-        raise ValueError(f'class {c} has {counts[c]} detections: the cumulative counts are kept exact only below 2**24')
+    det4, det_off, iou_off, _, _, cls_order, pairs, Dv, _ = rank_flat(flat, g['gt_off'], N, C, dev)
+    timer.mark('rank')
     iou = torch.empty(max(pairs, 1), dtype=torch.float32, device=dev)
     if pairs:
         check(lib.yv4_iou_coco_batched(det4.data_ptr(), g['gt'].data_ptr(), g['crowd'].data_ptr(), det_off.data_ptr(),
                                        g['gt_off'].data_ptr(), iou_off.data_ptr(), P, pairs, iou.data_ptr(), stream_ptr()),
               'yv4_iou_coco_batched')
-    matched = i32(max(B * Dv * T, 1))
+    matched = torch.empty(max(B * Dv * T, 1), dtype=torch.int32, device=dev)
     if Dv:
         Q = P * B
-        q_det_off, q_iou_off = i64(Q + 1), i64(Q + 1)
+        q_det_off, q_iou_off = (torch.empty(Q + 1, dtype=torch.int64, device=dev) for _ in range(2))
         check(lib.yv4_flex_tables(det_off.data_ptr(), iou_off.data_ptr(), P, B, q_det_off.data_ptr(), q_iou_off.data_ptr(),
                                   stream_ptr()), 'yv4_flex_tables')
         work = torch.empty(max(B * G * T, 1), dtype=torch.uint8, device=dev)
         check(lib.yv4_match_coco_batched(iou.data_ptr(), q_det_off.data_ptr(), g['q_gt_off'].data_ptr(), q_iou_off.data_ptr(),
                                          t_thr.data_ptr(), T, g['q_ignore'].data_ptr(), g['q_crowd'].data_ptr(), Q,
                                          work.data_ptr(), matched.data_ptr(), stream_ptr()), 'yv4_match_coco_batched')
-    if phases is not None:
-        marks.append(tick())
+    timer.mark('match')
     num_det = torch.empty((C, B, T), dtype=torch.int64, device=dev)
     recall = torch.empty((C, B, T), dtype=torch.float64, device=dev)
     ap = torch.empty((C, B, T), dtype=torch.float32, device=dev)
@@ -408,13 +357,10 @@ def flex_flat_device(flat, gt, iou_thrs, shared_tp=True, phases=None):
                                   g['gt_off'].data_ptr(), g['gt_bkd'].data_ptr(), g['num_gt'].data_ptr(),
                                   g['bounds'].data_ptr(), Dv, G, N, C, B, T, 1 if shared_tp else 0, work.data_ptr(),
                                   num_det.data_ptr(), recall.data_ptr(), ap.data_ptr(), stream_ptr()), 'yv4_flex_accumulate')
-    if phases is not None:
-        marks.append(tick())
+    timer.mark('accumulate')
     out = dict(num_det=num_det.cpu().numpy(), recall=recall.cpu().numpy(), mAP=ap.cpu().numpy(), num_gt=gt.num_gt,
                total_det=Dv, pairs=pairs)
-    if phases is not None:
-        marks.append(tick())
-        phases.update({k: b - a for k, a, b in zip(('upload', 'rank', 'match', 'accumulate', 'download'), marks, marks[1:])})
+    timer.mark('download')
     return out
 
 

@@ -52,28 +52,22 @@ tables of a dataset between calls.  Definition, where it is more than the list p
 ``eval_recalls`` (``recall.py``, ``metric='recall'``) is not built: it scores RPN proposal lists, which no detector of
 this package produces.
 """
-import logging
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _eval_common, _lib
+from ._eval_common import PhaseTimer, _dev, _flat_to_device, _is_flat, _log, _offsets, _ptr, rank_flat
 from ._lib import check
-from .coco_eval import _is_flat
-from .eval_utils import _dev, _offsets, average_precision
+from .eval_utils import average_precision
 from .ops import stream_ptr
 
 _F32_EPS = np.finfo(np.float32).eps
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError('map_eval runs on the GPU through libyv4_hip.so; no GPU is visible '
-                           '(there is no CPU fallback for this path)')
-    if not _lib.has_map_eval():
-        raise RuntimeError('the loaded libyv4_hip.so has no yv4_bbox_overlaps_batched / yv4_tpfp_batched; rebuild it')
-    return torch.device('cuda', torch.cuda.current_device())
+    return _eval_common._device('map_eval', _lib.has_map_eval, 'yv4_bbox_overlaps_batched / yv4_tpfp_batched')
 
 
 def _boxes(a, cols=4):
@@ -178,7 +172,6 @@ def tpfp_batched(tab, mode, iou_thrs, area_ranges=None, phases=None):
     """tp / fp of every detection of ``tab`` (a sorted MapTables) for every threshold and area range: upload, one
     overlaps call, one tpfp call, download.  Returns two (T, K, D) uint8 numpy arrays, columns in ``tab.det`` order.
     ``phases``: an optional dict that receives upload / launch / download seconds (each closed by a synchronise)."""
-    import time
     dev = _device()
     thrs = np.ascontiguousarray(iou_thrs, dtype=np.float32).reshape(-1)
     area = _area_table(area_ranges)
@@ -187,11 +180,7 @@ def tpfp_batched(tab, mode, iou_thrs, area_ranges=None, phases=None):
     imagenet = mode == _lib.TPFP_IMAGENET
     if D == 0:
         return np.zeros((T, K, 0), np.uint8), np.zeros((T, K, 0), np.uint8)
-
-    def tick():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
-    t0 = tick() if phases is not None else 0
+    timer = PhaseTimer(phases, dev)
     det4 = _dev(tab.det[:, :4], np.float32, dev)
     gt = _dev(tab.gt, np.float32, dev)
     ign = _dev(tab.gt_ignore, np.uint8, dev)
@@ -207,7 +196,7 @@ def tpfp_batched(tab, mode, iou_thrs, area_ranges=None, phases=None):
     t_io = _dev(_offsets(tab.nd * tab.ng), np.int64, dev)
     t_thr = _dev(thrs, np.float32, dev)
     t_area = None if area is None else _dev(area, np.float32, dev)
-    t1 = tick() if phases is not None else 0
+    timer.mark('upload')
     lib = _lib.lib()
     iou, _ = bbox_overlaps_batched(det4, gt_iou, tab.det_off, tab.gt_off, dev_tables=(t_do, t_go, t_io))
     if iou.numel() == 0:                                   # no problem has both detections and gts
@@ -215,16 +204,13 @@ def tpfp_batched(tab, mode, iou_thrs, area_ranges=None, phases=None):
     work = torch.empty(max(int(lib.yv4_tpfp_work(mode, D, G, T)), 4), dtype=torch.uint8, device=dev)
     tp = torch.empty((T, K, D), dtype=torch.uint8, device=dev)
     fp = torch.empty((T, K, D), dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()     # noqa: E731
-    check(lib.yv4_tpfp_batched(mode, ptr(det4), ptr(gt), ptr(ign), ptr(ratio), ptr(order), ptr(rank), t_do.data_ptr(),
-                               t_go.data_ptr(), t_io.data_ptr(), len(tab.nd), D, G, ptr(iou), t_thr.data_ptr(), T,
-                               ptr(t_area), K, work.data_ptr(), tp.data_ptr(), fp.data_ptr(), stream_ptr()),
+    check(lib.yv4_tpfp_batched(mode, _ptr(det4), _ptr(gt), _ptr(ign), _ptr(ratio), _ptr(order), _ptr(rank), t_do.data_ptr(),
+                               t_go.data_ptr(), t_io.data_ptr(), len(tab.nd), D, G, _ptr(iou), t_thr.data_ptr(), T,
+                               _ptr(t_area), K, work.data_ptr(), tp.data_ptr(), fp.data_ptr(), stream_ptr()),
           'yv4_tpfp_batched')
-    t2 = tick() if phases is not None else 0
+    timer.mark('launch')
     tp, fp = tp.cpu().numpy(), fp.cpu().numpy()
-    if phases is not None:
-        t3 = tick()
-        phases.update(upload=t1 - t0, launch=t2 - t1, download=t3 - t2)
+    timer.mark('download')
     return tp, fp
 
 
@@ -378,24 +364,8 @@ class MapGt:
 
 
 def _device_flat():
-    dev = _device()
-    if not _lib.has_map_flat():
-        raise RuntimeError('the loaded libyv4_hip.so has no yv4_map_rank / yv4_map_accumulate; rebuild it')
-    return dev
-
-
-def _flat_to_device(flat, dev):
-    dets, labels, img_index = flat
-
-    def put(x, np_dtype, t_dtype):
-        if isinstance(x, torch.Tensor):
-            return x.to(dev, t_dtype).contiguous()
-        return _dev(np.asarray(x), np_dtype, dev)
-    dets = put(dets, np.float32, torch.float32).reshape(-1, 5)
-    labels, img_index = put(labels, np.int64, torch.int64).reshape(-1), put(img_index, np.int64, torch.int64).reshape(-1)
-    if labels.numel() != dets.shape[0] or img_index.numel() != dets.shape[0]:
-        raise ValueError(f'flat results: {dets.shape[0]} detections, {labels.numel()} labels, {img_index.numel()} image indices')
-    return dets, labels, img_index
+    _device()
+    return _eval_common._device('map_eval', _lib.has_map_flat, 'yv4_map_rank / yv4_map_accumulate')
 
 
 def map_flat_device(flat, gt, mode, iou_thrs, area_ranges=None, ap_mode='area', curves=False, phases=None):
@@ -406,13 +376,8 @@ def map_flat_device(flat, gt, mode, iou_thrs, area_ranges=None, ap_mode='area', 
     (T, C, K), num_dets (C,), num_gts (C, K) and, with ``curves``, recall float64 / precision float32 (T, K, Dv) whose
     columns ``[cls_off[c], cls_off[c + 1])`` are class c's curve.  ``phases``: an optional dict that receives seconds
     per phase (each closed by a synchronise)."""
-    import time
     dev = _device_flat()
-
-    def tick():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
-    marks = [tick()] if phases is not None else None
+    timer = PhaseTimer(phases, dev)
     thrs = np.ascontiguousarray(iou_thrs, dtype=np.float32).reshape(-1)
     area = _area_table(area_ranges)
     T, K = len(thrs), 1 if area is None else len(area)
@@ -421,31 +386,14 @@ def map_flat_device(flat, gt, mode, iou_thrs, area_ranges=None, ap_mode='area', 
     imagenet = mode == _lib.TPFP_IMAGENET
     g = gt.device(dev, imagenet)
     num_gts = gt.num_gts(area)
-    dets, labels, img_index = _flat_to_device(flat, dev)
-    D = int(dets.shape[0])
+    flat = _flat_to_device(flat, dev)
     t_thr = _dev(thrs, np.float32, dev)
     t_area = None if area is None else _dev(area, np.float32, dev)
     t_ngts = _dev(num_gts, np.int64, dev)
-    if phases is not None:
-        marks.append(tick())
+    timer.mark('upload')
     lib = _lib.lib()
-    ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()     # noqa: E731
-    i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)            # noqa: E731
-    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)            # noqa: E731
-    det4 = torch.empty((max(D, 1), 4), dtype=torch.float32, device=dev)
-    det_off, iou_off, info = i64(P + 1), i64(P + 1), i64(C + 2)
-    order, rank, cls_order = i32(max(D, 1)), i32(max(D, 1)), i32(max(D, 1))
-    work = torch.empty(max(int(lib.yv4_map_rank_work(D)), 8), dtype=torch.uint8, device=dev)
-    check(lib.yv4_map_rank(ptr(dets), ptr(labels), ptr(img_index), D, N, C, g['gt_off'].data_ptr(), work.data_ptr(),
-                           det4.data_ptr(), det_off.data_ptr(), order.data_ptr(), rank.data_ptr(), iou_off.data_ptr(),
-                           cls_order.data_ptr(), info.data_ptr(), stream_ptr()), 'yv4_map_rank')
-    info_h = info.cpu().numpy()                                 # the one read-back between the device calls
-    pairs, Dv, counts = int(info_h[0]), int(info_h[1]), info_h[2:]
-    if phases is not None:
-        marks.append(tick())
-    for c in np.flatnonzero(counts >= 2 ** 24):
-        raise ValueError(f'class {c} has {counts[c]} detections: the float32 cumulative sums of the reference are '
-                         'exact only below 2**24')
+    det4, det_off, iou_off, order, rank, cls_order, pairs, Dv, counts = rank_flat(flat, g['gt_off'], N, C, dev)
+    timer.mark('rank')
     iou = torch.empty(max(pairs, 1), dtype=torch.float32, device=dev)
     if pairs:
         check(lib.yv4_bbox_overlaps_batched(det4.data_ptr(), (g['gt_m1'] if imagenet else g['gt']).data_ptr(),
@@ -458,33 +406,29 @@ def map_flat_device(flat, gt, mode, iou_thrs, area_ranges=None, ap_mode='area', 
     fp = torch.empty((T, K, Dv), dtype=torch.uint8, device=dev)
     if Dv:
         work = torch.empty(max(int(lib.yv4_tpfp_work(mode, Dv, G, T)), 4), dtype=torch.uint8, device=dev)
-        check(lib.yv4_tpfp_batched(mode, det4.data_ptr(), ptr(g['gt']), ptr(g['ign']), ptr(g.get('ratio')),
+        check(lib.yv4_tpfp_batched(mode, det4.data_ptr(), _ptr(g['gt']), _ptr(g['ign']), _ptr(g.get('ratio')),
                                    order.data_ptr() if imagenet else None, None if imagenet else rank.data_ptr(),
                                    det_off.data_ptr(), g['gt_off'].data_ptr(), iou_off.data_ptr(), P, Dv, G, iou.data_ptr(),
-                                   t_thr.data_ptr(), T, ptr(t_area), K, work.data_ptr(), tp.data_ptr(), fp.data_ptr(),
+                                   t_thr.data_ptr(), T, _ptr(t_area), K, work.data_ptr(), tp.data_ptr(), fp.data_ptr(),
                                    stream_ptr()), 'yv4_tpfp_batched')
-    if phases is not None:
-        marks.append(tick())
+    timer.mark('tpfp')
     ap = torch.empty((T, C, K), dtype=torch.float32, device=dev)
     last_r = torch.empty((T, C, K), dtype=torch.float64, device=dev)
     last_p = torch.empty((T, C, K), dtype=torch.float32, device=dev)
-    num_dets = i64(C)
+    num_dets = torch.empty(C, dtype=torch.int64, device=dev)
     rec = torch.empty((T, K, Dv), dtype=torch.float64, device=dev) if curves else None
     prec = torch.empty((T, K, Dv), dtype=torch.float32, device=dev) if curves else None
     work = torch.empty(max(int(lib.yv4_map_accumulate_work(Dv, T, K)), 4), dtype=torch.uint8, device=dev)
-    check(lib.yv4_map_accumulate(ptr(tp), ptr(fp), cls_order.data_ptr(), det_off.data_ptr(), t_ngts.data_ptr(), Dv, N, C, T,
+    check(lib.yv4_map_accumulate(_ptr(tp), _ptr(fp), cls_order.data_ptr(), det_off.data_ptr(), t_ngts.data_ptr(), Dv, N, C, T,
                                  K, _lib.MAP_AP_11POINTS if ap_mode == '11points' else _lib.MAP_AP_AREA, work.data_ptr(),
-                                 ap.data_ptr(), last_r.data_ptr(), last_p.data_ptr(), ptr(rec), ptr(prec),
+                                 ap.data_ptr(), last_r.data_ptr(), last_p.data_ptr(), _ptr(rec), _ptr(prec),
                                  num_dets.data_ptr(), stream_ptr()), 'yv4_map_accumulate')
-    if phases is not None:
-        marks.append(tick())
+    timer.mark('accumulate')
     out = dict(ap=ap.cpu().numpy(), last_recall=last_r.cpu().numpy(), last_precision=last_p.cpu().numpy(),
                num_dets=num_dets.cpu().numpy(), num_gts=num_gts, cls_off=_offsets(counts), total_det=Dv, pairs=pairs)
     if curves:
         out.update(recall=rec.cpu().numpy(), precision=prec.cpu().numpy())
-    if phases is not None:
-        marks.append(tick())
-        phases.update({k: b - a for k, a, b in zip(('upload', 'rank', 'tpfp', 'accumulate', 'download'), marks, marks[1:])})
+    timer.mark('download')
     return out
 
 
@@ -605,15 +549,6 @@ def evaluate_map(results, annotations, classes=None, iou_thr=0.5, scale_ranges=N
 
 
 # ---- the summary table (the project's own text; terminaltables is not used and no parity is claimed) -----------------
-def _log(msg, logger):
-    if logger is None:
-        print(msg)
-    elif isinstance(logger, logging.Logger):
-        logger.info(msg)
-    elif logger != 'silent':
-        logging.getLogger(logger).info(msg)
-
-
 def print_map_summary(mean_ap, results, dataset=None, scale_ranges=None, logger=None):
     """gts / dets / recall / ap per class and the mAP, one plain-text table per scale range.  ``dataset``: a list of
     class names (a dataset NAME such as 'voc07' only selects a metric variant here; classes are then numbered)."""

@@ -14,13 +14,10 @@
 // jpeg_sync_kernel, jpeg_chunk_scan_kernel, jpeg_chunk_decode_kernel (further down): many lanes per segment, one per chunk
 // of its bytes, entered through self-synchronised states (include/yv4.h, "self-synchronising chunks").
 #include "yv4_common.h"
+#include "jpeg_common.h"
 #include "jpeg_entropy_core.h"
 
 namespace yv4 {
-
-int jpeg_entropy_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_wg* wgs, int N,
-                          int64_t nseg, int64_t nwg, int64_t bytes_len, int64_t nhuff, int64_t coef_elems,
-                          int64_t* coef_lo, int64_t* coef_hi);
 
 constexpr int kHuffWords = (int)(sizeof(yv4_jpeg_huff) / 4);
 static_assert(sizeof(yv4_jpeg_huff) == 1344 && sizeof(yv4_jpeg_huff) % 4 == 0, "yv4_jpeg_huff is copied as 32-bit words");
@@ -52,11 +49,6 @@ __global__ __launch_bounds__(YV4_JPEG_WG_SEGMENTS) void jpeg_entropy_kernel(
 // 64 consecutive chunks of one image (yv4_jpeg_wg), the image's tables and the zigzag order in LDS -- 8.1 KB a
 // workgroup, so that LDS admits 19 workgroups on a CU and the waves of several share each SIMD.  No lane waits on
 // another workgroup: a synchronisation round is a launch, and a round reads the exit words the round before wrote.
-int jpeg_sync_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_chunk* chunks,
-                       const int32_t* seg_first, const yv4_jpeg_wg* wgs, int N, int64_t nseg, int64_t nchunk, int64_t nwg,
-                       int64_t bytes_len, int64_t nhuff, int32_t chunk_bytes, int32_t max_rounds, int64_t coef_elems,
-                       int64_t* coef_lo, int64_t* coef_hi);
-
 static_assert(sizeof(yv4_jpeg_chunk) == 16 && sizeof(yv4_jpeg_entry) == 48, "the chunk structures of include/yv4.h");
 
 __device__ __forceinline__ void jpeg_load_tables(yv4_jpeg_huff* tabs, uint8_t* zigzag, const yv4_jpeg_huff* huff,
@@ -170,6 +162,22 @@ __global__ __launch_bounds__(YV4_JPEG_WG_CHUNKS) void jpeg_chunk_decode_kernel(
 
 using namespace yv4;
 
+static bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// What both device entries do between the validation and the first launch: the zero-fill of coef[lo, hi), of the status
+// words and, for the chunk decode, of the undecided words.
+static int jpeg_zero_fill(const char* who, int16_t* coef, int64_t lo, int64_t hi, int32_t* status, int32_t* undecided, int N,
+                          hipStream_t s) {
+  if (hipMemsetAsync(coef + lo, 0, (size_t)(hi - lo) * sizeof(int16_t), s) != hipSuccess ||
+      hipMemsetAsync(status, 0, (size_t)N * sizeof(int32_t), s) != hipSuccess ||
+      (undecided && hipMemsetAsync(undecided, 0, (size_t)N * sizeof(int32_t), s) != hipSuccess)) {
+    (void)hipGetLastError();
+    set_error("%s: the zero-fill of the coefficients failed", who);
+    return YV4_E_LAUNCH;
+  }
+  return YV4_OK;
+}
+
 extern "C" int yv4_jpeg_entropy_decode_device(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs,
                                               const yv4_jpeg_wg* wgs, const yv4_jpeg_scan* scans_dev,
                                               const yv4_jpeg_segment* segs_dev, const yv4_jpeg_wg* wgs_dev, int N,
@@ -178,20 +186,14 @@ extern "C" int yv4_jpeg_entropy_decode_device(const yv4_jpeg_scan* scans, const 
                                               int64_t coef_elems, int32_t* status, void* stream) {
   YV4_REQUIRE(scans && segs && wgs && scans_dev && segs_dev && wgs_dev && bytes && huff && coef && status,
               "jpeg_entropy_decode_device: null pointer");
-  YV4_REQUIRE((reinterpret_cast<uintptr_t>(scans_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(segs_dev) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(wgs_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(huff) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(coef) & 1) == 0 && (reinterpret_cast<uintptr_t>(status) & 3) == 0,
+  YV4_REQUIRE(aligned(scans_dev, 8) && aligned(segs_dev, 8) && aligned(wgs_dev, 4) && aligned(huff, 4) && aligned(coef, 2) &&
+                  aligned(status, 4),
               "jpeg_entropy_decode_device: scans_dev / segs_dev must be 8-byte, wgs_dev / huff / status 4-byte aligned");
   int64_t lo, hi;
   const int st = jpeg_entropy_validate(scans, segs, wgs, N, nseg, nwg, bytes_len, nhuff, coef_elems, &lo, &hi);
   if (st != YV4_OK) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(coef + lo, 0, (size_t)(hi - lo) * sizeof(int16_t), s) != hipSuccess ||
-      hipMemsetAsync(status, 0, (size_t)N * sizeof(int32_t), s) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("jpeg_entropy_decode_device: the zero-fill of the coefficients failed");
-    return YV4_E_LAUNCH;
-  }
+  if (int rc = jpeg_zero_fill("jpeg_entropy_decode_device", coef, lo, hi, status, nullptr, N, s)) return rc;
   hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)nwg), dim3(YV4_JPEG_WG_SEGMENTS), 0, s, scans_dev, segs_dev,
                      wgs_dev, bytes, huff, coef, status);
   YV4_CHECK_LAUNCH("jpeg_entropy");
@@ -211,11 +213,9 @@ extern "C" int yv4_jpeg_entropy_decode_device_sync(const yv4_jpeg_scan* scans, c
   YV4_REQUIRE(scans && segs && chunks && seg_first && wgs && scans_dev && segs_dev && chunks_dev && seg_first_dev &&
                   wgs_dev && bytes && huff && entries_dev && coef && status && undecided,
               "jpeg_entropy_decode_device_sync: null pointer");
-  YV4_REQUIRE((reinterpret_cast<uintptr_t>(scans_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(segs_dev) & 7) == 0 &&
-                  (reinterpret_cast<uintptr_t>(entries_dev) & 7) == 0 && (reinterpret_cast<uintptr_t>(chunks_dev) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(seg_first_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(wgs_dev) & 3) == 0 &&
-                  (reinterpret_cast<uintptr_t>(huff) & 3) == 0 && (reinterpret_cast<uintptr_t>(coef) & 1) == 0 &&
-                  (reinterpret_cast<uintptr_t>(status) & 3) == 0 && (reinterpret_cast<uintptr_t>(undecided) & 3) == 0,
+  YV4_REQUIRE(aligned(scans_dev, 8) && aligned(segs_dev, 8) && aligned(entries_dev, 8) && aligned(chunks_dev, 4) &&
+                  aligned(seg_first_dev, 4) && aligned(wgs_dev, 4) && aligned(huff, 4) && aligned(coef, 2) &&
+                  aligned(status, 4) && aligned(undecided, 4),
               "jpeg_entropy_decode_device_sync: scans_dev / segs_dev / entries_dev must be 8-byte, the other tables 4-byte "
               "aligned");
   int64_t lo, hi;
@@ -223,13 +223,7 @@ extern "C" int yv4_jpeg_entropy_decode_device_sync(const yv4_jpeg_scan* scans, c
                                     max_rounds, coef_elems, &lo, &hi);
   if (st != YV4_OK) return st;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(coef + lo, 0, (size_t)(hi - lo) * sizeof(int16_t), s) != hipSuccess ||
-      hipMemsetAsync(status, 0, (size_t)N * sizeof(int32_t), s) != hipSuccess ||
-      hipMemsetAsync(undecided, 0, (size_t)N * sizeof(int32_t), s) != hipSuccess) {
-    (void)hipGetLastError();
-    set_error("jpeg_entropy_decode_device_sync: the zero-fill of the coefficients failed");
-    return YV4_E_LAUNCH;
-  }
+  if (int rc = jpeg_zero_fill("jpeg_entropy_decode_device_sync", coef, lo, hi, status, undecided, N, s)) return rc;
   for (int r = 0; r <= max_rounds; ++r) {
     hipLaunchKernelGGL(jpeg_sync_kernel, dim3((unsigned)nwg), dim3(YV4_JPEG_WG_CHUNKS), 0, s, scans_dev, segs_dev,
                        chunks_dev, wgs_dev, bytes, huff, entries_dev, (int)chunk_bytes, r);

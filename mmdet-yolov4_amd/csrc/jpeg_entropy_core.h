@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "yv4.h"
+#include "jpeg_common.h"      // YV4_JPEG_ZIGZAG
 
 #if defined(__HIPCC__) && defined(__HIP__)
 #define YV4_JPEG_HD __host__ __device__ __forceinline__
@@ -86,12 +87,6 @@ YV4_JPEG_HD int receive_extend(BitReader& b, int s) {
   b.skip(s);
   return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
-
-// natural-order index of the k-th coefficient of the scan (the kernel keeps a copy in LDS, next to the Huffman tables)
-#define YV4_JPEG_ZIGZAG                                                                                      \
-  {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,                     \
-   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,                     \
-   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
 
 // One block: blk[0] and the nonzero AC coefficients are written (the block was zero-filled before).  -> 0 or a
 // YV4_JPEG_ERR_* code.

@@ -4,29 +4,17 @@
 // the CPU (yv4_jpeg_chunks_build, yv4_jpeg_entropy_decode_sync).  No HIP call: plain C++, usable without a GPU, and
 // compiled on its own with sanitizers by tools/jpeg_entropy_sanitize.cpp and tools/jpeg_entropy_sync_sanitize.cpp.
 //
-// The bytes are untrusted.  yv4_jpeg_parse has checked every header segment's length against the file before the
-// table pass below walks the same segments; the marker walk reads below len only.
+// The bytes are untrusted.  The header parse (jpeg_host.cpp) has checked every header segment's length against the file
+// and hands over where the Huffman tables it accepted lie; the marker walk reads below len only.
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
 
 #include "yv4.h"
+#include "jpeg_common.h"
 #include "jpeg_entropy_core.h"
 
-namespace yv4 {
-void set_error(const char* fmt, ...);
-int jpeg_entropy_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, const yv4_jpeg_wg* wgs, int N,
-                          int64_t nseg, int64_t nwg, int64_t bytes_len, int64_t nhuff, int64_t coef_elems,
-                          int64_t* coef_lo, int64_t* coef_hi);
-}
-
 namespace {
-
-#define JPEG_FAIL(code, ...)        \
-  do {                              \
-    ::yv4::set_error(__VA_ARGS__);  \
-    return (code);                  \
-  } while (0)
 
 // One DHT table (16 counts, then the values) into the packed form.  jpeg_host.cpp's build_huff has accepted the counts.
 void pack_huff(yv4_jpeg_huff& h, const uint8_t* counts, const uint8_t* vals, int nvals) {
@@ -50,52 +38,38 @@ void pack_huff(yv4_jpeg_huff& h, const uint8_t* counts, const uint8_t* vals, int
   h.maxcode[7] = -1;
 }
 
-// The DHT segments in front of the scan: the last definition of each (class, slot) as a pointer to its counts.  The
-// header segments were validated by yv4_jpeg_parse (which returned YV4_OK for these bytes); every step is checked
-// against scan_offset all the same.
-void find_tables(const uint8_t* d, size_t scan_offset, const uint8_t* found[2][4]) {
-  memset(found, 0, sizeof(const uint8_t*) * 8);
-  size_t pos = 2;
-  while (pos + 4 <= scan_offset) {
-    if (d[pos] != 0xFF) return;
-    size_t q = pos + 1;
-    while (q < scan_offset && d[q] == 0xFF) ++q;      // fill bytes
-    if (q + 3 > scan_offset) return;
-    const unsigned m = d[q];
-    const size_t seglen = ((size_t)d[q + 1] << 8) | d[q + 2];
-    const size_t body = q + 3, next = q + 1 + seglen;
-    if (seglen < 2 || next > scan_offset) return;
-    if (m == 0xC4) {
-      size_t p = body;
-      while (p + 17 <= next) {
-        const unsigned tc = d[p] >> 4, th = d[p] & 15;
-        int nvals = 0;
-        for (int i = 0; i < 16; ++i) nvals += d[p + 1 + i];
-        if (tc > 1 || th > 3 || nvals > 256 || p + 17 + (size_t)nvals > next) return;
-        found[tc][th] = d + p + 1;
-        p += 17 + (size_t)nvals;
-      }
-    }
-    if (m == 0xDA) return;
-    pos = next;
-  }
-}
-
 const uint8_t kZigzag[64] = YV4_JPEG_ZIGZAG;
 
-int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// One run of a workgroup table (for_each_run): the builders' store, which only counts without a table, and the
+// validators' comparison.
+int put_run(const char* who, yv4_jpeg_wg* wgs, int64_t capacity, int64_t& n, int image, int64_t first, int64_t count) {
+  if (wgs) {
+    if (n >= capacity) {
+      ::yv4::set_error("%s: more than %lld workgroups", who, (long long)capacity);
+      return YV4_E_CAPACITY;
+    }
+    wgs[n] = {image, (int32_t)first, (int32_t)count, 0};
+  }
+  ++n;
+  return YV4_OK;
+}
+
+bool is_run(const yv4_jpeg_wg& w, int image, int64_t first, int64_t count) {
+  return w.image == image && w.first_seg == first && w.count == count;
+}
 
 }  // namespace
 
 extern "C" int yv4_jpeg_scan_prepare(const uint8_t* data, size_t len, yv4_jpeg_info* info, yv4_jpeg_scan* scan,
                                      yv4_jpeg_huff* huff, yv4_jpeg_segment* segs, int64_t seg_capacity) {
   if (!data || !info || !scan || !huff || !segs) JPEG_FAIL(YV4_E_INVALID, "jpeg_scan_prepare: null pointer");
-  const int st = yv4_jpeg_parse(data, len, info);
+  const uint8_t* dht[2][4];      // the one header walk: the info, and where the tables it accepted lie
+  const int st = yv4::jpeg_parse_tables(data, len, info, dht);
   if (st != YV4_OK) return st;
   memset(scan, 0, sizeof(*scan));
   const int64_t total = (int64_t)info->mcus_x * info->mcus_y;
   const int64_t ri = info->restart_interval;
-  const int64_t nseg = ri ? ceil_div64(total, ri) : 1;
+  const int64_t nseg = ri ? (total + ri - 1) / ri : 1;
   if (nseg > 0x7fffffff) JPEG_FAIL(YV4_E_INVALID, "jpeg_scan_prepare: %lld segments", (long long)nseg);
   scan->data_len = (int64_t)len;
   scan->ncoef = info->ncoef;
@@ -108,17 +82,15 @@ extern "C" int yv4_jpeg_scan_prepare(const uint8_t* data, size_t len, yv4_jpeg_i
     return YV4_E_CAPACITY;
   }
 
-  // the tables the scan references, each packed once
-  const uint8_t* found[2][4];
-  find_tables(data, (size_t)info->scan_offset, found);
+  // the tables the scan references, each packed once (the parse has refused a scan that names a missing one)
   int slot[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
   int nhuff = 0;
   for (int i = 0; i < info->ncomp; ++i)
     for (int cls = 0; cls < 2; ++cls) {
       const int id = cls ? info->ta[i] : info->td[i];
-      if (!found[cls][id]) JPEG_FAIL(YV4_E_INVALID, "jpeg_scan_prepare: Huffman table %d of class %d is missing", id, cls);
+      if (!dht[cls][id]) JPEG_FAIL(YV4_E_INVALID, "jpeg_scan_prepare: Huffman table %d of class %d is missing", id, cls);
       if (slot[cls][id] < 0) {
-        const uint8_t* counts = found[cls][id];
+        const uint8_t* counts = dht[cls][id];
         int nvals = 0;
         for (int k = 0; k < 16; ++k) nvals += counts[k];
         pack_huff(huff[nhuff], counts, counts + 16, nvals);
@@ -165,23 +137,14 @@ extern "C" int yv4_jpeg_entropy_workgroups(const yv4_jpeg_scan* scans, int N, yv
   int64_t n = 0;
   for (int i = 0; i < N; ++i) {
     if (scans[i].nseg < 1) JPEG_FAIL(YV4_E_INVALID, "jpeg_entropy_workgroups: image %d has no segment", i);
-    for (int32_t first = 0; first < scans[i].nseg; first += YV4_JPEG_WG_SEGMENTS, ++n) {
-      if (!wgs) continue;
-      if (n >= wg_capacity) {
-        ::yv4::set_error("jpeg_entropy_workgroups: more than %lld workgroups", (long long)wg_capacity);
-        return YV4_E_CAPACITY;
-      }
-      const int32_t left = scans[i].nseg - first;
-      wgs[n].image = i; wgs[n].first_seg = first;
-      wgs[n].count = left < YV4_JPEG_WG_SEGMENTS ? left : YV4_JPEG_WG_SEGMENTS;
-      wgs[n].reserved = 0;
-    }
+    const int st = yv4::for_each_run(0, scans[i].nseg, YV4_JPEG_WG_SEGMENTS, [&](int64_t first, int64_t cnt) {
+      return put_run("jpeg_entropy_workgroups", wgs, wg_capacity, n, i, first, cnt);
+    });
+    if (st != YV4_OK) return st;
   }
   *count = n;
   return YV4_OK;
 }
-
-#define REQUIRE(cond, ...) do { if (!(cond)) JPEG_FAIL(YV4_E_INVALID, __VA_ARGS__); } while (0)
 
 // Everything the decode indexes with, checked on the host copies: the kernel trusts the device copies.
 // -> [*coef_lo, *coef_hi): the batch's coefficient range.
@@ -225,13 +188,13 @@ int yv4::jpeg_entropy_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segmen
       mcu += g.mcu_count;
     }
     REQUIRE(mcu == total, "jpeg_entropy: image %d: its segments hold %lld of %lld MCUs", n, (long long)mcu, (long long)total);
-    for (int32_t first = 0; wgs && first < c.nseg; first += YV4_JPEG_WG_SEGMENTS, ++wg) {
+    const int st = for_each_run(0, wgs ? c.nseg : 0, YV4_JPEG_WG_SEGMENTS, [&](int64_t first, int64_t cnt) -> int {
       REQUIRE(wg < nwg, "jpeg_entropy: image %d: the workgroup table ends early", n);
-      const int32_t left = c.nseg - first;
-      REQUIRE(wgs[wg].image == n && wgs[wg].first_seg == first &&
-                  wgs[wg].count == (left < YV4_JPEG_WG_SEGMENTS ? left : YV4_JPEG_WG_SEGMENTS),
-              "jpeg_entropy: workgroup %lld is not the next run of image %d", (long long)wg, n);
-    }
+      REQUIRE(is_run(wgs[wg], n, first, cnt), "jpeg_entropy: workgroup %lld is not the next run of image %d", (long long)wg, n);
+      ++wg;
+      return YV4_OK;
+    });
+    if (st != YV4_OK) return st;
     seg += c.nseg;
     if (c.coef_off < lo) lo = c.coef_off;
     if (c.coef_off + c.ncoef > hi) hi = c.coef_off + c.ncoef;
@@ -265,13 +228,6 @@ extern "C" int yv4_jpeg_entropy_decode_segments(const yv4_jpeg_scan* scans, cons
 
 // ---- self-synchronising chunks (include/yv4.h) ----------------------------------------------------------------------------
 
-namespace {
-int64_t chunks_of(const yv4_jpeg_segment& g, int32_t chunk_bytes) {
-  const int64_t n = ceil_div64(g.end - g.begin, chunk_bytes);
-  return n < 1 ? 1 : n;
-}
-}  // namespace
-
 extern "C" int yv4_jpeg_chunks_build(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs, int N, int64_t nseg,
                                      int32_t chunk_bytes, yv4_jpeg_chunk* chunks, int64_t chunk_capacity,
                                      int32_t* seg_first, yv4_jpeg_wg* wgs, int64_t wg_capacity, int64_t* nchunk,
@@ -289,7 +245,7 @@ extern "C" int yv4_jpeg_chunks_build(const yv4_jpeg_scan* scans, const yv4_jpeg_
     for (int32_t s = 0; s < c.nseg; ++s, ++seg) {
       const yv4_jpeg_segment& g = segs[seg];
       REQUIRE(g.begin >= 0 && g.begin <= g.end, "jpeg_chunks_build: image %d: segment %d has end < begin", n, s);
-      const int64_t cnt = chunks_of(g, chunk_bytes);
+      const int64_t cnt = yv4::jpeg_chunks_of(g, chunk_bytes);
       REQUIRE(nc + cnt < (1ll << 31), "jpeg_chunks_build: the batch has 2^31 chunks or more");
       if (chunks) {
         if (nc + cnt > chunk_capacity) {
@@ -304,17 +260,10 @@ extern "C" int yv4_jpeg_chunks_build(const yv4_jpeg_scan* scans, const yv4_jpeg_
       }
       nc += cnt;
     }
-    for (int64_t first = image_first; first < nc; first += YV4_JPEG_WG_CHUNKS, ++nw) {
-      if (!chunks) continue;
-      if (nw >= wg_capacity) {
-        ::yv4::set_error("jpeg_chunks_build: more than %lld workgroups", (long long)wg_capacity);
-        return YV4_E_CAPACITY;
-      }
-      const int64_t left = nc - first;
-      wgs[nw].image = n; wgs[nw].first_seg = (int32_t)first;
-      wgs[nw].count = (int32_t)(left < YV4_JPEG_WG_CHUNKS ? left : YV4_JPEG_WG_CHUNKS);
-      wgs[nw].reserved = 0;
-    }
+    const int st = yv4::for_each_run(image_first, nc, YV4_JPEG_WG_CHUNKS, [&](int64_t first, int64_t cnt) {
+      return put_run("jpeg_chunks_build", chunks ? wgs : nullptr, wg_capacity, nw, n, first, cnt);
+    });
+    if (st != YV4_OK) return st;
   }
   REQUIRE(seg == nseg, "jpeg_chunks_build: %lld segments for a table of %lld", (long long)seg, (long long)nseg);
   if (chunks) seg_first[nseg] = (int32_t)nc;
@@ -343,7 +292,7 @@ int jpeg_sync_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs,
     const int64_t image_first = nc;
     for (int32_t s = 0; s < c.nseg; ++s) {
       const int64_t seg = c.seg_base + s;
-      const int64_t cnt = chunks_of(segs[seg], chunk_bytes);
+      const int64_t cnt = jpeg_chunks_of(segs[seg], chunk_bytes);
       REQUIRE(cnt <= nchunk - nc, "jpeg_entropy_sync: image %d: the chunk table ends early", n);
       REQUIRE(seg_first[seg] == nc, "jpeg_entropy_sync: image %d: seg_first of segment %d", n, s);
       for (int64_t i = 0; i < cnt; ++i) {
@@ -354,13 +303,13 @@ int jpeg_sync_validate(const yv4_jpeg_scan* scans, const yv4_jpeg_segment* segs,
       }
       nc += cnt;
     }
-    for (int64_t first = image_first; first < nc; first += YV4_JPEG_WG_CHUNKS, ++nw) {
+    const int st = for_each_run(image_first, nc, YV4_JPEG_WG_CHUNKS, [&](int64_t first, int64_t cnt) -> int {
       REQUIRE(nw < nwg, "jpeg_entropy_sync: image %d: the workgroup table ends early", n);
-      const int64_t left = nc - first;
-      REQUIRE(wgs[nw].image == n && wgs[nw].first_seg == first &&
-                  wgs[nw].count == (left < YV4_JPEG_WG_CHUNKS ? left : YV4_JPEG_WG_CHUNKS),
-              "jpeg_entropy_sync: workgroup %lld is not the next run of image %d", (long long)nw, n);
-    }
+      REQUIRE(is_run(wgs[nw], n, first, cnt), "jpeg_entropy_sync: workgroup %lld is not the next run of image %d", (long long)nw, n);
+      ++nw;
+      return YV4_OK;
+    });
+    if (st != YV4_OK) return st;
   }
   REQUIRE(nc == nchunk && nw == nwg && seg_first[nseg] == nchunk,
           "jpeg_entropy_sync: %lld chunks and %lld workgroups for tables of %lld and %lld", (long long)nc, (long long)nw,

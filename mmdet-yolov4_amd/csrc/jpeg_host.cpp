@@ -10,22 +10,11 @@
 #include <string.h>
 
 #include "yv4.h"
-
-namespace yv4 {
-void set_error(const char* fmt, ...);
-}
+#include "jpeg_common.h"
 
 namespace {
 
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-#define JPEG_FAIL(code, ...)        \
-  do {                              \
-    ::yv4::set_error(__VA_ARGS__);  \
-    return (code);                  \
-  } while (0)
+const uint8_t kZigzag[64] = YV4_JPEG_ZIGZAG;
 
 // One Huffman table: canonical codes by length, plus a 9-bit lookahead (code length << 8 | symbol, 0: longer code).
 struct Huff {
@@ -39,6 +28,7 @@ struct Huff {
 struct Tables {
   Huff dc[4], ac[4];
   bool quant_defined[4];
+  const uint8_t* dht[2][4];      // [class][slot]: the 16 counts of the table's last definition in the file, or null
 };
 
 struct Cursor {
@@ -180,6 +170,7 @@ int parse_headers(Cursor& c, yv4_jpeg_info* info, Tables* t) {
         if (nvals > 256 || (size_t)nvals > left) JPEG_FAIL(YV4_E_INVALID, "jpeg: Huffman table with %d symbols", nvals);
         const int st = build_huff(tc ? t->ac[th] : t->dc[th], counts, c.d + c.pos, nvals);
         if (st != YV4_OK) return st;
+        t->dht[tc][th] = counts;
         c.pos += (size_t)nvals;
         left -= (size_t)nvals;
       }
@@ -347,13 +338,18 @@ int decode_block(BitReader& b, const Huff& dc, const Huff& ac, int& pred, int16_
 
 }  // namespace
 
-extern "C" int yv4_jpeg_parse(const uint8_t* data, size_t len, yv4_jpeg_info* info) {
-  if (!data || !info) JPEG_FAIL(YV4_E_INVALID, "jpeg_parse: null pointer");
+int yv4::jpeg_parse_tables(const uint8_t* data, size_t len, yv4_jpeg_info* info, const uint8_t* dht[2][4]) {
   Cursor c = {data, len, 0};
   Tables* t = new Tables;
   const int st = parse_headers(c, info, t);
+  if (dht) memcpy(dht, t->dht, sizeof(t->dht));
   delete t;
   return st;
+}
+
+extern "C" int yv4_jpeg_parse(const uint8_t* data, size_t len, yv4_jpeg_info* info) {
+  if (!data || !info) JPEG_FAIL(YV4_E_INVALID, "jpeg_parse: null pointer");
+  return yv4::jpeg_parse_tables(data, len, info, nullptr);
 }
 
 extern "C" int yv4_jpeg_entropy_decode(const uint8_t* data, size_t len, yv4_jpeg_info* info, int16_t* coef,

@@ -370,12 +370,7 @@ class TrainLoader:
         t0 = time.perf_counter()
         bufs = list(self._readers.map(_read, [self._path(j) for j in sources]))
         t1 = time.perf_counter()
-        refused = {}
-        for k, b in enumerate(bufs):
-            try:
-                image_io.jpeg_parse(image_io._as_bytes(b))
-            except NotImplementedError as e:
-                refused[k] = e
+        refused = image_io.refusals(bufs)
         host = None
         if not refused:
             host = self._host_half(bufs, sources)
@@ -412,13 +407,8 @@ class TrainLoader:
                 self.resampled += 1
                 sources[k] = int(self.dataset._rand_another(sources[k], rng))
                 bufs[k] = _read(self._path(sources[k]))
-            again = {}
-            for k in refused:
-                try:
-                    image_io.jpeg_parse(image_io._as_bytes(bufs[k]))
-                except NotImplementedError as e:
-                    again[k] = e
-            refused = again
+            drawn = sorted(refused)
+            refused = {drawn[i]: e for i, e in image_io.refusals([bufs[k] for k in drawn]).items()}
             if not refused:
                 host = self._host_half(bufs, sources)
             self.times['host'] += time.perf_counter() - t0
@@ -446,10 +436,7 @@ class TrainLoader:
             out, table = image_io.decode_into(bufs, 'bgr', dev, orientation=self.orientation, host=host)
         except ValueError as e:      # a damaged scan found by the device decode's status read-back
             raise self._named(e, sources) from None
-        imgs = []
-        for t in table:
-            (h, w), off = image_io.oriented_size(t), int(t.out_off)
-            imgs.append(out[off:off + h * w * 3].view(h, w, 3))
+        imgs = image_io.image_views(out, table)
         t1 = time.perf_counter()
         anns = [self.dataset.get_ann_info(j) for j in sources]
         triples = [(im, a['bboxes'], a['labels']) for im, a in zip(imgs, anns)]

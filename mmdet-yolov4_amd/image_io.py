@@ -138,6 +138,44 @@ def _sync_params(chunk_bytes, max_rounds):
     return int(cb), int(mr)
 
 
+def _parse_all(bufs, what):
+    """``yv4_jpeg_parse`` of every file -> the ``JpegInfo`` array.  A refused or malformed file raises as ``jpeg_parse``
+    does, naming the image."""
+    L = _lib.lib()
+    infos = (JpegInfo * len(bufs))()
+    for n, b in enumerate(bufs):
+        st = L.yv4_jpeg_parse(b, len(b), C.byref(infos[n]))
+        if st != 0:
+            _raise(st, f'{what}: image {n}')
+    return infos
+
+
+def _host_decode_all(bufs, infos, base, coef_offs, what):
+    """The host Huffman decode of every file (``yv4_jpeg_entropy_decode``) straight to host address ``base``, image n at
+    int16 element ``coef_offs[n]``, on at most ``MAX_DECODE_THREADS`` threads."""
+    L = _lib.lib()
+
+    def one(n):
+        info = JpegInfo()
+        st = L.yv4_jpeg_entropy_decode(bufs[n], len(bufs[n]), C.byref(info), base + 2 * int(coef_offs[n]), int(infos[n].ncoef))
+        if st != 0:
+            _raise(st, f'{what}: image {n}')
+
+    if len(bufs) == 1:
+        one(0)
+    else:
+        with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, len(bufs))) as pool:      # ctypes releases the GIL
+            list(pool.map(one, range(len(bufs))))
+
+
+def _need(have, symbol, what=None):
+    """``RuntimeError`` unless the loaded library exports ``symbol``, which ``what`` (an argument as written) asks for."""
+    if not have:
+        why = f'{symbol} is not exported by the loaded libyv4_hip.so' if what is None else \
+            f'{what} needs {symbol}, which the loaded libyv4_hip.so does not export (there is no fallback)'
+        raise RuntimeError(why + ': rebuild it')
+
+
 class ScanTables:
     """The host tables of a device Huffman decode (``include/yv4.h``, "the Huffman scan on the device") for a list of
     files: ``infos``, ``scans`` (one per image, placed: files back to back at 4-byte aligned offsets, segments and packed
@@ -148,11 +186,7 @@ class ScanTables:
         L = _lib.lib()
         N = len(bufs)
         self.bufs = bufs
-        self.infos = (JpegInfo * N)()
-        for n, b in enumerate(bufs):
-            st = L.yv4_jpeg_parse(b, len(b), C.byref(self.infos[n]))
-            if st != 0:
-                _raise(st, f'{what}: image {n}')
+        self.infos = _parse_all(bufs, what)
         counts = [-(-f.mcus_x * f.mcus_y // f.restart_interval) if f.restart_interval else 1 for f in self.infos]
         self.nseg = sum(counts)
         self.scans = (JpegScan * N)()
@@ -183,14 +217,21 @@ class ScanTables:
               'yv4_jpeg_entropy_workgroups')
 
     def sections(self):
-        """``(ctypes object or None, byte count)`` of each table in upload order: scans, segs, wgs, huff, file bytes."""
+        """``(source, byte count)`` of each table in upload order (``_stage``): scans, segs, wgs, huff, file bytes."""
         return ((self.scans, C.sizeof(self.scans)), (self.segs, C.sizeof(self.segs)), (self.wgs, C.sizeof(self.wgs)),
-                (self.huff, self.nhuff * C.sizeof(JpegHuff)), (None, self.nbytes))
+                (self.huff, self.nhuff * C.sizeof(JpegHuff)), (self.write_bytes, self.nbytes))
 
     def write_bytes(self, base):
         """The files to host address ``base`` at their ``data_off``."""
         for sc, b in zip(self.scans, self.bufs):
             C.memmove(base + int(sc.data_off), b, len(b))
+
+    def cpu_buffers(self, flags):
+        """What a CPU run of the core decodes from and into: the files in a zeroed byte array, the int16 coefficient
+        array, and ``flags`` arrays of one int32 per image."""
+        data = np.zeros(max(self.nbytes, 1), np.uint8)
+        self.write_bytes(data.ctypes.data)
+        return (data, np.empty(self.ncoef, np.int16)) + tuple(np.empty(len(self.bufs), np.int32) for _ in range(flags))
 
 
 class ChunkTables:
@@ -212,14 +253,9 @@ class ChunkTables:
               'yv4_jpeg_chunks_build')
 
     def sections(self):
-        """``(ctypes object, byte count)`` of each table in upload order: chunks, seg_first, wgs."""
+        """``(source, byte count)`` of each table in upload order: chunks, seg_first, wgs."""
         return ((self.chunks, C.sizeof(self.chunks)), (self.seg_first, C.sizeof(self.seg_first)),
                 (self.wgs, C.sizeof(self.wgs)))
-
-
-def _one_chunk_each(scan, chunk_bytes):
-    """Every segment of the batch is at most one chunk long: chunks would add no lane."""
-    return all(g.end - g.begin <= chunk_bytes for g in scan.segs)
 
 
 def jpeg_entropy_decode_sync(bufs, chunk_bytes=None, max_rounds=None):
@@ -230,11 +266,7 @@ def jpeg_entropy_decode_sync(bufs, chunk_bytes=None, max_rounds=None):
     chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
     t = ScanTables(bufs)
     ch = ChunkTables(t, chunk_bytes)
-    data = np.zeros(max(t.nbytes, 1), np.uint8)
-    t.write_bytes(data.ctypes.data)
-    coef = np.empty(t.ncoef, np.int16)
-    status = np.empty(len(bufs), np.int32)
-    undecided = np.empty(len(bufs), np.int32)
+    data, coef, status, undecided = t.cpu_buffers(2)
     entries = (JpegEntry * ch.nchunk)()
     rounds = C.c_int32()
     check(_lib.lib().yv4_jpeg_entropy_decode_sync(
@@ -245,12 +277,48 @@ def jpeg_entropy_decode_sync(bufs, chunk_bytes=None, max_rounds=None):
     return t, ch, entries, coef, status, undecided, int(rounds.value)
 
 
-def _upload_plan(sections, start=0):
-    offs, end = [], start
+def jpeg_entropy_decode_segments(bufs):
+    """The device decode's tables and core run on the CPU (``yv4_jpeg_entropy_decode_segments``) -> ``(ScanTables, int16
+    coefficients of the batch, int32 status per image)``.  Needs no GPU."""
+    t = ScanTables(bufs)
+    data, coef, status = t.cpu_buffers(1)
+    check(_lib.lib().yv4_jpeg_entropy_decode_segments(
+        C.addressof(t.scans), C.addressof(t.segs), C.addressof(t.wgs), len(bufs), t.nseg, t.nwg, data.ctypes.data, t.nbytes,
+        C.addressof(t.huff), t.nhuff, coef.ctypes.data, coef.size, status.ctypes.data), 'yv4_jpeg_entropy_decode_segments')
+    return t, coef, status
+
+
+def _stage(sections):
+    """One pinned staging buffer holding ``sections``, each at the next 256-byte boundary -> ``(uint8 tensor, offsets)``.
+    A section is ``(source, byte count)``; a source is a ctypes object to copy, or a function that writes the section
+    at the host address it is given (the files, the quantisation tables, the host decode's coefficients)."""
+    offs, end = [], 0
     for _, size in sections:
         offs.append(end)
         end += _align(size)
-    return offs, end
+    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
+    for (src, size), off in zip(sections, offs):
+        if callable(src):
+            src(stage.data_ptr() + off)
+        else:
+            C.memmove(stage.data_ptr() + off, src, size)
+    return stage, offs
+
+
+def _quant_section(infos):
+    """The quantisation tables of a batch as a ``_stage`` section: (N, 4, 64) uint16."""
+    def write(base):
+        for n, f in enumerate(infos):
+            C.memmove(base + n * 512, f.quant, 512)
+    return write, len(infos) * 512
+
+
+def _launch_segments(L, scan, d, N, coef, ncoef, status):
+    """``yv4_jpeg_entropy_decode_device`` over uploaded tables: ``d`` holds the device addresses of ``scan.sections()``."""
+    check(L.yv4_jpeg_entropy_decode_device(
+        C.addressof(scan.scans), C.addressof(scan.segs), C.addressof(scan.wgs), d[0], d[1], d[2], N, scan.nseg, scan.nwg,
+        d[4], scan.nbytes, d[3], scan.nhuff, coef.data_ptr(), ncoef, status.data_ptr(), stream_ptr()),
+        'yv4_jpeg_entropy_decode_device')
 
 
 def _launch_sync(L, scan, ch, d, N, max_rounds, entries, coef, ncoef, status, undecided):
@@ -269,18 +337,11 @@ def jpeg_entropy_decode_device_sync(bufs, chunk_bytes=None, max_rounds=None, dev
     coefficient tensor, int32 status tensor, int32 undecided tensor)`` on the GPU, nothing read back.  ``coef`` /
     ``status`` / ``undecided``: the caller's tensors to decode into, as in ``jpeg_entropy_decode_device``."""
     chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
-    if not _lib.has_jpeg_sync():
-        raise RuntimeError('yv4_jpeg_entropy_decode_device_sync is not exported by the loaded libyv4_hip.so: rebuild it')
+    _need(_lib.has_jpeg_sync(), 'yv4_jpeg_entropy_decode_device_sync')
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     t = ScanTables(bufs) if tables is None else tables
     ch = ChunkTables(t, chunk_bytes)
-    sections = t.sections() + ch.sections()
-    offs, end = _upload_plan(sections)
-    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
-    for (obj, size), off in zip(sections, offs):
-        if obj is not None:
-            C.memmove(stage.data_ptr() + off, obj, size)
-    t.write_bytes(stage.data_ptr() + offs[4])
+    stage, offs = _stage(t.sections() + ch.sections())
     with torch.cuda.device(dev):
         up = stage.to(dev, non_blocking=True)
         coef = torch.empty(t.ncoef, dtype=torch.int16, device=dev) if coef is None else coef
@@ -292,44 +353,18 @@ def jpeg_entropy_decode_device_sync(bufs, chunk_bytes=None, max_rounds=None, dev
     return t, ch, coef, status, undecided
 
 
-def jpeg_entropy_decode_segments(bufs):
-    """The device decode's tables and core run on the CPU (``yv4_jpeg_entropy_decode_segments``) -> ``(ScanTables, int16
-    coefficients of the batch, int32 status per image)``.  Needs no GPU."""
-    t = ScanTables(bufs)
-    data = np.zeros(max(t.nbytes, 1), np.uint8)
-    t.write_bytes(data.ctypes.data)
-    coef = np.empty(t.ncoef, np.int16)
-    status = np.empty(len(bufs), np.int32)
-    check(_lib.lib().yv4_jpeg_entropy_decode_segments(
-        C.addressof(t.scans), C.addressof(t.segs), C.addressof(t.wgs), len(bufs), t.nseg, t.nwg, data.ctypes.data, t.nbytes,
-        C.addressof(t.huff), t.nhuff, coef.ctypes.data, coef.size, status.ctypes.data), 'yv4_jpeg_entropy_decode_segments')
-    return t, coef, status
-
-
 def jpeg_entropy_decode_device(bufs, device=None, coef=None, status=None, tables=None):
     """The device Huffman decode on its own -> ``(ScanTables, int16 coefficient tensor, int32 status tensor)`` on the GPU,
     nothing read back.  ``coef`` / ``status``: the caller's tensors to decode into (``tables.ncoef`` / ``len(bufs)``
     elements, views into larger buffers say); ``tables``: a ``ScanTables`` of ``bufs`` made before."""
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     t = ScanTables(bufs) if tables is None else tables
-    offs, end = [], 0
-    for _, size in t.sections():
-        offs.append(end)
-        end += _align(size)
-    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
-    for (obj, size), off in zip(t.sections(), offs):
-        if obj is not None:
-            C.memmove(stage.data_ptr() + off, obj, size)
-    t.write_bytes(stage.data_ptr() + offs[4])
+    stage, offs = _stage(t.sections())
     with torch.cuda.device(dev):
         up = stage.to(dev, non_blocking=True)
         coef = torch.empty(t.ncoef, dtype=torch.int16, device=dev) if coef is None else coef
         status = torch.empty(len(bufs), dtype=torch.int32, device=dev) if status is None else status
-        d = [up.data_ptr() + o for o in offs]
-        check(_lib.lib().yv4_jpeg_entropy_decode_device(
-            C.addressof(t.scans), C.addressof(t.segs), C.addressof(t.wgs), d[0], d[1], d[2], len(bufs), t.nseg, t.nwg, d[4],
-            t.nbytes, d[3], t.nhuff, coef.data_ptr(), coef.numel(), status.data_ptr(), stream_ptr()),
-            'yv4_jpeg_entropy_decode_device')
+        _launch_segments(_lib.lib(), t, [up.data_ptr() + o for o in offs], len(bufs), coef, coef.numel(), status)
     return t, coef, status
 
 
@@ -337,47 +372,64 @@ class HostHalf:
     """What the host does for a batch before any GPU call, so that a worker thread can do it ahead of time
     (``decode_into(host=...)``): the header parses (``infos``), with a device mode the scan and chunk tables, with
     ``'host'`` the Huffman decodes into ``coef`` (int16, the images back to back as ``yv4_jpeg_layout`` places them).
-    Makes no HIP and no torch call.  A refused or malformed file raises as ``imdecode`` does, naming the image."""
+    Makes no HIP and no torch call.  A refused or malformed file raises as ``imdecode`` does, naming the image.
+    ``run=False`` only validates the parameters: ``tables()`` then does the parses and the tables, and ``decode()`` the
+    ``'host'`` mode's Huffman decodes (``decode_into`` decodes into its staging buffer instead)."""
 
-    def __init__(self, bufs, entropy=None, chunk_bytes=None, max_rounds=None, what='imdecode'):
+    def __init__(self, bufs, entropy=None, chunk_bytes=None, max_rounds=None, what='imdecode', run=True):
         self.mode = _entropy_mode(entropy)
         self.chunk_bytes, self.max_rounds = chunk_bytes, max_rounds
         if self.mode == 'device_sync' or chunk_bytes is not None or max_rounds is not None:
             self.chunk_bytes, self.max_rounds = _sync_params(chunk_bytes, max_rounds)
-        L = _lib.lib()
-        N = len(bufs)
-        self.bufs, self.scan, self.chunks, self.coef = bufs, None, None, None
-        if self.mode != 'host':
-            self.scan = ScanTables(bufs, what=what)
-            self.infos = self.scan.infos
-            if self.mode == 'device_sync' and not _one_chunk_each(self.scan, self.chunk_bytes):
-                self.chunks = ChunkTables(self.scan, self.chunk_bytes)
+        self.bufs, self.what = bufs, what
+        self.infos = self.scan = self.chunks = self.coef = None
+        if run:
+            self.tables()
+            self.decode()
+
+    def tables(self):
+        """The table half: the parses, and with a device mode the scan and chunk tables.  No Huffman decode."""
+        if self.mode == 'host':
+            self.infos = _parse_all(self.bufs, self.what)
             return
-        self.infos = (JpegInfo * N)()
-        for n, b in enumerate(bufs):
-            st = L.yv4_jpeg_parse(b, len(b), C.byref(self.infos[n]))
-            if st != 0:
-                _raise(st, f'{what}: image {n}')
-        offs = np.concatenate([[0], np.cumsum([int(f.ncoef) for f in self.infos])])
-        self.coef = np.empty(int(offs[-1]), np.int16)
+        self.scan = ScanTables(self.bufs, what=self.what)
+        self.infos = self.scan.infos
+        # chunks add no lane to a batch whose every segment is at most one chunk long: it is decoded as 'device'
+        if self.mode == 'device_sync' and any(g.end - g.begin > self.chunk_bytes for g in self.scan.segs):
+            self.chunks = ChunkTables(self.scan, self.chunk_bytes)
 
-        def one(n):
-            info = JpegInfo()
-            st = L.yv4_jpeg_entropy_decode(bufs[n], len(bufs[n]), C.byref(info), self.coef.ctypes.data + 2 * int(offs[n]),
-                                           int(self.infos[n].ncoef))
-            if st != 0:
-                _raise(st, f'{what}: image {n}')
-
-        if N == 1:
-            one(0)
-        else:
-            with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, N)) as pool:      # ctypes releases the GIL
-                list(pool.map(one, range(N)))
+    def decode(self):
+        """The ``'host'`` mode's Huffman decodes into ``coef``; nothing in a device mode."""
+        if self.mode == 'host':
+            offs = np.concatenate([[0], np.cumsum([int(f.ncoef) for f in self.infos])])
+            self.coef = np.empty(int(offs[-1]), np.int16)
+            _host_decode_all(self.bufs, self.infos, self.coef.ctypes.data, offs, self.what)
 
 
 def oriented_size(t):
     """``(height, width)`` of the picture a ``JpegImage`` entry writes: swapped for orientations 5 to 8."""
     return (int(t.width), int(t.height)) if t.orientation >= 5 else (int(t.height), int(t.width))
+
+
+def image_views(out, table):
+    """The (h, w, 3) views of the images ``table`` places in the flat buffer ``out`` (``decode_into``'s results)."""
+    views = []
+    for t in table:
+        (h, w), off = oriented_size(t), int(t.out_off)
+        views.append(out[off:off + h * w * 3].view(h, w, 3))
+    return views
+
+
+def refusals(bufs):
+    """The files of ``bufs`` the decoder refuses -> ``{position: NotImplementedError}``: another format, or a JPEG that
+    ``jpeg_parse`` refuses.  A malformed header raises as ``jpeg_parse`` does."""
+    refused = {}
+    for k, b in enumerate(bufs):
+        try:
+            jpeg_parse(_as_bytes(b))
+        except NotImplementedError as e:
+            refused[k] = e
+    return refused
 
 
 def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None, entropy=None, chunk_bytes=None,
@@ -405,41 +457,19 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
     if not torch.cuda.is_available():
         raise RuntimeError('the JPEG decoder reconstructs the pixels on the GPU through libyv4_hip.so (there is no CPU '
                            'fallback)')
-    if host is not None:
-        mode, chunk_bytes, max_rounds = host.mode, host.chunk_bytes, host.max_rounds
-    else:
-        mode = _entropy_mode(entropy)
-        if mode == 'device_sync' or chunk_bytes is not None or max_rounds is not None:
-            chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
-    if orientation and not _lib.has_jpeg_orientation():
-        raise RuntimeError('orientation=True needs yv4_jpeg_layout_oriented, which the loaded libyv4_hip.so does not export '
-                           '(there is no fallback): rebuild it')
+    own = host is None      # no host half made ahead: its table half here, its Huffman decodes straight into the stage
+    if own:
+        host = HostHalf(bufs, entropy, chunk_bytes, max_rounds, run=False)
+    mode = host.mode
+    _need(not orientation or _lib.has_jpeg_orientation(), 'yv4_jpeg_layout_oriented', 'orientation=True')
+    _need(mode == 'host' or _lib.has_jpeg_entropy(), 'yv4_jpeg_entropy_decode_device', "entropy='device'")
+    _need(mode != 'device_sync' or _lib.has_jpeg_sync(), 'yv4_jpeg_entropy_decode_device_sync', "entropy='device_sync'")
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     L = _lib.lib()
     N = len(bufs)
-    scan = chunks = None
-    if mode != 'host':
-        if not _lib.has_jpeg_entropy():
-            raise RuntimeError("entropy='device' needs yv4_jpeg_entropy_decode_device, which the loaded libyv4_hip.so "
-                               'does not export (there is no fallback): rebuild it')
-        if mode == 'device_sync' and not _lib.has_jpeg_sync():
-            raise RuntimeError("entropy='device_sync' needs yv4_jpeg_entropy_decode_device_sync, which the loaded "
-                               'libyv4_hip.so does not export (there is no fallback): rebuild it')
-        if host is not None:
-            scan, chunks = host.scan, host.chunks
-        else:
-            scan = ScanTables(bufs, what='imdecode')
-            if mode == 'device_sync' and not _one_chunk_each(scan, chunk_bytes):
-                chunks = ChunkTables(scan, chunk_bytes)
-        infos = scan.infos
-    elif host is not None:
-        infos = host.infos
-    else:
-        infos = (JpegInfo * N)()
-        for n, b in enumerate(bufs):
-            st = L.yv4_jpeg_parse(b, len(b), C.byref(infos[n]))
-            if st != 0:
-                _raise(st, f'imdecode: image {n}')
+    if own:
+        host.tables()
+    infos, scan, chunks = host.infos, host.scan, host.chunks
     table = (JpegImage * N)()
     totals = (C.c_int64 * 3)()
     if orientation:
@@ -457,42 +487,17 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
                 raise ValueError(f'imdecode: image {n}: pitch {int(pitch)} is narrower than its oriented row of '
                                  f'{3 * oriented_size(table[n])[1]} bytes')
 
-    # one pinned staging buffer: [per-image table | quantisation tables (N, 4, 64) uint16 | ...
-    quant_off = _align(C.sizeof(table))
-    coef_off = quant_off + _align(N * 4 * 64 * 2)
-    if scan is None:      # ... coefficients int16]
-        stage = torch.empty(coef_off + 2 * ncoef, dtype=torch.uint8, pin_memory=True)
-    else:                 # ... scans | segments | workgroups | packed Huffman tables | the files | chunk tables]: no coefficients
-        sections = scan.sections() + (chunks.sections() if chunks is not None else ())
-        offs, end = _upload_plan(sections, coef_off)
-        stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
-    base = stage.data_ptr()
-    C.memmove(base, table, C.sizeof(table))
-    for n in range(N):
-        C.memmove(base + quant_off + n * 512, infos[n].quant, 512)
-
-    def entropy_host(n):
-        info = JpegInfo()
-        st = L.yv4_jpeg_entropy_decode(bufs[n], len(bufs[n]), C.byref(info), base + coef_off + 2 * int(table[n].coef_off),
-                                       int(infos[n].ncoef))
-        if st != 0:
-            _raise(st, f'imdecode: image {n}')
-
-    if scan is not None:
-        for (obj, size), off in zip(sections, offs):
-            if obj is not None:
-                C.memmove(base + off, obj, size)
-        scan.write_bytes(base + offs[4])
-    elif host is not None:
-        C.memmove(base + coef_off, host.coef.ctypes.data, 2 * ncoef)
-    elif N == 1:
-        entropy_host(0)
-    else:
-        with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, N)) as pool:      # ctypes releases the GIL
-            list(pool.map(entropy_host, range(N)))
+    # one pinned staging buffer: [per-image table | quantisation tables | ...
+    if scan is not None:      # ... scans | segments | workgroups | packed Huffman tables | the files | chunk tables]
+        tail = scan.sections() + (chunks.sections() if chunks is not None else ())
+    elif own:                 # ... coefficients int16], decoded in place
+        tail = ((lambda p: _host_decode_all(bufs, infos, p, [t.coef_off for t in table], 'imdecode'), 2 * ncoef),)
+    else:                     # ... coefficients int16], decoded ahead
+        tail = ((lambda p: C.memmove(p, host.coef.ctypes.data, 2 * ncoef), 2 * ncoef),)
+    stage, offs = _stage(((table, C.sizeof(table)), _quant_section(infos)) + tail)
 
     def reconstruct(coef_ptr):
-        check(L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, coef_ptr, ncoef, up.data_ptr() + quant_off,
+        check(L.yv4_jpeg_reconstruct(table, up.data_ptr(), N, coef_ptr, ncoef, up.data_ptr() + offs[1],
                                      work.data_ptr(), work_bytes, out.data_ptr(), out_bytes,
                                      int(channel_order == 'rgb'), stream_ptr()), 'yv4_jpeg_reconstruct')
 
@@ -503,21 +508,18 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
         if placement is None:
             out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
         if scan is None:
-            coef_ptr = up.data_ptr() + coef_off
+            coef_ptr = up.data_ptr() + offs[2]
         else:
             coef = torch.empty(ncoef, dtype=torch.int16, device=dev)
             flags = torch.empty(2 * N, dtype=torch.int32, device=dev)      # status | undecided: one read-back
             status = flags[:N]
-            d = [up.data_ptr() + o for o in offs]
+            d = [up.data_ptr() + o for o in offs[2:]]
             if chunks is None:
-                check(L.yv4_jpeg_entropy_decode_device(
-                    C.addressof(scan.scans), C.addressof(scan.segs), C.addressof(scan.wgs), d[0], d[1], d[2], N, scan.nseg,
-                    scan.nwg, d[4], scan.nbytes, d[3], scan.nhuff, coef.data_ptr(), ncoef, status.data_ptr(),
-                    stream_ptr()), 'yv4_jpeg_entropy_decode_device')
+                _launch_segments(L, scan, d, N, coef, ncoef, status)
             else:
                 undecided = flags[N:]
                 entries = torch.empty(chunks.nchunk * C.sizeof(JpegEntry), dtype=torch.uint8, device=dev)
-                _launch_sync(L, scan, chunks, d, N, max_rounds, entries, coef, ncoef, status, undecided)
+                _launch_sync(L, scan, chunks, d, N, host.max_rounds, entries, coef, ncoef, status, undecided)
             coef_ptr = coef.data_ptr()
         reconstruct(coef_ptr)
         if status is not None:
@@ -563,10 +565,7 @@ def imdecode(buffers, channel_order='bgr', device=None, entropy=None, chunk_byte
         return []
     out, table = decode_into(bufs, channel_order, device, entropy=entropy, chunk_bytes=chunk_bytes, max_rounds=max_rounds,
                              orientation=orientation)
-    imgs = []
-    for t in table:
-        (h, w), off = oriented_size(t), int(t.out_off)
-        imgs.append(out[off:off + h * w * 3].view(h, w, 3))
+    imgs = image_views(out, table)
     return imgs[0] if single else imgs
 
 

@@ -96,20 +96,14 @@ def main():
     res = dict(images=N, height=480, width=640, sampling='4:2:0', quality=90, mean_file_bytes=file_bytes // N)
 
     # ---- host half ------------------------------------------------------------------------------------------------
-    infos = (JpegInfo * N)()
-    for n, b in enumerate(bufs):
-        assert L.yv4_jpeg_parse(b, len(b), C.byref(infos[n])) == 0
+    infos = image_io._parse_all(bufs, 'jpeg_bench')
     table = (JpegImage * N)()
     totals = (C.c_int64 * 3)()
     assert L.yv4_jpeg_layout(infos, N, table, totals) == 0
     ncoef, work_bytes, out_bytes = (int(t) for t in totals)
-    quant_off = image_io._align(C.sizeof(table))
-    coef_off = quant_off + image_io._align(N * 512)
-    stage = torch.empty(coef_off + 2 * ncoef, dtype=torch.uint8, pin_memory=True)
+    stage, (_, quant_off, coef_off) = image_io._stage(((table, C.sizeof(table)), image_io._quant_section(infos),
+                                                       (lambda p: None, 2 * ncoef)))      # coefficients: host() below
     base = stage.data_ptr()
-    C.memmove(base, table, C.sizeof(table))
-    for n in range(N):
-        C.memmove(base + quant_off + n * 512, infos[n].quant, 512)
 
     def host(n):
         info = JpegInfo()
@@ -266,18 +260,8 @@ def device_phases(kind, src, B, repeats, dev):
     totals = (C.c_int64 * 3)()
     assert L.yv4_jpeg_layout(t.infos, B, table, totals) == 0
     ncoef, work_bytes, out_bytes = (int(v) for v in totals)
-    sections = ((table, C.sizeof(table)), (None, B * 512)) + tuple(t.sections())
-    offs, end = [], 0
-    for _, size in sections:
-        offs.append(end)
-        end += image_io._align(size)
-    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
-    for (obj, size), off in zip(sections, offs):
-        if obj is not None:
-            C.memmove(stage.data_ptr() + off, obj, size)
-    for n in range(B):
-        C.memmove(stage.data_ptr() + offs[1] + n * 512, t.infos[n].quant, 512)
-    t.write_bytes(stage.data_ptr() + offs[6])
+    stage, offs = image_io._stage(((table, C.sizeof(table)), image_io._quant_section(t.infos)) + t.sections())
+    end = stage.numel()
     r['staging_bytes'], r['host_path_staging_bytes'] = end, offs[2] + 2 * ncoef
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     up = torch.empty(end, dtype=torch.uint8, device=dev)
@@ -303,10 +287,7 @@ def device_phases(kind, src, B, repeats, dev):
     calls = 3
 
     def entropy():
-        st = L.yv4_jpeg_entropy_decode_device(C.addressof(t.scans), C.addressof(t.segs), C.addressof(t.wgs), d[2], d[3], d[4], B,
-                                              t.nseg, t.nwg, d[6], t.nbytes, d[5], t.nhuff, coef.data_ptr(), ncoef,
-                                              status.data_ptr(), stream_ptr())
-        assert st == 0
+        image_io._launch_segments(L, t, d[2:], B, coef, ncoef, status)
 
     def reconstruct():
         st = L.yv4_jpeg_reconstruct(table, d[0], B, coef.data_ptr(), ncoef, d[1], work.data_ptr(), work_bytes, out.data_ptr(),
@@ -391,15 +372,9 @@ def sync_phases(kind, src, B, repeats, dev, chunk_bytes, max_rounds):
     t = image_io.ScanTables(bufs)
     ch = image_io.ChunkTables(t, chunk_bytes)
     r['chunks'], r['workgroups'] = ch.nchunk, ch.nwg
-    sections = t.sections() + ch.sections()
-    offs, end = image_io._upload_plan(sections)
-    stage = torch.empty(end, dtype=torch.uint8, pin_memory=True)
-    for (obj, size), off in zip(sections, offs):
-        if obj is not None:
-            C.memmove(stage.data_ptr() + off, obj, size)
-    t.write_bytes(stage.data_ptr() + offs[4])
+    stage, offs = image_io._stage(t.sections() + ch.sections())
     up = stage.to(dev)
-    r['staging_bytes'] = end
+    r['staging_bytes'] = stage.numel()
     coef = torch.empty(t.ncoef, dtype=torch.int16, device=dev)
     flags = torch.empty(2 * B, dtype=torch.int32, device=dev)
     entries = torch.empty(ch.nchunk * C.sizeof(JpegEntry), dtype=torch.uint8, device=dev)

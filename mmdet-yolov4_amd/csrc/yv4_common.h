@@ -182,9 +182,15 @@ __device__ __forceinline__ float mish_f32(float x) {
 
 // Epilogue form: hardware exp2 and reciprocal (v_exp_f32 / v_rcp_f32, 1 ulp each) instead of the
 // libm expf and the IEEE divide: ~10 VALU instructions instead of ~35 per output element, which
-// matters for the K <= 256 layers whose epilogue is as long as their MFMA phase.  Absolute error
-// vs mish_f32 is < 2e-6 over the whole range (tests/test_gpu_parity.py::test_conv_*), far inside
-// the 1e-4 parity budget.
+// matters for the K <= 256 layers whose epilogue is as long as their MFMA phase.  Against the float64
+// x * tanh(softplus(x)), with n = e^x (e^x + 2) and eps = 2^-23:
+//   |error| <= eps * ((2|x| + 3) * 2 / (n + 2) + 3) * |mish(x)| + |x| * 2^-124 + 2^-125
+// (derived in tests/_act_ref.py; the floor terms are the flushed exponential below x = -87.3), which is
+// relative, not absolute: 3 ulp of the result for x >= 9, growing with |x| for negative x, where the
+// rounding of x * log2e is an absolute error of the exponent.  Measured on the MI355X over every conv
+// route and tile id, both forms (tests/test_gpu_act_exact.py): at most 0.38 of that bound (0.53 of its
+// own for the Swish line of apply_act); in ulp of the result 10.4 over x >= -20 and 39.6 over the whole
+// range down to results of 2^-100.
 __device__ __forceinline__ float mish_fast_f32(float x) {
   // no contraction in here: whether  n + 2  became fma(e, e + 2, 2) used to depend on the loop around the call, so two
   // kernels with the same accumulator could round an output differently (the fp32 plans promise the same bits from

@@ -153,7 +153,7 @@ class Launch:
         d.KH, d.KW, d.stride, d.pad = K, K, s, p
         d.x_cstride, d.x_coff, d.y_cstride, d.y_coff = self.x_cs, self.x_co, self.y_cs, self.y_co
         d.r_cstride, d.r_coff = self.r_cs, self.r_co
-        d.act1, d.act2, d.slope1, d.slope2 = ep.act1, ep.act2, ep.slope, ep.slope
+        d.act1, d.act2, d.slope1, d.slope2 = ep.act1, ep.act2, ep.slope, getattr(ep, 'slope2', ep.slope)
         d.tile = tile
         self.d = d
 

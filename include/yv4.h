@@ -1152,6 +1152,42 @@ int yv4_letterbox_u8_flip(const uint8_t* src, int src_h, int src_w, int src_pitc
                           int64_t plane_stride, int new_h, int new_w, const float* mean3, const float* std3,
                           int to_rgb, int pad_val, int pad_before_normalize, int flip, void* stream);
 
+/* ---- a whole test batch in one launch (csrc/preprocess.hip; additive within ABI 8) --------------------------------
+ * One entry per output slot, that is per (augmentation, image) of a MultiScaleFlipAug batch:
+ *   src, src_h, src_w,      the 8-bit HWC source in DEVICE memory and its row pitch in bytes (>= 3 * src_w: a view
+ *   src_pitch               inside a wider canvas is taken where it lies)
+ *   new_h, new_w            the resized extent (Resize(keep_ratio=True))
+ *   pad_h, pad_w            the image's own padded extent (Pad(size_divisor)); new <= pad <= canvas
+ *   H, W                    the slot's canvas: what collate pads every image of its batch to.  Canvases differ between
+ *                           the scales of a pipeline, so one table covers all of them
+ *   flip                    YV4_FLIP_* of the resized region
+ *   dst_off                 where the slot's 3 * H * W floats (planar C, H, W) begin in dst, in floats
+ *   inv_sx, inv_sy          the resize ratios, computed on the host with yv4_letterbox_u8's expression:
+ *                           1.0 / ((double)new_w / (double)src_w) and 1.0 / ((double)new_h / (double)src_h) */
+typedef struct yv4_letterbox_slot {
+  const uint8_t* src;
+  double inv_sx, inv_sy;
+  int64_t dst_off;
+  int32_t src_h, src_w, src_pitch;
+  int32_t new_h, new_w;
+  int32_t pad_h, pad_w;
+  int32_t H, W;
+  int32_t flip;
+} yv4_letterbox_slot;
+
+/* yv4_letterbox_u8_flip for N slots in ONE launch on `stream`, the batch's collate included: every element of every
+ * slot is written -- inside new_h x new_w the interpolated pixel, from there to pad_h x pad_w the pad value (normalised
+ * if pad_before_normalize), from there to H x W 0.0f (collate pads after Normalize) -- so dst needs no zero fill, and
+ * every element is bit-equal to yv4_letterbox_u8_flip into a (pad_h, pad_w) image placed in a zeroed canvas.  table:
+ * the HOST table, validated here (every slot by yv4_letterbox_u8's checks; pad_h <= H, pad_w <= W; the ratios equal
+ * the expression above; dst_off >= 0 and dst_off + 3*H*W <= dst_elems; N <= 65535: YV4_E_INVALID before the launch);
+ * table_dev: the same N entries in DEVICE memory (8-byte aligned), which the kernel trusts.  A slot whose W is a
+ * multiple of 4 and whose first float is 16-byte aligned is written with 16-byte stores, four x a thread; any other
+ * slot one float at a time.  Slots that overlap in dst are the caller's error. */
+int yv4_letterbox_u8_batch(const yv4_letterbox_slot* table, const yv4_letterbox_slot* table_dev, int N, float* dst,
+                           int64_t dst_elems, const float* mean3, const float* std3, int to_rgb, int pad_val,
+                           int pad_before_normalize, void* stream);
+
 /* Slot tables of YOLOV3Head.get_bboxes(with_nms=False) (yolo_head.py:254-311): per image, the levels' boxes in the
  * reference's concatenation order.  A level of n_l = H_l*W_l*A boxes contributes k_l = nms_pre slots when
  * 0 < nms_pre < n_l (conf.topk(nms_pre), sorted: descending objectness, ties to the lower anchor index), else n_l

@@ -33,7 +33,7 @@ from .map_eval import (MapGt, bbox_overlaps, eval_map, evaluate_map, print_map_s
                        tpfp_imagenet)
 from .coco_eval import COCOeval, CocoGt, evaluate_bbox, flatten_results  # noqa: F401
 from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: F401
-from .datasets import (CocoDataset, DistributedGroupSampler, GroupSampler, TrainLoader, build_dataset,  # noqa: F401
-                       build_train_loader)
+from .datasets import (CocoDataset, DistributedGroupSampler, GroupSampler, TestLoader, TrainLoader,  # noqa: F401
+                       build_dataset, build_test_loader, build_train_loader)
 
 __all__ = [n for n in dir() if not n.startswith('_')]

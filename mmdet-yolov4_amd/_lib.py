@@ -139,6 +139,12 @@ class V3AugImage(C.Structure):
                [(n, C.c_int32) for n in ('cx', 'cy', 'cw', 'ch', 'rh', 'rw', 'ph', 'pw', 'flip', 'reserved')]
 
 
+class LetterboxSlot(C.Structure):
+    """``yv4_letterbox_slot``: one (augmentation, image) slot of a ``yv4_letterbox_u8_batch`` call."""
+    _fields_ = [('src', C.c_void_p), ('inv_sx', C.c_double), ('inv_sy', C.c_double), ('dst_off', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('src_h', 'src_w', 'src_pitch', 'new_h', 'new_w', 'pad_h', 'pad_w', 'H', 'W', 'flip')]
+
+
 class PackDesc(C.Structure):
     """yv4_pack_desc (include/yv4.h)."""
     _fields_ = [('w', C.c_void_p), ('s_co', C.c_int64), ('s_ci', C.c_int64), ('s_kh', C.c_int64), ('s_kw', C.c_int64),
@@ -303,6 +309,7 @@ SIGNATURES = {
     'yv4_quantize_f8': (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _vp]),
     'yv4_spp_pool_fwd_f8': (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
     'yv4_letterbox_u8_flip': (C.c_int, [_vp, _i, _i, _i, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'yv4_letterbox_u8_batch': (C.c_int, [C.POINTER(LetterboxSlot), _vp, _i, _vp, _i64, _vp, _vp, _i, _i, _i, _vp]),
     'yv4_topk_slots_work': (_sz, [_i, _vp, _i]),
     'yv4_topk_slots': (C.c_int, [_vp, _i, _i64, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp]),
     'yv4_tta_merge': (C.c_int, [C.POINTER(TtaAug), _i, _i, _i, _f, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
@@ -360,6 +367,8 @@ ABI8_SYMBOLS = frozenset(('yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'))
 FP8_SYMBOLS = frozenset(('yv4_conv_bn_act_fwd_f8', 'yv4_conv_f8_pick_tile', 'yv4_quantize_f8', 'yv4_spp_pool_fwd_f8'))
 #: the YOLOv3 test-time augmentation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_tta()
 TTA_SYMBOLS = frozenset(('yv4_letterbox_u8_flip', 'yv4_topk_slots_work', 'yv4_topk_slots', 'yv4_tta_merge'))
+#: a whole test batch's letterbox in one launch (additive within ABI 8, bound like FP8_SYMBOLS); has_letterbox_batch()
+LETTERBOX_BATCH_SYMBOLS = frozenset(('yv4_letterbox_u8_batch',))
 #: the soft-NMS entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_soft_nms()
 SOFT_NMS_SYMBOLS = frozenset(('yv4_soft_nms_images', 'yv4_soft_nms_split_work', 'yv4_soft_nms_split'))
 #: the YOLOv3 train-side input pipeline (additive within ABI 8, bound like FP8_SYMBOLS); has_v3_augment()
@@ -436,7 +445,7 @@ def lib():
                     or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
                     or name in FLEX_FLAT_SYMBOLS
                     or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS
-                    or name in JPEG_ORIENT_SYMBOLS) \
+                    or name in JPEG_ORIENT_SYMBOLS or name in LETTERBOX_BATCH_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -469,6 +478,12 @@ def has_tta():
     """The loaded library exports the YOLOv3 test-time augmentation entry points."""
     h = lib()
     return all(hasattr(h, n) for n in TTA_SYMBOLS)
+
+
+def has_letterbox_batch():
+    """The loaded library exports ``yv4_letterbox_u8_batch`` (a whole test batch's letterbox in one launch)."""
+    h = lib()
+    return all(hasattr(h, n) for n in LETTERBOX_BATCH_SYMBOLS)
 
 
 def has_soft_nms():

@@ -10,6 +10,9 @@ img_prefix=..., pipeline=train_pipeline)``) goes through ``build_train_loader`` 
 * ``TrainLoader`` takes the sampler's indices, reads the files on a thread pool, decodes the whole batch with ONE
   ``image_io.decode_into`` call and hands the device views to the fused pipeline (``build_train_pipeline``).  No pixel
   crosses back to the host.
+* ``TestLoader`` (``build_test_loader`` over ``cfg.data.val`` / ``cfg.data.test``) is the test side's counterpart: the
+  order of ``DistributedSampler(shuffle=False)``, the same reads and ONE decode per batch, then the test pipeline
+  (``FusedTestPipeline``), in the nested form ``single_gpu_test`` / ``EvalHook`` take.
 
 What is pinned draw for draw against the reference (tests/golden/coco_train_set.npz): ``CocoDataset._rand_another`` /
 ``batch_rand_others`` and both samplers' orders, given the same generator state.  What is this loader's own: the ORDER
@@ -296,7 +299,93 @@ def _read(path):
         return f.read()
 
 
-class TrainLoader:
+class _FileLoader:
+    """What ``TrainLoader`` and ``TestLoader`` share: the files' paths, the reader pool, the host work of one batch
+    (reads, header parses, ``image_io.HostHalf``), the naming of a damaged file, and the ``prefetch`` worker that does the
+    next batch's host work while the caller uses this one.  A subclass gives ``_start(batch)`` -- whatever must happen on
+    the caller's thread before the host work, ending in ``_submit(sources)`` -- and ``_finish(started)``."""
+
+    def __init__(self, dataset, rank, world, device, entropy, prefetch, orientation):
+        if prefetch not in (0, 1):
+            raise ValueError(f'prefetch {prefetch!r} is not 0 or 1')
+        if not 0 <= rank < world:
+            raise ValueError(f'rank {rank} of world {world}')
+        self.dataset = dataset
+        self.rank, self.world = int(rank), int(world)
+        self.device = torch.device(device) if device is not None else None
+        self.entropy = image_io._entropy_mode(entropy)
+        self.prefetch, self.orientation = prefetch, bool(orientation)
+        self._readers = ThreadPoolExecutor(max_workers=MAX_READ_THREADS, thread_name_prefix='yv4-read')
+        self._worker = ThreadPoolExecutor(max_workers=1, thread_name_prefix='yv4-prefetch') if prefetch else None
+
+    def close(self):
+        """Ends the loader's threads (they are idle between batches; an interpreter exit ends them as well)."""
+        self._readers.shutdown(wait=True)
+        if self._worker is not None:
+            self._worker.shutdown(wait=True)
+
+    def _dev(self):
+        return self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+
+    def _path(self, j):
+        name = self.dataset.data_infos[j]['filename']
+        return os.path.join(self.dataset.img_prefix, name) if self.dataset.img_prefix is not None else name
+
+    # ---- host work of one batch: no HIP call, no torch call, no draw (may run on the worker thread) -----------------------
+    def _host(self, sources):
+        """Reads and parses the files of ``sources`` (a flat list of dataset indices) -> ``(bufs, refused, host,
+        (read seconds, parse seconds))``: ``refused`` maps positions to the decoder's refusal; ``host`` is the batch's
+        ``HostHalf`` when none was."""
+        t0 = time.perf_counter()
+        bufs = list(self._readers.map(_read, [self._path(j) for j in sources]))
+        t1 = time.perf_counter()
+        refused = image_io.refusals(bufs)
+        host = None
+        if not refused:
+            host = self._host_half(bufs, sources)
+        t2 = time.perf_counter()
+        return bufs, refused, host, (t1 - t0, t2 - t1)
+
+    def _named(self, e, sources):
+        """The decoder's ``ValueError`` about "image n" of a batch, naming the file."""
+        m = re.search(r'image (\d+)', str(e))
+        where = self._path(sources[int(m.group(1))]) if m else f'batch of {[self._path(j) for j in sources]}'
+        return ValueError(f'{type(self).__name__}: {where}: {e}')
+
+    def _host_half(self, bufs, sources):
+        try:
+            return image_io.HostHalf(bufs, self.entropy, what=type(self).__name__)
+        except ValueError as e:      # a damaged scan found by the host Huffman decode or the segment walk
+            raise self._named(e, sources) from None
+
+    def _submit(self, sources):
+        """The host work of ``sources``: a future with ``prefetch``, else its result."""
+        return self._worker.submit(self._host, list(sources)) if self._worker is not None else self._host(list(sources))
+
+    def _result(self, job):
+        return job.result() if self._worker is not None else job
+
+    def _decode(self, bufs, host, sources):
+        """ONE ``decode_into`` of the batch -> its (h, w, 3) device views."""
+        try:
+            out, table = image_io.decode_into(bufs, 'bgr', self._dev(), orientation=self.orientation, host=host)
+        except ValueError as e:      # a damaged scan found by the device decode's status read-back
+            raise self._named(e, sources) from None
+        return image_io.image_views(out, table)
+
+    def _pipelined(self, batches):
+        """``_finish(_start(batch))`` per batch; with ``prefetch`` the next batch is started before this one is yielded."""
+        started = self._start(batches[0]) if batches else None
+        for k in range(len(batches)):
+            if self.prefetch:
+                data = self._finish(started)
+                started = self._start(batches[k + 1]) if k + 1 < len(batches) else None
+            else:
+                data = self._finish(started if k == 0 else self._start(batches[k]))
+            yield data
+
+
+class TrainLoader(_FileLoader):
     """What ``Runner.data_loader`` and the hooks expect of a loader (``hooks.BatchSource``), fed from image files:
     iterable over ``train_step`` data dicts (``img`` (N, 3, H, W) float32 on the device, ``img_metas``, ``gt_bboxes``,
     ``gt_labels``), with ``__len__`` (batches an epoch), ``.dataset`` and ``.sampler`` (``samples_per_gpu``,
@@ -323,16 +412,10 @@ class TrainLoader:
                  on_unsupported='raise', orientation=True):
         if on_unsupported not in ('raise', 'resample'):
             raise ValueError(f"on_unsupported {on_unsupported!r} is not 'raise' or 'resample'")
-        if prefetch not in (0, 1):
-            raise ValueError(f'prefetch {prefetch!r} is not 0 or 1')
-        if not 0 <= rank < world:
-            raise ValueError(f'rank {rank} of world {world}')
-        self.dataset, self.pipeline = dataset, pipeline
+        super().__init__(dataset, rank, world, device, entropy, prefetch, orientation)
+        self.pipeline = pipeline
         self.mosaic = isinstance(pipeline, FusedTrainPipeline)
-        self.seed, self.rank, self.world = int(seed), int(rank), int(world)
-        self.device = torch.device(device) if device is not None else None
-        self.entropy = image_io._entropy_mode(entropy)
-        self.prefetch, self.on_unsupported, self.orientation = prefetch, on_unsupported, bool(orientation)
+        self.seed, self.on_unsupported = int(seed), on_unsupported
         if world == 1:
             self.sampler = GroupSampler(dataset, samples_per_gpu, seed=self.seed)
         else:
@@ -340,54 +423,16 @@ class TrainLoader:
         self.resampled = 0
         self._logged = set()
         self.draws = None
+        self._rng = None
         #: host seconds of the last epoch by phase (tools/loader_bench.py): index draws, file reads, header parse and
         #: host half, the decode call, the pipeline call
         self.times = dict(draws=0.0, read=0.0, host=0.0, decode=0.0, pipeline=0.0)
-        self._readers = ThreadPoolExecutor(max_workers=MAX_READ_THREADS, thread_name_prefix='yv4-read')
-        self._worker = ThreadPoolExecutor(max_workers=1, thread_name_prefix='yv4-prefetch') if prefetch else None
 
     def __len__(self):
         return len(self.sampler) // self.sampler.samples_per_gpu
 
     def set_epoch(self, epoch):
         self.sampler.set_epoch(epoch)
-
-    def close(self):
-        """Ends the loader's threads (they are idle between batches; an interpreter exit ends them as well)."""
-        self._readers.shutdown(wait=True)
-        if self._worker is not None:
-            self._worker.shutdown(wait=True)
-
-    def _path(self, j):
-        name = self.dataset.data_infos[j]['filename']
-        return os.path.join(self.dataset.img_prefix, name) if self.dataset.img_prefix is not None else name
-
-    # ---- host work of one batch: no HIP call, no torch call, no draw (may run on the worker thread) -----------------------
-    def _host(self, sources):
-        """Reads and parses the files of ``sources`` (a flat list of dataset indices) -> ``(bufs, refused, host,
-        (read seconds, parse seconds))``: ``refused`` maps positions to the decoder's refusal; ``host`` is the batch's
-        ``HostHalf`` when none was."""
-        t0 = time.perf_counter()
-        bufs = list(self._readers.map(_read, [self._path(j) for j in sources]))
-        t1 = time.perf_counter()
-        refused = image_io.refusals(bufs)
-        host = None
-        if not refused:
-            host = self._host_half(bufs, sources)
-        t2 = time.perf_counter()
-        return bufs, refused, host, (t1 - t0, t2 - t1)
-
-    def _named(self, e, sources):
-        """The decoder's ``ValueError`` about "image n" of a batch, naming the file."""
-        m = re.search(r'image (\d+)', str(e))
-        where = self._path(sources[int(m.group(1))]) if m else f'batch of {[self._path(j) for j in sources]}'
-        return ValueError(f'TrainLoader: {where}: {e}')
-
-    def _host_half(self, bufs, sources):
-        try:
-            return image_io.HostHalf(bufs, self.entropy, what='TrainLoader')
-        except ValueError as e:      # a damaged scan found by the host Huffman decode or the segment walk
-            raise self._named(e, sources) from None
 
     def _settle(self, sources, job, rng):
         """The refusals of a batch, on the caller's thread: raise, or draw replacements until every file is accepted."""
@@ -414,29 +459,24 @@ class TrainLoader:
             self.times['host'] += time.perf_counter() - t0
         return bufs, host
 
-    def _start(self, indices, rng):
+    def _start(self, indices):
         """The draws of a batch's sources (caller's thread), then its host work: a future with ``prefetch``."""
         t0 = time.perf_counter()
         if self.mosaic:
             sources = []
             for idx in indices:
-                sources += [idx] + [int(j) for j in self.dataset.batch_rand_others(idx, 3, rng)]
+                sources += [idx] + [int(j) for j in self.dataset.batch_rand_others(idx, 3, self._rng)]
         else:
             sources = list(indices)
         self.times['draws'] += time.perf_counter() - t0
-        job = self._worker.submit(self._host, list(sources)) if self._worker is not None else self._host(list(sources))
-        return indices, sources, job
+        return indices, sources, self._submit(sources)
 
-    def _finish(self, started, rng):
+    def _finish(self, started):
         indices, sources, job = started
-        bufs, host = self._settle(sources, job.result() if self._worker is not None else job, rng)
-        dev = self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
+        rng = self._rng
+        bufs, host = self._settle(sources, self._result(job), rng)
         t0 = time.perf_counter()
-        try:
-            out, table = image_io.decode_into(bufs, 'bgr', dev, orientation=self.orientation, host=host)
-        except ValueError as e:      # a damaged scan found by the device decode's status read-back
-            raise self._named(e, sources) from None
-        imgs = image_io.image_views(out, table)
+        imgs = self._decode(bufs, host, sources)
         t1 = time.perf_counter()
         anns = [self.dataset.get_ann_info(j) for j in sources]
         triples = [(im, a['bboxes'], a['labels']) for im, a in zip(imgs, anns)]
@@ -462,21 +502,105 @@ class TrainLoader:
 
     def __iter__(self):
         epoch = self.sampler.epoch
-        rng = np.random.RandomState([self.seed, int(epoch), self.rank, 1])
+        self._rng = np.random.RandomState([self.seed, int(epoch), self.rank, 1])
         for k in self.times:
             self.times[k] = 0.0
         order = list(iter(self.sampler))
         n = self.sampler.samples_per_gpu
-        batches = [order[i:i + n] for i in range(0, len(order), n)]
-        started = self._start(batches[0], rng) if batches else None
-        for k in range(len(batches)):
-            if self.prefetch:
-                data = self._finish(started, rng)
-                started = self._start(batches[k + 1], rng) if k + 1 < len(batches) else None
-            else:
-                data = self._finish(started if k == 0 else self._start(batches[k], rng), rng)
-            yield data
+        yield from self._pipelined([order[i:i + n] for i in range(0, len(order), n)])
         self.sampler.set_epoch(epoch + 1)
+
+
+#: ``build_test_loader``'s pipeline form: the one-launch batched letterbox (``FusedTestPipeline(batched=True)``), which
+#: DESIGN 22 measured as not slower than the per-image path at batch 32
+TEST_LOADER_BATCHED = True
+
+
+class TestLoader(_FileLoader):
+    """The test side's loader, what ``single_gpu_test`` / ``multi_gpu_test`` / ``EvalHook`` / ``DistEvalHook`` take, fed
+    from image files: iterable over ``dict(img=[batch per augmentation], img_metas=[[meta per image] per augmentation])``
+    (the nested form of the reference's test collate), with ``__len__`` (batches) and ``.dataset`` (a ``CocoDataset`` in
+    test mode, which ``accepts_flat``).
+
+    Order: ``dist.sampler_indices(len(dataset), rank, world)`` -- ``DistributedSampler(shuffle=False)``, for one rank
+    ``range(len(dataset))`` -- in consecutive batches of ``samples_per_gpu``, the last one ragged.  Per batch: the files
+    read on at most ``MAX_READ_THREADS`` threads, every header parsed, ONE ``image_io.decode_into`` in the ``entropy`` mode
+    asked for, the device views into ``pipeline`` (a ``FusedTestPipeline``; with ``batched=True`` ONE launch).  Each meta
+    gains ``filename`` and ``ori_filename``.  ``prefetch=1`` as in ``TrainLoader``: the next batch's reads and host half on a
+    worker thread, every HIP and torch call on the caller's.
+
+    A file the decoder refuses (progressive, CMYK, another format ...) cannot be replaced by another in a test run: it
+    raises ``NotImplementedError`` naming the file, unless ``fallback`` is given -- a callable ``path -> (h, w, 3) uint8
+    BGR array`` (``cv2.imread``, say), whose array is uploaded by the pipeline and joins the batch's launch.  A damaged
+    scan is a ``ValueError`` naming the file."""
+
+    __test__ = False      # (not a test class, whatever its name says to a collector)
+
+    def __init__(self, dataset, pipeline, samples_per_gpu=1, rank=0, world=1, device=None, entropy=None, prefetch=0,
+                 fallback=None, orientation=True):
+        if int(samples_per_gpu) < 1:
+            raise ValueError(f'samples_per_gpu {samples_per_gpu!r} is not positive')
+        if fallback is not None and not callable(fallback):
+            raise ValueError('fallback is not callable')
+        super().__init__(dataset, rank, world, device, entropy, prefetch, orientation)
+        from .dist import sampler_indices
+        self.pipeline, self.samples_per_gpu, self.fallback = pipeline, int(samples_per_gpu), fallback
+        self.indices = sampler_indices(len(dataset), self.rank, self.world)
+        n = self.samples_per_gpu
+        self.batches = [self.indices[i:i + n] for i in range(0, len(self.indices), n)]
+        #: host seconds of the last pass by phase (tools/test_loader_bench.py): file reads, header parse and host half,
+        #: the decode call, the pipeline call
+        self.times = dict(read=0.0, host=0.0, decode=0.0, pipeline=0.0)
+
+    def __len__(self):
+        return len(self.batches)
+
+    def _start(self, indices):
+        return list(indices), self._submit(indices)
+
+    def _finish(self, started):
+        sources, job = started
+        bufs, refused, host, (t_read, t_host) = self._result(job)
+        self.times['read'] += t_read
+        self.times['host'] += t_host
+        images = [None] * len(sources)
+        if refused:
+            t0 = time.perf_counter()
+            for k in sorted(refused):
+                path = self._path(sources[k])
+                if self.fallback is None:
+                    raise NotImplementedError(f'TestLoader: {path}: {refused[k]}')
+                arr = self.fallback(path)
+                if not isinstance(arr, np.ndarray) or arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] != 3:
+                    raise ValueError(f'TestLoader: {path}: fallback must return an (h, w, 3) uint8 array')
+                images[k] = arr
+            keep = [k for k in range(len(sources)) if k not in refused]
+            bufs, sources_dec = [bufs[k] for k in keep], [sources[k] for k in keep]
+            host = self._host_half(bufs, sources_dec) if keep else None
+            self.times['host'] += time.perf_counter() - t0
+        else:
+            keep, sources_dec = list(range(len(sources))), sources
+        t0 = time.perf_counter()
+        if keep:
+            for k, im in zip(keep, self._decode(bufs, host, sources_dec)):
+                images[k] = im
+        t1 = time.perf_counter()
+        batch, metas = self.pipeline(images)
+        if not isinstance(batch, list):
+            batch, metas = [batch], [metas]
+        t2 = time.perf_counter()
+        self.times['decode'] += t1 - t0
+        self.times['pipeline'] += t2 - t1
+        for per_aug in metas:
+            for m, j in zip(per_aug, sources):
+                m['ori_filename'] = self.dataset.data_infos[j]['filename']
+                m['filename'] = self._path(j)
+        return dict(img=list(batch), img_metas=[list(m) for m in metas])
+
+    def __iter__(self):
+        for k in self.times:
+            self.times[k] = 0.0
+        yield from self._pipelined(self.batches)
 
 
 def build_dataset(cfg, default_args=None):
@@ -488,6 +612,22 @@ def build_dataset(cfg, default_args=None):
     return build_from_cfg(cfg, DATASETS, default_args)
 
 
+def _reads_oriented(pipeline):
+    """Whether the block's ``LoadImageFromFile`` applies the EXIF orientation, with the reference's meaning:
+    ``color_type='color'`` (the default) does, ``'color_ignore_orientation'`` does not; nothing else is built."""
+    color_type = 'color'
+    stack = list(pipeline)
+    while stack:
+        t = stack.pop()
+        if t['type'] == 'LoadImageFromFile':
+            color_type = t.get('color_type', 'color')
+        stack += list(t.get('individual_pipeline', ()))
+    if color_type not in ('color', 'color_ignore_orientation'):
+        raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' and "
+                                  "'color_ignore_orientation' only)")
+    return color_type == 'color'
+
+
 def build_train_loader(cfg, samples_per_gpu, seed=0, rank=0, world=1, device=None, entropy=None, prefetch=0,
                        on_unsupported='raise'):
     """``cfg``: ``cfg.data.train`` of a reference config, a dataset block with its ``pipeline`` -> ``TrainLoader``.  The
@@ -497,17 +637,32 @@ def build_train_loader(cfg, samples_per_gpu, seed=0, rank=0, world=1, device=Non
     dataset = build_dataset(cfg)
     if dataset.pipeline is None:
         raise ValueError('build_train_loader: the dataset block has no pipeline')
-    color_type = 'color'
-    stack = list(dataset.pipeline)
-    while stack:
-        t = stack.pop()
-        if t['type'] == 'LoadImageFromFile':
-            color_type = t.get('color_type', 'color')
-        stack += list(t.get('individual_pipeline', ()))
-    if color_type not in ('color', 'color_ignore_orientation'):
-        raise NotImplementedError(f"LoadImageFromFile(color_type={color_type!r}) is not built ('color' and "
-                                  "'color_ignore_orientation' only)")
+    orientation = _reads_oriented(dataset.pipeline)
     pipeline = build_train_pipeline(dataset.pipeline, device=device)
     return TrainLoader(dataset, pipeline, samples_per_gpu, seed=seed, rank=rank, world=world, device=device,
                        entropy=entropy, prefetch=prefetch, on_unsupported=on_unsupported,
-                       orientation=color_type == 'color')
+                       orientation=orientation)
+
+
+def build_test_loader(cfg, samples_per_gpu=None, rank=0, world=1, device=None, entropy=None, prefetch=0, fallback=None,
+                      batched=None):
+    """``cfg``: ``cfg.data.val`` or ``cfg.data.test`` of a reference config, a dataset block with its test ``pipeline``
+    -> ``TestLoader``.  The dataset is built with ``test_mode=True`` whatever the block says (``apis/train.py:140``), so no
+    image is filtered.  ``samples_per_gpu``: ``None`` takes the block's own key (the YOLOv4 configs put
+    ``samples_per_gpu=8`` into ``val``), else 1; the key never reaches the dataset.  The pipeline block goes through
+    ``FusedTestPipeline.from_config`` (a transform it does not build is refused by name), its ``LoadImageFromFile`` decides
+    the orientation as in ``build_train_loader``.  ``batched``: the pipeline's form, ``None`` for ``TEST_LOADER_BATCHED``."""
+    from .preprocess import FusedTestPipeline
+    cfg = dict(cfg)
+    own = cfg.pop('samples_per_gpu', None)
+    if samples_per_gpu is None:
+        samples_per_gpu = 1 if own is None else own
+    cfg['test_mode'] = True
+    dataset = build_dataset(cfg)
+    if dataset.pipeline is None:
+        raise ValueError('build_test_loader: the dataset block has no pipeline')
+    orientation = _reads_oriented(dataset.pipeline)
+    pipeline = FusedTestPipeline.from_config(dataset.pipeline, device=device,
+                                             batched=TEST_LOADER_BATCHED if batched is None else batched)
+    return TestLoader(dataset, pipeline, samples_per_gpu, rank=rank, world=world, device=device, entropy=entropy,
+                      prefetch=prefetch, fallback=fallback, orientation=orientation)

@@ -1560,6 +1560,136 @@ int yv4_jpeg_entropy_decode_device_sync(const yv4_jpeg_scan* scans, const yv4_jp
                                         int16_t* coef, int64_t coef_elems, int32_t* status, int32_t* undecided,
                                         void* stream);
 
+/* ---- baseline JPEG encoding (csrc/jpeg_enc_core.h, csrc/jpeg_enc_host.cpp, csrc/jpeg_enc.hip; additive within ABI 8) --
+ * libjpeg's default encoder, restated: jccolor.c's 16-bit fixed-point YCbCr, jcsample.c's h2v1 / h2v2 box filters,
+ * jccoefct.c's edge rules (replicated last column and row, dummy blocks that repeat the previous block's quantised DC),
+ * jfdctint.c's islow forward DCT, jcdctmgr.c's rounding division by 8 q, jpeg_set_quality(force_baseline)'s scaling of
+ * the Annex K tables, the four Annex K Huffman tables, one interleaved scan without restart markers.  It is integer
+ * arithmetic from the first pixel to the last stuffed byte, so the file equals what libjpeg-turbo writes (through
+ * Pillow, turbojpeg or cv2.imwrite) for the same pixels, quality and sampling, byte for byte; tests/_jpeg_enc_ref.py is
+ * the definition.  A batch of images of mixed sizes, samplings and qualities goes through in one call per stage.
+ *
+ * Two seams.  Pixels -> quantised coefficients (yv4_jpeg_encode_coefficients): int16 in the DECODER's coefficient layout
+ * (natural order, one plane per component over the MCU-padded grid, component 0 first), dummy blocks filled, so that
+ * yv4_jpeg_entropy_decode of libjpeg's file is the expected buffer element for element.  Coefficients -> the stuffed
+ * scan bytes and their count (yv4_jpeg_encode_scan).  The host writes SOI .. SOS in front (yv4_jpeg_encode_header) and
+ * FF D9 behind.  yv4_jpeg_encode_host is both stages on the CPU, compiled from the core the kernels run.
+ *
+ * yv4_jpeg_enc_image, one per image.  The caller fills width, height (1 .. 65535), channels (3: interleaved pixels,
+ * B G R or R G B; 1: a gray plane, one component taken as is), hs x vs (the luma sampling: 1x1, 2x1 or 2x2 for three
+ * channels -- 4:4:4, 4:2:2, 4:2:0 -- and 1x1 for one) and quality (1 .. 100); yv4_jpeg_encode_layout fills the rest
+ * and places the batch densely.  The caller may then move an image's regions (src_off / src_pitch, coef_off, work_off,
+ * out_off / out_cap); every entry point validates the table against the buffers' sizes before it runs anything.
+ *   src_off, src_pitch      byte offset of the first pixel in the pixel buffer, and the row pitch (>= channels * width)
+ *   coef_off                first coefficient in the coefficient buffer (int16 elements, % 64 == 0)
+ *   work_off                byte offset of the image's work region (% 8 == 0): bit counts, running sums, the packed
+ *                           stream before stuffing
+ *   out_off, out_cap        where the scan bytes go and the room there.  The room is a derived bound, never read back
+ *                           from the device: a block codes to at most YV4_JPEG_ENC_BLOCK_BITS bits -- a DC code of up to 11
+ *                           bits (the chrominance table's category 11) with 11 value bits, 63 AC codes of up to 16 bits
+ *                           with 10 value bits each -- and stuffing at most doubles the bytes:
+ *                           out_cap >= 2 * ceil(nblocks * YV4_JPEG_ENC_BLOCK_BITS / 8)
+ *   wg_base, swg_base       workgroups of the images before this one in the block grid (YV4_JPEG_ENC_WG_BLOCKS blocks
+ *                           each) and in the stuffing grid (as many 32-bit words of the bound each): dense
+ *                           (a call takes fewer than 2^24 workgroups a grid: YV4_E_INVALID past that)
+ *   nblocks .. quant        blocks of the image; MCU grid; blocks per component on the MCU-padded grid and on the real
+ *                           grid (ceil(ceil(width * h_c / hs) / 8), rows likewise); the luminance and chrominance
+ *                           quantisation tables in natural order */
+#define YV4_JPEG_ENC_WG_BLOCKS 256     /* blocks one workgroup of the bit-offset scan covers */
+#define YV4_JPEG_ENC_BLOCK_BITS 1660   /* (11 + 11) + 63 * (16 + 10) */
+#define YV4_JPEG_ENC_HEADER_MAX 640    /* room yv4_jpeg_encode_header asks for (it writes 623 bytes for three components) */
+
+typedef struct yv4_jpeg_enc_image {
+  int64_t src_off, coef_off, work_off, out_off, out_cap;
+  int64_t wg_base, swg_base;
+  int64_t nblocks;
+  int32_t src_pitch, width, height, channels, ncomp, hs, vs, quality;
+  int32_t mcus_x, mcus_y;
+  int32_t blocks_w[3], blocks_h[3], real_w[3], real_h[3];
+  uint16_t quant[2][64];
+} yv4_jpeg_enc_image;
+
+/* Host only, no HIP call: checks what the caller filled in (YV4_E_INVALID naming the image: an empty image, a side
+ * above 65535, a quality outside 1 .. 100, another sampling), fills the rest and places the batch: pixels at pitch
+ * channels * width and work / output regions at 256-byte aligned offsets, coefficients back to back.  totals[0 .. 5]:
+ * pixel bytes, coefficient elements, workspace bytes, output bytes, block workgroups, stuffing workgroups. */
+int yv4_jpeg_encode_layout(yv4_jpeg_enc_image* table, int N, int64_t* totals);
+
+/* Host only: the check every entry point below makes before it runs anything -- each entry is what its size, sampling
+ * and quality give, the workgroup bases are dense, and every region lies inside its buffer (pitch >= the row, out_cap >=
+ * the bound).  YV4_OK or YV4_E_INVALID. */
+int yv4_jpeg_encode_validate(const yv4_jpeg_enc_image* table, int N, int64_t pixel_bytes, int64_t coef_elems,
+                             int64_t work_bytes, int64_t out_bytes);
+
+/* Host only: SOI, APP0 (JFIF 1.01, density 1:1), one DQT per table, SOF0, the DHT segments (DC0, AC0, DC1, AC1; a gray
+ * image DC0 and AC0) and SOS of one image, as libjpeg writes them -> out (capacity >= YV4_JPEG_ENC_HEADER_MAX, else
+ * YV4_E_CAPACITY), *length bytes.  The file is this, the scan bytes, FF D9. */
+int yv4_jpeg_encode_header(const yv4_jpeg_enc_image* im, uint8_t* out, int64_t capacity, int64_t* length);
+
+/* Host only, all pointers HOST memory: the method on the CPU over the same table and the same work regions.  stage 1:
+ * pixels -> coef; stage 2: coef -> out and sizes (N int64: the scan bytes of each image); stage 3: both.  Buffers a stage
+ * does not use may be NULL.  rgb != 0: the pixels are R, G, B.  coef 2-byte, work 8-byte aligned. */
+int yv4_jpeg_encode_host(const yv4_jpeg_enc_image* table, int N, int stage, const uint8_t* pixels, int64_t pixel_bytes,
+                         int rgb, int16_t* coef, int64_t coef_elems, uint8_t* work, int64_t work_bytes, uint8_t* out,
+                         int64_t out_bytes, int64_t* sizes);
+
+/* Stage 1 on `stream`, one launch: one lane per 8x8 block.  table: HOST, validated here; table_dev: the same N entries in
+ * DEVICE memory (8-byte aligned), trusted.  pixels and coef are DEVICE memory, coef 16-byte aligned.  Elements of coef
+ * outside the images' regions are not touched. */
+int yv4_jpeg_encode_coefficients(const yv4_jpeg_enc_image* table, const yv4_jpeg_enc_image* table_dev, int N,
+                                 const uint8_t* pixels, int64_t pixel_bytes, int rgb, int16_t* coef, int64_t coef_elems,
+                                 void* stream);
+
+/* Stage 2 on `stream`, seven launches: bits per block; their running sum across workgroups; the zero-fill of the words
+ * the stream will touch; the pack (atomic OR); 0xFF bytes per word; their running sum; the stuffed write.  No workgroup
+ * waits on another inside a launch and no result depends on arrival order.  coef, work (8-byte aligned), out and sizes
+ * (N int64, 8-byte aligned) are DEVICE memory; bytes outside the images' regions are not touched. */
+int yv4_jpeg_encode_scan(const yv4_jpeg_enc_image* table, const yv4_jpeg_enc_image* table_dev, int N, const int16_t* coef,
+                         int64_t coef_elems, uint8_t* work, int64_t work_bytes, uint8_t* out, int64_t out_bytes,
+                         int64_t* sizes, void* stream);
+
+/* ---- drawing detections (csrc/draw.hip; additive within ABI 8) -------------------------------------------------------
+ * Boxes and their labels onto interleaved 8-bit images in place: one launch per batch, one lane per pixel.  The rule is
+ * the package's own (tests/_draw_ref.py restates it; the reference's matplotlib rendering is not reproduced).  A pixel
+ * takes the LAST box of its image, in input order, whose label or frame covers it, the label over the frame; boxes whose
+ * score is not above score_thr are skipped.  Corners are truncated to int32.  The frame is `thickness` pixels inward
+ * from the rectangle [x1, x2] x [y1, y2], clipped to the image, in bbox_color.  The label's top-left is at (x1, y1): the
+ * class name, '|' and the score as d.dd with floor(score * 100 + 0.5) in float32, in a 5x7 glyph table scaled by
+ * max(1, font_size / 7), one scaled pixel of padding at the left and top and of spacing behind each glyph, nine scaled
+ * rows high; glyph pixels take text_color, the rest of the label the pixel's own value / 5.
+ *
+ * yv4_draw_image: pix_off / pitch / width / height place the image in the pixel buffer; box_base / nbox name its rows of
+ * dets ((nbox_total, 5) float32: x1, y1, x2, y2, score) and labels (int32); wg_base: workgroups (256 pixels each) of the
+ * images before it, filled by yv4_draw_layout.  names: (num_classes + 1) rows of YV4_DRAW_NAME_BYTES bytes, a row's
+ * first byte its length and the characters (0x20 .. 0x7E) behind it; the last row is the name of a label outside
+ * 0 .. num_classes - 1.  Colours are B, G, R in 0 .. 255 (the channel order of the pixels is the caller's business). */
+#define YV4_DRAW_NAME_BYTES 32
+
+typedef struct yv4_draw_image {
+  int64_t pix_off, box_base, wg_base;
+  int32_t pitch, width, height, nbox;
+} yv4_draw_image;
+
+typedef struct yv4_draw_style {
+  int32_t bbox_color[3], text_color[3];
+  int32_t thickness, font_size, num_classes;
+  float score_thr;
+} yv4_draw_style;
+
+/* Host only: fills wg_base of every entry; *workgroups: their total. */
+int yv4_draw_layout(yv4_draw_image* table, int N, int64_t* workgroups);
+
+/* One launch on `stream`.  table: HOST, validated against pixel_bytes and nbox_total before the launch (YV4_E_INVALID);
+ * table_dev, pixels, dets, labels and names are DEVICE memory.  Bytes that are no pixel of a frame or label keep their
+ * value. */
+int yv4_draw_boxes(const yv4_draw_image* table, const yv4_draw_image* table_dev, int N, uint8_t* pixels, int64_t pixel_bytes,
+                   const float* dets, const int32_t* labels, int64_t nbox_total, const uint8_t* names,
+                   const yv4_draw_style* style, void* stream);
+
+/* The same per-pixel function on the CPU, all pointers HOST memory. */
+int yv4_draw_boxes_host(const yv4_draw_image* table, int N, uint8_t* pixels, int64_t pixel_bytes, const float* dets,
+                        const int32_t* labels, int64_t nbox_total, const uint8_t* names, const yv4_draw_style* style);
+
 #ifdef __cplusplus
 }
 #endif

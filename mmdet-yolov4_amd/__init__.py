@@ -22,11 +22,12 @@ from .single_stage import SingleStageDetector, bbox2result
 from .yolov3 import Darknet, DetectionBlock, ResBlock, YOLOBBoxCoder, YOLOV3, YOLOV3Head, YOLOV3Neck
 from .plan import Plan
 from .preprocess import FusedTestPipeline
-from .image_io import LoadImageFromFile, imdecode, imread, set_default_entropy
+from .image_io import LoadImageFromFile, encode_into, imdecode, imencode, imread, imwrite, set_default_entropy
 from .augment import FusedTrainPipeline
 from .augment_v3 import FusedV3TrainPipeline, build_train_pipeline
 from . import tta  # noqa: F401  (YOLOv3 test-time augmentation)
 from .apis import inference_detector, single_gpu_test, multi_gpu_test
+from .draw import color_val, draw_boxes, draw_boxes_into
 from .eval_utils import (coco_test_annotation, evaluate_fast_bbox, FlexGt, EVAL_BREAKDOWN, EVAL_IOU_CALCULATOR, EVAL_MATCHER, FlexibleStatisticsEval, IOU2DCoCo,
                          MatcherCoCo, ScaleBreakdown, average_precision, eval_map_flexible, iou_coco, match_coco)
 from .map_eval import (MapGt, bbox_overlaps, eval_map, evaluate_map, print_map_summary, tpfp_default,  # noqa: F401

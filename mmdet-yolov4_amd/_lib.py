@@ -207,6 +207,34 @@ class JpegEntry(C.Structure):
 #: ``YV4_JPEG_MAX_HUFF`` / ``YV4_JPEG_WG_SEGMENTS`` (include/yv4.h)
 JPEG_MAX_HUFF, JPEG_WG_SEGMENTS = 6, 64
 
+
+class JpegEncImage(C.Structure):
+    """``yv4_jpeg_enc_image``: one image of a JPEG encode call."""
+    _fields_ = [(n, C.c_int64) for n in ('src_off', 'coef_off', 'work_off', 'out_off', 'out_cap', 'wg_base', 'swg_base',
+                                         'nblocks')] + \
+               [(n, C.c_int32) for n in ('src_pitch', 'width', 'height', 'channels', 'ncomp', 'hs', 'vs', 'quality',
+                                         'mcus_x', 'mcus_y')] + \
+               [(n, C.c_int32 * 3) for n in ('blocks_w', 'blocks_h', 'real_w', 'real_h')] + [('quant', (C.c_uint16 * 64) * 2)]
+
+
+class DrawImage(C.Structure):
+    """``yv4_draw_image``: one image of a ``yv4_draw_boxes`` call."""
+    _fields_ = [(n, C.c_int64) for n in ('pix_off', 'box_base', 'wg_base')] + \
+               [(n, C.c_int32) for n in ('pitch', 'width', 'height', 'nbox')]
+
+
+class DrawStyle(C.Structure):
+    """``yv4_draw_style``."""
+    _fields_ = [('bbox_color', C.c_int32 * 3), ('text_color', C.c_int32 * 3), ('thickness', C.c_int32),
+                ('font_size', C.c_int32), ('num_classes', C.c_int32), ('score_thr', C.c_float)]
+
+
+#: ``YV4_DRAW_NAME_BYTES`` (include/yv4.h): a row of the class-name table, its first byte the length
+DRAW_NAME_BYTES = 32
+#: ``YV4_JPEG_ENC_WG_BLOCKS`` / ``YV4_JPEG_ENC_BLOCK_BITS`` / ``YV4_JPEG_ENC_HEADER_MAX`` (include/yv4.h): the blocks one
+#: workgroup of the encoder's bit-offset scan covers, the bound on a block's bits, the room the header writer asks for
+JPEG_ENC_WG_BLOCKS, JPEG_ENC_BLOCK_BITS, JPEG_ENC_HEADER_MAX = 256, 1660, 640
+
 _vp, _i, _i64, _f, _sz, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 
 #: every exported symbol: name -> (restype, argtypes).  tests/test_abi.py checks
@@ -357,6 +385,15 @@ SIGNATURES = {
     'yv4_jpeg_entropy_decode_device_sync': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i64,
                                                       _vp, _i64, _vp, _i64, C.c_int32, C.c_int32, _vp, _vp, _i64, _vp, _vp,
                                                       _vp]),
+    'yv4_jpeg_encode_layout': (C.c_int, [C.POINTER(JpegEncImage), _i, C.POINTER(C.c_int64)]),
+    'yv4_jpeg_encode_validate': (C.c_int, [C.POINTER(JpegEncImage), _i, _i64, _i64, _i64, _i64]),
+    'yv4_jpeg_encode_header': (C.c_int, [C.POINTER(JpegEncImage), _vp, _i64, C.POINTER(C.c_int64)]),
+    'yv4_jpeg_encode_host': (C.c_int, [C.POINTER(JpegEncImage), _i, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    'yv4_jpeg_encode_coefficients': (C.c_int, [C.POINTER(JpegEncImage), _vp, _i, _vp, _i64, _i, _vp, _i64, _vp]),
+    'yv4_jpeg_encode_scan': (C.c_int, [C.POINTER(JpegEncImage), _vp, _i, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    'yv4_draw_layout': (C.c_int, [C.POINTER(DrawImage), _i, C.POINTER(C.c_int64)]),
+    'yv4_draw_boxes': (C.c_int, [C.POINTER(DrawImage), _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(DrawStyle), _vp]),
+    'yv4_draw_boxes_host': (C.c_int, [C.POINTER(DrawImage), _i, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(DrawStyle)]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -397,6 +434,11 @@ JPEG_ENTROPY_SYMBOLS = frozenset(('yv4_jpeg_scan_prepare', 'yv4_jpeg_entropy_wor
 #: the self-synchronising chunk decode of the Huffman scan (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_sync()
 JPEG_SYNC_SYMBOLS = frozenset(('yv4_jpeg_chunks_build', 'yv4_jpeg_entropy_decode_sync',
                                'yv4_jpeg_entropy_decode_device_sync'))
+#: the baseline JPEG encoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_encode()
+JPEG_ENCODE_SYMBOLS = frozenset(('yv4_jpeg_encode_layout', 'yv4_jpeg_encode_validate', 'yv4_jpeg_encode_header',
+                                 'yv4_jpeg_encode_host', 'yv4_jpeg_encode_coefficients', 'yv4_jpeg_encode_scan'))
+#: drawing detections onto images (additive within ABI 8, bound like FP8_SYMBOLS); has_draw()
+DRAW_SYMBOLS = frozenset(('yv4_draw_layout', 'yv4_draw_boxes', 'yv4_draw_boxes_host'))
 #: ``YV4_JPEG_MIN_CHUNK_BYTES`` / ``YV4_JPEG_MAX_CHUNK_BYTES`` / ``YV4_JPEG_MAX_ROUNDS`` (include/yv4.h)
 JPEG_MIN_CHUNK_BYTES, JPEG_MAX_CHUNK_BYTES, JPEG_MAX_ROUNDS = 4, 1 << 20, 4096
 #: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
@@ -445,7 +487,8 @@ def lib():
                     or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
                     or name in FLEX_FLAT_SYMBOLS
                     or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS
-                    or name in JPEG_ORIENT_SYMBOLS or name in LETTERBOX_BATCH_SYMBOLS) \
+                    or name in JPEG_ORIENT_SYMBOLS or name in LETTERBOX_BATCH_SYMBOLS or name in JPEG_ENCODE_SYMBOLS
+                    or name in DRAW_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -559,6 +602,18 @@ def has_jpeg_sync():
     ``yv4_jpeg_entropy_decode_device_sync``)."""
     h = lib()
     return has_jpeg_entropy() and all(hasattr(h, n) for n in JPEG_SYNC_SYMBOLS)
+
+
+def has_jpeg_encode():
+    """The loaded library exports the baseline JPEG encoder (``yv4_jpeg_encode_layout`` .. ``yv4_jpeg_encode_scan``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in JPEG_ENCODE_SYMBOLS)
+
+
+def has_draw():
+    """The loaded library exports the drawing entry points (``yv4_draw_layout`` / ``yv4_draw_boxes``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in DRAW_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

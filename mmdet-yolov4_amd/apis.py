@@ -89,14 +89,42 @@ def _flat_loop(model, data_loader, position):
     return table.tensors()
 
 
-def single_gpu_test(model, data_loader, flat=False):
+def _show_metas(metas):
+    """The per-image metas of a batch: a test-time-augmentation batch nests them per augmentation."""
+    return metas[0] if metas and isinstance(metas[0], (list, tuple)) else metas
+
+
+def _show_batch(model, metas, batch_results, out_dir, score_thr):
+    """The visualisation branch of the reference's loop (``mmdet/apis/test.py:30-57``) for one batch: the ORIGINAL files
+    (``img_meta['filename']``) are decoded, drawn on and written to ``out_dir / ori_filename`` in one ``show_results``
+    call.  The reference draws on the de-normalised network input resized back to the original size; the boxes are in
+    original coordinates either way."""
+    metas = _show_metas(metas)
+    for m in metas:
+        for key in ('filename', 'ori_filename'):
+            if not m.get(key):
+                raise ValueError(f"single_gpu_test(out_dir=...) reads the picture from img_meta[{key!r}], which this "
+                                 'batch does not carry')
+    model.show_results([m['filename'] for m in metas], batch_results,
+                       [os.path.join(out_dir, m['ori_filename']) for m in metas], score_thr=score_thr)
+
+
+def single_gpu_test(model, data_loader, flat=False, show=False, out_dir=None, show_score_thr=0.3):
     """Run the detector over ``data_loader`` and return the list of per-image results
-    (``mmdet/apis/test.py:16-68`` without the visualisation branch).  Each item is ``dict(img=..., img_metas=...)``
+    (``mmdet/apis/test.py:16-68``).  Each item is ``dict(img=..., img_metas=...)``
     as the test pipeline's collate produces; ``rescale=True`` like the reference's test loop.
+
+    ``out_dir``: every image is drawn with its detections above ``show_score_thr`` and written to ``out_dir /
+    img_meta['ori_filename']`` (a JPEG), one decode, draw and encode call per batch (``show_results``); the picture
+    drawn on is the original file, not the de-normalised network input.  ``show=True`` raises: there is no display.
 
     ``flat=True`` returns the flat form instead -- ``(dets (D, 5) float32, labels (D,) int64, img_index (D,) int64)`` as
     GPU tensors, ``img_index`` the running image number -- equal to ``coco_eval.flatten_results`` of the list bit for
     bit, without the detections leaving the device."""
+    if show:
+        raise NotImplementedError('single_gpu_test(show=True): there is no display window; pass out_dir=')
+    if flat and out_dir is not None:
+        raise ValueError('single_gpu_test(flat=True, out_dir=...): drawing from the flat result table is not built')
     if flat:
         return _flat_loop(model, data_loader, lambda j: j)
     model.eval()
@@ -109,9 +137,11 @@ def single_gpu_test(model, data_loader, flat=False):
                 # test-time augmentation: BaseDetector.forward_test -> aug_test (detectors/base.py:147-153)
                 results.extend(model.forward_test([t.to(device, non_blocking=True) for t in img], list(metas),
                                                   rescale=True))
-                continue
-            img, metas = _unwrap(img), _unwrap(metas)
-            results.extend(model.simple_test(img.to(device, non_blocking=True), metas, rescale=True))
+            else:
+                img, metas = _unwrap(img), _unwrap(metas)
+                results.extend(model.simple_test(img.to(device, non_blocking=True), metas, rescale=True))
+            if out_dir is not None:
+                _show_batch(model, list(metas), results[len(results) - len(_show_metas(metas)):], out_dir, show_score_thr)
     return results
 
 

@@ -20,6 +20,12 @@ loader (``datasets.TrainLoader``) turns it on for ``color_type='color'``, as the
 
 Accepted: 8-bit baseline (SOF0 / SOF1 Huffman) files, grayscale or YCbCr in 4:4:4, 4:2:2 or 4:2:0.  Progressive,
 arithmetic-coded, 12-bit, lossless, CMYK and multi-scan files and every other format raise ``NotImplementedError``.
+
+The other direction is at the end of the module: ``imencode`` / ``imwrite`` / ``encode_into`` write baseline JPEG on the
+device (``include/yv4.h``, "baseline JPEG encoding"): libjpeg's default encoder restated in integer arithmetic, so the
+file equals what libjpeg-turbo -- ``cv2.imwrite``, and so ``mmcv.imwrite`` -- writes for the same pixels, quality and
+sampling, byte for byte.  The scan bytes are compacted on the device before the read-back, so what crosses to the host
+is the size of the files.
 """
 import ctypes as C
 import os
@@ -633,3 +639,238 @@ class LoadImageFromFile:
     def __repr__(self):
         return (f'{self.__class__.__name__}(to_float32={self.to_float32}, color_type={self.color_type!r}, '
                 f'file_client_args={self.file_client_args})')
+
+
+# ---- the other direction: pixels -> baseline JPEG files (include/yv4.h, "baseline JPEG encoding") ---------------------
+#: ``subsampling=`` -> the luma sampling factors (chroma is 1x1); ``'gray'``: one component, for a (h, w) image
+ENCODE_SAMPLINGS = {'444': (1, 1), '422': (2, 1), '420': (2, 2), 'gray': (1, 1)}
+
+
+class EncodeTable:
+    """The host table of a JPEG encode (``yv4_jpeg_encode_layout``) for images of the given ``shapes`` -- ``(h, w, 3)``
+    or ``(h, w)`` -- ``qualities`` and ``subsamplings`` (one value, or one per image): ``table`` (``JpegEncImage`` array,
+    placed densely) and the batch's ``pixel_bytes``, ``ncoef``, ``work_bytes``, ``out_bytes``.  Needs no GPU.
+    ``ValueError`` by name for a quality outside 1 .. 100, an unknown sampling, an empty image or a side above 65 535."""
+
+    def __init__(self, shapes, quality=95, subsampling='420', what='imencode'):
+        N = len(shapes)
+        quals = list(quality) if isinstance(quality, (list, tuple)) else [quality] * N
+        samps = list(subsampling) if isinstance(subsampling, (list, tuple)) else [subsampling] * N
+        if len(quals) != N or len(samps) != N:
+            raise ValueError(f'{what}: {N} images, {len(quals)} qualities and {len(samps)} samplings')
+        self.table = (_lib.JpegEncImage * N)()
+        self.subsamplings = []
+        for n, (shape, q, s) in enumerate(zip(shapes, quals, samps)):
+            shape = tuple(int(v) for v in shape)
+            if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+                raise ValueError(f'{what}: image {n}: shape {shape} is not (h, w, 3) or (h, w)')
+            if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= q <= 100:
+                raise ValueError(f'{what}: image {n}: quality {q!r} is not an integer in 1 .. 100')
+            if s not in ENCODE_SAMPLINGS:
+                raise ValueError(f"{what}: image {n}: subsampling {s!r} is not '444', '422', '420' or 'gray'")
+            if len(shape) == 2:
+                s = 'gray'                      # a single plane is one component, whatever the batch's sampling says
+            elif s == 'gray':
+                raise ValueError(f"{what}: image {n}: subsampling 'gray' needs a (h, w) image, not {shape}")
+            if shape[0] < 1 or shape[1] < 1:
+                raise ValueError(f'{what}: image {n} is empty: shape {shape}')
+            if shape[0] > 65535 or shape[1] > 65535:
+                raise ValueError(f'{what}: image {n}: a side above 65535: shape {shape}')
+            t = self.table[n]
+            t.height, t.width, t.channels, t.quality = shape[0], shape[1], 1 if len(shape) == 2 else 3, int(q)
+            t.hs, t.vs = ENCODE_SAMPLINGS[s]
+            self.subsamplings.append(s)
+        totals = (C.c_int64 * 6)()
+        st = _lib.lib().yv4_jpeg_encode_layout(self.table, N, totals)
+        if st != 0:
+            _raise(st, what)
+        self.pixel_bytes, self.ncoef, self.work_bytes, self.out_bytes = (int(v) for v in totals[:4])
+
+    def __len__(self):
+        return len(self.table)
+
+    def work_region_bytes(self, n):
+        """The bytes of image ``n``'s work region (csrc/jpeg_enc_core.h ``work_bytes``): two totals, the running sums of
+        both grids' workgroups, the bits per block, the packed words of the bound."""
+        nb, per = int(self.table[n].nblocks), _lib.JPEG_ENC_WG_BLOCKS
+        words = ((nb * _lib.JPEG_ENC_BLOCK_BITS + 7) // 8 + 3) // 4
+        return 16 + 8 * (-(-nb // per)) + 8 * (-(-words // per)) + 4 * ((nb + 1) & ~1) + 4 * ((words + 1) & ~1)
+
+    def header(self, n):
+        """SOI .. SOS of image ``n`` (``yv4_jpeg_encode_header``)."""
+        buf = (C.c_uint8 * _lib.JPEG_ENC_HEADER_MAX)()
+        length = C.c_int64()
+        check(_lib.lib().yv4_jpeg_encode_header(C.byref(self.table[n]), C.addressof(buf), len(buf), C.byref(length)),
+              'yv4_jpeg_encode_header')
+        return bytes(buf[:length.value])
+
+    def files(self, out, sizes, offsets=None):
+        """The files of the batch from the scan bytes (``out``: a host uint8 array, ``sizes``: the byte counts; image n's
+        bytes start at ``offsets[n]``, default: the table's ``out_off``)."""
+        offs = [int(t.out_off) for t in self.table] if offsets is None else offsets
+        return [self.header(n) + out[int(o):int(o) + int(sizes[n])].tobytes() + b'\xff\xd9' for n, o in enumerate(offs)]
+
+
+def jpeg_encode_host(imgs, quality=95, subsampling='420', channel_order='bgr'):
+    """The whole encoder on the CPU (``yv4_jpeg_encode_host``: the core the kernels run) -> ``(EncodeTable, int16
+    coefficients, scan bytes of the batch, int64 sizes)``.  ``imgs``: numpy uint8 arrays.  Needs no GPU; for tests and
+    tools -- ``imencode`` never takes this path."""
+    imgs = [np.ascontiguousarray(a, np.uint8) for a in imgs]
+    et = EncodeTable([a.shape for a in imgs], quality, subsampling, 'jpeg_encode_host')
+    pix = np.zeros(max(et.pixel_bytes, 1), np.uint8)
+    for t, a in zip(et.table, imgs):
+        pix[int(t.src_off):int(t.src_off) + a.size] = a.reshape(-1)
+    coef = np.empty(et.ncoef, np.int16)
+    work = np.empty(et.work_bytes // 8 + 1, np.uint64)
+    out = np.empty(et.out_bytes, np.uint8)
+    sizes = np.empty(len(imgs), np.int64)
+    check(_lib.lib().yv4_jpeg_encode_host(et.table, len(imgs), 3, pix.ctypes.data, pix.size, int(channel_order == 'rgb'),
+                                          coef.ctypes.data, coef.size, work.ctypes.data, et.work_bytes, out.ctypes.data,
+                                          out.size, sizes.ctypes.data), 'yv4_jpeg_encode_host')
+    return et, coef, out, sizes
+
+
+def encode_stages(et, pixels, channel_order='bgr', coef=None, work=None, out=None, sizes=None, stages=3):
+    """The two device stages over a placed table: ``yv4_jpeg_encode_coefficients`` (``stages & 1``) and
+    ``yv4_jpeg_encode_scan`` (``stages & 2``) on the current stream -> ``(coef, work, out, sizes)`` device tensors, nothing
+    read back.  ``pixels``: the flat uint8 device buffer the table's ``src_off`` / ``src_pitch`` point into.  ``coef`` /
+    ``work`` / ``out`` / ``sizes``: the caller's tensors (larger ones with the table's offsets moved, say); the library
+    checks every region against their sizes before any launch."""
+    _need(_lib.has_jpeg_encode(), 'yv4_jpeg_encode_scan')
+    L, N, dev = _lib.lib(), len(et), pixels.device
+    with torch.cuda.device(dev):
+        stage = torch.empty(C.sizeof(et.table), dtype=torch.uint8, pin_memory=True)
+        C.memmove(stage.data_ptr(), et.table, C.sizeof(et.table))
+        up = stage.to(dev, non_blocking=True)
+        coef = torch.empty(et.ncoef, dtype=torch.int16, device=dev) if coef is None else coef
+        if stages & 1:
+            st = L.yv4_jpeg_encode_coefficients(et.table, up.data_ptr(), N, pixels.data_ptr(), pixels.numel(),
+                                                int(channel_order == 'rgb'), coef.data_ptr(), coef.numel(), stream_ptr())
+            if st != 0:
+                _raise(st, 'yv4_jpeg_encode_coefficients')
+        if stages & 2:
+            work = torch.empty(et.work_bytes, dtype=torch.uint8, device=dev) if work is None else work
+            out = torch.empty(et.out_bytes, dtype=torch.uint8, device=dev) if out is None else out
+            sizes = torch.empty(N, dtype=torch.int64, device=dev) if sizes is None else sizes
+            st = L.yv4_jpeg_encode_scan(et.table, up.data_ptr(), N, coef.data_ptr(), coef.numel(), work.data_ptr(),
+                                        work.numel(), out.data_ptr(), out.numel(), sizes.data_ptr(), stream_ptr())
+            if st != 0:
+                _raise(st, 'yv4_jpeg_encode_scan')
+    return coef, work, out, sizes
+
+
+def _read_back(et, out, sizes):
+    """The files of a finished encode.  Two read-backs: the N byte counts; then the scan bytes alone -- the images'
+    exact slices of the bound-sized output gathered into one dense device buffer (``torch.cat``) and copied through
+    pinned memory, ``sum(counts)`` bytes.  The unused part of every image's bound never leaves the device."""
+    counts = sizes.cpu().numpy()
+    dense = torch.cat([out[int(t.out_off):int(t.out_off) + int(c)] for t, c in zip(et.table, counts)])
+    host = torch.empty(dense.numel(), dtype=torch.uint8, pin_memory=True)
+    host.copy_(dense)
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    return et.files(host.numpy(), counts, starts)
+
+
+def encode_into(pixels, placement, quality=95, subsampling='420', channel_order='bgr'):
+    """The batch encode behind ``imencode`` and ``imwrite``: images already lying in the flat ``torch.uint8`` device
+    buffer ``pixels`` -> the list of their JPEG files (``bytes``).  ``placement``: per image ``(shape, byte offset, row
+    pitch)`` -- or ``decode_into``'s ``JpegImage`` table, so that a decode -> draw -> encode chain never copies pixels.
+    One call per stage for the whole batch, one read-back of the byte counts and one of the scan bytes, compacted on the
+    device first (what crosses to the host is the files' size, not the bound the output buffer is sized by); the headers
+    are written on the host."""
+    if not torch.cuda.is_available() or pixels.device.type != 'cuda':
+        raise RuntimeError('the JPEG encoder runs on the GPU through libyv4_hip.so (there is no CPU fallback)')
+    if channel_order not in ('bgr', 'rgb'):
+        raise ValueError(f"channel_order {channel_order!r} is not 'bgr' or 'rgb'")
+    if pixels.dtype != torch.uint8 or not pixels.is_contiguous():
+        raise ValueError('pixels must be a contiguous torch.uint8 tensor')
+    if isinstance(placement, C.Array) and placement._type_ is JpegImage:
+        placement = [(oriented_size(t) + (3,), int(t.out_off), int(t.out_pitch)) for t in placement]
+    et = EncodeTable([p[0] for p in placement], quality, subsampling)
+    for t, (_, off, pitch) in zip(et.table, placement):
+        t.src_off, t.src_pitch = int(off), int(pitch)
+    with torch.cuda.device(pixels.device):
+        _, _, out, sizes = encode_stages(et, pixels.view(-1), channel_order)
+        return _read_back(et, out, sizes)
+
+
+def imencode(imgs, quality=95, subsampling='420', channel_order='bgr', device=None):
+    """``imgs``: one image or a list -- each a ``torch.uint8`` (h, w, 3) or (h, w) tensor on the GPU, or a numpy array of
+    that shape, which is uploaded -> the bytes of its baseline JPEG file, or a list of them.  The file is what
+    libjpeg-turbo writes for the same pixels: ``cv2.imwrite``'s at its defaults, quality 95 and 4:2:0, which are the
+    defaults here.  ``quality`` (1 .. 100) and ``subsampling`` (``'444'``, ``'422'``, ``'420'``; a (h, w) image is always
+    one gray component) may be lists, one value per image.  ``channel_order``: what the three channels are, ``'bgr'``
+    (what ``imread`` returns) or ``'rgb'``.  A list is one batch: the images are placed in one flat device buffer (the
+    host ones through one pinned upload of their own bytes), then one call per stage and the two read-backs of
+    ``encode_into``."""
+    if not torch.cuda.is_available():
+        raise RuntimeError('the JPEG encoder runs on the GPU through libyv4_hip.so (there is no CPU fallback)')
+    if channel_order not in ('bgr', 'rgb'):
+        raise ValueError(f"channel_order {channel_order!r} is not 'bgr' or 'rgb'")
+    single = not isinstance(imgs, (list, tuple))
+    imgs = [imgs] if single else list(imgs)
+    if not imgs:
+        return []
+    for n, a in enumerate(imgs):
+        if not isinstance(a, (np.ndarray, torch.Tensor)) or (a.dtype != np.uint8 if isinstance(a, np.ndarray) else a.dtype != torch.uint8):
+            raise ValueError(f'imencode: image {n} is not a uint8 array or tensor')
+    et = EncodeTable([tuple(a.shape) for a in imgs], quality, subsampling)       # validates before any upload
+    dev = torch.device(device) if device is not None else next(
+        (a.device for a in imgs if isinstance(a, torch.Tensor) and a.device.type == 'cuda'),
+        torch.device('cuda', torch.cuda.current_device()))
+    with torch.cuda.device(dev):
+        pixels = torch.empty(et.pixel_bytes, dtype=torch.uint8, device=dev)
+        where = [(int(t.src_off), int(t.src_pitch) * int(t.height)) for t in et.table]
+        hosts = [k for k, a in enumerate(imgs) if isinstance(a, np.ndarray)]
+        if hosts:                                   # the host images back to back in one pinned buffer, one copy each
+            stage = torch.empty(sum(where[k][1] for k in hosts), dtype=torch.uint8, pin_memory=True)
+            at = 0
+            for k in hosts:
+                n = where[k][1]
+                stage[at:at + n] = torch.from_numpy(np.ascontiguousarray(imgs[k]).reshape(-1))
+                pixels[where[k][0]:where[k][0] + n].copy_(stage[at:at + n], non_blocking=True)
+                at += n
+        for (off, n), a in zip(where, imgs):
+            if isinstance(a, torch.Tensor):
+                pixels[off:off + n].view(a.shape).copy_(a)
+        _, _, out, sizes = encode_stages(et, pixels, channel_order)
+        files = _read_back(et, out, sizes)
+    return files[0] if single else files
+
+
+def _write_files(files, paths, auto_mkdir):
+    def one(k):
+        p = os.fspath(paths[k])
+        if auto_mkdir and os.path.dirname(p):
+            os.makedirs(os.path.dirname(p), exist_ok=True)
+        with open(p, 'wb') as f:
+            f.write(files[k])
+
+    if len(files) == 1:
+        one(0)
+    else:
+        with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, len(files))) as pool:
+            list(pool.map(one, range(len(files))))
+
+
+def check_jpeg_paths(paths, what='imwrite'):
+    """``NotImplementedError`` naming the format for a path that does not end in ``.jpg`` / ``.jpeg`` (any case)."""
+    for p in paths:
+        ext = os.path.splitext(os.fspath(p))[1]
+        if ext.lower() not in ('.jpg', '.jpeg'):
+            raise NotImplementedError(f'{what}: {os.fspath(p)!r}: the {ext.lstrip(".").upper() or "extensionless"} format is '
+                                      'not built: the encoder writes baseline JPEG (.jpg / .jpeg) only')
+
+
+def imwrite(imgs, paths, quality=95, subsampling='420', channel_order='bgr', auto_mkdir=True):
+    """``mmcv.imwrite`` for JPEG: ``imencode`` of one image or a list (one batch), then the files written on at most
+    ``MAX_DECODE_THREADS`` threads.  ``paths``: one file name or a list, each ending in ``.jpg`` / ``.jpeg``; the
+    directories are made with ``auto_mkdir``.  Returns ``True``, as ``mmcv.imwrite`` does."""
+    single = not isinstance(imgs, (list, tuple))
+    imgs, paths = ([imgs], [paths]) if single else (list(imgs), list(paths))
+    if len(imgs) != len(paths):
+        raise ValueError(f'imwrite: {len(imgs)} images and {len(paths)} paths')
+    check_jpeg_paths(paths)
+    if imgs:
+        _write_files(imencode(imgs, quality, subsampling, channel_order), paths, auto_mkdir)
+    return True

@@ -10,6 +10,7 @@ SPP, 2 upsamples, decode+filter, NMS -- built once per (batch, height, width) by
 ``compile``; the host touches the device twice per batch (scale factors in, detections
 out).
 """
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -176,6 +177,83 @@ class SingleStageDetector(HipModule):
 
     def forward_dummy(self, img):
         return self.bbox_head(self.extract_feat(img))
+
+    def show_results(self, imgs, results, out_files=None, score_thr=0.3, bbox_color=(72, 101, 241),
+                     text_color=(72, 101, 241), mask_color=None, thickness=2, font_size=13):
+        """The batched form behind ``show_result``: one decode of the file names among ``imgs``, one draw launch, and with
+        ``out_files`` one encode (``imwrite``'s batch).  Returns the drawn (h, w, 3) device tensors, or ``out_files``."""
+        from . import image_io
+        from .draw import draw_boxes_into
+        if len(imgs) != len(results) or (out_files is not None and len(out_files) != len(imgs)):
+            raise ValueError(f'show_results: {len(imgs)} images, {len(results)} results'
+                             + ('' if out_files is None else f' and {len(out_files)} output files'))
+        if mask_color is not None:
+            raise NotImplementedError('show_result(mask_color=...): masks are not built')
+        if out_files is not None:
+            image_io.check_jpeg_paths(out_files, 'show_result')
+        if not imgs:
+            return []
+        device = next(self.parameters()).device
+        dets, labels = [], []
+        for res in results:
+            if isinstance(res, tuple) and len(res) == 2 and isinstance(res[0], torch.Tensor):
+                d, lab = res                                   # (dets, labels) device tensors
+            elif isinstance(res, tuple):
+                raise NotImplementedError('show_result: a (bbox, segm) result carries masks, which are not built')
+            else:                                              # the per-class list (base.py:296-304)
+                d = np.concatenate([np.asarray(r, np.float32).reshape(-1, 5) for r in res], 0) if len(res) else \
+                    np.zeros((0, 5), np.float32)
+                lab = np.concatenate([np.full(np.asarray(r).reshape(-1, 5).shape[0], k, np.int64)
+                                      for k, r in enumerate(res)]) if len(res) else np.zeros(0, np.int64)
+                d, lab = torch.from_numpy(d), torch.from_numpy(lab)
+            dets.append(d.to(device, torch.float32).reshape(-1, 5))
+            labels.append(lab.to(device).reshape(-1))
+        classes = getattr(self, 'CLASSES', None)
+        if classes is None:
+            classes = [f'class {k}' for k in range(self.bbox_head.num_classes)]
+        # every picture into one flat buffer: the files of the call are one decode batch, arrays and tensors are copied
+        imgs = list(imgs)
+        names = [k for k, a in enumerate(imgs) if isinstance(a, (str, os.PathLike))]
+        if names:
+            for k, a in zip(names, image_io.imread([imgs[k] for k in names], device=device)):
+                imgs[k] = a
+        offs, end = [], 0
+        for k, a in enumerate(imgs):
+            if isinstance(a, np.ndarray):
+                imgs[k] = a = torch.from_numpy(np.ascontiguousarray(a))
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.uint8 or a.dim() != 3 or a.shape[2] != 3:
+                raise ValueError(f'show_result: image {k} is not a file name or a (h, w, 3) uint8 array or tensor')
+            offs.append(end)
+            end += (a.numel() + 255) // 256 * 256
+        flat = torch.empty(end, dtype=torch.uint8, device=device)
+        views = [flat[o:o + a.numel()].view(a.shape) for o, a in zip(offs, imgs)]
+        for v, a in zip(views, imgs):
+            v.copy_(a, non_blocking=True)
+        places = [(a.shape[0], a.shape[1], o, 3 * a.shape[1]) for o, a in zip(offs, imgs)]
+        draw_boxes_into(flat, places, dets, labels, list(classes), score_thr=score_thr, bbox_color=bbox_color,
+                        text_color=text_color, thickness=thickness, font_size=font_size)
+        if out_files is None:
+            return views
+        files = image_io.encode_into(flat, [(tuple(a.shape), o, 3 * a.shape[1]) for o, a in zip(offs, imgs)])
+        image_io._write_files(files, list(out_files), True)
+        return list(out_files)
+
+    def show_result(self, img, result, score_thr=0.3, bbox_color=(72, 101, 241), text_color=(72, 101, 241), mask_color=None,
+                    thickness=2, font_size=13, win_name='', show=False, wait_time=0, out_file=None):
+        """``BaseDetector.show_result`` (``mmdet/models/detectors/base.py:256-341``) on the GPU.  ``img``: a file name
+        (a baseline JPEG, decoded on the device), a (h, w, 3) BGR uint8 array or a device tensor; ``result``: the
+        per-class list ``simple_test`` returns for one image, or ``(dets (k, 5), labels (k,))`` device tensors.  Boxes
+        with ``score > score_thr`` are drawn with their class name (``self.CLASSES``, else ``class {label}``) and score
+        by the package's own rule (``draw.py``: a 5x7 bitmap font, not matplotlib's rendering -- parity with the
+        reference's picture is not claimed).  Returns the drawn device tensor, or with ``out_file`` writes it as a JPEG
+        (``imwrite``'s defaults: quality 95, 4:2:0).  There is no display: ``show=True`` raises, and so do a result
+        with masks and a ``mask_color``."""
+        if show:
+            raise NotImplementedError('show_result(show=True): there is no display window; pass out_file=')
+        out = self.show_results([img], [result], None if out_file is None else [out_file], score_thr=score_thr,
+                                bbox_color=bbox_color, text_color=text_color, mask_color=mask_color, thickness=thickness,
+                                font_size=font_size)
+        return None if out_file is not None else out[0]
 
     def simple_test(self, img, img_metas, rescale=False, results=None, img_index=None):
         """``results``: a ``results.DeviceResults``.  The batch is then appended to it on the device, at the dataset

@@ -985,6 +985,43 @@ int yv4_map_accumulate(const uint8_t* tp, const uint8_t* fp, const int32_t* cls_
                        void* work, float* ap, double* last_recall, float* last_precision, double* recall,
                        float* precision, int64_t* num_dets, void* stream);
 
+/* ---- per-image mAP (csrc/map_image.hip; additive within ABI 8) --------------------------------------------------------
+ * tools/analysis_tools/analyze_results.py's bbox_map_eval for every image of a dataset at once: the accumulation of
+ * yv4_map_accumulate per PROBLEM p = class * N + image instead of per class, then per image the mean over its classes
+ * and over the thresholds.  It follows yv4_map_rank, yv4_bbox_overlaps_batched and yv4_tpfp_batched (num_ranges == 1),
+ * unchanged.  All pointers but `stream` are device pointers; every table comes with its element count, checked against
+ * N, C, num_thrs, total_det and total_gt on the host before any launch (YV4_E_INVALID, nothing is written).  No float
+ * atomics: two runs give identical bytes.  The definition is restated in tests/_image_map_ref.py.
+ *
+ * yv4_map_image_ap: per problem p and threshold t.
+ *   tp, fp (num_thrs, 1, total_det) bytes as yv4_tpfp_batched wrote them for total_det = Dv columns (tpfp_elems >=
+ *     num_thrs * total_det); a problem's columns [det_off[p], det_off[p+1]) are already in visiting order.
+ *   det_off, gt_off (P+1) int64 (off_elems >= P + 1); gt_ignore (total_gt) bytes.
+ *   ngt[p] = the gts of [gt_off[p], gt_off[p+1]) whose gt_ignore byte is 0.
+ *   ap[t, p]: yv4_map_accumulate's YV4_MAP_AP_AREA rule over the problem's own detections: integer cumulative ctp /
+ *     cfp, recall = float32(ctp) / max(ngt, float32 eps) in float64, precision = float32(ctp) / max(float32(ctp) +
+ *     float32(cfp), float32 eps) in float32, mrec = [0, recall, 1], mpre = [0, precision, 0] in float64, mpre's suffix
+ *     maximum, the terms (mrec[i+1] - mrec[i]) * mpre[i+1] where recall changes added in ascending i into ONE float64
+ *     accumulator, rounded to float32.  A problem without detections scores 0.
+ *   ap (num_thrs, P) float32 (ap_elems >= num_thrs * P); ngt (P) int32 (ngt_elems >= P).
+ *   work: yv4_map_image_ap_work(total_det) bytes (4 bytes a detection: the thresholds are walked in turn; only
+ *     problems of more than 64 detections use it), 4-byte aligned.  total_det == 0 is legal (tp / fp may be null).  An offset outside its table is clamped.
+ *
+ * yv4_map_image_mean: per image i and threshold t the ap[t, c*N+i] of the classes with ngt[c*N+i] > 0, in ascending c.
+ *   image_map_thr[t, i] (num_thrs, N) float32 = their numpy float32 mean: numpy's pairwise sum, then ONE float32
+ *     division by the count -- fewer than 8 values: added left to right from 0; 8 to 128: eight accumulators over the
+ *     multiples of 8, combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the tail then added left to right; more: split
+ *     at n2 = n / 2, n2 -= n2 % 8, each half by the same rule, the two sums added.  No class with gts: 0.
+ *   image_map[i] (N) float64 = (((0 + m_0) + m_1) + .. + m_{T-1}) / T in float64 over the widened image_map_thr[t, i]. */
+size_t yv4_map_image_ap_work(int64_t total_det);
+int yv4_map_image_ap(const uint8_t* tp, const uint8_t* fp, int64_t tpfp_elems, const int64_t* det_off,
+                     const int64_t* gt_off, int64_t off_elems, const uint8_t* gt_ignore, int64_t total_gt,
+                     int64_t total_det, int N, int C, int num_thrs, void* work, size_t work_bytes, float* ap,
+                     int64_t ap_elems, int32_t* ngt, int64_t ngt_elems, void* stream);
+int yv4_map_image_mean(const float* ap, int64_t ap_elems, const int32_t* ngt, int64_t ngt_elems, int N, int C,
+                       int num_thrs, double* image_map, int64_t map_elems, float* image_map_thr, int64_t thr_elems,
+                       void* stream);
+
 /* ---- metric='fast-bbox' from the flat result table (csrc/flex_eval.hip; additive within ABI 8) -----------------------
  * mean_ap_flexible.py's eval_map_flexible with IOU2DCoCo, MatcherCoCo and the 'All' + ScaleBreakdown groups
  * (datasets/coco.py:464-496), scored from the flat table without a visit to the host.  The definition, restated in
@@ -1689,6 +1726,17 @@ int yv4_draw_boxes(const yv4_draw_image* table, const yv4_draw_image* table_dev,
 /* The same per-pixel function on the CPU, all pointers HOST memory. */
 int yv4_draw_boxes_host(const yv4_draw_image* table, int N, uint8_t* pixels, int64_t pixel_bytes, const float* dets,
                         const int32_t* labels, int64_t nbox_total, const uint8_t* names, const yv4_draw_style* style);
+
+/* The same two calls with `flags` (yv4_draw_boxes / yv4_draw_boxes_host are these with flags 0).  YV4_DRAW_NO_SCORE:
+ * boxes without a score, as ground truth is drawn -- the rows of dets are still five floats wide and the fifth is not
+ * read, the label is the class name alone, and no box is skipped by score_thr.  Any other bit: YV4_E_INVALID. */
+#define YV4_DRAW_NO_SCORE 1
+int yv4_draw_boxes_ex(const yv4_draw_image* table, const yv4_draw_image* table_dev, int N, uint8_t* pixels,
+                      int64_t pixel_bytes, const float* dets, const int32_t* labels, int64_t nbox_total,
+                      const uint8_t* names, const yv4_draw_style* style, int flags, void* stream);
+int yv4_draw_boxes_host_ex(const yv4_draw_image* table, int N, uint8_t* pixels, int64_t pixel_bytes, const float* dets,
+                           const int32_t* labels, int64_t nbox_total, const uint8_t* names, const yv4_draw_style* style,
+                           int flags);
 
 #ifdef __cplusplus
 }

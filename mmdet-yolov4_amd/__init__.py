@@ -27,13 +27,14 @@ from .augment import FusedTrainPipeline
 from .augment_v3 import FusedV3TrainPipeline, build_train_pipeline
 from . import tta  # noqa: F401  (YOLOv3 test-time augmentation)
 from .apis import inference_detector, single_gpu_test, multi_gpu_test
-from .draw import color_val, draw_boxes, draw_boxes_into
+from .draw import color_val, draw_boxes, draw_boxes_into, imshow_gt_det_bboxes
 from .eval_utils import (coco_test_annotation, evaluate_fast_bbox, FlexGt, EVAL_BREAKDOWN, EVAL_IOU_CALCULATOR, EVAL_MATCHER, FlexibleStatisticsEval, IOU2DCoCo,
                          MatcherCoCo, ScaleBreakdown, average_precision, eval_map_flexible, iou_coco, match_coco)
 from .map_eval import (MapGt, bbox_overlaps, eval_map, evaluate_map, print_map_summary, tpfp_default,  # noqa: F401
                        tpfp_imagenet)
 from .coco_eval import COCOeval, CocoGt, evaluate_bbox, flatten_results  # noqa: F401
 from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: F401
+from .analysis import ResultVisualizer, bbox_map_eval, image_maps  # noqa: F401
 from .datasets import (CocoDataset, DistributedGroupSampler, GroupSampler, TestLoader, TrainLoader,  # noqa: F401
                        build_dataset, build_test_loader, build_train_loader)
 

@@ -355,6 +355,10 @@ SIGNATURES = {
     'yv4_map_accumulate_work': (_sz, [_i64, _i, _i]),
     'yv4_map_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp]),
+    'yv4_map_image_ap_work': (_sz, [_i64]),
+    'yv4_map_image_ap': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _vp, _sz, _vp, _i64, _vp, _i64,
+                                   _vp]),
+    'yv4_map_image_mean': (C.c_int, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _vp]),
     'yv4_flex_tables': (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'yv4_flex_accumulate_work': (_sz, [_i64, _i, _i]),
     'yv4_flex_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp,
@@ -394,6 +398,9 @@ SIGNATURES = {
     'yv4_draw_layout': (C.c_int, [C.POINTER(DrawImage), _i, C.POINTER(C.c_int64)]),
     'yv4_draw_boxes': (C.c_int, [C.POINTER(DrawImage), _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(DrawStyle), _vp]),
     'yv4_draw_boxes_host': (C.c_int, [C.POINTER(DrawImage), _i, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(DrawStyle)]),
+    'yv4_draw_boxes_ex': (C.c_int, [C.POINTER(DrawImage), _vp, _i, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(DrawStyle), _i,
+                                    _vp]),
+    'yv4_draw_boxes_host_ex': (C.c_int, [C.POINTER(DrawImage), _i, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(DrawStyle), _i]),
 }
 
 #: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
@@ -439,6 +446,11 @@ JPEG_ENCODE_SYMBOLS = frozenset(('yv4_jpeg_encode_layout', 'yv4_jpeg_encode_vali
                                  'yv4_jpeg_encode_host', 'yv4_jpeg_encode_coefficients', 'yv4_jpeg_encode_scan'))
 #: drawing detections onto images (additive within ABI 8, bound like FP8_SYMBOLS); has_draw()
 DRAW_SYMBOLS = frozenset(('yv4_draw_layout', 'yv4_draw_boxes', 'yv4_draw_boxes_host'))
+#: drawing with flags -- boxes without a score (additive within ABI 8, bound like FP8_SYMBOLS); has_draw_ex()
+DRAW_EX_SYMBOLS = frozenset(('yv4_draw_boxes_ex', 'yv4_draw_boxes_host_ex'))
+DRAW_NO_SCORE = 1          # YV4_DRAW_NO_SCORE
+#: the per-image mAP (additive within ABI 8, bound like FP8_SYMBOLS); has_map_image()
+MAP_IMAGE_SYMBOLS = frozenset(('yv4_map_image_ap_work', 'yv4_map_image_ap', 'yv4_map_image_mean'))
 #: ``YV4_JPEG_MIN_CHUNK_BYTES`` / ``YV4_JPEG_MAX_CHUNK_BYTES`` / ``YV4_JPEG_MAX_ROUNDS`` (include/yv4.h)
 JPEG_MIN_CHUNK_BYTES, JPEG_MAX_CHUNK_BYTES, JPEG_MAX_ROUNDS = 4, 1 << 20, 4096
 #: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
@@ -488,7 +500,7 @@ def lib():
                     or name in FLEX_FLAT_SYMBOLS
                     or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS
                     or name in JPEG_ORIENT_SYMBOLS or name in LETTERBOX_BATCH_SYMBOLS or name in JPEG_ENCODE_SYMBOLS
-                    or name in DRAW_SYMBOLS) \
+                    or name in DRAW_SYMBOLS or name in DRAW_EX_SYMBOLS or name in MAP_IMAGE_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -614,6 +626,18 @@ def has_draw():
     """The loaded library exports the drawing entry points (``yv4_draw_layout`` / ``yv4_draw_boxes``)."""
     h = lib()
     return all(hasattr(h, n) for n in DRAW_SYMBOLS)
+
+
+def has_draw_ex():
+    """The loaded library exports ``yv4_draw_boxes_ex`` / ``yv4_draw_boxes_host_ex`` (boxes without a score)."""
+    h = lib()
+    return has_draw() and all(hasattr(h, n) for n in DRAW_EX_SYMBOLS)
+
+
+def has_map_image():
+    """The loaded library exports the per-image mAP entry points (``yv4_map_image_ap`` / ``yv4_map_image_mean``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in MAP_IMAGE_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

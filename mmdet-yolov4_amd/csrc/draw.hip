@@ -51,7 +51,8 @@ YV4_DRAW_HD int trunc_coord(float v) {      // int32 truncation; NaN and values 
   return (int)v;
 }
 
-// character k of box's label: the class name, then '|', then the score as d.dd (floor(score * 100 + 0.5) in float32).
+// character k of box's label: the class name, then '|', then the score as d.dd (floor(score * 100 + 0.5) in float32);
+// with YV4_DRAW_NO_SCORE the name is the whole label and this is never asked for k >= len.
 // A name byte outside 0x20 .. 0x7E reads as '?', whoever made the table: the glyph table is never indexed outside.
 YV4_DRAW_HD int label_char(const uint8_t* name, int len, float score, int k) {
   if (k < len) {
@@ -74,20 +75,23 @@ enum Paint { kKeep = 0, kFrame = 1, kText = 2, kDim = 3 };      // what a pixel 
 
 // what pixel (x, y) of image im becomes: decided once a pixel, by the last box whose label or frame covers it
 YV4_DRAW_HD Paint decide(const yv4_draw_image& im, const float* dets, const int32_t* labels, const uint8_t* names,
-                         const yv4_draw_style& st, int x, int y) {
+                         const yv4_draw_style& st, int flags, int x, int y) {
   const int s = st.font_size / 7 > 1 ? st.font_size / 7 : 1;
+  const bool scored = !(flags & YV4_DRAW_NO_SCORE);
+  const int tail = scored ? 5 : 0;      // the characters behind the name: '|' and d.dd
   for (int64_t k = im.box_base + im.nbox - 1; k >= im.box_base; --k) {
     const float* d = dets + 5 * k;
-    if (!(d[4] > st.score_thr)) continue;
+    const float score = scored ? d[4] : 0.0f;
+    if (scored && !(score > st.score_thr)) continue;
     const int x1 = trunc_coord(d[0]), y1 = trunc_coord(d[1]), x2 = trunc_coord(d[2]), y2 = trunc_coord(d[3]);
     // the label: its top-left at (x1, y1); one scaled pixel of padding, 5 + 1 columns a character, 7 rows
     const int lab = labels[k];
     const uint8_t* name = names + (int64_t)(lab >= 0 && lab < st.num_classes ? lab : st.num_classes) * YV4_DRAW_NAME_BYTES;
     const int len = name[0] < YV4_DRAW_NAME_BYTES ? name[0] : YV4_DRAW_NAME_BYTES - 1;
     const int64_t lx = (int64_t)x - x1, ly = (int64_t)y - y1;
-    if (lx >= 0 && ly >= 0 && lx < (int64_t)s * (1 + 6 * (len + 5)) && ly < 9 * s) {
+    if (lx >= 0 && ly >= 0 && lx < (int64_t)s * (1 + 6 * (len + tail)) && ly < 9 * s) {
       const int gx = (int)lx / s - 1, gy = (int)ly / s - 1;
-      if (gx >= 0 && gy >= 0 && gy < 7 && gx % 6 < 5 && glyph_bit(label_char(name, len, d[4], gx / 6), gx % 6, gy))
+      if (gx >= 0 && gy >= 0 && gy < 7 && gx % 6 < 5 && glyph_bit(label_char(name, len, score, gx / 6), gx % 6, gy))
         return kText;
       return kDim;
     }
@@ -109,7 +113,7 @@ YV4_DRAW_HD void paint(uint8_t* p, Paint what, const yv4_draw_style& st) {
 
 __global__ __launch_bounds__(kWg) void draw_kernel(const yv4_draw_image* __restrict__ table, int N, uint8_t* __restrict__ pixels,
                                                    const float* __restrict__ dets, const int32_t* __restrict__ labels,
-                                                   const uint8_t* __restrict__ names, yv4_draw_style st) {
+                                                   const uint8_t* __restrict__ names, yv4_draw_style st, int flags) {
   int lo = 0, hi = N - 1;
   while (lo < hi) {      // the image of this workgroup: the last one whose base is <= blockIdx.x
     const int mid = (lo + hi + 1) >> 1;
@@ -121,14 +125,15 @@ __global__ __launch_bounds__(kWg) void draw_kernel(const yv4_draw_image* __restr
   if (im.nbox == 0 || i >= (int64_t)im.width * im.height) return;
   const int y = (int)(i / im.width), x = (int)(i % im.width);
   uint8_t* p = pixels + im.pix_off + (int64_t)y * im.pitch + 3 * x;
-  paint(p, decide(im, dets, labels, names, st, x, y), st);
+  paint(p, decide(im, dets, labels, names, st, flags, x, y), st);
 }
 
 static int64_t wgs_of(const yv4_draw_image& im) { return ((int64_t)im.width * im.height + kWg - 1) / kWg; }
 
 static int validate(const char* who, const yv4_draw_image* table, int N, int64_t pixel_bytes, int64_t nbox_total,
-                    const yv4_draw_style* st) {
+                    const yv4_draw_style* st, int flags) {
   YV4_REQUIRE(table && st && N >= 1, "%s: null pointer or no images", who);
+  YV4_REQUIRE((flags & ~YV4_DRAW_NO_SCORE) == 0, "%s: flags 0x%x holds a bit other than YV4_DRAW_NO_SCORE", who, flags);
   YV4_REQUIRE(st->thickness >= 1 && st->font_size >= 1 && st->font_size <= 7 * 64 && st->num_classes >= 0,
               "%s: thickness %d and font_size %d must be at least 1 (font_size at most 448)", who, st->thickness, st->font_size);
   for (int c = 0; c < 3; ++c)
@@ -170,32 +175,44 @@ extern "C" int yv4_draw_layout(yv4_draw_image* table, int N, int64_t* workgroups
   return YV4_OK;
 }
 
-extern "C" int yv4_draw_boxes(const yv4_draw_image* table, const yv4_draw_image* table_dev, int N, uint8_t* pixels,
-                              int64_t pixel_bytes, const float* dets, const int32_t* labels, int64_t nbox_total,
-                              const uint8_t* names, const yv4_draw_style* style, void* stream) {
+extern "C" int yv4_draw_boxes_ex(const yv4_draw_image* table, const yv4_draw_image* table_dev, int N, uint8_t* pixels,
+                                 int64_t pixel_bytes, const float* dets, const int32_t* labels, int64_t nbox_total,
+                                 const uint8_t* names, const yv4_draw_style* style, int flags, void* stream) {
   YV4_REQUIRE(table_dev && pixels && names && (nbox_total == 0 || (dets && labels)), "draw_boxes: null pointer");
-  const int st = draw::validate("draw_boxes", table, N, pixel_bytes, nbox_total, style);
+  const int st = draw::validate("draw_boxes", table, N, pixel_bytes, nbox_total, style, flags);
   if (st != YV4_OK) return st;
   const int64_t nwg = table[N - 1].wg_base + draw::wgs_of(table[N - 1]);
   hipLaunchKernelGGL(draw::draw_kernel, dim3((unsigned)nwg), dim3(draw::kWg), 0, reinterpret_cast<hipStream_t>(stream),
-                     table_dev, N, pixels, dets, labels, names, *style);
+                     table_dev, N, pixels, dets, labels, names, *style, flags);
   YV4_CHECK_LAUNCH("draw_boxes");
   return YV4_OK;
 }
 
-extern "C" int yv4_draw_boxes_host(const yv4_draw_image* table, int N, uint8_t* pixels, int64_t pixel_bytes,
-                                   const float* dets, const int32_t* labels, int64_t nbox_total, const uint8_t* names,
-                                   const yv4_draw_style* style) {
+extern "C" int yv4_draw_boxes(const yv4_draw_image* table, const yv4_draw_image* table_dev, int N, uint8_t* pixels,
+                              int64_t pixel_bytes, const float* dets, const int32_t* labels, int64_t nbox_total,
+                              const uint8_t* names, const yv4_draw_style* style, void* stream) {
+  return yv4_draw_boxes_ex(table, table_dev, N, pixels, pixel_bytes, dets, labels, nbox_total, names, style, 0, stream);
+}
+
+extern "C" int yv4_draw_boxes_host_ex(const yv4_draw_image* table, int N, uint8_t* pixels, int64_t pixel_bytes,
+                                      const float* dets, const int32_t* labels, int64_t nbox_total, const uint8_t* names,
+                                      const yv4_draw_style* style, int flags) {
   YV4_REQUIRE(pixels && names && (nbox_total == 0 || (dets && labels)), "draw_boxes_host: null pointer");
-  const int st = draw::validate("draw_boxes_host", table, N, pixel_bytes, nbox_total, style);
+  const int st = draw::validate("draw_boxes_host", table, N, pixel_bytes, nbox_total, style, flags);
   if (st != YV4_OK) return st;
   for (int n = 0; n < N; ++n) {
     const yv4_draw_image& im = table[n];
     for (int y = 0; y < im.height; ++y)
       for (int x = 0; x < im.width; ++x) {
         uint8_t* p = pixels + im.pix_off + (int64_t)y * im.pitch + 3 * x;
-        draw::paint(p, draw::decide(im, dets, labels, names, *style, x, y), *style);
+        draw::paint(p, draw::decide(im, dets, labels, names, *style, flags, x, y), *style);
       }
   }
   return YV4_OK;
+}
+
+extern "C" int yv4_draw_boxes_host(const yv4_draw_image* table, int N, uint8_t* pixels, int64_t pixel_bytes,
+                                   const float* dets, const int32_t* labels, int64_t nbox_total, const uint8_t* names,
+                                   const yv4_draw_style* style) {
+  return yv4_draw_boxes_host_ex(table, N, pixels, pixel_bytes, dets, labels, nbox_total, names, style, 0);
 }

@@ -1,0 +1,137 @@
+"""The per-image mAP without a GPU: the numpy restatement (tests/_image_map_ref.py) against what the reference's
+``bbox_map_eval`` produced (tests/golden/image_map.npz), the pairwise mean against numpy, the threshold rounding, the
+ranking rules of ``ResultVisualizer`` and the new symbols."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import mmdet_yolov4_amd as pkg
+from mmdet_yolov4_amd import analysis as A
+
+import _image_map_ref as I
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize('name', I.SETS)
+def test_restatement_equals_the_reference_fixture(name, golden):
+    dets, annos, want, want_thr = I.load_set(golden('image_map'), name)
+    got, got_thr = I.image_maps(dets, annos)
+    assert got.dtype == want.dtype == np.float64 and got_thr.dtype == want_thr.dtype == np.float32
+    np.testing.assert_array_equal(got_thr, want_thr)
+    np.testing.assert_array_equal(got, want)
+
+
+def test_fixture_holds_the_stated_cases(golden):
+    z = golden('image_map')
+    dets, annos, maps, per_thr = I.load_set(z, 'main')
+    i = int(z['main/iou07_image'])
+    assert I.R.overlaps(dets[i][0], annos[i]['bboxes'])[0, 0] == np.float32(0.7)
+    # a miss at 0.7 (compared in float64), where a float32-rounded threshold calls it a hit
+    assert per_thr[4, i] == 0.0 and per_thr[3, i] == 1.0
+    assert I.tpfp(dets[i][0], annos[i]['bboxes'], None, np.float32(I.IOU_THRS[4]))[0].all()
+    hand = {k.split('/')[-1]: int(z[k]) for k in z.files if k.startswith('main/hand/')}
+    assert sorted(hand) == ['det_of_class_without_gt', 'ignore_only', 'no_dets', 'no_gts', 'perfect']
+    assert len(annos[hand['no_gts']]['labels']) == 0 and 'labels_ignore' not in annos[hand['no_gts']]
+    assert len(annos[hand['no_dets']]['labels']) and not any(len(d) for d in dets[hand['no_dets']])
+    assert len(annos[hand['ignore_only']]['labels']) == 0 and len(annos[hand['ignore_only']]['labels_ignore'])
+    assert maps[hand['perfect']] == 1.0 and maps[hand['no_dets']] == 0.0
+    _, wannos, _, _ = I.load_set(z, 'wide')
+    assert [len(a['labels']) for a in wannos] == [7, 8, 9, 129, 300]
+    for name in I.SETS:                       # no stored value depends on a tie order
+        for per_cls in I.load_set(z, name)[0]:
+            assert all(len(np.unique(d[:, 4])) == len(d) for d in per_cls)
+
+
+def test_pairwise_mean_equals_numpy():
+    rng = np.random.default_rng(7)
+    for n in list(range(0, 301)) + [1203]:
+        # values whose float32 sum depends on the order: thirds, sevenths and random fractions
+        a = rng.choice(np.array([1 / 3, 1 / 7, 0.2, 1.0, 0.0], np.float32), n) * rng.random(n, dtype=np.float32)
+        want = np.array(list(a), np.float32).mean() if n else np.float32(0)
+        got = I.pairwise_mean(a)
+        assert got.dtype == np.float32 and got == want, (n, got, want)
+
+
+def test_ceil32_makes_the_float32_comparison_the_float64_one():
+    thrs = A.default_iou_thrs()
+    assert thrs.dtype == np.float64 and len(thrs) == 10 and (thrs == I.IOU_THRS).all()
+    c = A.ceil32(thrs)
+    assert c.dtype == np.float32 and (c.astype(np.float64) >= thrs).all()
+    assert (np.nextafter(c, np.float32(-np.inf)).astype(np.float64) < thrs).all()          # the smallest such float32
+    rng = np.random.default_rng(11)
+    x = rng.random(20000, dtype=np.float32)
+    for t, ct in zip(thrs, c):
+        near = np.float32(t)
+        edge = np.array([near, np.nextafter(near, np.float32(0)), np.nextafter(near, np.float32(2)),
+                         np.nextafter(np.nextafter(near, np.float32(0)), np.float32(0)),
+                         np.nextafter(np.nextafter(near, np.float32(2)), np.float32(2))], np.float32)
+        for v in (x, edge):
+            np.testing.assert_array_equal(v >= np.float64(t), v >= ct)
+            np.testing.assert_array_equal(v.astype(np.float64) >= float(t), v >= ct)
+    assert np.float32(0.7) < thrs[4] and c[4] > np.float32(0.7)                            # the 0.7 trap
+    assert A.ceil32(0.5) == np.float32(0.5)
+
+
+def test_ranking_topk_clipping_and_file_names():
+    maps = [0.5, 0.0, 1.0, 0.5, 0.0, 0.25, 0.5]                      # ties: 0.0 twice, 0.5 three times
+    bad, good = A.rank_images(maps, 3)
+    assert bad == [(1, 0.0), (4, 0.0), (5, 0.25)]                     # equal scores stay in index order
+    assert good == [(3, 0.5), (6, 0.5), (2, 1.0)]
+    want = sorted(dict(enumerate(maps)).items(), key=lambda kv: kv[1])
+    assert bad == want[:3] and good == want[-3:]
+    assert A.clip_topk(20, 7) == 3 and A.clip_topk(3, 7) == 3 and A.clip_topk(4, 7) == 3 and A.clip_topk(2, 7) == 2
+    assert A.clip_topk(1, 1) == 0
+    with pytest.raises(AssertionError):
+        A.clip_topk(0, 7)
+    assert A.gallery_name('val2017/000000000139.jpg', 0.123456) == '000000000139_0.123.jpg'
+    assert A.gallery_name('a.b.JPEG', 1.0) == 'a.b_1.0.JPEG'
+    assert A.gallery_name('/x/y/img.jpg', 0.0) == 'img_0.0.jpg'
+    assert A.gallery_name('img.jpg', 0.45) == 'img_' + str(round(0.45, 3)) + '.jpg'
+
+
+def test_visualizer_refuses_a_display_and_a_foreign_format(tmp_path):
+    class Data:
+        CLASSES = ('a',)
+        img_prefix = str(tmp_path)
+        data_infos = [dict(filename='one.png'), dict(filename='two.jpg')]
+
+        def __len__(self):
+            return 2
+
+        def get_ann_info(self, i):
+            return dict(bboxes=np.zeros((0, 4), np.float32), labels=np.zeros(0, np.int64))
+
+    results = [[np.zeros((0, 5), np.float32)]] * 2
+    with pytest.raises(NotImplementedError, match='display'):
+        A.ResultVisualizer(show=True).evaluate_and_show(Data(), results, topk=1, show_dir=str(tmp_path / 'o'),
+                                                        eval_fn=lambda r, a: 0.0)
+    with pytest.raises(NotImplementedError, match=r'one\.png.*PNG'):
+        A.ResultVisualizer().evaluate_and_show(Data(), results, topk=1, show_dir=str(tmp_path / 'o'),
+                                               eval_fn=lambda r, a: 0.0)
+    assert not (tmp_path / 'o').exists()
+    with pytest.raises(NotImplementedError, match='display'):
+        pkg.imshow_gt_det_bboxes(np.zeros((8, 8, 3), np.uint8), dict(gt_bboxes=[], gt_labels=[]), [[]], ['a'], show=True)
+
+
+def test_headers_binding_and_library_hold_the_new_symbols():
+    text = open(os.path.join(ROOT, 'include', 'yv4.h')).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    declared = set(re.findall(r'\b(yv4_[a-z0-9_]+)\s*\(', text))
+    new = {'yv4_map_image_ap_work', 'yv4_map_image_ap', 'yv4_map_image_mean', 'yv4_draw_boxes_ex', 'yv4_draw_boxes_host_ex'}
+    assert new <= declared and new <= set(pkg._lib.SIGNATURES)
+    assert re.search(r'#define\s+YV4_DRAW_NO_SCORE\s+1\b', text) and pkg._lib.DRAW_NO_SCORE == 1
+    assert re.search(r'#define\s+YV4_ABI_VERSION\s+8\b', text) and pkg._lib.ABI_VERSION == 8
+    lib = pkg._lib.lib()
+    for name in new:
+        assert hasattr(lib, name), name
+    assert pkg._lib.has_map_image() and pkg._lib.has_draw_ex()
+    assert lib.yv4_map_image_ap_work(0) == 4 and lib.yv4_map_image_ap_work(1000) == 4000     # sized by Dv alone
+    # arguments are checked on the host before any device work
+    assert lib.yv4_map_image_ap(None, None, 0, None, None, 0, None, 0, 0, 1, 1, 10, None, 0, None, 0, None, 0, None) == -1
+    assert b'null' in lib.yv4_last_error()
+    assert lib.yv4_map_image_mean(None, 0, None, 0, 0, 1, 10, None, 0, None, 0, None) == -1
+    for name in ('image_maps', 'bbox_map_eval', 'ResultVisualizer', 'imshow_gt_det_bboxes'):
+        assert hasattr(pkg, name), name

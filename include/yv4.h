@@ -1022,6 +1022,40 @@ int yv4_map_image_mean(const float* ap, int64_t ap_elems, const int32_t* ngt, in
                        int num_thrs, double* image_map, int64_t map_elems, float* image_map_thr, int64_t thr_elems,
                        void* stream);
 
+/* ---- proposal recall (csrc/recall.hip; additive within ABI 8) -----------------------------------------------------------
+ * mmdet/core/evaluation/recall.py's _recalls for every image and every proposal number of a dataset in ONE launch.  It
+ * follows yv4_map_rank called with C = 1 and a zero label column, unchanged: that leaves the boxes image-major, inside
+ * an image in descending-score order with equal scores in the caller's order, and det_off.  (For boxes without scores
+ * the caller builds the two tables itself.)  All pointers but `prop_nums` and `stream` are device pointers; every table
+ * comes with its element count, checked against N, M, T, total_det and total_gt on the host before any launch
+ * (YV4_E_INVALID, nothing is written).  No float atomics: two runs give identical bytes.  The definition is restated in
+ * tests/_recall_ref.py.
+ *
+ * yv4_recall_match:
+ *   det4 (total_det, 4) float32 and det_off (N+1) int64: image i owns the boxes [det_off[i], det_off[i+1]) in visiting
+ *     order; gt4 (total_gt, 4) float32 and gt_off (N+1) int64 likewise (off_elems >= N + 1 for both).  Boxes 16-byte
+ *     aligned and expected finite.  An offset outside its table is clamped.
+ *   prop_nums (M <= 16) int32 on the HOST, each >= 0, in any order; iou_thrs (T <= 256) float64.
+ *   Per image: cols = min(n, prop_nums[M-1]) -- the LAST entry, as recall.py:96 has it.  Per image and k, on the first
+ *     c = min(cols, prop_nums[k]) boxes: the IoU block is bbox_overlaps(gts, boxes) of yv4_bbox_overlaps_batched (fp32,
+ *     the reference's operation order, `eps`), computed in the kernel and never stored; then G steps (G = the image's
+ *     gts), each: every row's maximum with its first-occurrence argmax, the FIRST row holding the largest maximum, that
+ *     value recorded, its row and its column set to -1.  With G > c the surplus steps record -1; with c == 0 the G
+ *     steps record 0; an image without gts records nothing.
+ *   gt_ious (M, total_gt) float32 or null (gt_ious_elems >= M * total_gt): image i's step j at [k, gt_off[i] + j].
+ *   counts (M, T) int64 (counts_elems >= M * T), zeroed by the call: counts[k, t] = the recorded values v of row k with
+ *     (double)v >= iou_thrs[t].  recall = counts / total_gt is the caller's division.
+ *   lds_cap: a pair with G + c <= min(lds_cap, 1280) keeps its boxes and its row state in LDS; a larger pair reads the
+ *     boxes from the tables and keeps its state in `work`.  0 selects 1280.  Both forms give the same bytes; nothing is
+ *     ever truncated.
+ *   work: yv4_recall_work(total_det, total_gt, N, M) bytes, 8-byte aligned (12 bytes per gt and proposal number, one
+ *     bit per box and proposal number).  total_det == 0 and total_gt == 0 are legal (det4 / gt4 may then be null). */
+size_t yv4_recall_work(int64_t total_det, int64_t total_gt, int N, int M);
+int yv4_recall_match(const float* det4, const int64_t* det_off, const float* gt4, const int64_t* gt_off, int64_t off_elems,
+                     int N, int64_t total_det, int64_t total_gt, const int32_t* prop_nums, int M, const double* iou_thrs,
+                     int T, float eps, int lds_cap, void* work, size_t work_bytes, float* gt_ious, int64_t gt_ious_elems,
+                     int64_t* counts, int64_t counts_elems, void* stream);
+
 /* ---- metric='fast-bbox' from the flat result table (csrc/flex_eval.hip; additive within ABI 8) -----------------------
  * mean_ap_flexible.py's eval_map_flexible with IOU2DCoCo, MatcherCoCo and the 'All' + ScaleBreakdown groups
  * (datasets/coco.py:464-496), scored from the flat table without a visit to the host.  The definition, restated in

@@ -32,6 +32,7 @@ from .eval_utils import (coco_test_annotation, evaluate_fast_bbox, FlexGt, EVAL_
                          MatcherCoCo, ScaleBreakdown, average_precision, eval_map_flexible, iou_coco, match_coco)
 from .map_eval import (MapGt, bbox_overlaps, eval_map, evaluate_map, print_map_summary, tpfp_default,  # noqa: F401
                        tpfp_imagenet)
+from .recall_eval import RecallGt, eval_recalls, print_recall_summary, recall_device, set_recall_param  # noqa: F401
 from .coco_eval import COCOeval, CocoGt, evaluate_bbox, flatten_results  # noqa: F401
 from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: F401
 from .analysis import ResultVisualizer, bbox_map_eval, image_maps  # noqa: F401

@@ -359,6 +359,9 @@ SIGNATURES = {
     'yv4_map_image_ap': (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i, _i, _i, _vp, _sz, _vp, _i64, _vp, _i64,
                                    _vp]),
     'yv4_map_image_mean': (C.c_int, [_vp, _i64, _vp, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _vp]),
+    'yv4_recall_work': (_sz, [_i64, _i64, _i, _i]),
+    'yv4_recall_match': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i, _i64, _i64, _vp, _i, _vp, _i, C.c_float, _i, _vp, _sz, _vp,
+                                   _i64, _vp, _i64, _vp]),
     'yv4_flex_tables': (C.c_int, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'yv4_flex_accumulate_work': (_sz, [_i64, _i, _i]),
     'yv4_flex_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp,
@@ -451,6 +454,9 @@ DRAW_EX_SYMBOLS = frozenset(('yv4_draw_boxes_ex', 'yv4_draw_boxes_host_ex'))
 DRAW_NO_SCORE = 1          # YV4_DRAW_NO_SCORE
 #: the per-image mAP (additive within ABI 8, bound like FP8_SYMBOLS); has_map_image()
 MAP_IMAGE_SYMBOLS = frozenset(('yv4_map_image_ap_work', 'yv4_map_image_ap', 'yv4_map_image_mean'))
+#: the proposal recall (additive within ABI 8, bound like FP8_SYMBOLS); has_recall()
+RECALL_SYMBOLS = frozenset(('yv4_recall_work', 'yv4_recall_match'))
+RECALL_MAX_NUMS, RECALL_MAX_THRS, RECALL_LDS_BOXES = 16, 256, 1280      # csrc/recall.hip: kRcMaxNums, kRcMaxThrs, kRcLdsBoxes
 #: ``YV4_JPEG_MIN_CHUNK_BYTES`` / ``YV4_JPEG_MAX_CHUNK_BYTES`` / ``YV4_JPEG_MAX_ROUNDS`` (include/yv4.h)
 JPEG_MIN_CHUNK_BYTES, JPEG_MAX_CHUNK_BYTES, JPEG_MAX_ROUNDS = 4, 1 << 20, 4096
 #: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
@@ -500,7 +506,8 @@ def lib():
                     or name in FLEX_FLAT_SYMBOLS
                     or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS
                     or name in JPEG_ORIENT_SYMBOLS or name in LETTERBOX_BATCH_SYMBOLS or name in JPEG_ENCODE_SYMBOLS
-                    or name in DRAW_SYMBOLS or name in DRAW_EX_SYMBOLS or name in MAP_IMAGE_SYMBOLS) \
+                    or name in DRAW_SYMBOLS or name in DRAW_EX_SYMBOLS or name in MAP_IMAGE_SYMBOLS
+                    or name in RECALL_SYMBOLS) \
                     and not hasattr(handle, name):
                 continue
             fn = getattr(handle, name)  # AttributeError if a symbol is missing
@@ -638,6 +645,12 @@ def has_map_image():
     """The loaded library exports the per-image mAP entry points (``yv4_map_image_ap`` / ``yv4_map_image_mean``)."""
     h = lib()
     return all(hasattr(h, n) for n in MAP_IMAGE_SYMBOLS)
+
+
+def has_recall():
+    """The loaded library exports the proposal-recall entry points (``yv4_recall_work`` / ``yv4_recall_match``)."""
+    h = lib()
+    return all(hasattr(h, n) for n in RECALL_SYMBOLS)
 
 
 class Yv4Error(RuntimeError):

@@ -372,7 +372,11 @@ def evaluate_bbox(results, coco_gt, classes=None, cat_ids=None, img_ids=None, lo
     path.  ``classes`` selects ``cat_ids = coco_gt.get_cat_ids(cat_names=classes)`` as ``CocoDataset.load_annotations``
     does; ``cat_ids`` / ``img_ids`` give the label -> category and index -> image maps directly.  ``classwise`` reads
     ``precisions[:, :, idx, 0, -1]`` with ``idx`` running over ``cat_ids`` as given, literally as the reference indexes
-    it; the table is plain text of this package's own."""
+    it; the table is plain text of this package's own.
+
+    ``metric='proposal_fast'`` is scored by ``CocoBBoxDataset.evaluate`` itself (``fast_eval_recall`` on
+    ``recall_eval.eval_recalls``), before anything reaches this function, which keeps refusing the name together with
+    ``'proposal'`` (COCOeval with ``useCats = 0``, not built)."""
     metrics = metric if isinstance(metric, list) else [metric]
     for m in metrics:
         if m not in ('bbox', 'segm', 'proposal', 'proposal_fast'):

@@ -1,6 +1,6 @@
-// Helpers shared by the evaluation kernels (eval.hip, map_eval.hip, map_flat.hip, flex_eval.hip, coco_eval.hip): the
-// descending-score key, the problem search over an offset table, the offsets-from-sorted-keys kernel, the radix sorts'
-// sizing and the three chunk primitives of the per-class walk of map_flat.hip / flex_eval.hip (the kernels keep their
+// Helpers shared by the evaluation kernels (eval.hip, map_eval.hip, map_flat.hip, flex_eval.hip, coco_eval.hip,
+// recall.hip): the descending-score key, the problem search over an offset table, the offsets-from-sorted-keys kernel,
+// the radix sorts' sizing, the box overlap of one pair and the three chunk primitives of the per-class walk of map_flat.hip / flex_eval.hip (the kernels keep their
 // definitions: what counts, which IEEE operation gives precision and recall, what the AP mode selects).
 // Translation units including this header must be built with -ffp-contract=off.
 #pragma once
@@ -52,6 +52,29 @@ __global__ __launch_bounds__(256) void offsets_kernel(const K* __restrict__ keys
 static inline int key_bits_hi32(int max_hi) { return max_hi < 65535 ? 48 : 64; }
 // the sorts' counters: reserves one tile more than rs_sort counts
 static inline size_t sort_hist_bytes(int64_t n) { return rs_hist_bytes(n + kRsTile); }
+
+// ---- the reference's numpy box overlap (bbox_overlaps.py:4-48) for one pair: map_eval.hip and recall.hip -------------
+// np.maximum / np.minimum: a NaN in either operand is the result (fmaxf would drop it)
+__device__ __forceinline__ float np_max(float a, float b) { return (a >= b || a != a) ? a : b; }
+__device__ __forceinline__ float np_min(float a, float b) { return (a <= b || a != a) ? a : b; }
+
+__device__ __forceinline__ float box_area(const float4 b) { return (b.z - b.x) * (b.w - b.y); }
+
+// out = the overlap of a (a float4: the box of the first argument) and b (of the second); iof divides by a's area.
+// fp32, the reference's operation order.  A statement macro on purpose: as a function of any signature (float4 by value
+// or by reference, eight scalars) it changed how the compiler pairs the loads and subtractions of bbox_overlaps_kernel,
+// and with them that kernel's machine code; expanded in place the kernel compiles to the bytes it had with the
+// expression written out (tools/kernel_isa_diff.py).
+#define YV4_BOX_OVERLAP(out, a, b, iof, eps)                                                \
+  do {                                                                                      \
+    const float xs_ = np_max((a).x, (b).x), ys_ = np_max((a).y, (b).y);                     \
+    const float xe_ = np_min((a).z, (b).z), ye_ = np_min((a).w, (b).w);                     \
+    const float overlap_ = np_max(xe_ - xs_, 0.f) * np_max(ye_ - ys_, 0.f);                 \
+    float uni_ = box_area(a);                                                               \
+    if (!(iof)) uni_ = (uni_ + box_area(b)) - overlap_;                                     \
+    uni_ = np_max(uni_, eps);                                                               \
+    (out) = overlap_ / uni_;                                                                \
+  } while (0)
 
 // ---- the chunked walk of a list by a workgroup of kEvalWaves waves: thread = position inside a chunk of kEvalThreads ---
 // Each primitive puts ONE barrier between its LDS writes and its reads and takes its LDS arrays from the kernel.  Before

@@ -12,15 +12,10 @@
 namespace yv4 {
 namespace {
 
-// np.maximum / np.minimum: a NaN in either operand is the result (fmaxf would drop it)
-__device__ __forceinline__ float np_max(float a, float b) { return (a >= b || a != a) ? a : b; }
-__device__ __forceinline__ float np_min(float a, float b) { return (a <= b || a != a) ? a : b; }
-
-__device__ __forceinline__ float box_area(const float4 b) { return (b.z - b.x) * (b.w - b.y); }
-
-// One thread per pair.  The reference swaps its operands when rows > cols (bbox_overlaps.py:27-30) and transposes the
-// result back; per pair that only turns area1 + area2 into area2 + area1, and an IEEE add is commutative, so no bit of
-// the result depends on the swap ('iof' keeps the FIRST argument's area through the swap, line 43).  This kernel
+// One thread per pair (the expression is eval_common.h's YV4_BOX_OVERLAP; np_max / np_min / box_area live there too).
+// The reference swaps its operands when rows > cols (bbox_overlaps.py:27-30) and transposes the result back; per pair
+// that only turns area1 + area2 into area2 + area1, and an IEEE add is commutative, so no bit of the result depends on
+// the swap ('iof' keeps the FIRST argument's area through the swap, line 43).  This kernel
 // therefore never swaps.
 __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const float* __restrict__ b1, const float* __restrict__ b2,
                                                             const int64_t* __restrict__ off1,
@@ -35,13 +30,7 @@ __global__ __launch_bounds__(256) void bbox_overlaps_kernel(const float* __restr
     const int64_t local = i - iou_off[p];
     const float4 a = reinterpret_cast<const float4*>(b1)[off1[p] + local / n2];
     const float4 b = reinterpret_cast<const float4*>(b2)[off2[p] + local % n2];
-    const float xs = np_max(a.x, b.x), ys = np_max(a.y, b.y);
-    const float xe = np_min(a.z, b.z), ye = np_min(a.w, b.w);
-    const float overlap = np_max(xe - xs, 0.f) * np_max(ye - ys, 0.f);
-    float uni = box_area(a);
-    if (!iof) uni = (uni + box_area(b)) - overlap;
-    uni = np_max(uni, eps);
-    iou[i] = overlap / uni;
+    YV4_BOX_OVERLAP(iou[i], a, b, iof, eps);
   }
 }
 

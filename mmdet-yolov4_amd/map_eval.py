@@ -49,8 +49,8 @@ tables of a dataset between calls.  Definition, where it is more than the list p
   table and ``evaluate_map`` read); ``curves=True`` downloads the full arrays.
 * A foreign ``tpfp_fn`` has no device form: with flat input it raises.
 
-``eval_recalls`` (``recall.py``, ``metric='recall'``) is not built: it scores RPN proposal lists, which no detector of
-this package produces.
+``eval_recalls`` (``recall.py``) lives in ``recall_eval.py``; ``evaluate_map(metric='recall')`` keeps refusing the name
+(``CustomBBoxDataset.eval_recalls`` is the way in).
 """
 from collections import OrderedDict
 

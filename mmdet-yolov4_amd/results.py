@@ -8,15 +8,19 @@ it: ``yv4_results_append`` (csrc/results.hip) copies a batch's rows from the pla
 ``_det2json`` order -- image, class, the row order NMS left -- so the table equals
 ``flatten_results([bbox2result(...)])`` bit for bit and nothing but the ``(N,)`` counts visits the host.
 """
+from collections import OrderedDict
+
 import numpy as np
 import torch
 
 from . import _lib
+from ._eval_common import _log
 from ._lib import check
 from .coco_eval import CocoGt, evaluate_bbox, flatten_results
 from .eval_utils import FAST_BBOX_SCALE_RANGES, FlexGt, coco_test_annotation, evaluate_fast_bbox
 from .map_eval import MapGt, evaluate_map
 from .ops import stream_ptr
+from .recall_eval import RecallGt, eval_recalls
 
 
 def _host_index(img_index, n):
@@ -133,9 +137,29 @@ class CocoBBoxDataset:
         self.cat_ids = self.coco.get_cat_ids(cat_names=self.CLASSES)
         self.img_ids = self.coco.get_img_ids()
         self._flex_gt = None
+        self._recall_gt = None
 
     def __len__(self):
         return len(self.img_ids)
+
+    def recall_gt(self):
+        """The ground truth of ``fast_eval_recall`` (``datasets/coco.py:305-322``): per image of ``img_ids`` every
+        annotation, of any category, that is neither ``ignore`` nor ``iscrowd``, in the file's order; ``x1, y1, x1 + w,
+        y1 + h`` formed in float64, then cast to float32.  One ``RecallGt``, built on first use and kept."""
+        if self._recall_gt is None:
+            per_img = {i: [] for i in self.img_ids}
+            for ann in self.coco.dataset.get('annotations', []):
+                if ann['image_id'] in per_img and not (ann.get('ignore', False) or ann.get('iscrowd', 0)):
+                    x1, y1, w, h = ann['bbox']
+                    per_img[ann['image_id']].append([x1, y1, x1 + w, y1 + h])
+            self._recall_gt = RecallGt([np.array(per_img[i], dtype=np.float32).reshape(-1, 4) for i in self.img_ids])
+        return self._recall_gt
+
+    def fast_eval_recall(self, results, proposal_nums, iou_thrs, logger=None):
+        """``datasets/coco.py:305-327``: ``eval_recalls`` of the results, labels dropped, against ``recall_gt()``;
+        returns the average recall per proposal number, ``recalls.mean(axis=1)``.  ``results``: the per-image lists or
+        the flat tuple."""
+        return eval_recalls(self.recall_gt(), results, proposal_nums, iou_thrs, logger=logger).mean(axis=1)
 
     def flex_gt(self):
         """The ground truth of ``metric='fast-bbox'``: per image of ``img_ids`` what ``CocoDataset.get_ann_info_test``
@@ -154,8 +178,11 @@ class CocoBBoxDataset:
 
     def evaluate(self, results, metric='bbox', logger=None, **kwargs):
         """``CocoDataset.evaluate`` (``datasets/coco.py:451-643``): ``metric='bbox'`` through ``evaluate_bbox``,
-        ``metric='fast-bbox'`` (alone, as in the reference) through ``evaluate_fast_bbox`` against ``flex_gt()``;
-        ``results``: the per-image lists or the flat tuple, ``img_index`` being positions in ``img_ids``."""
+        ``metric='fast-bbox'`` (alone, as in the reference) through ``evaluate_fast_bbox`` against ``flex_gt()``,
+        ``metric='proposal_fast'`` through ``fast_eval_recall`` (``AR@{num}`` keys; ``proposal_nums`` and ``iou_thrs``
+        are the keywords ``evaluate_bbox`` takes, with its defaults).  In a list the metrics keep their order and
+        merge into one ``OrderedDict``.  ``results``: the per-image lists or the flat tuple, ``img_index`` being
+        positions in ``img_ids``."""
         metrics = list(metric) if isinstance(metric, (list, tuple)) else [metric]
         if 'fast-bbox' in metrics:
             assert len(metrics) == 1, 'fast-bbox evaluation can only be used alone!'
@@ -163,8 +190,31 @@ class CocoBBoxDataset:
                 raise TypeError(f"metric='fast-bbox' takes no further arguments (its thresholds, scale ranges and report "
                                 f'are fixed), got {sorted(kwargs)}')
             return evaluate_fast_bbox(results, self.flex_gt(), self.CLASSES, logger=logger)
-        return evaluate_bbox(results, self.coco, cat_ids=self.cat_ids, img_ids=self.img_ids, logger=logger, metric=metric,
-                             **kwargs)
+        if 'proposal_fast' not in metrics:
+            return evaluate_bbox(results, self.coco, cat_ids=self.cat_ids, img_ids=self.img_ids, logger=logger,
+                                 metric=metric, **kwargs)
+        for m in metrics:             # (as the reference: before anything is scored)
+            if m not in ('bbox', 'segm', 'proposal', 'proposal_fast'):
+                raise KeyError(f'metric {m} is not supported')
+        proposal_nums = kwargs.get('proposal_nums', (100, 300, 1000))
+        iou_thrs = kwargs.get('iou_thrs', None)
+        if iou_thrs is None:
+            iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+        eval_results = OrderedDict()
+        for m in metrics:
+            if m != 'proposal_fast':
+                eval_results.update(evaluate_bbox(results, self.coco, cat_ids=self.cat_ids, img_ids=self.img_ids,
+                                                  logger=logger, metric=m, **kwargs))
+                continue
+            msg = f'Evaluating {m}...'
+            _log('\n' + msg if logger is None else msg, logger)
+            ar = self.fast_eval_recall(results, proposal_nums, iou_thrs, logger='silent')
+            log_msg = []
+            for i, num in enumerate(proposal_nums):
+                eval_results[f'AR@{num}'] = ar[i]
+                log_msg.append(f'\nAR@{num}\t{ar[i]:.4f}')
+            _log(''.join(log_msg), logger)
+        return eval_results
 
 
 class CustomBBoxDataset:
@@ -181,6 +231,7 @@ class CustomBBoxDataset:
         self.CLASSES = tuple(classes)
         self.annotations = list(annotations)
         self.map_gt = MapGt(self.annotations, len(self.CLASSES))
+        self._recall_gt = None
 
     def __len__(self):
         return len(self.annotations)
@@ -194,3 +245,22 @@ class CustomBBoxDataset:
         ``evaluate_map`` raises."""
         return evaluate_map(results, self.map_gt, classes=list(self.CLASSES), iou_thr=iou_thr, scale_ranges=scale_ranges,
                             logger=logger, metric=metric)
+
+    def eval_recalls(self, results, proposal_nums=(100, 300, 1000), iou_thr=0.5, logger=None):
+        """The ``metric='recall'`` branch of ``CustomDataset.evaluate`` (``datasets/custom.py:326-336``) as a method of
+        its own (``evaluate(metric='recall')`` keeps raising): the results, labels dropped, against the annotations'
+        ``bboxes``.  ``recall@{num}@{iou}`` per proposal number and threshold, and ``AR@{num}`` when there is more than
+        one threshold.  ``results``: the per-image lists or the flat tuple."""
+        if self._recall_gt is None:
+            self._recall_gt = RecallGt([a['bboxes'] for a in self.annotations])
+        iou_thrs = [iou_thr] if isinstance(iou_thr, float) else iou_thr
+        recalls = eval_recalls(self._recall_gt, results, proposal_nums, iou_thr, logger=logger)
+        eval_results = OrderedDict()
+        for i, num in enumerate(proposal_nums):
+            for j, iou in enumerate(iou_thrs):
+                eval_results[f'recall@{num}@{iou}'] = recalls[i, j]
+        if recalls.shape[1] > 1:
+            ar = recalls.mean(axis=1)
+            for i, num in enumerate(proposal_nums):
+                eval_results[f'AR@{num}'] = ar[i]
+        return eval_results

@@ -26,7 +26,8 @@ from .image_io import LoadImageFromFile, encode_into, imdecode, imencode, imread
 from .augment import FusedTrainPipeline
 from .augment_v3 import FusedV3TrainPipeline, build_train_pipeline
 from . import tta  # noqa: F401  (YOLOv3 test-time augmentation)
-from .apis import inference_detector, single_gpu_test, multi_gpu_test
+from .apis import (get_root_logger, inference_detector, init_detector, multi_gpu_test, set_random_seed, single_gpu_test,
+                   train_detector)
 from .draw import color_val, draw_boxes, draw_boxes_into, imshow_gt_det_bboxes
 from .eval_utils import (coco_test_annotation, evaluate_fast_bbox, FlexGt, EVAL_BREAKDOWN, EVAL_IOU_CALCULATOR, EVAL_MATCHER, FlexibleStatisticsEval, IOU2DCoCo,
                          MatcherCoCo, ScaleBreakdown, average_precision, eval_map_flexible, iou_coco, match_coco)
@@ -38,5 +39,9 @@ from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: 
 from .analysis import ResultVisualizer, bbox_map_eval, image_maps  # noqa: F401
 from .datasets import (CocoDataset, DistributedGroupSampler, GroupSampler, TestLoader, TrainLoader,  # noqa: F401
                        build_dataset, build_test_loader, build_train_loader)
+
+from .hooks import (EpochBasedRunner, IterTimerHook, StepLrUpdaterHook, TextLoggerHook, build_runner)  # noqa: F401
+
+__version__ = '1.0.0'          # written into every checkpoint's meta by tools/train.py
 
 __all__ = [n for n in dir() if not n.startswith('_')]

@@ -164,3 +164,218 @@ def multi_gpu_test(model, data_loader, size=None, gpu_collect=True, flat=False):
         return D.collect_flat(dets, labels, img_index, size, device=device)
     results = single_gpu_test(model, data_loader)
     return D.collect_results(results, size, device=device)
+
+
+# ---- the reference's ``mmdet/apis`` entry points for a run from a config file ----------------------------------------
+def set_random_seed(seed, deterministic=False):
+    """``apis/train.py:18-34``: seeds ``random``, ``numpy`` and ``torch`` (CPU and every device).  ``deterministic``
+    additionally turns on this package's deterministic mode (``set_deterministic(True)``: the kernels whose reductions
+    race take their ordered forms), which is what makes two runs of one seed bit-equal here; the cudnn switches the
+    reference sets are set too and touch no kernel of this package."""
+    import random
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed)
+    if deterministic:
+        from .ops import set_deterministic
+        set_deterministic(True)
+        torch.backends.cudnn.deterministic = True
+        torch.backends.cudnn.benchmark = False
+
+
+def get_root_logger(log_file=None, log_level='INFO'):
+    """``mmdet/utils/logger.py`` over mmcv's ``get_logger`` (third-party, restated): THE logger ``'mmdet'``.  The first
+    call gives it a stream handler on every rank and, on rank 0 when ``log_file`` is given, a file handler; ranks other
+    than 0 log at ``ERROR``.  Later calls return it as it is."""
+    import logging
+    from .dist import env_world, rank_world
+    logger = logging.getLogger('mmdet')
+    if getattr(logger, '_yv4_initialised', False):
+        return logger
+    rank, world = rank_world()
+    if world == 1:
+        rank = env_world()[0]
+    fmt = logging.Formatter('%(asctime)s - %(name)s - %(levelname)s - %(message)s')
+    level = getattr(logging, log_level) if isinstance(log_level, str) else log_level
+    handlers = [logging.StreamHandler()]
+    if rank == 0 and log_file is not None:
+        handlers.append(logging.FileHandler(log_file, 'w'))
+    for h in handlers:
+        h.setFormatter(fmt)
+        h.setLevel(level)
+        logger.addHandler(h)
+    logger.setLevel(level if rank == 0 else logging.ERROR)
+    logger.propagate = False
+    logger._yv4_initialised = True
+    return logger
+
+
+def _load_config(config, cfg_options=None):
+    from .registry import Config
+    if isinstance(config, (str, os.PathLike)):
+        config = Config.fromfile(os.fspath(config))
+    elif not isinstance(config, Config):
+        raise TypeError(f'config must be a filename or Config object, but got {type(config)}')
+    if cfg_options is not None:
+        config.merge_from_dict(cfg_options)
+    return config
+
+
+_DTYPES = {None: None, 'fp32': None, 'f32': None, torch.float32: None, 'fp16': torch.float16, 'f16': torch.float16,
+           torch.float16: torch.float16, 'bf16': torch.bfloat16, torch.bfloat16: torch.bfloat16}
+
+
+def load_weights(model, filename, map_location='cpu', strict=False):
+    """mmcv ``load_checkpoint`` as ``Runner.load_checkpoint`` does it: a ``module.`` prefix is stripped, the load is
+    not strict, the plans learn of the new weights.  Returns the checkpoint."""
+    from .hooks import Runner
+    return Runner(model, None).load_checkpoint(filename, map_location=map_location, strict=strict)
+
+
+def init_detector(config, checkpoint=None, device='cuda:0', cfg_options=None, dtype=None):
+    """``apis/inference.py:16-53``: the detector of ``config`` (a file name or a ``Config``) with the weights of
+    ``checkpoint``, on ``device``, in eval mode, with ``model.cfg`` and ``model.CLASSES`` (the checkpoint's, else the 80
+    COCO names with a warning) -- ready for ``inference_detector(model, 'file.jpg')``.  ``dtype`` (this package's):
+    ``torch.float16`` / ``torch.bfloat16`` run the plans with 16-bit activations (``wrap_fp16_model``); a config with an
+    ``fp16`` block means ``torch.float16``."""
+    import warnings
+    from .bricks import wrap_fp16_model
+    from .datasets import COCO_CLASSES
+    from .registry import build_detector
+    config = _load_config(config, cfg_options)
+    if dtype not in _DTYPES:
+        raise ValueError(f'dtype {dtype!r} is not fp32, fp16 or bf16')
+    config.model.pretrained = None
+    config.model.train_cfg = None
+    model = build_detector(config.model, test_cfg=config.get('test_cfg'))
+    if checkpoint is not None:
+        ckpt = load_weights(model, checkpoint, map_location='cpu')
+        if 'CLASSES' in ckpt.get('meta', {}):
+            model.CLASSES = ckpt['meta']['CLASSES']
+        else:
+            warnings.warn("Class names are not saved in the checkpoint's meta data, use COCO classes by default.")
+            model.CLASSES = COCO_CLASSES
+    model.cfg = config
+    model.to(device)
+    model.eval()
+    compute = _DTYPES[dtype]
+    if compute is None and config.get('fp16', None) is not None:
+        compute = torch.float16
+    if compute is not None:
+        wrap_fp16_model(model, compute)
+    return model
+
+
+def samples_per_gpu(cfg, logger=None):
+    """``cfg.data.samples_per_gpu``, or the deprecated ``imgs_per_gpu`` with the reference's warnings
+    (``apis/train.py:48-60``); the config is left holding the value under the new name."""
+    if 'imgs_per_gpu' in cfg.data:
+        logger = logger or get_root_logger(log_level=cfg.get('log_level', 'INFO'))
+        logger.warning('"imgs_per_gpu" is deprecated in MMDet V2.0. Please use "samples_per_gpu" instead')
+        if 'samples_per_gpu' in cfg.data:
+            logger.warning(f'Got "imgs_per_gpu"={cfg.data.imgs_per_gpu} and "samples_per_gpu"={cfg.data.samples_per_gpu}, '
+                           f'"imgs_per_gpu"={cfg.data.imgs_per_gpu} is used in this experiments')
+        else:
+            logger.warning(f'Automatically set "samples_per_gpu"="imgs_per_gpu"={cfg.data.imgs_per_gpu} in this '
+                           'experiments')
+        cfg.data.samples_per_gpu = cfg.data.imgs_per_gpu
+    return cfg.data.samples_per_gpu
+
+
+def broadcast_model_state(model, src=0):
+    """Every rank takes rank ``src``'s parameters and buffers: what constructing the reference's
+    ``MMDistributedDataParallel`` does (``apis/train.py:74-82``; torch's DDP broadcasts the module's state from rank 0),
+    so that ranks which initialised their weights from different random streams train ONE model.  Two broadcasts, the
+    float arena and the integer arena of the model's ``FlatState``; a no-op without a process group.  Returns the
+    number of collectives."""
+    import torch.distributed as tdist
+    if not (tdist.is_available() and tdist.is_initialized()):
+        return 0
+    from .flat_state import FlatState
+    flat = FlatState.of(model.module if hasattr(model, 'module') and isinstance(model.module, torch.nn.Module) else model)
+    sent = 0
+    for arena in (flat.values, flat.ints):
+        if arena.numel():
+            tdist.broadcast(arena, src)
+            sent += 1
+    flat.bump_versions()
+    return sent
+
+
+def train_detector(model, dataset, cfg, distributed=False, validate=False, timestamp=None, meta=None, entropy=None,
+                   prefetch=0):
+    """``apis/train.py:37-170`` on this package's parts.  ``dataset``: ``cfg.data.train`` (a dataset block with its
+    pipeline; ``build_train_loader`` makes the loader from it with ``cfg.data.samples_per_gpu``, ``cfg.seed`` and the
+    process group's rank and world) or a ready ``TrainLoader``.  Optimizer: ``build_optimizer(model, cfg.optimizer)``;
+    runner: ``cfg.runner`` (``EpochBasedRunner``; without it ``total_epochs``, with the reference's warning); hooks:
+    ``register_training_hooks`` with the optimizer hook of ``build_optimizer_hook``, ``DistSamplerSeedHook`` (always: the
+    loader's order is a function of the epoch, which a resumed run has to tell it), with ``validate`` the evaluation hook
+    over ``build_test_loader(cfg.data.val)``, then ``custom_hooks`` at their priorities.  ``cfg.resume_from`` /
+    ``cfg.load_from``, with ``distributed`` rank 0's parameters and buffers to every rank
+    (``broadcast_model_state``: the reference's DDP wrapper does it), then the run.  ``entropy`` / ``prefetch``: the loaders' (``TrainLoader``)."""
+    import warnings
+    from . import dist as D
+    from .datasets import TrainLoader, build_test_loader, build_train_loader
+    from .hooks import (DistEvalHook, DistSamplerSeedHook, EvalHook, HOOKS, build_optimizer_hook, build_runner)
+    from .optim import build_optimizer
+    from .registry import build_from_cfg
+    logger = get_root_logger(log_level=cfg.get('log_level', 'INFO'))
+    workflow = cfg.get('workflow', [('train', 1)])
+    if [tuple(w) for w in workflow] != [('train', 1)]:
+        raise NotImplementedError(f"workflow={workflow!r}: only [('train', 1)] is built (validation runs through "
+                                  'EvalHook)')
+    if 'runner' not in cfg:
+        cfg.runner = {'type': 'EpochBasedRunner', 'max_epochs': cfg.total_epochs}
+        warnings.warn('config is now expected to have a `runner` section, please set `runner` in your config.',
+                      UserWarning)
+    elif 'total_epochs' in cfg:
+        assert cfg.total_epochs == cfg.runner.max_epochs
+    if cfg.runner['type'] != 'EpochBasedRunner':
+        raise NotImplementedError(f"runner type {cfg.runner['type']!r} is not built: EpochBasedRunner is")
+
+    rank, world = D.rank_world() if distributed else (0, 1)
+    model = model.cuda() if next(model.parameters()).device.type != 'cuda' else model
+    device = next(model.parameters()).device
+    if isinstance(dataset, TrainLoader):
+        loader = dataset
+    else:
+        if isinstance(dataset, (list, tuple)):
+            if len(dataset) != 1:
+                raise NotImplementedError('train_detector: one training dataset (the workflow has one phase)')
+            dataset = dataset[0]
+        loader = build_train_loader(dataset, samples_per_gpu(cfg, logger), seed=cfg.get('seed') or 0, rank=rank, world=world,
+                                    device=device, entropy=entropy, prefetch=prefetch)
+
+    optimizer = build_optimizer(model, cfg.optimizer)
+    runner = build_runner(cfg.runner, default_args=dict(model=model, optimizer=optimizer, work_dir=cfg.get('work_dir'),
+                                                        logger=logger, meta=meta))
+    runner.timestamp = timestamp           # (so that the .log and .log.json names agree)
+    optimizer_hook = build_optimizer_hook(cfg, distributed=distributed)
+    runner.register_training_hooks(cfg.get('lr_config'), optimizer_hook, cfg.get('checkpoint_config'),
+                                   cfg.get('log_config'), cfg.get('momentum_config', None))
+    runner.register_hook(DistSamplerSeedHook())
+    if validate:
+        val_loader = build_test_loader(cfg.data.val, rank=rank, world=world, device=device, entropy=entropy,
+                                       prefetch=prefetch)
+        eval_cfg = dict(cfg.get('evaluation', {}) or {})
+        eval_cfg['by_epoch'] = True
+        runner.register_hook((DistEvalHook if distributed else EvalHook)(val_loader, **eval_cfg))
+    if cfg.get('custom_hooks', None):
+        custom_hooks = cfg.custom_hooks
+        assert isinstance(custom_hooks, list), f'custom_hooks expect list type, but got {type(custom_hooks)}'
+        for hook_cfg in custom_hooks:
+            assert isinstance(hook_cfg, dict), f'Each item in custom_hooks expects dict type, but got {type(hook_cfg)}'
+            hook_cfg = dict(hook_cfg)
+            priority = hook_cfg.pop('priority', 'NORMAL')
+            runner.register_hook(build_from_cfg(hook_cfg, HOOKS), priority=priority)
+    if cfg.get('resume_from'):
+        runner.resume(cfg.resume_from)
+    elif cfg.get('load_from'):
+        runner.load_checkpoint(cfg.load_from)
+    if distributed:
+        # the ranks' own init_weights() drew from their own random streams: one model from here on
+        broadcast_model_state(model, 0)
+    runner.run(loader, workflow)
+    return runner

@@ -22,6 +22,7 @@ The schedule arithmetic is exposed as pure functions (``warmup_factor``, ``ema_m
 """
 import math
 import os
+import time
 import warnings
 from collections import OrderedDict
 
@@ -31,7 +32,7 @@ from . import _lib
 from ._lib import check
 from .flat_state import FlatState
 from .ops import stream_ptr
-from .registry import HOOKS
+from .registry import HOOKS, RUNNERS
 
 # ---- pure schedule arithmetic ------------------------------------------------------------------
 
@@ -449,13 +450,35 @@ class DetailedLinearWarmUpHook(Hook):
                 logger.warning('optimizer config does not support preheat because'
                                ' it is not using seperate param-group for each parameter')
             return
+        # a checkpoint written by this package carries the bases (``sync_meta``): a run resumed inside the warm-up
+        # window then warms up from them, not from the warmed values its optimizer state holds (the reference reads
+        # the groups as they were saved, warmup_hooks.py:22-36, and so does this hook when the meta has no bases)
+        saved = (getattr(runner, 'meta', None) or {}).get(self.META_KEY)
+        n = len(runner.optimizer.param_groups)
+        if not (isinstance(saved, dict) and len(saved.get('lr', ())) == n and len(saved.get('momentum', ())) == n):
+            saved = None
         for group_ind, (name, param) in enumerate(model.named_parameters()):
             group = runner.optimizer.param_groups[group_ind]
-            self.base_momentum[group_ind] = group['momentum']
+            lr, momentum = (saved['lr'][group_ind], saved['momentum'][group_ind]) if saved else \
+                (group['lr'], group['momentum'])
+            self.base_momentum[group_ind] = momentum
             if name.endswith('.bias'):
-                self.bias_base_lr[group_ind] = group['lr']
+                self.bias_base_lr[group_ind] = lr
             elif name.endswith('.weight'):
-                self.weight_base_lr[group_ind] = group['lr']
+                self.weight_base_lr[group_ind] = lr
+        self._bases = dict(lr=[{**self.bias_base_lr, **self.weight_base_lr}.get(i, g['lr'])
+                               for i, g in enumerate(runner.optimizer.param_groups)],
+                           momentum=[self.base_momentum[i] for i in range(n)])
+
+    META_KEY = 'detailed_warmup_base'
+    _bases = None
+
+    def sync_meta(self, runner):
+        """The base lr and momentum of every group into ``runner.meta`` (``Runner.save_checkpoint`` calls this): what a
+        resumed run needs beyond the optimizer's state."""
+        meta = getattr(runner, 'meta', None)
+        if isinstance(meta, dict) and self._bases is not None:
+            meta[self.META_KEY] = self._bases
 
     def before_train_iter(self, runner):
         if runner.iter <= self.warmup_iters:
@@ -472,39 +495,140 @@ class DetailedLinearWarmUpHook(Hook):
 
 
 # ---- lr_config = dict(policy='CosineAnnealing', min_lr_ratio=0.2) ----------------------------------------
-@HOOKS.register_module()
-class CosineAnnealingLrUpdaterHook(Hook):
-    """mmcv's epoch-based cosine annealing (third-party; restated): at the start of every epoch
-    ``lr = min + 0.5 (base - min)(1 + cos(pi * epoch / max_epochs))`` per group from its
-    ``initial_lr``.  No warm-up of its own: the recipe warms up through
-    ``DetailedLinearWarmUpHook`` (``configs/yolov4/yolov4l_coco_mosaic.py:124-139``)."""
+def warmup_lr(regular_lr, cur_iter, warmup, warmup_iters, warmup_ratio):
+    """mmcv ``LrUpdaterHook.get_warmup_lr`` for one group: the lr of iteration ``cur_iter < warmup_iters``."""
+    if warmup == 'constant':
+        return regular_lr * warmup_ratio
+    if warmup == 'linear':
+        k = (1 - cur_iter / warmup_iters) * (1 - warmup_ratio)
+        return regular_lr * (1 - k)
+    k = warmup_ratio ** (1 - cur_iter / warmup_iters)          # 'exp'
+    return regular_lr * k
 
-    def __init__(self, min_lr=None, min_lr_ratio=None, by_epoch=True, **kwargs):
-        assert (min_lr is None) ^ (min_lr_ratio is None)
-        self.min_lr, self.min_lr_ratio, self.by_epoch = min_lr, min_lr_ratio, by_epoch
+
+class LrUpdaterHook(Hook):
+    """mmcv's ``LrUpdaterHook`` (``mmcv/runner/hooks/lr_updater.py``, mmcv 1.3.2 .. 1.4.0; third-party, restated, parity
+    unpinned): every group's ``initial_lr`` is its base; a subclass gives ``get_lr(runner, base_lr)``, the regular lr at
+    ``runner.epoch`` (``by_epoch``) or ``runner.iter``; the optional warm-up replaces it during the first
+    ``warmup_iters`` iterations (epochs with ``warmup_by_epoch``) by ``warmup_lr`` of it, and the regular lr comes back
+    at iteration ``warmup_iters``.  With ``warmup=None`` the lr is written at the start of every epoch (``by_epoch``)
+    or of every iteration, and nowhere else."""
+
+    def __init__(self, by_epoch=True, warmup=None, warmup_iters=0, warmup_ratio=0.1, warmup_by_epoch=False):
+        if warmup is not None:
+            if warmup not in ('constant', 'linear', 'exp'):
+                raise ValueError(f'"{warmup}" is not a supported type for warming up, valid types are "constant", '
+                                 '"linear" and "exp"')
+            assert warmup_iters > 0, '"warmup_iters" must be a positive integer'
+            assert 0 < warmup_ratio <= 1.0, '"warmup_ratio" must be in range (0,1]'
+        self.by_epoch, self.warmup, self.warmup_ratio = by_epoch, warmup, warmup_ratio
+        self.warmup_by_epoch = warmup_by_epoch
+        if warmup_by_epoch:
+            self.warmup_epochs, self.warmup_iters = warmup_iters, None
+        else:
+            self.warmup_epochs, self.warmup_iters = None, warmup_iters
         self.base_lr = []
+        self.regular_lr = []
 
-    @staticmethod
-    def annealing_cos(start, end, factor):
-        return end + 0.5 * (start - end) * (math.cos(math.pi * factor) + 1)
+    def get_lr(self, runner, base_lr):
+        raise NotImplementedError
+
+    def _set_lr(self, runner, lrs):
+        for g, lr in zip(runner.optimizer.param_groups, lrs):
+            g['lr'] = lr
+
+    def get_regular_lr(self, runner):
+        return [self.get_lr(runner, base) for base in self.base_lr]
+
+    def get_warmup_lr(self, cur_iter):
+        return [warmup_lr(lr, cur_iter, self.warmup, self.warmup_iters, self.warmup_ratio) for lr in self.regular_lr]
 
     def before_run(self, runner):
         for g in runner.optimizer.param_groups:
             g.setdefault('initial_lr', g['lr'])
         self.base_lr = [g['initial_lr'] for g in runner.optimizer.param_groups]
 
-    def _set(self, runner, progress, max_progress):
-        for g, base in zip(runner.optimizer.param_groups, self.base_lr):
-            target = base * self.min_lr_ratio if self.min_lr_ratio is not None else self.min_lr
-            g['lr'] = self.annealing_cos(base, target, progress / max_progress)
-
     def before_train_epoch(self, runner):
-        if self.by_epoch:
-            self._set(runner, runner.epoch, runner.max_epochs)
+        if self.warmup_iters is None:
+            self.warmup_iters = self.warmup_epochs * len(runner.data_loader)
+        if not self.by_epoch:
+            return
+        self.regular_lr = self.get_regular_lr(runner)
+        self._set_lr(runner, self.regular_lr)
 
     def before_train_iter(self, runner):
+        cur_iter = runner.iter
         if not self.by_epoch:
-            self._set(runner, runner.iter, runner.max_iters)
+            self.regular_lr = self.get_regular_lr(runner)
+            if self.warmup is None or cur_iter >= self.warmup_iters:
+                self._set_lr(runner, self.regular_lr)
+            else:
+                self._set_lr(runner, self.get_warmup_lr(cur_iter))
+        elif self.warmup is None or cur_iter > self.warmup_iters:
+            return
+        elif cur_iter == self.warmup_iters:
+            self._set_lr(runner, self.regular_lr)
+        else:
+            self._set_lr(runner, self.get_warmup_lr(cur_iter))
+
+
+@HOOKS.register_module()
+class StepLrUpdaterHook(LrUpdaterHook):
+    """mmcv's ``StepLrUpdaterHook`` (``lr_config = dict(policy='step', step=[218, 246])`` of the YOLOv3 recipe,
+    ``configs/yolo/yolov3_d53_mstrain-608_273e_coco.py``): ``base * gamma ** k``, ``k`` the number of ``step`` entries
+    already reached (``progress // step`` for an int), not below ``min_lr``."""
+
+    def __init__(self, step, gamma=0.1, min_lr=None, **kwargs):
+        if isinstance(step, (list, tuple)):
+            assert all(isinstance(s, int) and s > 0 for s in step), '"step" must be a list of positive integers'
+            step = list(step)
+        elif isinstance(step, int):
+            assert step > 0
+        else:
+            raise TypeError('"step" must be a list or integer')
+        self.step, self.gamma, self.min_lr = step, gamma, min_lr
+        super().__init__(**kwargs)
+
+    def get_lr(self, runner, base_lr):
+        progress = runner.epoch if self.by_epoch else runner.iter
+        if isinstance(self.step, int):
+            exp = progress // self.step
+        else:
+            exp = len(self.step)
+            for i, s in enumerate(self.step):
+                if progress < s:
+                    exp = i
+                    break
+        lr = base_lr * self.gamma ** exp
+        if self.min_lr is not None:
+            lr = max(lr, self.min_lr)
+        return lr
+
+
+@HOOKS.register_module()
+class CosineAnnealingLrUpdaterHook(LrUpdaterHook):
+    """mmcv's cosine annealing (third-party; restated): ``lr = min + 0.5 (base - min)(1 + cos(pi * epoch /
+    max_epochs))`` per group from its ``initial_lr``, at the start of every epoch (of every iteration from ``iter /
+    max_iters`` with ``by_epoch=False``).  The YOLOv4 recipe gives it no warm-up of its own and warms up through
+    ``DetailedLinearWarmUpHook`` (``configs/yolov4/yolov4l_coco_mosaic.py:124-139``); the shared ``warmup`` options of
+    ``LrUpdaterHook`` are accepted."""
+
+    def __init__(self, min_lr=None, min_lr_ratio=None, **kwargs):
+        assert (min_lr is None) ^ (min_lr_ratio is None)
+        self.min_lr, self.min_lr_ratio = min_lr, min_lr_ratio
+        super().__init__(**kwargs)
+
+    @staticmethod
+    def annealing_cos(start, end, factor):
+        return end + 0.5 * (start - end) * (math.cos(math.pi * factor) + 1)
+
+    def get_lr(self, runner, base_lr):
+        if self.by_epoch:
+            progress, max_progress = runner.epoch, runner.max_epochs
+        else:
+            progress, max_progress = runner.iter, runner.max_iters
+        target = base_lr * self.min_lr_ratio if self.min_lr_ratio is not None else self.min_lr
+        return self.annealing_cos(base_lr, target, progress / max_progress)
 
 
 # ---- validation in training: mmdet/core/evaluation/eval_hooks.py, and the slice of mmcv's CheckpointHook it needs ----
@@ -772,12 +896,42 @@ class BatchSource:
 class LogBuffer:
     def __init__(self):
         self.history = []
+        self.by_name = OrderedDict()      # name -> [(entry, count)]: mmcv's val_history / n_history, entries by reference
         self.output = OrderedDict()      # mmcv LogBuffer.output: what the evaluation hooks write their metrics into
         self.ready = False
 
+    #: ``False``: ``update`` drops what it is given (``EpochBasedRunner`` sets it when no logger hook would ever read or
+    #: clear the history, which would otherwise grow, pinned buffers and events included, for the whole run)
+    keep = True
+
     def update(self, values, count=1):
-        # a DeferredLogVars stays as it is (copying it would wait for the device)
-        self.history.append((values if getattr(values, 'pending', False) else dict(values), count))
+        if not self.keep:
+            return
+        # a DeferredLogVars stays as it is (copying it would wait for the device); its names are known without its values
+        entry = values if getattr(values, 'pending', False) else dict(values)
+        self.history.append((entry, count))
+        for k in dict.keys(entry):
+            self.by_name.setdefault(k, []).append((entry, count))
+
+    def average(self, n=0):
+        """mmcv ``LogBuffer.average``: per variable the mean of its last ``n`` entries (all of them for ``n=0``)
+        weighted by their ``count``, into ``output``, in the order the variables first appeared.  This is where pending
+        entries are read: the caller -- a logger hook at its interval -- waits for their copies, nobody else does.
+        Per-variable lists (mmcv's ``val_history``) make a call cost ``n`` reads a variable, wherever in the epoch."""
+        assert n >= 0
+        for k, entries in self.by_name.items():
+            last = entries[-n:]
+            self.output[k] = sum(e[k] * c for e, c in last) / sum(c for _, c in last)
+        self.ready = True
+
+    def clear(self):
+        self.history.clear()
+        self.by_name.clear()
+        self.clear_output()
+
+    def clear_output(self):
+        self.output.clear()
+        self.ready = False
 
 
 class Runner:
@@ -813,6 +967,79 @@ class Runner:
         cfg = dict(cfg)
         priority = cfg.pop('priority', 'NORMAL')
         self.register_hook(build_from_cfg(cfg, HOOKS), priority)
+
+    # ---- mmcv ``BaseRunner.register_training_hooks`` and its helpers (``base_runner.py``, mmcv 1.3.2 .. 1.4.0) ---------
+    def register_lr_hook(self, lr_config):
+        """``policy='step'`` names ``StepLrUpdaterHook``: the policy, title-cased when it is all lower case, plus
+        ``LrUpdaterHook``.  A hook object is registered as it is."""
+        if lr_config is None:
+            return
+        if isinstance(lr_config, dict):
+            assert 'policy' in lr_config
+            cfg = dict(lr_config)
+            policy = cfg.pop('policy')
+            if policy == policy.lower():
+                policy = policy.title()
+            name = policy + 'LrUpdaterHook'
+            if HOOKS.get(name) is None:
+                raise NotImplementedError(f"lr_config policy {lr_config['policy']!r} ({name}) is not built: "
+                                          "'step' and 'CosineAnnealing' are")
+            cfg['type'] = name
+            hook = HOOKS.build(cfg)
+        else:
+            hook = lr_config
+        self.register_hook(hook, 'VERY_HIGH')
+
+    def register_momentum_hook(self, momentum_config):
+        if momentum_config is not None:
+            raise NotImplementedError(f'momentum_config={momentum_config!r}: no momentum updater hook is built (the '
+                                      'YOLOv4 recipe warms the momentum up through DetailedLinearWarmUpHook)')
+
+    def register_optimizer_hook(self, optimizer_config):
+        if optimizer_config is None:
+            return
+        if isinstance(optimizer_config, dict):
+            cfg = dict(optimizer_config)
+            cfg.setdefault('type', 'OptimizerHook')
+            hook = HOOKS.build(cfg)
+        else:
+            hook = optimizer_config
+        self.register_hook(hook, 'ABOVE_NORMAL')
+
+    def register_checkpoint_hook(self, checkpoint_config):
+        if checkpoint_config is None:
+            return
+        if isinstance(checkpoint_config, dict):
+            cfg = dict(checkpoint_config)
+            cfg.setdefault('type', 'CheckpointHook')
+            hook = HOOKS.build(cfg)
+        else:
+            hook = checkpoint_config
+        self.register_hook(hook, 'NORMAL')
+
+    def register_logger_hooks(self, log_config):
+        if log_config is None:
+            return
+        log_interval = log_config['interval']
+        for info in log_config['hooks']:
+            if HOOKS.get(info['type']) is None or not issubclass(HOOKS.get(info['type']), LoggerHook):
+                raise NotImplementedError(f"log_config: logger hook {info['type']!r} is not built: TextLoggerHook is")
+            self.register_hook(HOOKS.build(dict(info), default_args=dict(interval=log_interval)), 'VERY_LOW')
+
+    def register_training_hooks(self, lr_config, optimizer_config=None, checkpoint_config=None, log_config=None,
+                                momentum_config=None):
+        """The default training hooks in mmcv's order and at mmcv's priorities: lr updater ``VERY_HIGH``, (momentum
+        updater ``HIGH``: refused), optimizer ``ABOVE_NORMAL``, checkpoint ``NORMAL``, ``IterTimerHook`` ``LOW``, logger
+        hooks ``VERY_LOW``.  Hooks of one priority run in the order they were registered."""
+        self.register_lr_hook(lr_config)
+        self.register_momentum_hook(momentum_config)
+        self.register_optimizer_hook(optimizer_config)
+        self.register_checkpoint_hook(checkpoint_config)
+        self.register_hook(IterTimerHook(), 'LOW')
+        self.register_logger_hooks(log_config)
+
+    def current_lr(self):
+        return [g['lr'] for g in self.optimizer.param_groups]
 
     def call_hook(self, stage):
         for h in self._hooks:
@@ -900,3 +1127,243 @@ class Runner:
             self.call_hook('after_train_epoch')
             self.epoch += 1
         self.call_hook('after_run')
+
+
+# ---- the timer and the text logger (mmcv/runner/hooks/iter_timer.py, logger/base.py, logger/text.py) ---------------
+@HOOKS.register_module()
+class IterTimerHook(Hook):
+    """mmcv's ``IterTimerHook``: ``data_time`` (from the end of the last iteration to the start of this one: the
+    loader) and ``time`` (the same, to the end of this iteration's hooks) into the log buffer, from ``time.time()``.
+    Nothing waits for the device here, so ``time`` is host time: how long the host took to QUEUE the iteration.  Over a
+    logging interval its mean is the device's time per iteration as soon as the host runs ahead of the device and is
+    held back by it (the loader's decode status read, a full launch queue); a single value says little."""
+
+    def before_epoch(self, runner):
+        self.t = time.time()
+
+    def before_iter(self, runner):
+        runner.log_buffer.update({'data_time': time.time() - self.t})
+
+    def after_iter(self, runner):
+        runner.log_buffer.update({'time': time.time() - self.t})
+        self.t = time.time()
+
+
+class LoggerHook(Hook):
+    """mmcv's ``LoggerHook`` base: when to average the log buffer and call ``log``."""
+
+    def __init__(self, interval=10, ignore_last=True, reset_flag=False, by_epoch=True):
+        self.interval, self.ignore_last, self.reset_flag, self.by_epoch = interval, ignore_last, reset_flag, by_epoch
+
+    def log(self, runner):
+        raise NotImplementedError
+
+    def before_run(self, runner):
+        for hook in runner._hooks[::-1]:            # the last logger hook of the run clears the output
+            if isinstance(hook, LoggerHook):
+                hook.reset_flag = True
+                break
+
+    def before_epoch(self, runner):
+        runner.log_buffer.clear()
+
+    def _flush(self, runner):
+        if runner.log_buffer.ready:
+            self.log(runner)
+            if self.reset_flag:
+                runner.log_buffer.clear_output()
+
+    def after_train_iter(self, runner):
+        if self.by_epoch and (runner.inner_iter + 1) % self.interval == 0:
+            runner.log_buffer.average(self.interval)
+        elif not self.by_epoch and self.every_n_iters(runner, self.interval):
+            runner.log_buffer.average(self.interval)
+        elif runner.inner_iter + 1 == len(runner.data_loader) and not self.ignore_last:
+            runner.log_buffer.average(self.interval)      # not precise, but more stable (mmcv)
+        self._flush(runner)
+
+    def after_train_epoch(self, runner):
+        self._flush(runner)
+
+
+def _round_float(items):
+    if isinstance(items, (list, tuple)):
+        return [_round_float(x) for x in items]
+    if isinstance(items, float):
+        return round(items, 5)
+    if hasattr(items, 'item') and getattr(items, 'ndim', 1) == 0:          # a numpy scalar (the scorers return them)
+        return _round_float(items.item())
+    return items
+
+
+@HOOKS.register_module()
+class TextLoggerHook(LoggerHook):
+    """mmcv's ``TextLoggerHook`` on rank 0: every ``interval`` iterations one line through ``runner.logger`` --
+    ``Epoch [e][i/n]\\tlr: 1.000e-02, eta: 0:00:10, time: 0.100, data_time: 0.010, memory: 123, loss_cls: 0.5000, ...``
+    -- and one JSON object in ``<work_dir>/<timestamp>.log.json`` (``mode``, ``epoch``, ``iter``, ``lr``, ``memory``,
+    then the averaged variables in the order they reached the buffer, floats rounded to 5 digits).  After an evaluation
+    the metrics the evaluation hook left in ``log_buffer.output`` go out as a ``mode: 'val'`` line.  The first JSON line
+    is ``runner.meta``.  ``memory`` is ``torch.cuda.max_memory_allocated`` in MB, the maximum over the ranks (one
+    reduce per logged line).  ``lr`` is the first group's."""
+
+    def __init__(self, by_epoch=True, interval=10, ignore_last=True, reset_flag=False, interval_exp_name=1000):
+        super().__init__(interval, ignore_last, reset_flag, by_epoch)
+        self.time_sec_tot = 0
+        self.interval_exp_name = interval_exp_name
+        self.json_log_path = None
+
+    def before_run(self, runner):
+        super().before_run(runner)
+        self.start_iter = runner.iter
+        if runner.work_dir is not None:
+            self.json_log_path = os.path.join(runner.work_dir, f"{getattr(runner, 'timestamp', None)}.log.json")
+            if runner.meta is not None:
+                self._dump_log(runner.meta, runner)
+
+    def _max_memory(self, runner):
+        import torch.distributed as dist
+        device = next(_unwrap(runner.model).parameters()).device
+        mem_mb = int(torch.cuda.max_memory_allocated(device) / (1024 * 1024)) if device.type == 'cuda' else 0
+        if _world_size() > 1:
+            t = torch.tensor([mem_mb], dtype=torch.int, device=device if str(dist.get_backend()) == 'nccl' else 'cpu')
+            dist.reduce(t, 0, op=dist.ReduceOp.MAX)
+            mem_mb = int(t.item())
+        return mem_mb
+
+    def _log_info(self, log_dict, runner):
+        if runner.logger is None:
+            return
+        import datetime
+        meta = runner.meta
+        if meta is not None and 'exp_name' in meta:
+            if self.every_n_iters(runner, self.interval_exp_name) or \
+                    (self.by_epoch and runner.inner_iter + 1 == len(runner.data_loader)):
+                runner.logger.info(f"Exp name: {meta['exp_name']}")
+        if log_dict['mode'] == 'train':
+            lr_str = f"lr: {log_dict['lr']:.3e}"
+            if self.by_epoch:
+                log_str = f"Epoch [{log_dict['epoch']}][{log_dict['iter']}/{len(runner.data_loader)}]\t"
+            else:
+                log_str = f"Iter [{log_dict['iter']}/{runner.max_iters}]\t"
+            log_str += f'{lr_str}, '
+            if 'time' in log_dict:
+                self.time_sec_tot += log_dict['time'] * self.interval
+                time_sec_avg = self.time_sec_tot / (runner.iter - self.start_iter + 1)
+                eta_sec = time_sec_avg * (runner.max_iters - runner.iter - 1)
+                log_str += f'eta: {datetime.timedelta(seconds=int(eta_sec))}, '
+                log_str += f"time: {log_dict['time']:.3f}, data_time: {log_dict['data_time']:.3f}, "
+                if 'memory' in log_dict:
+                    log_str += f"memory: {log_dict['memory']}, "
+        elif self.by_epoch:
+            log_str = f"Epoch({log_dict['mode']}) [{log_dict['epoch']}][{log_dict['iter']}]\t"
+        else:
+            log_str = f"Iter({log_dict['mode']}) [{log_dict['iter']}]\t"
+        items = []
+        for name, val in log_dict.items():
+            if name in ('mode', 'Epoch', 'iter', 'lr', 'time', 'data_time', 'memory', 'epoch'):
+                continue
+            if isinstance(val, float):
+                val = f'{val:.4f}'
+            items.append(f'{name}: {val}')
+        runner.logger.info(log_str + ', '.join(items))
+
+    def _dump_log(self, log_dict, runner):
+        if runner.rank != 0 or self.json_log_path is None:
+            return
+        import json
+        json_log = OrderedDict((k, _round_float(v)) for k, v in log_dict.items())
+        with open(self.json_log_path, 'a+') as f:
+            f.write(json.dumps(json_log, default=str) + '\n')
+
+    def log(self, runner):
+        out = runner.log_buffer.output
+        cur_iter = out.pop('eval_iter_num') if 'eval_iter_num' in out else runner.inner_iter + 1
+        # (the evaluation hooks run inside the train workflow: a line without 'time' is theirs)
+        log_dict = OrderedDict(mode='train' if 'time' in out else 'val', epoch=runner.epoch + 1, iter=cur_iter)
+        log_dict['lr'] = runner.current_lr()[0]
+        if 'time' in out and torch.cuda.is_available():
+            log_dict['memory'] = self._max_memory(runner)
+        log_dict = OrderedDict(log_dict, **{k: (v.item() if hasattr(v, 'item') and getattr(v, 'ndim', 1) == 0 else v)
+                                            for k, v in out.items()})
+        if runner.rank == 0:
+            self._log_info(log_dict, runner)
+        self._dump_log(log_dict, runner)
+        return log_dict
+
+
+# ---- the runner a config names ---------------------------------------------------------------------------------------
+@RUNNERS.register_module()
+class EpochBasedRunner(Runner):
+    """``Runner`` plus what mmcv's ``EpochBasedRunner`` does for its logger hooks: after every iteration
+    ``outputs['log_vars']`` goes into the log buffer weighted by ``num_samples`` -- a ``DeferredLogVars`` as it is,
+    still pending, so the loop waits for nothing and the logger pays the read-back at its interval --, ``timestamp``
+    names the ``.log.json`` file, and a resumed run keeps the ``config`` text of the run that resumes (``StateEMAHook``
+    looks for ``resume_from`` in it)."""
+
+    def __init__(self, model, optimizer=None, work_dir=None, logger=None, meta=None, max_epochs=None, max_iters=None,
+                 batch_processor=None):
+        if max_iters is not None or batch_processor is not None:
+            raise NotImplementedError('EpochBasedRunner: max_iters / batch_processor are not built; give max_epochs')
+        super().__init__(model, optimizer, logger=logger, meta=meta, max_epochs=max_epochs, work_dir=work_dir)
+        self.timestamp = None
+        self.mode = 'train'
+        if work_dir is not None:
+            os.makedirs(work_dir, exist_ok=True)
+
+    @property
+    def world_size(self):
+        return _world_size()
+
+    @property
+    def rank(self):
+        """The process group's rank; without a group the launcher's ``RANK`` (0 when unset), as ``get_root_logger``."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_rank()
+        return int(os.environ.get('RANK', '0'))
+
+    def resume(self, checkpoint, resume_optimizer=True, map_location='cpu'):
+        mine = {k: self.meta[k] for k in ('config', 'exp_name', 'seed', 'env_info') if k in (self.meta or {})}
+        ckpt = super().resume(checkpoint, resume_optimizer=resume_optimizer, map_location=map_location)
+        self.meta.update(mine)
+        if self.logger is not None:
+            self.logger.info('resumed epoch %d, iter %d', self.epoch, self.iter)
+        return ckpt
+
+    def run(self, data_loader, workflow=None, max_epochs=None):
+        if workflow is not None and [tuple(w) for w in workflow] != [('train', 1)]:
+            raise NotImplementedError(f"workflow={workflow!r}: only [('train', 1)] is built (validation runs through "
+                                      'EvalHook)')
+        if isinstance(data_loader, (list, tuple)):
+            assert len(data_loader) == 1
+            data_loader = data_loader[0]
+        if max_epochs is not None:
+            self.max_epochs = max_epochs
+        assert self.max_epochs is not None, 'max_epochs must be specified during instantiation'
+        self.data_loader = data_loader
+        self.log_buffer.keep = any(isinstance(h, LoggerHook) for h in self._hooks)
+        if self.logger is not None:
+            self.logger.info('Start running, work_dir: %s, max: %d epochs', self.work_dir, self.max_epochs)
+        self.call_hook('before_run')
+        while self.epoch < self.max_epochs:
+            self.model.train()
+            self.call_hook('before_train_epoch')
+            for i, data in enumerate(data_loader):
+                self.inner_iter = i
+                self.call_hook('before_train_iter')
+                self.outputs = self.model.train_step(data, self.optimizer)
+                if 'log_vars' in self.outputs:
+                    self.log_buffer.update(self.outputs['log_vars'], self.outputs['num_samples'])
+                self.call_hook('after_train_iter')
+                self.iter += 1
+            self.call_hook('after_train_epoch')
+            self.epoch += 1
+        self.call_hook('after_run')
+
+
+def build_runner(cfg, default_args=None):
+    """mmcv ``build_runner``: ``cfg.runner`` (``dict(type='EpochBasedRunner', max_epochs=...)``) with the model,
+    optimizer, work_dir, logger and meta as ``default_args``."""
+    if cfg.get('type') != 'EpochBasedRunner':
+        raise NotImplementedError(f"runner type {cfg.get('type')!r} is not built: EpochBasedRunner is")
+    return RUNNERS.build(dict(cfg), default_args=default_args)

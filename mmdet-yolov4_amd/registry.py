@@ -11,6 +11,7 @@ python-file configs with ``_base_`` inheritance and ``_delete_`` -- so the
 ``model = dict(type='SingleStageDetector', backbone=dict(type='DarknetCSP', ...))``
 blocks of ``configs/yolov4/*`` build unchanged.
 """
+import argparse
 import copy
 import inspect
 import os
@@ -176,6 +177,7 @@ NORM_LAYERS = Registry('norm layer')
 HOOKS = Registry('hook')
 PIPELINES = Registry('pipeline')      # mmdet/datasets/builder.py:13
 DATASETS = Registry('dataset')        # mmdet/datasets/builder.py:12
+RUNNERS = Registry('runner')          # mmcv/runner/builder.py
 
 
 def build_backbone(cfg):
@@ -220,6 +222,34 @@ def build_sampler(cfg, **default_args):
 
 
 # ---- python-file configs ---------------------------------------------------------
+def _literal(v, indent=0):
+    """``v`` (nested dicts, lists, tuples and plain values) as Python source: ``dict(k=v, ...)`` for dicts whose keys
+    are identifiers, one entry a line, four spaces a level -- the look of mmcv's ``Config.pretty_text``, without yapf."""
+    import keyword
+    import math
+    pad, inner = ' ' * indent, ' ' * (indent + 4)
+    if isinstance(v, dict):
+        if not v:
+            return 'dict()'
+        if all(isinstance(k, str) and k.isidentifier() and not keyword.iskeyword(k) for k in v):
+            body = [f'{inner}{k}={_literal(x, indent + 4)}' for k, x in v.items()]
+            return 'dict(\n' + ',\n'.join(body) + ')'
+        body = [f'{inner}{k!r}: {_literal(x, indent + 4)}' for k, x in v.items()]
+        return '{\n' + ',\n'.join(body) + '\n' + pad + '}'
+    if isinstance(v, (list, tuple)):
+        open_, close = ('[', ']') if isinstance(v, list) else ('(', ',)' if len(v) == 1 else ')')
+        if not any(isinstance(x, (dict, list, tuple)) for x in v):
+            return open_ + ', '.join(_literal(x) for x in v) + close
+        return open_ + '\n' + ',\n'.join(inner + _literal(x, indent + 4) for x in v) + '\n' + pad + close
+    if isinstance(v, float) and not math.isfinite(v):
+        return f"float('{v!r}')"
+    if v is None or isinstance(v, (bool, int, float, str, bytes, complex)):
+        return repr(v)
+    if hasattr(v, 'tolist') and not isinstance(v, type):          # a numpy scalar or array that reached the config
+        return _literal(v.tolist(), indent)
+    raise TypeError(f'Config.pretty_text: a {type(v).__name__} cannot be written as a Python literal')
+
+
 def _merge(base, child):
     """mmcv Config._merge_a_into_b: child overrides base; ``_delete_=True`` replaces."""
     out = copy.deepcopy(base)
@@ -286,6 +316,26 @@ class Config:
     def get(self, key, default=None):
         return self._cfg_dict.get(key, default)
 
+    def to_dict(self):
+        return self._cfg_dict.to_dict()
+
+    @property
+    def pretty_text(self):
+        """The config as Python source, one assignment per top-level key: ``exec`` of it, or ``Config.fromfile`` of a
+        file holding it, gives a dict equal to this one (mmcv's ``Config.pretty_text``; what the training script
+        stores in ``meta['config']``)."""
+        return ''.join(f'{k} = {_literal(v)}\n' for k, v in self._cfg_dict.to_dict().items())
+
+    def dump(self, path=None):
+        """mmcv's ``Config.dump``: ``pretty_text`` into ``path`` (a ``.py`` file), or returned when ``path`` is None."""
+        text = self.pretty_text
+        if path is None:
+            return text
+        if not str(path).endswith('.py'):
+            raise NotImplementedError(f'Config.dump({path!r}): only python-file configs (.py) are written')
+        with open(path, 'w') as f:
+            f.write(text)
+
     def merge_from_dict(self, options):
         """``--cfg-options a.b=1`` style overrides."""
         nested = {}
@@ -296,3 +346,64 @@ class Config:
                 d = d.setdefault(p, {})
             d[parts[-1]] = v
         object.__setattr__(self, '_cfg_dict', ConfigDict(_merge(self._cfg_dict.to_dict(), nested)))
+
+
+# ---- ``--cfg-options key=value ...`` (mmcv ``DictAction``, mmcv/utils/config.py; third-party, restated) ---------------
+def parse_option_value(val):
+    """One value of a ``key=value`` option: int, float, ``true`` / ``false``, ``None``, ``a,b`` and ``[a,b]`` lists,
+    ``(a,b)`` tuples (nested: ``[(a,b),(c,d)]``), else the string."""
+    def scalar(v):
+        for cast in (int, float):
+            try:
+                return cast(v)
+            except ValueError:
+                pass
+        if v.lower() in ('true', 'false'):
+            return v.lower() == 'true'
+        if v == 'None':
+            return None
+        return v
+
+    def next_comma(s):
+        """The position of the first comma outside brackets (``len(s)`` when there is none)."""
+        assert s.count('(') == s.count(')') and s.count('[') == s.count(']'), f'Imbalanced brackets exist in {s}'
+        depth = 0
+        for i, ch in enumerate(s):
+            depth += ch in '(['
+            depth -= ch in ')]'
+            if ch == ',' and depth == 0:
+                return i
+        return len(s)
+
+    val = val.strip('\'"').replace(' ', '')
+    is_tuple = False
+    if val.startswith('(') and val.endswith(')'):
+        is_tuple, val = True, val[1:-1]
+    elif val.startswith('[') and val.endswith(']'):
+        val = val[1:-1]
+    elif ',' not in val:
+        return scalar(val)
+    values = []
+    while len(val) > 0:
+        end = next_comma(val)
+        values.append(parse_option_value(val[:end]))
+        val = val[end + 1:]
+    return tuple(values) if is_tuple else values
+
+
+def parse_options(pairs):
+    """``['a.b=1', 'c=x,y']`` -> ``{'a.b': 1, 'c': ['x', 'y']}``."""
+    options = {}
+    for kv in pairs or ():
+        key, sep, val = kv.partition('=')
+        if not sep:
+            raise ValueError(f'option {kv!r} is not of the form key=value')
+        options[key] = parse_option_value(val)
+    return options
+
+
+class DictAction(argparse.Action):
+    """``argparse`` action of ``--cfg-options`` / ``--eval-options``: the ``key=value`` words as one dict."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, parse_options(values))

@@ -176,6 +176,49 @@ class CocoBBoxDataset:
             self._flex_gt = FlexGt(annotations, len(self.CLASSES), FAST_BBOX_SCALE_RANGES)
         return self._flex_gt
 
+    def _det2json(self, results):
+        """``datasets/coco.py:210-225``: one record per detection -- image, class, row order -- with ``bbox`` as
+        ``[x1, y1, x2 - x1, y2 - y1]`` formed from the Python floats of the float32 values (``xyxy2xywh``).
+        ``results``: the per-image lists or the flat tuple (tensors or arrays); the flat rows are in that order
+        already."""
+        if isinstance(results, tuple) and len(results) == 3 and not isinstance(results[0], (list, tuple)):
+            dets, labels, img_index = (t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in results)
+        else:
+            if len(results) != len(self):
+                raise AssertionError(f'The length of results is not equal to the dataset len: {len(results)} != '
+                                     f'{len(self)}')
+            dets, labels, img_index = flatten_results(results)
+        if dets.shape[0] and (int(labels.max()) >= len(self.cat_ids) or int(img_index.max()) >= len(self.img_ids)):
+            raise ValueError('results name a class or an image the dataset does not have')
+        rows = np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 5).tolist()
+        return [dict(image_id=self.img_ids[i], bbox=[r[0], r[1], r[2] - r[0], r[3] - r[1]], score=r[4],
+                     category_id=self.cat_ids[c]) for r, c, i in zip(rows, labels.tolist(), img_index.tolist())]
+
+    def results2json(self, results, outfile_prefix):
+        """``datasets/coco.py:265-303`` for box results: ``<outfile_prefix>.bbox.json`` (what ``json.dump`` writes with
+        its defaults, as ``mmcv.dump`` does); returns ``dict(bbox=..., proposal=...)``, both that file."""
+        import json
+        path = f'{outfile_prefix}.bbox.json'
+        with open(path, 'w') as f:
+            json.dump(self._det2json(results), f)
+        return dict(bbox=path, proposal=path)
+
+    def format_results(self, results, jsonfile_prefix=None, **kwargs):
+        """``datasets/coco.py:329-355``: the results as a COCO result file (the form a test server takes).  Returns
+        ``(result_files, tmp_dir)``; without ``jsonfile_prefix`` the file goes into a ``tempfile.TemporaryDirectory``,
+        returned as ``tmp_dir`` (the caller cleans it up), else ``tmp_dir`` is None.  The per-image lists and the flat
+        tuple (``DeviceResults``) give the same bytes."""
+        import os
+        import tempfile
+        if not isinstance(results, (list, tuple)):
+            raise AssertionError('results must be a list')
+        if jsonfile_prefix is None:
+            tmp_dir = tempfile.TemporaryDirectory()
+            jsonfile_prefix = os.path.join(tmp_dir.name, 'results')
+        else:
+            tmp_dir = None
+        return self.results2json(results, jsonfile_prefix), tmp_dir
+
     def evaluate(self, results, metric='bbox', logger=None, **kwargs):
         """``CocoDataset.evaluate`` (``datasets/coco.py:451-643``): ``metric='bbox'`` through ``evaluate_bbox``,
         ``metric='fast-bbox'`` (alone, as in the reference) through ``evaluate_fast_bbox`` against ``flex_gt()``,

@@ -310,16 +310,17 @@ inline int receive_extend(BitReader& b, int s) {
   return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
+// The texts are yv4_jpeg_entropy_strerror's, so that a file fails with the same words in every entropy mode.
 int decode_block(BitReader& b, const Huff& dc, const Huff& ac, int& pred, int16_t* blk) {
   int s = decode_symbol(b, dc);
-  if (s < 0) JPEG_FAIL(YV4_E_INVALID, "jpeg: a DC code that is in no table");
-  if (s > 11) JPEG_FAIL(YV4_E_INVALID, "jpeg: DC magnitude category %d", s);
+  if (s < 0) JPEG_FAIL(YV4_E_INVALID, "jpeg: a code that is in no Huffman table");
+  if (s > 11) JPEG_FAIL(YV4_E_INVALID, "jpeg: a DC magnitude category above 11");
   if (s) pred += receive_extend(b, s);
   pred = (int16_t)pred;      // libjpeg stores the running value as a 16-bit coefficient: wrap, do not grow
   blk[0] = (int16_t)pred;
   for (int k = 1; k < 64;) {
     const int rs = decode_symbol(b, ac);
-    if (rs < 0) JPEG_FAIL(YV4_E_INVALID, "jpeg: an AC code that is in no table");
+    if (rs < 0) JPEG_FAIL(YV4_E_INVALID, "jpeg: a code that is in no Huffman table");
     const int r = rs >> 4;
     s = rs & 15;
     if (s == 0) {
@@ -328,7 +329,7 @@ int decode_block(BitReader& b, const Huff& dc, const Huff& ac, int& pred, int16_
       continue;
     }
     k += r;
-    if (k > 63) JPEG_FAIL(YV4_E_INVALID, "jpeg: coefficient index %d past 63", k);
+    if (k > 63) JPEG_FAIL(YV4_E_INVALID, "jpeg: a coefficient index past 63");
     blk[kZigzag[k]] = (int16_t)receive_extend(b, s);
     ++k;
   }

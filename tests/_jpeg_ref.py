@@ -222,7 +222,8 @@ def entropy_decode(data, info=None):
                         if s > 11:
                             raise Invalid('DC category')
                         if s:
-                            pred[i] += bits.value(s)
+                            # libjpeg keeps the running DC value as a 16-bit coefficient: it wraps
+                            pred[i] = ((pred[i] + bits.value(s) + 0x8000) & 0xFFFF) - 0x8000
                         blk[0] = pred[i]
                         k = 1
                         while k < 64:

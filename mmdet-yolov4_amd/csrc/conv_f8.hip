@@ -22,6 +22,7 @@
 // (r, h) holds column r, rows 8*(e>>2) + 4h + (e&3)); tests/test_gpu_fp8.py checks both maps with integer data, bit
 // for bit.
 #include "yv4_common.h"
+#include "conv_desc.h"
 
 namespace yv4 {
 
@@ -78,6 +79,23 @@ struct ConvArgsF8 {
   int M, K;
   int tiles_n;
 };
+
+// The argument block of a descriptor and its tensors (the shape of conv_args, conv_f32_common.h); the launch sets tiles_n.
+static inline ConvArgsF8 conv_args_f8(const yv4_conv_desc* d, int out_f32, const void* x, const void* w, const float* s1,
+                                      const float* t1, const float* s2, const float* t2, const void* res, float r_scale,
+                                      float y_inv, void* y) {
+  ConvArgsF8 a{};
+  a.x = (const unsigned char*)x; a.w = (const unsigned char*)w; a.s1 = s1; a.t1 = t1; a.s2 = s2; a.t2 = t2;
+  a.res = (const unsigned char*)res; a.y = y;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
+  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
+  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
+  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
+  a.r_scale = r_scale; a.y_inv = y_inv; a.out_f32 = out_f32;
+  a.M = (int)((long long)d->N * d->Ho * d->Wo); a.K = d->KH * d->KW * d->Cin;
+  return a;
+}
 
 // GENERAL_K = false: Cin % 128 == 0, a slice lies inside one (kh, kw) tap (scalar walk).  GENERAL_K = true: Cin % 16
 // == 0, each 16-byte chunk derives its own (tap, channel).
@@ -358,39 +376,16 @@ extern "C" int yv4_conv_bn_act_fwd_f8(const yv4_conv_desc* d, int out_dtype, con
   YV4_REQUIRE(d && x && w && scale1 && shift1 && y, "conv f8: null argument");
   YV4_REQUIRE(out_dtype == YV4_F8E4M3 || out_dtype == YV4_F32, "conv f8: out_dtype must be YV4_F8E4M3 or YV4_F32");
   YV4_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), "conv f8: scale2/shift2 must come together");
-  YV4_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "conv f8: empty shape");
-  YV4_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "conv f8: bad kernel/stride/pad");
-  YV4_UNSUPPORTED_IF(d->Cin % 16 != 0, "conv f8: Cin = %d is not a multiple of 16 (one 16-byte chunk of codes)", d->Cin);
-  YV4_UNSUPPORTED_IF(d->x_cstride % 16 != 0 || d->x_coff % 16 != 0 || ((uintptr_t)x & 15) || ((uintptr_t)w & 15),
-                     "conv f8: the input view must be 16-channel aligned (cstride %d, coff %d) and x / w 16-byte aligned",
-                     d->x_cstride, d->x_coff);
-  YV4_UNSUPPORTED_IF(out_dtype == YV4_F32 && ((uintptr_t)y & 3), "conv f8: an fp32 output must be 4-byte aligned");
-  YV4_REQUIRE(d->x_coff >= 0 && d->x_coff + d->Cin <= d->x_cstride, "conv f8: input view exceeds its pixel stride");
-  YV4_REQUIRE(d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride, "conv f8: output view exceeds its pixel stride");
-  const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-  YV4_REQUIRE(Ho == d->Ho && Wo == d->Wo && Ho > 0 && Wo > 0, "conv f8: Ho/Wo (%d,%d) do not match the geometry (%d,%d)",
-              d->Ho, d->Wo, Ho, Wo);
-  if (residual)
-    YV4_REQUIRE(d->r_coff >= 0 && d->r_coff + d->Cout <= d->r_cstride, "conv f8: residual view exceeds its pixel stride");
-  YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH && d->act2 >= 0 && d->act2 <= YV4_ACT_SWISH,
-              "conv f8: activation id out of range");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  YV4_REQUIRE(M < (1LL << 31) && (long long)d->N * d->H * d->W < (1LL << 31), "conv f8: pixel count does not fit 31 bits");
-  const long long K = (long long)d->KH * d->KW * d->Cin;
-  YV4_REQUIRE(K < (1LL << 30), "conv f8: K too large");
-  ConvArgsF8 a;
-  a.x = (const unsigned char*)x; a.w = (const unsigned char*)w; a.s1 = scale1; a.t1 = shift1; a.s2 = scale2;
-  a.t2 = shift2; a.res = (const unsigned char*)residual; a.y = y;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.y_cs = d->y_cstride; a.y_co = d->y_coff;
-  a.r_cs = d->r_cstride; a.r_co = d->r_coff;
-  a.act1 = d->act1; a.act2 = d->act2; a.slope1 = d->slope1; a.slope2 = d->slope2;
-  a.r_scale = r_scale; a.y_inv = y_inv_scale;
-  a.out_f32 = out_dtype == YV4_F32 ? 1 : 0;
-  a.M = (int)M; a.K = (int)K; a.tiles_n = 0;
+  ConvDescRules rules{16, residual != nullptr};      // (16 channels = one 16-byte chunk of codes)
+  rules.any_taps = rules.misaligned_is_unsupported = true;
+  if (int rc = check_conv_desc(d, "conv f8", rules)) return rc;
+  YV4_UNSUPPORTED_IF(((uintptr_t)x & 15) || ((uintptr_t)w & 15) || (out_dtype == YV4_F32 && ((uintptr_t)y & 3)),
+                     "conv f8: x / w must be 16-byte aligned, an fp32 output 4-byte aligned");
+  YV4_REQUIRE((long long)d->KH * d->KW * d->Cin < (1LL << 30), "conv f8: K too large");
+  ConvArgsF8 a = conv_args_f8(d, out_dtype == YV4_F32 ? 1 : 0, x, w, scale1, shift1, scale2, shift2, residual, r_scale,
+                              y_inv_scale, y);
   const bool general = d->Cin % kF8BK != 0;
-  const int tile = d->tile ? d->tile : pick_tile_f8(M, d->Cout);
+  const int tile = d->tile ? d->tile : pick_tile_f8(a.M, d->Cout);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   switch (tile) {
     case YV4_F8TILE_128x128: return general ? launch_f8<128, 128, true>(a, s) : launch_f8<128, 128, false>(a, s);

@@ -19,6 +19,8 @@
 // are output channels, so every accumulator register stores 2 x 128 contiguous
 // bytes of NHWC output.
 #include "conv_f32_common.h"
+#include "conv_desc.h"
+#include "conv_route.h"
 
 namespace yv4 {
 
@@ -714,11 +716,9 @@ static int prefer_w3_f32(const ConvArgs& a) {      // the shape index, or -1
   static const int waste = YV4_ENV_INT("YV4_W3F_MAXWASTE", 25);
   static const int min_out = YV4_ENV_INT("YV4_W3F_MINOUT", 32768);
   if (!mode || !conv3x3_wide_f32_applies(a) || a.Cin < 64) return -1;
-  if ((long long)a.M * a.Cout < 256LL * min_out) return -1;
   double eff = 0.0;
   const int shape = conv3x3_wide_f32_pick(a, &eff);
-  if (shape < 0 || eff * 100.0 > 100.0 + waste) return -1;
-  return shape;
+  return shape >= 0 && fills_rounds(a.M, a.Cout, min_out, waste, eff) ? shape : -1;
 }
 
 // The general wide-tile fp32 kernel takes the stride-2 3x3 layers with >= YV4_WGF_S2CIN input channels and the 1x1
@@ -735,11 +735,9 @@ static int prefer_wide_f32(const ConvArgs& a) {    // the shape index, or -1
   const bool s2 = a.KH == 3 && a.KW == 3 && a.stride == 2 && a.Cin >= s2cin;
   const bool p1 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.Cin >= p1cin;
   if (!s2 && !p1) return -1;
-  if ((long long)a.M * a.Cout < 256LL * min_out) return -1;
   double eff = 0.0;
   const int shape = conv_wide_f32_pick(a, &eff);
-  if (shape < 0 || eff * 100.0 > 100.0 + waste) return -1;
-  return shape;
+  return shape >= 0 && fills_rounds(a.M, a.Cout, min_out, waste, eff) ? shape : -1;
 }
 
 static bool fast_ok(const ConvArgs& a) { return a.Cin % kBK == 0 && dma_addressable(a); }
@@ -747,8 +745,7 @@ static bool fast_ok(const ConvArgs& a) { return a.Cin % kBK == 0 && dma_addressa
 // What the AUTO path launches: the family as its tile id and, for the two wide families, the shape index (else -1).
 // conv_f32_impl launches it and yv4_conv_pick_tile reports it: a plan, the benchmark's output check and the tests
 // read the latter to learn the former.
-struct Route { int tile, shape; };
-static Route auto_route(const ConvArgs& a) {
+static TileId auto_route(const ConvArgs& a) {
   const bool fast = fast_ok(a);
   if (fast) {
     const int w3 = prefer_w3_f32(a);
@@ -773,7 +770,7 @@ extern "C" double yv4_conv_flops(const yv4_conv_desc* d) {
 // (a residual or a second affine, unknown here, keeps the tile kernels)
 extern "C" int yv4_conv_pick_tile(const yv4_conv_desc* d) {
   if (!d) return YV4_TILE_AUTO;
-  const Route r = auto_route(conv_args(d));
+  const TileId r = auto_route(conv_args(d));
   if (r.tile == YV4_TILE_W3x3) return YV4_TILE_W3x3_SHAPE(r.shape);   // the pinned form: a plan can copy it (see include/yv4.h)
   if (r.tile == YV4_TILE_WIDE) return YV4_TILE_WIDE_SHAPE(r.shape);
   return r.tile;
@@ -786,79 +783,50 @@ static int conv_f32_impl(const yv4_conv_desc* d, const float* x, const float* w,
                          bool* stats_done, void* stream) {
   YV4_REQUIRE(d && x && w && scale1 && shift1 && y, "conv: null argument");
   YV4_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), "conv: scale2/shift2 must come together");
-  YV4_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "conv: empty shape");
-  YV4_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "conv: bad kernel/stride/pad");
-  YV4_REQUIRE(d->KH * d->KW <= 64, "conv: kernels above 64 taps are not supported");
-  YV4_REQUIRE(d->Cin % 4 == 0 && d->x_cstride % 4 == 0 && d->x_coff % 4 == 0,
-              "conv: Cin (%d), x_cstride (%d), x_coff (%d) must be multiples of 4", d->Cin,
-              d->x_cstride, d->x_coff);
+  if (int rc = check_conv_desc(d, "conv", {4, residual != nullptr})) return rc;
   YV4_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv: x / w must be 16-byte aligned");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride, "conv: input view exceeds its pixel stride");
-  YV4_REQUIRE(d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride, "conv: output view exceeds its pixel stride");
-  const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-  const int Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-  YV4_REQUIRE(Ho == d->Ho && Wo == d->Wo, "conv: Ho/Wo (%d,%d) do not match the geometry (%d,%d)",
-              d->Ho, d->Wo, Ho, Wo);
-  if (residual)
-    YV4_REQUIRE(d->r_coff >= 0 && d->r_coff + d->Cout <= d->r_cstride, "conv: residual view exceeds its pixel stride");
-  YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH && d->act2 >= 0 && d->act2 <= YV4_ACT_SWISH,
-              "conv: unknown activation id");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  YV4_REQUIRE(M < (1LL << 31), "conv: N*Ho*Wo = %lld does not fit 31 bits", M);
-  YV4_REQUIRE((long long)d->N * d->H * d->W < (1LL << 31), "conv: N*H*W does not fit 31 bits");
 
   ConvArgs a = conv_args(d, x, w, scale1, shift1, scale2, shift2, residual, y);
   const bool uniform = (d->Cin % kBK) == 0;
   const bool fast = fast_ok(a);
-  const bool can_stem = stem_ok(a);
-  const Route route = d->tile == YV4_TILE_AUTO ? auto_route(a) : Route{d->tile, -1};
+  const bool forced = d->tile != YV4_TILE_AUTO;
+  const TileId route = forced ? decode_tile_f32(d->tile) : auto_route(a);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (stats_done) *stats_done = false;
-  {
-    const int forced = (d->tile > 16 && (d->tile & 15) == YV4_TILE_W3x3 && d->tile <= YV4_TILE_W3x3_SHAPE(4)) ? (d->tile >> 4) - 1 : -1;
-    if (d->tile == YV4_TILE_W3x3 || forced >= 0)
-      YV4_REQUIRE(fast && conv3x3_wide_f32_applies(a), "conv: the wide 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with "
-                  "Cin %% 32 == 0, Cout %% 16 == 0 (64 .. 1024) and 4-aligned channel strides / offsets");
-    if (route.tile == YV4_TILE_W3x3 || forced >= 0) {
-      if (stats) { a.stats = stats; *stats_done = true; }
-      static const int env_shape = YV4_ENV_INT("YV4_W3F_SHAPE", -1);
-      return conv3x3_wide_f32_launch(a, forced >= 0 ? forced : (route.shape >= 0 && env_shape < 0 ? route.shape : env_shape), s);
-    }
-  }
-  {
-    const int forced = (d->tile > 16 && (d->tile & 15) == YV4_TILE_WIDE && d->tile <= YV4_TILE_WIDE_SHAPE(4)) ? (d->tile >> 4) - 1 : -1;
-    if (d->tile == YV4_TILE_WIDE || forced >= 0)
-      YV4_REQUIRE(fast && conv_wide_f32_applies(a), "conv: the wide tile needs Cin %% 32 == 0, Cout %% 16 == 0 (64 .. 2048) and "
-                  "4-aligned channel strides / offsets");
-    if (route.tile == YV4_TILE_WIDE || forced >= 0) {
-      if (stats) { a.stats = stats; *stats_done = true; }
-      static const int env_shape = YV4_ENV_INT("YV4_WGF_SHAPE", -1);
-      return conv_wide_f32_launch(a, forced >= 0 ? forced : (route.shape >= 0 && env_shape < 0 ? route.shape : env_shape), s);
-    }
-  }
-  if (d->tile == YV4_TILE_WS_1x1)
-    YV4_REQUIRE(fast && conv1x1_ws_f32_applies(a), "conv: the weight-stationary tile needs a 1x1 / stride 1 conv with Cin 64, "
-                "128 or 256, Cout >= 32 and no residual");
-  if (route.tile == YV4_TILE_WS_1x1) {
-    if (stats) { a.stats = stats; *stats_done = true; }
-    return conv1x1_ws_f32_launch(a, s);
-  }
   const int tile = route.tile;
-  if (stats && fast && (tile == YV4_TILE_DMA_64x64 || tile == YV4_TILE_DMA_128x64 || tile == YV4_TILE_DMA_128x128)) {
-    a.stats = stats;
-    *stats_done = true;
+  // the kernels with the statistics epilogue: the wide and weight-stationary families, the LDS-DMA tiles
+  const bool family = tile == YV4_TILE_W3x3 || tile == YV4_TILE_WIDE || tile == YV4_TILE_WS_1x1;
+  const bool dma_tile = tile == YV4_TILE_DMA_64x64 || tile == YV4_TILE_DMA_128x64 || tile == YV4_TILE_DMA_128x128;
+  if (stats_done) *stats_done = stats && (family || (fast && dma_tile));
+  if (stats_done && *stats_done) a.stats = stats;
+  // (a forced id's shape wins; the measurement build's YV4_*_SHAPE overrides the automatic one; -1: the launch picks)
+  auto shape_of = [&](int env_shape) { return route.shape >= 0 && (forced || env_shape < 0) ? route.shape : env_shape; };
+  if (tile == YV4_TILE_W3x3) {
+    YV4_REQUIRE(!forced || (fast && conv3x3_wide_f32_applies(a)), "conv: the wide 3x3 tile needs a 3x3 / stride 1 / pad 1 conv "
+                "with Cin %% 32 == 0, Cout %% 16 == 0 (64 .. 1024) and 4-aligned channel strides / offsets");
+    static const int env_shape = YV4_ENV_INT("YV4_W3F_SHAPE", -1);
+    return conv3x3_wide_f32_launch(a, shape_of(env_shape), s);
+  }
+  if (tile == YV4_TILE_WIDE) {
+    YV4_REQUIRE(!forced || (fast && conv_wide_f32_applies(a)), "conv: the wide tile needs Cin %% 32 == 0, Cout %% 16 == 0 "
+                "(64 .. 2048) and 4-aligned channel strides / offsets");
+    static const int env_shape = YV4_ENV_INT("YV4_WGF_SHAPE", -1);
+    return conv_wide_f32_launch(a, shape_of(env_shape), s);
+  }
+  if (tile == YV4_TILE_WS_1x1) {
+    YV4_REQUIRE(!forced || (fast && conv1x1_ws_f32_applies(a)), "conv: the weight-stationary tile needs a 1x1 / stride 1 conv "
+                "with Cin 64, 128 or 256, Cout >= 32 and no residual");
+    return conv1x1_ws_f32_launch(a, s);
   }
   switch (tile) {
     case YV4_TILE_128x128: return launch_conv<128, 128, 2, 2>(a, uniform, s);
     case YV4_TILE_128x64: return launch_conv<128, 64, 2, 2>(a, uniform, s);
     case YV4_TILE_64x128: return launch_conv<64, 128, 2, 2>(a, uniform, s);
     case YV4_TILE_64x64: return launch_conv<64, 64, 2, 2>(a, uniform, s);
-    case YV4_TILE_STEM: if (can_stem) return conv_stem_f32_launch(a, YV4_F32, s); break;
+    case YV4_TILE_STEM: if (stem_ok(a)) return conv_stem_f32_launch(a, YV4_F32, s); break;
     case YV4_TILE_DMA_64x64: if (fast) return launch_conv_dma<64, 64, 2, 2, 2>(a, s); break;
     case YV4_TILE_DMA_128x64: if (fast) return launch_conv_dma<128, 64, 2, 2, 2>(a, s); break;
     case YV4_TILE_DMA_128x128: if (fast) return launch_conv_dma<128, 128, 2, 2, 2>(a, s); break;
-    default:
-      break;
+    default: break;
   }
   set_error("conv: unknown or inapplicable tile id %d", tile);
   return YV4_E_INVALID;
@@ -906,31 +874,24 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(ConvArgs p) {
   }
 }
 
-// how many ways to split K for this layer on a 256-CU chip: enough workgroups to give every CU ~2, at least 4 slices
-// per split; 1 = do not split (enough tiles already, or a kernel without the split path)
-static int splitk_choice(const yv4_conv_desc* d, int* tile_out) {
+// how many ways to split K for this layer's 64 x 64 LDS-DMA tiles (splitk_ways, conv_route.h): ~2 workgroups per CU, at
+// least 8 slices of 32 per split; 1 = do not split (enough tiles already, or a layer outside the LDS-DMA kernels)
+static int splitk_choice(const yv4_conv_desc* d) {
   const long long M = (long long)d->N * d->Ho * d->Wo;
   const ConvArgs a = conv_args(d);
   if (!fast_ok(a)) return 1;
-  const int tile = YV4_TILE_DMA_64x64;
   const long long tiles = ((M + 63) / 64) * ((d->Cout + 63) / 64);
-  const int nk = a.K / kBK;
   static const long long target = (long long)YV4_ENV_INT("YV4_SPLITK_TARGET", (int)(512LL));
   static const int min_slices = YV4_ENV_INT("YV4_SPLITK_MINSL", 8);
-  int ks = 1;
-  while (tiles * ks < target && nk / (ks * 2) >= min_slices && ks < 32) ks *= 2;
-  if (tile_out) *tile_out = tile;
-  return ks;
+  return splitk_ways(tiles, a.K / kBK, target, min_slices);
 }
 }  // namespace yv4
 
 extern "C" size_t yv4_conv_splitk_workspace(const yv4_conv_desc* d, int* ksplit) {
   if (!d) return 0;
-  const int ks = splitk_choice(d, nullptr);
+  const int ks = splitk_choice(d);
   if (ksplit) *ksplit = ks;
-  if (ks <= 1) return 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  return (size_t)ks * (size_t)M * (size_t)((d->Cout + 3) / 4 * 4) * sizeof(float);
+  return splitk_workspace_bytes(d, ks, 4);
 }
 
 extern "C" int yv4_conv_bn_act_fwd_splitk(const yv4_conv_desc* d, const float* x, const float* w, const float* scale1,
@@ -938,32 +899,19 @@ extern "C" int yv4_conv_bn_act_fwd_splitk(const yv4_conv_desc* d, const float* x
                                           const float* residual, float* y, float* workspace, size_t workspace_bytes,
                                           void* stream) {
   YV4_REQUIRE(d, "conv splitk: null descriptor");
-  int tile = 0;
-  const int ks = splitk_choice(d, &tile);
+  const int ks = splitk_choice(d);
   if (ks <= 1) return yv4_conv_bn_act_fwd(d, x, w, scale1, shift1, scale2, shift2, residual, y, stream);
   YV4_REQUIRE(x && w && scale1 && shift1 && y && workspace, "conv splitk: null argument");
   YV4_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), "conv splitk: scale2/shift2 must come together");
-  YV4_REQUIRE(d->x_cstride % 4 == 0 && d->x_coff % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 &&
-              ((uintptr_t)workspace & 15) == 0, "conv splitk: alignment");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride && d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride,
-              "conv splitk: view exceeds its pixel stride");
-  const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-  YV4_REQUIRE(Ho == d->Ho && Wo == d->Wo, "conv splitk: Ho/Wo do not match the geometry");
-  if (residual) YV4_REQUIRE(d->r_coff >= 0 && d->r_coff + d->Cout <= d->r_cstride, "conv splitk: residual view");
-  YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH && d->act2 >= 0 && d->act2 <= YV4_ACT_SWISH, "conv splitk: activation id");
-  YV4_REQUIRE(workspace_bytes >= yv4_conv_splitk_workspace(d, nullptr), "conv splitk: workspace too small");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
+  if (int rc = check_conv_desc(d, "conv splitk", {4, residual != nullptr})) return rc;
+  YV4_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)workspace & 15) == 0,
+              "conv splitk: x / w / workspace must be 16-byte aligned");
+  YV4_REQUIRE(workspace_bytes >= splitk_workspace_bytes(d, ks, 4), "conv splitk: workspace too small");
   ConvArgs a = conv_args(d, x, w, scale1, shift1, scale2, shift2, residual, y);
-  const int nk = a.K / kBK;
-  a.ks_slices = (nk + ks - 1) / ks;
-  a.ksplit = (nk + a.ks_slices - 1) / a.ks_slices;      // no empty split
-  a.ws_cs = (d->Cout + 3) / 4 * 4; a.ws = workspace;
+  splitk_set(a, ks, kBK, 4, workspace);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (int rc = launch_conv_dma<64, 64, 2, 2, 2>(a, s)) return rc;
-  const long long work = M * (a.ws_cs / 4);
-  unsigned g = (unsigned)((work + 255) / 256);
-  if (g > 2048) g = 2048;
-  hipLaunchKernelGGL(splitk_finish_kernel, dim3(g), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(splitk_finish_kernel, dim3(splitk_finish_grid(a, 4)), dim3(256), 0, s, a);
   YV4_CHECK_LAUNCH("conv splitk finish");
   return YV4_OK;
 }
@@ -1004,17 +952,15 @@ extern "C" int yv4_conv_scatter_fwd(const yv4_conv_desc* d, const float* x, cons
                                     const float* shift1, float* y, int Hy, int Wy, int sh, int sw, int oh, int ow,
                                     void* stream) {
   YV4_REQUIRE(d && x && w && scale1 && shift1 && y, "conv scatter: null argument");
-  YV4_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->Ho > 0 && d->Wo > 0, "conv scatter: empty shape");
-  YV4_REQUIRE(d->KH > 0 && d->KW > 0 && d->KH * d->KW <= 64 && d->stride == 1 && d->pad >= 0, "conv scatter: stride-1 kernels only");
-  YV4_REQUIRE(d->Cin % kBK == 0 && d->x_cstride % 4 == 0 && d->x_coff % 4 == 0, "conv scatter: Cin must be a multiple of 32");
+  ConvDescRules rules{4};
+  rules.scatter = true; rules.acts = 0;      // (identity epilogue, whatever the descriptor's activation fields hold)
+  if (int rc = check_conv_desc(d, "conv scatter", rules)) return rc;
+  YV4_REQUIRE(d->Cin % kBK == 0, "conv scatter: Cin must be a multiple of 32 (the LDS-DMA tiles)");
   YV4_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv scatter: x / w must be 16-byte aligned");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride && d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride,
-              "conv scatter: view exceeds its pixel stride");
   YV4_REQUIRE(sh > 0 && sw > 0 && oh >= 0 && ow >= 0 && (d->Ho - 1) * sh + oh < Hy && (d->Wo - 1) * sw + ow < Wy,
               "conv scatter: the scattered grid does not fit the output tensor");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
   ConvArgs a = conv_args(d, x, w, scale1, shift1, nullptr, nullptr, nullptr, y);
-  YV4_REQUIRE(M < (1LL << 31) && dma_addressable(a), "conv scatter: tensors of 4 GiB or more are not supported");
+  YV4_REQUIRE(dma_addressable(a), "conv scatter: tensors of 4 GiB or more are not supported");
   a.act1 = 0; a.act2 = 0;      // identity epilogue, whatever the descriptor's activation fields hold
   a.ys_on = 1; a.ys_H = Hy; a.ys_W = Wy; a.ys_sh = sh; a.ys_sw = sw; a.ys_oh = oh; a.ys_ow = ow;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);

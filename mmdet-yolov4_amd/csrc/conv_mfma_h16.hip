@@ -16,6 +16,8 @@
 // darknetcsp.py:15-35): conv in half with fp32 accumulation -> round -> BN in fp32 -> round -> Mish ->
 // round.  Here the chain after the accumulator stays in fp32 and is rounded once.
 #include "conv_h16_common.h"
+#include "conv_desc.h"
+#include "conv_route.h"
 
 namespace yv4 {
 
@@ -331,33 +333,28 @@ static int launch_h16(const ConvArgsH& a, hipStream_t stream) {
   return YV4_OK;
 }
 
-template <bool BF16, int NBUF>
-static int dispatch_h16_n(const ConvArgsH& a, int shape, bool general, hipStream_t s) {
-  switch (shape) {
+// Deeper rings (NBUF 3: two slices in flight) were measured slower on every YOLOv4-L shape: a
+// slice costs ~1.3 us of memory latency against 0.2 us of MFMA, so throughput is set by the bytes in
+// flight per CU, and a third slot costs exactly the occupancy it buys; a 4-slot ring that issues a
+// whole K <= 256 reduction up front was slower still on the 1x1 layers (64x64: 4112 vs 2975 us over the
+// network's 1x1 layers): resident workgroups per CU, not prefetch depth, hide the prologue / epilogue.
+// (A 256x128 workgroup tile -- 128x64 per wave, 0.75 fragment reads per MFMA, one workgroup per CU, 2- or
+// 3-slot ring -- measured 3-4x SLOWER on every YOLOv4-L shape: 128 accumulator registers plus the 12 DMA
+// address sets do not fit the 256-VGPR budget of this 4-wave kernel without spilling.)
+template <bool BF16>
+static int dispatch_h16(const ConvArgsH& a, int tile, bool general, hipStream_t s) {
+  constexpr int NBUF = 2;
+  switch (tile) {
     case YV4_HTILE_128x128:
       return general ? launch_h16<BF16, 128, 128, true, NBUF>(a, s) : launch_h16<BF16, 128, 128, false, NBUF>(a, s);
     case YV4_HTILE_128x64:
       return general ? launch_h16<BF16, 128, 64, true, NBUF>(a, s) : launch_h16<BF16, 128, 64, false, NBUF>(a, s);
     case YV4_HTILE_64x64:
       return general ? launch_h16<BF16, 64, 64, true, NBUF>(a, s) : launch_h16<BF16, 64, 64, false, NBUF>(a, s);
-    default:
-      break;
+    default: break;
   }
-  set_error("conv h16: unknown tile id %d", shape);
+  set_error("conv h16: unknown tile id %d", tile);
   return YV4_E_INVALID;
-}
-
-// Deeper rings (NBUF 3: two slices in flight) were measured slower on every YOLOv4-L shape: a
-// slice costs ~1.3 us of memory latency against 0.2 us of MFMA, so throughput is set by the bytes in
-// flight per CU, and a third slot costs exactly the occupancy it buys; a 4-slot ring that issues a
-// whole K <= 256 reduction up front was slower still on the 1x1 layers (64x64: 4112 vs 2975 us over the
-// network's 1x1 layers): resident workgroups per CU, not prefetch depth, hide the prologue / epilogue.
-template <bool BF16>
-static int dispatch_h16(const ConvArgsH& a, int tile, bool general, hipStream_t s) {
-  // (a 256x128 workgroup tile -- 128x64 per wave, 0.75 fragment reads per MFMA, one workgroup per CU, 2- or
-  // 3-slot ring -- measured 3-4x SLOWER on every YOLOv4-L shape: 128 accumulator registers plus the 12 DMA
-  // address sets do not fit the 256-VGPR budget of this 4-wave kernel without spilling)
-  return dispatch_h16_n<BF16, 2>(a, tile, general, s);
 }
 
 // conv3x3_pp_h16.hip
@@ -397,14 +394,13 @@ static bool prefer_w3(const ConvArgsH& a) {
   // (64 input channels -- one chunk, nine K tiles per output tile -- only with a full 128-channel tile of outputs:
   // YOLOv4-S 64 -> 128 @52 at batch 256 143 us against 193 on the 128 x 64 tile, 64 -> 64 122 against 108)
   if (!mode || !conv3x3_wide_h16_applies(a) || a.Cin < 64) return false;
-  if ((long long)a.M * a.Cout < 256LL * min_out) return false;
   double eff = 0.0;
-  if (conv3x3_wide_h16_pick(a, &eff) < 0) return false;
+  if (conv3x3_wide_h16_pick(a, &eff) < 0 || !fills_rounds(a.M, a.Cout, min_out, kAnyFill, eff)) return false;
   // 64 input channels (one chunk, nine K tiles per output tile): whatever the rounds -- the alternatives are the 128 x 64
   // tile and the few-channel kernel, 15-25 % behind on these layers at any fill (64 -> 64 on the 384 x 64 shape: @52 batch
   // 256 92 us against 113, @152 batch 32 94 against 116; 64 -> 128 @52 143 against 193; profiles/r06_w3_bn64.txt)
   if (a.Cin < 128) return true;
-  if (eff * 100.0 <= 100.0 + waste) return true;
+  if (fills_rounds(a.M, a.Cout, min_out, waste, eff)) return true;
   // A worse fill still wins where the alternative is the ping-pong kernel, whose 256 x 128 tiles quantise the same way
   // (YOLOv5-L at 640: 256->256 @40 is 800 such tiles = 3.1 rounds for either kernel; train step 1 045 -> 1 063, bf16
   // inference 3 698 -> 3 916 images/s with this rule, YOLOv4-L at 608 unchanged).
@@ -433,10 +429,9 @@ static bool prefer_wide(const ConvArgsH& a) {
   const bool s2 = a.KH == 3 && a.KW == 3 && a.stride == 2 && a.Cin >= 64;
   const bool pw = a.KH == 1 && a.KW == 1 && a.Cin >= min_cin;
   if (!(s2 || pw || a.ys_on)) return false;
-  if ((long long)a.M * a.Cout < 256LL * min_out || a.K < 256) return false;
+  if (a.K < 256) return false;
   double eff = 0.0;
-  if (conv_wide_h16_pick(a, &eff) < 0) return false;
-  return eff * 100.0 <= 100.0 + waste;
+  return conv_wide_h16_pick(a, &eff) >= 0 && fills_rounds(a.M, a.Cout, min_out, waste, eff);
 }
 
 // conv1x1_ws_h16.hip
@@ -507,25 +502,8 @@ static int conv_h16_impl(const yv4_conv_desc* d, int dtype, int out_dtype, const
   YV4_REQUIRE(dtype == YV4_F16 || dtype == YV4_BF16, "conv h16: dtype must be YV4_F16 or YV4_BF16");
   YV4_REQUIRE(out_dtype == dtype || out_dtype == YV4_F32, "conv h16: out_dtype must be the operand type or YV4_F32");
   YV4_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), "conv h16: scale2/shift2 must come together");
-  YV4_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "conv h16: empty shape");
-  YV4_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "conv h16: bad kernel/stride/pad");
-  YV4_REQUIRE(d->KH * d->KW <= 64, "conv h16: kernels above 64 taps are not supported");
-  YV4_REQUIRE(d->Cin % 8 == 0 && d->x_cstride % 8 == 0 && d->x_coff % 8 == 0,
-              "conv h16: Cin (%d), x_cstride (%d), x_coff (%d) must be multiples of 8", d->Cin, d->x_cstride, d->x_coff);
+  if (int rc = check_conv_desc(d, "conv h16", {8, residual != nullptr})) return rc;
   YV4_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv h16: x / w must be 16-byte aligned");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride, "conv h16: input view exceeds its pixel stride");
-  YV4_REQUIRE(d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride, "conv h16: output view exceeds its pixel stride");
-  const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-  const int Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-  YV4_REQUIRE(Ho == d->Ho && Wo == d->Wo, "conv h16: Ho/Wo (%d,%d) do not match the geometry (%d,%d)", d->Ho, d->Wo, Ho,
-              Wo);
-  if (residual)
-    YV4_REQUIRE(d->r_coff >= 0 && d->r_coff + d->Cout <= d->r_cstride, "conv h16: residual view exceeds its pixel stride");
-  YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH && d->act2 >= 0 && d->act2 <= YV4_ACT_SWISH,
-              "conv h16: unknown activation id");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  YV4_REQUIRE(M < (1LL << 31), "conv h16: N*Ho*Wo = %lld does not fit 31 bits", M);
-  YV4_REQUIRE((long long)d->N * d->H * d->W < (1LL << 31), "conv h16: N*H*W does not fit 31 bits");
 
   ConvArgsH a = conv_args_h(d, out_dtype == YV4_F32 ? 1 : 0, x, w, scale1, shift1, scale2, shift2, residual, y);
   YV4_REQUIRE(dma_addressable(a), "conv h16: tensors of 4 GiB or more are not addressable through a buffer descriptor");
@@ -535,36 +513,38 @@ static int conv_h16_impl(const yv4_conv_desc* d, int dtype, int out_dtype, const
   a.stats = stats;
   const bool general = (d->Cin % kHBK) != 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int tile = d->tile == YV4_TILE_AUTO ? auto_route_h16(a) : d->tile;
-  const int w3_forced = (d->tile > 8 && (d->tile & 7) == YV4_HTILE_W3x3 && d->tile <= YV4_HTILE_W3x3_SHAPE(6)) ? (d->tile >> 3) - 1 : -1;
-  if (d->tile == YV4_HTILE_W3x3 || w3_forced >= 0)
-    YV4_REQUIRE(conv3x3_wide_h16_applies(a), "conv h16: the wide 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with Cin %% 64 == 0, "
-                "Cout %% 16 == 0 (64 .. 1024), 16-bit output and 8-aligned channel strides / offsets");
-  if (tile == YV4_HTILE_W3x3 || w3_forced >= 0) {
+  const bool forced = d->tile != YV4_TILE_AUTO;      // (a forced id alone can pin a wide family's shape; else the launch picks)
+  const TileId id = forced ? decode_tile_h16(d->tile) : TileId{auto_route_h16(a), -1};
+  const int tile = id.tile;
+  const bool bf16 = dtype == YV4_BF16;
+  if (tile == YV4_HTILE_W3x3) {
+    YV4_REQUIRE(!forced || conv3x3_wide_h16_applies(a), "conv h16: the wide 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with Cin %% 64 "
+                "== 0, Cout %% 16 == 0 (64 .. 1024), 16-bit output and 8-aligned channel strides / offsets");
     static const int shape = YV4_ENV_INT("YV4_W3_SHAPE", -1);
-    return conv3x3_wide_h16_launch(a, dtype == YV4_BF16, w3_forced >= 0 ? w3_forced : shape, s);
+    return conv3x3_wide_h16_launch(a, bf16, id.shape >= 0 ? id.shape : shape, s);
   }
-  const int wide_forced = (d->tile >= YV4_HTILE_WIDE_SHAPE(0) && (d->tile & 7) == 0 && d->tile <= YV4_HTILE_WIDE_SHAPE(4)) ? (d->tile >> 3) - 2 : -1;
-  if (d->tile == YV4_HTILE_WIDE || wide_forced >= 0)
-    YV4_REQUIRE(conv_wide_h16_applies(a), "conv h16: the wide general tile needs Cin %% 64 == 0, Cout %% 16 == 0 (64 .. 2048), 16-bit "
-                "output and 8-aligned channel strides / offsets");
-  if (tile == YV4_HTILE_WIDE || wide_forced >= 0) {
+  if (tile == YV4_HTILE_WIDE) {
+    YV4_REQUIRE(!forced || conv_wide_h16_applies(a), "conv h16: the wide general tile needs Cin %% 64 == 0, Cout %% 16 == 0 (64 .. 2048), "
+                "16-bit output and 8-aligned channel strides / offsets");
     static const int shape = YV4_ENV_INT("YV4_WIDE_SHAPE", -1);
-    return conv_wide_h16_launch(a, dtype == YV4_BF16, wide_forced >= 0 ? wide_forced : shape, s);
+    return conv_wide_h16_launch(a, bf16, id.shape >= 0 ? id.shape : shape, s);
   }
-  if (d->tile == YV4_HTILE_PP3x3)
-    YV4_REQUIRE(conv3x3_pp_h16_applies(a), "conv h16: the ping-pong 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with "
+  if (tile == YV4_HTILE_PP3x3) {
+    YV4_REQUIRE(!forced || conv3x3_pp_h16_applies(a), "conv h16: the ping-pong 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with "
                 "Cin %% 64 == 0, even Cout >= 64, 16-bit output and even channel strides / offsets");
-  if (tile == YV4_HTILE_PP3x3) return conv3x3_pp_h16_launch(a, dtype == YV4_BF16, s);
-  if (d->tile == YV4_HTILE_WS_1x1)
-    YV4_REQUIRE(conv1x1_ws_applies(a), "conv h16: the weight-stationary tile needs a 1x1 / stride 1 conv with Cin <= 256, "
+    return conv3x3_pp_h16_launch(a, bf16, s);
+  }
+  if (tile == YV4_HTILE_WS_1x1) {
+    YV4_REQUIRE(!forced || conv1x1_ws_applies(a), "conv h16: the weight-stationary tile needs a 1x1 / stride 1 conv with Cin <= 256, "
                 "Cout >= 16 (even unless the output is fp32); a residual needs a 16-bit output");
-  if (tile == YV4_HTILE_WS_1x1) return conv1x1_ws_launch(a, dtype == YV4_BF16, s);
-  if (d->tile == YV4_HTILE_S3x3)
-    YV4_REQUIRE(conv3x3_small_applies(a), "conv h16: the few-channel 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with Cin 16, 32 "
-                "or 64, even Cout in [16, 64] and 16-bit output");
-  if (tile == YV4_HTILE_S3x3) return conv3x3_small_launch(a, dtype == YV4_BF16, s);
-  return dtype == YV4_BF16 ? dispatch_h16<true>(a, tile, general, s) : dispatch_h16<false>(a, tile, general, s);
+    return conv1x1_ws_launch(a, bf16, s);
+  }
+  if (tile == YV4_HTILE_S3x3) {
+    YV4_REQUIRE(!forced || conv3x3_small_applies(a), "conv h16: the few-channel 3x3 tile needs a 3x3 / stride 1 / pad 1 conv with Cin 16, "
+                "32 or 64, even Cout in [16, 64] and 16-bit output");
+    return conv3x3_small_launch(a, bf16, s);
+  }
+  return bf16 ? dispatch_h16<true>(a, tile, general, s) : dispatch_h16<false>(a, tile, general, s);
 }
 
 extern "C" int yv4_conv_bn_act_fwd_h16(const yv4_conv_desc* d, int dtype, int out_dtype, const void* x, const void* w,
@@ -660,19 +640,16 @@ __global__ __launch_bounds__(256) void splitk_finish_h16_kernel(ConvArgsH p) {
   }
 }
 
-// how many ways to split K on a 256-CU chip: double while the 64 x 64 tiles x splits stay under ~2 per CU and every split
-// keeps at least 4 slices of 64; 1 = do not split (enough tiles already, or a layer outside the uniform-K tiles)
+// how many ways to split K for this layer's 64 x 64 tiles (splitk_ways, conv_route.h): ~2 workgroups per CU, at least 4
+// slices of 64 per split; 1 = do not split (enough tiles already, or a layer outside the uniform-K tiles)
 static int splitk_choice_h16(const yv4_conv_desc* d) {
   const long long M = (long long)d->N * d->Ho * d->Wo;
   const ConvArgsH a = conv_args_h(d, 0);
   if (d->Cin % kHBK != 0 || M >= (1LL << 31) || !dma_addressable(a)) return 1;
   const long long tiles = ((M + 63) / 64) * ((d->Cout + 63) / 64);
-  const int nk = a.K / kHBK;
   static const int target = YV4_ENV_INT("YV4_SPLITK_TARGET_H16", 512);
   static const int min_slices = YV4_ENV_INT("YV4_SPLITK_MINSL_H16", 4);
-  int ks = 1;
-  while (tiles * ks < target && nk / (ks * 2) >= min_slices && ks < 32) ks *= 2;
-  return ks;
+  return splitk_ways(tiles, a.K / kHBK, target, min_slices);
 }
 }  // namespace yv4
 
@@ -681,9 +658,7 @@ extern "C" size_t yv4_conv_h16_splitk_workspace(const yv4_conv_desc* d, int* ksp
   if (!d) return 0;
   const int ks = splitk_choice_h16(d);
   if (ksplit) *ksplit = ks;
-  if (ks <= 1) return 0;
-  const long long M = (long long)d->N * d->Ho * d->Wo;
-  return (size_t)ks * (size_t)M * (size_t)((d->Cout + 7) / 8 * 8) * sizeof(float);
+  return splitk_workspace_bytes(d, ks, 8);
 }
 
 extern "C" int yv4_conv_bn_act_fwd_h16_splitk(const yv4_conv_desc* d, int dtype, int out_dtype, const void* x, const void* w,
@@ -697,28 +672,15 @@ extern "C" int yv4_conv_bn_act_fwd_h16_splitk(const yv4_conv_desc* d, int dtype,
   YV4_REQUIRE(dtype == YV4_F16 || dtype == YV4_BF16, "conv h16 splitk: dtype must be YV4_F16 or YV4_BF16");
   YV4_REQUIRE(out_dtype == dtype || out_dtype == YV4_F32, "conv h16 splitk: out_dtype must be the operand type or YV4_F32");
   YV4_REQUIRE((scale2 == nullptr) == (shift2 == nullptr), "conv h16 splitk: scale2/shift2 must come together");
-  YV4_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->KH * d->KW <= 64 &&
-              d->stride > 0 && d->pad >= 0, "conv h16 splitk: bad shape");
-  YV4_REQUIRE(d->x_cstride % 8 == 0 && d->x_coff % 8 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 &&
-              ((uintptr_t)workspace & 15) == 0, "conv h16 splitk: alignment");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride && d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride,
-              "conv h16 splitk: view exceeds its pixel stride");
-  const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-  YV4_REQUIRE(Ho == d->Ho && Wo == d->Wo, "conv h16 splitk: Ho/Wo do not match the geometry");
-  if (residual) YV4_REQUIRE(d->r_coff >= 0 && d->r_coff + d->Cout <= d->r_cstride, "conv h16 splitk: residual view");
-  YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH && d->act2 >= 0 && d->act2 <= YV4_ACT_SWISH, "conv h16 splitk: activation id");
-  YV4_REQUIRE(workspace_bytes >= yv4_conv_h16_splitk_workspace(d, nullptr), "conv h16 splitk: workspace too small");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
+  if (int rc = check_conv_desc(d, "conv h16 splitk", {8, residual != nullptr})) return rc;
+  YV4_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)workspace & 15) == 0,
+              "conv h16 splitk: x / w / workspace must be 16-byte aligned");
+  YV4_REQUIRE(workspace_bytes >= splitk_workspace_bytes(d, ks, 8), "conv h16 splitk: workspace too small");
   ConvArgsH a = conv_args_h(d, out_dtype == YV4_F32 ? 1 : 0, x, w, scale1, shift1, scale2, shift2, residual, y);
-  const int nk = a.K / kHBK;
-  a.ks_slices = (nk + ks - 1) / ks;
-  a.ksplit = (nk + a.ks_slices - 1) / a.ks_slices;      // no empty split (72 slices 16 ways = 15 splits of 5, the last of 2)
-  a.ws_cs = (d->Cout + 7) / 8 * 8; a.ws = workspace;
+  splitk_set(a, ks, kHBK, 8, workspace);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (int rc = dtype == YV4_BF16 ? launch_h16<true, 64, 64, false, 2>(a, s) : launch_h16<false, 64, 64, false, 2>(a, s)) return rc;
-  const long long work = M * (a.ws_cs / 8);
-  unsigned g = (unsigned)((work + 255) / 256);
-  if (g > 2048) g = 2048;
+  const unsigned g = splitk_finish_grid(a, 8);
   if (dtype == YV4_BF16) hipLaunchKernelGGL(splitk_finish_h16_kernel<true>, dim3(g), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(splitk_finish_h16_kernel<false>, dim3(g), dim3(256), 0, s, a);
   YV4_CHECK_LAUNCH("conv h16 splitk finish");
@@ -731,30 +693,26 @@ extern "C" int yv4_conv_scatter_fwd_h16(const yv4_conv_desc* d, int dtype, const
                                         int oh, int ow, void* stream) {
   YV4_REQUIRE(d && x && w && scale1 && shift1 && y, "conv scatter h16: null argument");
   YV4_REQUIRE(dtype == YV4_F16 || dtype == YV4_BF16, "conv scatter h16: dtype must be YV4_F16 or YV4_BF16");
-  YV4_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->Ho > 0 && d->Wo > 0,
-              "conv scatter h16: empty shape");
-  YV4_REQUIRE(d->KH > 0 && d->KW > 0 && d->KH * d->KW <= 64 && d->stride == 1 && d->pad >= 0,
-              "conv scatter h16: stride-1 kernels only");
-  YV4_REQUIRE(d->Cin % 8 == 0 && d->x_cstride % 8 == 0 && d->x_coff % 8 == 0 && d->y_cstride % 8 == 0 && d->y_coff % 8 == 0,
-              "conv scatter h16: channel counts / strides / offsets must be multiples of 8");
+  ConvDescRules rules{8};
+  rules.scatter = rules.align_y = true; rules.acts = 0;
+  if (int rc = check_conv_desc(d, "conv scatter h16", rules)) return rc;
   YV4_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0, "conv scatter h16: x / w must be 16-byte aligned");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride && d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride,
-              "conv scatter h16: view exceeds its pixel stride");
   YV4_REQUIRE(sh > 0 && sw > 0 && oh >= 0 && ow >= 0 && (d->Ho - 1) * sh + oh < Hy && (d->Wo - 1) * sw + ow < Wy,
               "conv scatter h16: the scattered grid does not fit the output tensor");
-  const long long M = (long long)d->N * d->Ho * d->Wo;
   ConvArgsH a = conv_args_h(d, 0, x, w, scale1, shift1, nullptr, nullptr, nullptr, y);
-  YV4_REQUIRE(M < (1LL << 31) && dma_addressable(a), "conv scatter h16: tensors of 4 GiB or more are not supported");
+  YV4_REQUIRE(dma_addressable(a), "conv scatter h16: tensors of 4 GiB or more are not supported");
   a.act1 = 0; a.act2 = 0;      // identity epilogue, whatever the descriptor's activation fields hold
   a.nt_out = (d->flags & YV4_CONV_NT_OUT) ? 1 : 0;
   a.ys_on = 1; a.ys_H = Hy; a.ys_W = Wy; a.ys_sh = sh; a.ys_sw = sw; a.ys_oh = oh; a.ys_ow = ow;
   const bool general = (d->Cin % kHBK) != 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // the classes of the wide stride-2 layers' data gradients: the general wide-tile kernel (same bits as the generic tiles)
-  if (d->tile == YV4_HTILE_WIDE || (d->tile == YV4_TILE_AUTO && prefer_wide(a))) {
+  // (the family alone: an id that pins a shape goes on to the generic tiles' dispatch, which refuses it)
+  const TileId id = decode_tile_h16(d->tile);
+  if ((id.tile == YV4_HTILE_WIDE && id.shape < 0) || (d->tile == YV4_TILE_AUTO && prefer_wide(a))) {
     YV4_REQUIRE(conv_wide_h16_applies(a), "conv scatter h16: the wide tile needs Cin %% 64 == 0, Cout %% 16 == 0 and 8-aligned views");
     return conv_wide_h16_launch(a, dtype == YV4_BF16, -1, s);
   }
-  const int tile = d->tile == YV4_TILE_AUTO ? pick_tile_h16(M, d->Cout, a.K) : d->tile;
+  const int tile = d->tile == YV4_TILE_AUTO ? pick_tile_h16(a.M, d->Cout, a.K) : d->tile;
   return dtype == YV4_BF16 ? dispatch_h16<true>(a, tile, general, s) : dispatch_h16<false>(a, tile, general, s);
 }

@@ -8,6 +8,7 @@
 // the buffer descriptor), holds the 18 weight values it needs for the whole kernel, issues
 // 18 MFMAs per tile and streams the epilogue to HBM in 128-byte rows.
 #include "conv_f32_common.h"
+#include "conv_desc.h"
 
 namespace yv4 {
 
@@ -166,12 +167,10 @@ extern "C" int yv4_conv_stem_fwd(const yv4_conv_desc* d, const float* x, const f
                                  const float* shift1, void* y, int out_dtype, void* stream) {
   YV4_REQUIRE(d && x && w && scale1 && shift1 && y, "conv stem: null argument");
   YV4_REQUIRE(out_dtype == YV4_F32 || out_dtype == YV4_F16 || out_dtype == YV4_BF16, "conv stem: bad out_dtype");
+  ConvDescRules rules{1};      // (alignment is part of the shape rule below, with which the geometry check says Ho/Wo == H/W)
+  rules.acts = 1;
+  if (int rc = check_conv_desc(d, "conv stem", rules)) return rc;
   const ConvArgs a = conv_args(d, x, w, scale1, shift1, nullptr, nullptr, nullptr, reinterpret_cast<float*>(y));
   YV4_REQUIRE(stem_ok(a), "conv stem: needs Cin 4 (3 padded), 3x3, stride 1, pad 1, Cout <= 64");
-  YV4_REQUIRE(d->Ho == d->H && d->Wo == d->W, "conv stem: Ho/Wo must equal H/W");
-  YV4_REQUIRE(d->x_coff + d->Cin <= d->x_cstride && d->y_coff >= 0 && d->y_coff + d->Cout <= d->y_cstride,
-              "conv stem: view exceeds its pixel stride");
-  YV4_REQUIRE(d->act1 >= 0 && d->act1 <= YV4_ACT_SWISH, "conv stem: unknown activation id");
-  YV4_REQUIRE((long long)d->N * d->Ho * d->Wo < (1LL << 31), "conv stem: N*Ho*Wo does not fit 31 bits");
   return conv_stem_f32_launch(a, out_dtype, reinterpret_cast<hipStream_t>(stream));
 }

@@ -9,6 +9,7 @@
 // weights transposed and flipped; for stride 2 dY is first zero-dilated (yv4_dilate2_fwd, elementwise_bwd.hip).
 #include "train_common.h"
 #include "wgrad_common.h"
+#include "conv_desc.h"
 
 namespace yv4 {
 
@@ -618,13 +619,14 @@ static const bool g_wgrad_xcd = YV4_ENV_INT("YV4_WGRAD_XCD", 1) != 0;
 static void wgrad_chunks(const yv4_conv_desc* d, int dtype, long long* chunks, long long* rows) {
   const long long M = (long long)d->N * d->Ho * d->Wo;
   const int K = d->KH * d->KW * d->Cin;
+  // `ch` chunks wanted: whole slices of `unit` rows per chunk, and the chunks that leaves
+  auto split = [&](long long ch, int unit) {
+    *rows = ((M + ch - 1) / ch + unit - 1) / unit * unit;
+    *chunks = (M + *rows - 1) / *rows;
+  };
   if (!g_wgrad_widen && wgrad_fc_cin(d, dtype)) {
     // one round of workgroups (two per CU; one for Cin 64), every one with at least four slices (wgrad_fc_cin)
-    long long ch = wgrad_fc_cin(d, dtype) == 64 ? 256 : 512;
-    long long rw = (M + ch - 1) / ch;
-    rw = (rw + kFcRows - 1) / kFcRows * kFcRows;
-    *rows = rw;
-    *chunks = (M + rw - 1) / rw;
+    split(wgrad_fc_cin(d, dtype) == 64 ? 256 : 512, kFcRows);
     return;
   }
   if (!g_wgrad_widen && wgrad3x3_applies(d, dtype)) {
@@ -642,10 +644,7 @@ static void wgrad_chunks(const yv4_conv_desc* d, int dtype, long long* chunks, l
     if (ch > 65535) ch = 65535;
     // XCD-aware mapping (wgrad_tile_chunk): a chunk's tiles on ONE XCD need the chunk count in whole groups of eight
     if (w3_xcd_map(tl, ch)) ch = ch / 8 * 8;
-    long long rw = (M + ch - 1) / ch;
-    rw = (rw + kW3Rows - 1) / kW3Rows * kW3Rows;
-    *rows = rw;
-    *chunks = (M + rw - 1) / rw;
+    split(ch, kW3Rows);
     return;
   }
   if (dtype != YV4_F32 && !g_wgrad_widen) {
@@ -673,10 +672,7 @@ static void wgrad_chunks(const yv4_conv_desc* d, int dtype, long long* chunks, l
     if (ch < 1) ch = 1;
     if (tl >= 2 && ch >= 16 && d->Cout >= 128) ch = ch / 8 * 8;   // whole groups of 8 chunks, one per XCD (wgrad_tile_chunk)
     if (ch > 65528) ch = 65528;
-    long long rw = (M + ch - 1) / ch;
-    rw = (rw + kWhRows - 1) / kWhRows * kWhRows;
-    *rows = rw;
-    *chunks = (M + rw - 1) / rw;
+    split(ch, kWhRows);
     return;
   }
   const long long tiles = (long long)((K + 63) / 64) * ((d->Cout + 63) / 64);
@@ -685,37 +681,21 @@ static void wgrad_chunks(const yv4_conv_desc* d, int dtype, long long* chunks, l
   if (ch > mx) ch = mx;
   if (ch < 1) ch = 1;
   if (ch > 65535) ch = 65535;
-  long long rw = (M + ch - 1) / ch;
-  rw = (rw + kWgRows - 1) / kWgRows * kWgRows;
-  *rows = rw;
-  *chunks = (M + rw - 1) / rw;
+  split(ch, kWgRows);
 }
 
 static int wgrad_impl(const yv4_conv_desc* d, int dtype, const void* x, const void* dy, float* dw, void* stream,
                       float* ws = nullptr, size_t ws_bytes = 0) {
   YV4_REQUIRE(d && x && dy && dw, "wgrad: null argument");
   YV4_REQUIRE(dtype == YV4_F32 || dtype == YV4_F16 || dtype == YV4_BF16, "wgrad: dtype must be f32, f16 or bf16");
-  const int al = dtype == YV4_F32 ? 4 : 8;
   const int es = dtype == YV4_F32 ? 4 : 2;
-  YV4_REQUIRE(d->Cin % al == 0 && d->x_cstride % al == 0 && d->x_coff % al == 0,
-              "wgrad: input channels/stride/offset must be multiples of %d", al);
-  YV4_REQUIRE(d->Cout % al == 0 && d->y_cstride % al == 0 && d->y_coff % al == 0,
-              "wgrad: dY channels/stride/offset must be multiples of %d", al);
-  YV4_REQUIRE(d->KH > 0 && d->KW > 0 && d->KH * d->KW <= 64 && d->stride > 0, "wgrad: bad kernel/stride");
-  const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-  const int Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-  YV4_REQUIRE(Ho == d->Ho && Wo == d->Wo, "wgrad: Ho/Wo do not match the geometry");
+  ConvDescRules rules{dtype == YV4_F32 ? 4 : 8};
+  rules.align_cout = rules.align_y = true; rules.acts = 0;      // (dY, the descriptor's y view, is an operand: aligned like x)
+  if (int rc = check_conv_desc(d, "wgrad", rules)) return rc;
   const long long M = (long long)d->N * d->Ho * d->Wo;
   const long long xb = (long long)d->N * d->H * d->W * d->x_cstride * es, db = M * d->y_cstride * es;
-  YV4_REQUIRE(M < (1LL << 31) && desc_addressable(xb) && desc_addressable(db), "wgrad: tensors of 4 GiB or more are not supported");
-  WgradArgs a;
-  a.x = x; a.dy = dy; a.dw = dw;
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.dy_cs = d->y_cstride; a.dy_co = d->y_coff;
-  a.M = (int)M; a.K = d->KH * d->KW * d->Cin;
-  a.fd_hw = make_fastdiv((unsigned)(d->Ho * d->Wo));
-  a.fd_wo = make_fastdiv((unsigned)d->Wo);
+  YV4_REQUIRE(desc_addressable(xb) && desc_addressable(db), "wgrad: tensors of 4 GiB or more are not supported");
+  WgradArgs a = wgrad_args(d, x, dy, dw);
   long long ch = 1, rw = M;
   wgrad_chunks(d, dtype, &ch, &rw);
   a.rows_per_chunk = (int)rw;

@@ -31,6 +31,19 @@ struct WgradArgs {
   long long ws_stride = 0;
 };
 
+// The argument block of a descriptor (its y view is dY) and its tensors, as conv_args (conv_f32_common.h).  The dispatcher
+// sets the chunking and the deterministic slabs, a launch function its family's fields.
+static inline WgradArgs wgrad_args(const yv4_conv_desc* d, const void* x, const void* dy, float* dw) {
+  WgradArgs a{};
+  a.x = x; a.dy = dy; a.dw = dw;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
+  a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+  a.x_cs = d->x_cstride; a.x_co = d->x_coff; a.dy_cs = d->y_cstride; a.dy_co = d->y_coff;
+  a.M = (int)((long long)d->N * d->Ho * d->Wo); a.K = d->KH * d->KW * d->Cin;
+  a.fd_hw = make_fastdiv((unsigned)(d->Ho * d->Wo)); a.fd_wo = make_fastdiv((unsigned)d->Wo);
+  return a;
+}
+
 constexpr int kWgRows = 32;   // reduction rows per slice: the generic fp32 / widening kernel
 constexpr int kW3Rows = 64;   // the 3x3 kernels (conv_wgrad3x3_h16.hip)
 constexpr int kFcRows = 64;   // the few-channel kernels (conv_wgrad_fc_h16.hip)

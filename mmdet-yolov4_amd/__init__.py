@@ -39,6 +39,10 @@ from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: 
 from .analysis import ResultVisualizer, bbox_map_eval, image_maps  # noqa: F401
 from .datasets import (CocoDataset, DistributedGroupSampler, GroupSampler, TestLoader, TrainLoader,  # noqa: F401
                        build_dataset, build_test_loader, build_train_loader)
+from .augment_plain import PlainTrainPipeline  # noqa: F401
+from .custom_datasets import (CustomDataset, GarbageDataset, TrafficSignDataset, VOCDataset,  # noqa: F401
+                              XMLDataset)
+from .dataset_wrappers import ClassBalancedDataset, ConcatDataset, RepeatDataset  # noqa: F401
 
 from .hooks import (EpochBasedRunner, IterTimerHook, StepLrUpdaterHook, TextLoggerHook, build_runner)  # noqa: F401
 

@@ -44,7 +44,15 @@ class FusedTrainPipeline:
                  mean=(114, 114, 114), std=(255, 255, 255), to_rgb=True, max_boxes=512, device=None):
         self.img_scale = tuple(img_scale)
         self.pad_val, self.pad_to, self.crop, self.out = int(pad_val), int(pad_to), int(crop), int(out_size)
-        self.scale_limit, self.flip_p = float(scale_limit), float(flip_p)
+        # albumentations' to_tuple(scale_limit): one number s is the range (-s, s), a pair is the range itself; the
+        # factor is 1 + a draw from it (the traffic-sign recipe scales down only: scale_limit=(-0.5, 0))
+        if isinstance(scale_limit, (tuple, list)):
+            self.scale_limit = (float(scale_limit[0]), float(scale_limit[1]))
+            self.scale_range = (min(self.scale_limit), max(self.scale_limit))
+        else:
+            self.scale_limit = float(scale_limit)
+            self.scale_range = (-self.scale_limit, self.scale_limit)
+        self.flip_p = float(flip_p)
         self.min_area, self.min_visibility = float(min_area), float(min_visibility)
         self.hsv = None if hsv is None else tuple(float(v) for v in hsv)
         self.min_size, self.max_ar = float(min_size), float(max_aspect_ratio)
@@ -53,7 +61,7 @@ class FusedTrainPipeline:
         self.to_rgb = bool(to_rgb)
         self.max_boxes = int(max_boxes)
         self.device = device
-        if int(self.crop * (1 - self.scale_limit)) < self.out:
+        if int(self.crop * (1 + self.scale_range[0])) < self.out:
             raise ValueError('CenterCrop larger than the smallest RandomScale output')
 
     @classmethod
@@ -110,7 +118,7 @@ class FusedTrainPipeline:
         """One sample's random parameters: RandomCrop's (h_start, w_start), RandomScale's factor, HorizontalFlip, the
         three colour gains ``uniform(-1, 1) * ratio + 1`` (transforms.py:1998-1999)."""
         p = dict(h_start=float(rng.random()), w_start=float(rng.random()),
-                 scale=float(1.0 + rng.uniform(-self.scale_limit, self.scale_limit)),
+                 scale=float(1.0 + rng.uniform(*self.scale_range)),
                  flip=bool(rng.random() < self.flip_p), pad_to=self.pad_to, crop=self.crop, out=self.out)
         if self.hsv is not None:
             p['hsv'] = tuple(float(rng.uniform(-1.0, 1.0)) * r + 1.0 for r in self.hsv)

@@ -52,6 +52,102 @@ def _centres_in(boxes, patch):
     return (c[:, 0] > patch[0]) & (c[:, 1] > patch[1]) & (c[:, 0] < patch[2]) & (c[:, 1] < patch[3])
 
 
+def draw_resize_scale(rng, img_scale, multiscale_mode):
+    """``Resize._random_scale`` without ``ratio_range`` (transforms.py:101-203): one scale as it is, ``'range'`` through
+    ``random_sample`` (long edge, then short edge), ``'value'`` through ``random_select``.  ``img_scale``: a list of
+    (long, short) tuples.  Shared with ``augment_plain.PlainTrainPipeline``."""
+    if len(img_scale) == 1:
+        scale = img_scale[0]
+    elif multiscale_mode == 'range':
+        longs, shorts = [max(s) for s in img_scale], [min(s) for s in img_scale]
+        long_edge = rng.randint(min(longs), max(longs) + 1)
+        short_edge = rng.randint(min(shorts), max(shorts) + 1)
+        scale = (long_edge, short_edge)
+    else:
+        scale = img_scale[rng.randint(len(img_scale))]
+    return scale
+
+
+def draw_flip(rng, flip_ratio, flip_direction):
+    """``RandomFlip.__call__``'s draw for one direction (transforms.py:430-452): the direction, or ``None``."""
+    single = flip_ratio / 1
+    cur = rng.choice([flip_direction, None], p=[single, 1 - flip_ratio])
+    return None if cur is None else str(cur)
+
+
+def resize_flip_boxes(boxes, h, w, rh, rw, flip):
+    """``Resize._resize_bboxes`` (transforms.py:236-244: scale by the float32 ``scale_factor``, clip to the resized image)
+    and ``RandomFlip.bbox_flip`` (:384-416) for float32 (k, 4) boxes of an (h, w) image resized to (rh, rw) -> (boxes, scale_factor)."""
+    scale_factor = np.array([rw / w, rh / h, rw / w, rh / h], dtype=np.float32)
+    boxes = boxes * scale_factor
+    boxes[:, 0::2] = np.clip(boxes[:, 0::2], 0, rw)
+    boxes[:, 1::2] = np.clip(boxes[:, 1::2], 0, rh)
+    if flip is not None:
+        f = boxes.copy()
+        if flip in ('horizontal', 'diagonal'):
+            f[:, 0], f[:, 2] = rw - boxes[:, 2], rw - boxes[:, 0]
+        if flip in ('vertical', 'diagonal'):
+            f[:, 1], f[:, 3] = rh - boxes[:, 3], rh - boxes[:, 1]
+        boxes = f
+    return boxes, scale_factor
+
+
+def upload_boxes(boxes, labels, dev):
+    """The boxes and labels of a whole batch in one upload -- (T, 4) float32 followed by (T,) int64 -- split per image
+    again: ``(gt_bboxes, gt_labels)``, lists of device tensors."""
+    counts = [len(b) for b in boxes]
+    T = sum(counts)
+    blob = np.concatenate(boxes, 0).tobytes() + np.concatenate(labels, 0).tobytes()
+    if T:
+        d_blob = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
+        d_boxes, d_labels = d_blob[:16 * T].view(torch.float32).view(T, 4), d_blob[16 * T:].view(torch.int64)
+    else:
+        d_boxes = torch.empty((0, 4), dtype=torch.float32, device=dev)
+        d_labels = torch.empty((0,), dtype=torch.int64, device=dev)
+    return list(torch.split(d_boxes, counts)), list(torch.split(d_labels, counts))
+
+
+def parse_geometry_transform(t, kw):
+    """The options of one ``Resize`` / ``RandomFlip`` / ``Normalize`` / ``Pad`` block into the keyword dict ``kw``, every
+    option outside the built set refused by name; ``False`` for any other transform.  Shared with
+    ``augment_plain.PlainTrainPipeline``."""
+    typ = t['type']
+    if typ == 'Resize':
+        _only(t, ('img_scale', 'multiscale_mode', 'ratio_range', 'keep_ratio', 'bbox_clip_border', 'backend',
+                  'override'))
+        if t.get('ratio_range') is not None:
+            raise NotImplementedError('Resize: ratio_range is not built')
+        if not t.get('keep_ratio', True):
+            raise NotImplementedError('Resize: keep_ratio=False is not built')
+        if not t.get('bbox_clip_border', True):
+            raise NotImplementedError('Resize: bbox_clip_border=False is not built')
+        if t.get('backend', 'cv2') != 'cv2' or t.get('override', False):
+            raise NotImplementedError('Resize: backend / override are not built')
+        if t.get('img_scale') is None:
+            raise NotImplementedError('Resize: img_scale=None is not built')
+        kw.update(img_scale=t['img_scale'], multiscale_mode=t.get('multiscale_mode', 'range'))
+    elif typ == 'RandomFlip':
+        _only(t, ('flip_ratio', 'direction'))
+        if isinstance(t.get('direction', 'horizontal'), (list, tuple)):
+            raise NotImplementedError('RandomFlip: direction lists are not built')
+        if not isinstance(t.get('flip_ratio'), float):
+            raise NotImplementedError('RandomFlip: flip_ratio must be one float')
+        kw.update(flip_ratio=t['flip_ratio'], flip_direction=t.get('direction', 'horizontal'))
+    elif typ == 'Normalize':
+        _only(t, ('mean', 'std', 'to_rgb'))
+        kw.update(mean=t['mean'], std=t['std'], to_rgb=t.get('to_rgb', True))
+    elif typ == 'Pad':
+        _only(t, ('size', 'size_divisor', 'pad_val'))
+        if t.get('size') is not None:
+            raise NotImplementedError('Pad: size= is not built (size_divisor only)')
+        if t.get('size_divisor') is None or t.get('pad_val', 0) != 0:
+            raise NotImplementedError('Pad: size_divisor with pad_val=0 is the only form built')
+        kw['size_divisor'] = t['size_divisor']
+    else:
+        return False
+    return True
+
+
 class FusedV3TrainPipeline:
 
     def __init__(self, brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5), hue_delta=18,
@@ -118,37 +214,8 @@ class FusedV3TrainPipeline:
                 if not t.get('bbox_clip_border', True):
                     raise NotImplementedError('MinIoURandomCrop: bbox_clip_border=False is not built')
                 kw.update(min_ious=t.get('min_ious', (0.1, 0.3, 0.5, 0.7, 0.9)), min_crop_size=t.get('min_crop_size', 0.3))
-            elif typ == 'Resize':
-                _only(t, ('img_scale', 'multiscale_mode', 'ratio_range', 'keep_ratio', 'bbox_clip_border', 'backend',
-                          'override'))
-                if t.get('ratio_range') is not None:
-                    raise NotImplementedError('Resize: ratio_range is not built')
-                if not t.get('keep_ratio', True):
-                    raise NotImplementedError('Resize: keep_ratio=False is not built')
-                if not t.get('bbox_clip_border', True):
-                    raise NotImplementedError('Resize: bbox_clip_border=False is not built')
-                if t.get('backend', 'cv2') != 'cv2' or t.get('override', False):
-                    raise NotImplementedError('Resize: backend / override are not built')
-                if t.get('img_scale') is None:
-                    raise NotImplementedError('Resize: img_scale=None is not built')
-                kw.update(img_scale=t['img_scale'], multiscale_mode=t.get('multiscale_mode', 'range'))
-            elif typ == 'RandomFlip':
-                _only(t, ('flip_ratio', 'direction'))
-                if isinstance(t.get('direction', 'horizontal'), (list, tuple)):
-                    raise NotImplementedError('RandomFlip: direction lists are not built')
-                if not isinstance(t.get('flip_ratio'), float):
-                    raise NotImplementedError('RandomFlip: flip_ratio must be one float')
-                kw.update(flip_ratio=t['flip_ratio'], flip_direction=t.get('direction', 'horizontal'))
-            elif typ == 'Normalize':
-                _only(t, ('mean', 'std', 'to_rgb'))
-                kw.update(mean=t['mean'], std=t['std'], to_rgb=t.get('to_rgb', True))
-            elif typ == 'Pad':
-                _only(t, ('size', 'size_divisor', 'pad_val'))
-                if t.get('size') is not None:
-                    raise NotImplementedError('Pad: size= is not built (size_divisor only)')
-                if t.get('size_divisor') is None or t.get('pad_val', 0) != 0:
-                    raise NotImplementedError('Pad: size_divisor with pad_val=0 is the only form built')
-                kw['size_divisor'] = t['size_divisor']
+            elif parse_geometry_transform(t, kw):
+                pass
             else:
                 raise NotImplementedError(f'train pipeline transform {typ!r} is not built')
         if tuple(seen) != _ORDER:
@@ -218,21 +285,11 @@ class FusedV3TrainPipeline:
             x1, y1, x2, y2 = p['crop']
             ch, cw = min(y2, H) - y1, min(x2, W) - x1
         # Resize
-        if len(self.img_scale) == 1:
-            scale = self.img_scale[0]
-        elif self.multiscale_mode == 'range':
-            longs, shorts = [max(s) for s in self.img_scale], [min(s) for s in self.img_scale]
-            long_edge = rng.randint(min(longs), max(longs) + 1)
-            short_edge = rng.randint(min(shorts), max(shorts) + 1)
-            scale = (long_edge, short_edge)
-        else:
-            scale = self.img_scale[rng.randint(len(self.img_scale))]
+        scale = draw_resize_scale(rng, self.img_scale, self.multiscale_mode)
         p['scale'] = (int(scale[0]), int(scale[1]))
         p['rh'], p['rw'] = rescale_size(ch, cw, scale)
         # RandomFlip
-        single = self.flip_ratio / 1
-        cur = rng.choice([self.flip_direction, None], p=[single, 1 - self.flip_ratio])
-        p['flip'] = None if cur is None else str(cur)
+        p['flip'] = draw_flip(rng, self.flip_ratio, self.flip_direction)
         return p
 
     # ---- boxes (host, numpy float32 as the reference) ---------------------------------------------------------------
@@ -262,18 +319,7 @@ class FusedV3TrainPipeline:
             boxes[:, 2:] = np.minimum(boxes[:, 2:], pf[2:])
             boxes[:, :2] = np.maximum(boxes[:, :2], pf[:2])
             boxes -= np.tile(pf[:2], 2)
-        rh, rw = p['rh'], p['rw']
-        scale_factor = np.array([rw / cw, rh / ch, rw / cw, rh / ch], dtype=np.float32)
-        boxes = boxes * scale_factor
-        boxes[:, 0::2] = np.clip(boxes[:, 0::2], 0, rw)
-        boxes[:, 1::2] = np.clip(boxes[:, 1::2], 0, rh)
-        if p['flip'] is not None:
-            f = boxes.copy()
-            if p['flip'] in ('horizontal', 'diagonal'):
-                f[:, 0], f[:, 2] = rw - boxes[:, 2], rw - boxes[:, 0]
-            if p['flip'] in ('vertical', 'diagonal'):
-                f[:, 1], f[:, 3] = rh - boxes[:, 3], rh - boxes[:, 1]
-            boxes = f
+        boxes, scale_factor = resize_flip_boxes(boxes, ch, cw, p['rh'], p['rw'], p['flip'])
         return boxes, labels, scale_factor
 
     def pad_shape(self, p):
@@ -362,26 +408,21 @@ class FusedV3TrainPipeline:
             check(_lib.lib().yv4_v3_augment_u8(d_table.data_ptr(), N, img.data_ptr(), Hmax, Wmax,
                                                self.mean.ctypes.data_as(C.c_void_p), self.std.ctypes.data_as(C.c_void_p),
                                                int(self.to_rgb), stream_ptr()), 'yv4_v3_augment_u8')
-        # boxes and labels of the whole batch in one upload: (T, 4) float32 followed by (T,) int64
-        counts = [len(b) for b in boxes]
-        T = sum(counts)
-        blob = np.concatenate(boxes, 0).tobytes() + np.concatenate(labels, 0).tobytes()
-        if T:
-            d_blob = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
-            d_boxes, d_labels = d_blob[:16 * T].view(torch.float32).view(T, 4), d_blob[16 * T:].view(torch.int64)
-        else:
-            d_boxes = torch.empty((0, 4), dtype=torch.float32, device=dev)
-            d_labels = torch.empty((0,), dtype=torch.int64, device=dev)
-        return dict(img=img, gt_bboxes=list(torch.split(d_boxes, counts)), gt_labels=list(torch.split(d_labels, counts)),
-                    img_metas=metas, params=params)
+        gt_bboxes, gt_labels = upload_boxes(boxes, labels, dev)
+        return dict(img=img, gt_bboxes=gt_bboxes, gt_labels=gt_labels, img_metas=metas, params=params)
 
 
 def build_train_pipeline(pipeline, **kw):
     """The fused train pipeline of a reference ``train_pipeline`` block: ``FusedTrainPipeline`` for the mosaic recipes,
-    ``FusedV3TrainPipeline`` for the YOLOv3 mstrain recipe."""
+    ``FusedV3TrainPipeline`` for the YOLOv3 mstrain recipe, ``PlainTrainPipeline`` for the plain ``Resize -> RandomFlip ->
+    Normalize -> Pad`` block of the dataset base configs."""
     types = [t['type'] for t in pipeline]
     if 'MosaicPipeline' in types:
         return FusedTrainPipeline.from_config(pipeline, **kw)
     if 'PhotoMetricDistortion' in types:
         return FusedV3TrainPipeline.from_config(pipeline, **kw)
-    raise NotImplementedError(f'no fused train pipeline for {types}: neither MosaicPipeline nor PhotoMetricDistortion')
+    if 'Resize' in types:
+        from .augment_plain import PlainTrainPipeline
+        return PlainTrainPipeline.from_config(pipeline, **kw)
+    raise NotImplementedError(f'no fused train pipeline for {types}: neither MosaicPipeline nor PhotoMetricDistortion nor '
+                              'a plain Resize block')

@@ -14,6 +14,14 @@ img_prefix=..., pipeline=train_pipeline)``) goes through ``build_train_loader`` 
   order of ``DistributedSampler(shuffle=False)``, the same reads and ONE decode per batch, then the test pipeline
   (``FusedTestPipeline``), in the nested form ``single_gpu_test`` / ``EvalHook`` take.
 
+What the loaders ask of a dataset, and nothing else: ``data_infos[i]['filename']``, ``img_prefix``, ``flag``,
+``get_ann_info``, ``batch_rand_others`` / ``_rand_another``, ``pipeline``, ``CLASSES`` and, on the test side, ``evaluate``
+-- so ``custom_datasets`` (the middle-format pickle, VOC XML, the traffic-sign folders, whose ``data_infos`` carry no
+size) serve as ``CocoDataset`` does.  Under a wrapper (``dataset_wrappers``: ``RepeatDataset``, ``ConcatDataset``,
+``ClassBalancedDataset``) the sampler works on the wrapper's ``flag`` and length, and every sample is resolved to
+``(innermost dataset, index)``: its file, its annotation and its mosaic partners come from the dataset that owns it;
+``draws['sources']`` then names samples as ``(owner's number, index)``.
+
 What is pinned draw for draw against the reference (tests/golden/coco_train_set.npz): ``CocoDataset._rand_another`` /
 ``batch_rand_others`` and both samplers' orders, given the same generator state.  What is this loader's own: the ORDER
 in which the samples of a batch take their draws.  The reference spreads them over its worker processes, each with its
@@ -34,6 +42,7 @@ import torch
 from . import image_io
 from .augment import FusedTrainPipeline
 from .augment_v3 import build_train_pipeline
+from .dataset_wrappers import build_dataset  # noqa: F401  (builder.py:53-73: plain blocks, wrappers, lists of blocks)
 from .registry import DATASETS
 from .results import CocoBBoxDataset
 
@@ -315,6 +324,9 @@ class _FileLoader:
         self.device = torch.device(device) if device is not None else None
         self.entropy = image_io._entropy_mode(entropy)
         self.prefetch, self.orientation = prefetch, bool(orientation)
+        # under a wrapper (dataset_wrappers) a sample is named by (number of the innermost dataset that owns it, its index there)
+        self._leaves = dataset.leaves() if hasattr(dataset, 'resolve') else None
+        self._leaf_no = {id(d): k for k, d in enumerate(self._leaves)} if self._leaves is not None else None
         self._readers = ThreadPoolExecutor(max_workers=MAX_READ_THREADS, thread_name_prefix='yv4-read')
         self._worker = ThreadPoolExecutor(max_workers=1, thread_name_prefix='yv4-prefetch') if prefetch else None
 
@@ -327,9 +339,31 @@ class _FileLoader:
     def _dev(self):
         return self.device if self.device is not None else torch.device('cuda', torch.cuda.current_device())
 
+    def _own(self, idx):
+        """The name of the loader's sample ``idx`` from here on: ``idx`` itself for a plain dataset, under a wrapper
+        ``(owner's number, index in the owner)``."""
+        if self._leaves is None:
+            return idx
+        ds, i = self.dataset.resolve(idx)
+        return self._leaf_no[id(ds)], int(i)
+
+    def _at(self, j):
+        """``(the dataset that owns sample j, j's index in it)``."""
+        return (self._leaves[j[0]], j[1]) if isinstance(j, tuple) else (self.dataset, j)
+
+    @staticmethod
+    def _sibling(j, i):
+        """Index ``i`` of the dataset that owns ``j``, named as ``j`` is."""
+        return (j[0], int(i)) if isinstance(j, tuple) else int(i)
+
+    def _filename(self, j):
+        ds, i = self._at(j)
+        return ds.data_infos[i]['filename']
+
     def _path(self, j):
-        name = self.dataset.data_infos[j]['filename']
-        return os.path.join(self.dataset.img_prefix, name) if self.dataset.img_prefix is not None else name
+        ds, i = self._at(j)
+        name = ds.data_infos[i]['filename']
+        return os.path.join(ds.img_prefix, name) if ds.img_prefix is not None else name
 
     # ---- host work of one batch: no HIP call, no torch call, no draw (may run on the worker thread) -----------------------
     def _host(self, sources):
@@ -450,7 +484,8 @@ class TrainLoader(_FileLoader):
                     logging.getLogger(__name__).warning('TrainLoader: %s is refused (%s): another image of its group is '
                                                         'drawn in its place', path, refused[k])
                 self.resampled += 1
-                sources[k] = int(self.dataset._rand_another(sources[k], rng))
+                ds, i = self._at(sources[k])
+                sources[k] = self._sibling(sources[k], ds._rand_another(i, rng))
                 bufs[k] = _read(self._path(sources[k]))
             drawn = sorted(refused)
             refused = {drawn[i]: e for i, e in image_io.refusals([bufs[k] for k in drawn]).items()}
@@ -465,9 +500,11 @@ class TrainLoader(_FileLoader):
         if self.mosaic:
             sources = []
             for idx in indices:
-                sources += [idx] + [int(j) for j in self.dataset.batch_rand_others(idx, 3, self._rng)]
+                own = self._own(idx)
+                ds, i = self._at(own)          # the partners come from the dataset that owns the sample
+                sources += [own] + [self._sibling(own, j) for j in ds.batch_rand_others(i, 3, self._rng)]
         else:
-            sources = list(indices)
+            sources = [self._own(idx) for idx in indices]
         self.times['draws'] += time.perf_counter() - t0
         return indices, sources, self._submit(sources)
 
@@ -478,7 +515,7 @@ class TrainLoader(_FileLoader):
         t0 = time.perf_counter()
         imgs = self._decode(bufs, host, sources)
         t1 = time.perf_counter()
-        anns = [self.dataset.get_ann_info(j) for j in sources]
+        anns = [ds.get_ann_info(i) for ds, i in map(self._at, sources)]
         triples = [(im, a['bboxes'], a['labels']) for im, a in zip(imgs, anns)]
         if self.mosaic:
             samples = [tuple(triples[4 * n:4 * n + 4]) for n in range(len(indices))]
@@ -496,7 +533,7 @@ class TrainLoader(_FileLoader):
             shape = tuple(res['img'].shape[2:]) + (3,)
             metas = [dict(img_shape=shape, pad_shape=shape, scale_factor=1.0, flip=False) for _ in indices]
         for m, g in zip(metas, groups):
-            m['ori_filename'] = self.dataset.data_infos[g[0]]['filename']
+            m['ori_filename'] = self._filename(g[0])
             m['filename'] = self._path(g[0])
         return dict(img=res['img'], img_metas=metas, gt_bboxes=res['gt_bboxes'], gt_labels=res['gt_labels'])
 
@@ -519,8 +556,8 @@ TEST_LOADER_BATCHED = True
 class TestLoader(_FileLoader):
     """The test side's loader, what ``single_gpu_test`` / ``multi_gpu_test`` / ``EvalHook`` / ``DistEvalHook`` take, fed
     from image files: iterable over ``dict(img=[batch per augmentation], img_metas=[[meta per image] per augmentation])``
-    (the nested form of the reference's test collate), with ``__len__`` (batches) and ``.dataset`` (a ``CocoDataset`` in
-    test mode, which ``accepts_flat``).
+    (the nested form of the reference's test collate), with ``__len__`` (batches) and ``.dataset`` (a dataset in test
+    mode -- ``CocoDataset``, one of ``custom_datasets``, a ``ConcatDataset`` of them --, which ``accepts_flat``).
 
     Order: ``dist.sampler_indices(len(dataset), rank, world)`` -- ``DistributedSampler(shuffle=False)``, for one rank
     ``range(len(dataset))`` -- in consecutive batches of ``samples_per_gpu``, the last one ragged.  Per batch: the files
@@ -556,7 +593,8 @@ class TestLoader(_FileLoader):
         return len(self.batches)
 
     def _start(self, indices):
-        return list(indices), self._submit(indices)
+        sources = [self._own(j) for j in indices]
+        return sources, self._submit(sources)
 
     def _finish(self, started):
         sources, job = started
@@ -593,7 +631,7 @@ class TestLoader(_FileLoader):
         self.times['pipeline'] += t2 - t1
         for per_aug in metas:
             for m, j in zip(per_aug, sources):
-                m['ori_filename'] = self.dataset.data_infos[j]['filename']
+                m['ori_filename'] = self._filename(j)
                 m['filename'] = self._path(j)
         return dict(img=list(batch), img_metas=[list(m) for m in metas])
 
@@ -601,15 +639,6 @@ class TestLoader(_FileLoader):
         for k in self.times:
             self.times[k] = 0.0
         yield from self._pipelined(self.batches)
-
-
-def build_dataset(cfg, default_args=None):
-    """``mmdet/datasets/builder.py`` ``build_dataset`` for a plain dataset block (the wrappers -- ``RepeatDataset``,
-    ``ConcatDataset``, ``ClassBalancedDataset`` -- are not built)."""
-    from .registry import build_from_cfg
-    if isinstance(cfg, (list, tuple)) or cfg.get('type') in ('RepeatDataset', 'ConcatDataset', 'ClassBalancedDataset'):
-        raise NotImplementedError('dataset wrappers are not built: pass one dataset block')
-    return build_from_cfg(cfg, DATASETS, default_args)
 
 
 def _reads_oriented(pipeline):
@@ -630,8 +659,9 @@ def _reads_oriented(pipeline):
 
 def build_train_loader(cfg, samples_per_gpu, seed=0, rank=0, world=1, device=None, entropy=None, prefetch=0,
                        on_unsupported='raise'):
-    """``cfg``: ``cfg.data.train`` of a reference config, a dataset block with its ``pipeline`` -> ``TrainLoader``.  The
-    pipeline block goes through ``build_train_pipeline`` (the mosaic recipes and the YOLOv3 mstrain recipe).  Its
+    """``cfg``: ``cfg.data.train`` of a reference config -- a dataset block with its ``pipeline``, a wrapper around one, or
+    a list of blocks (``build_dataset``) -> ``TrainLoader``.  The pipeline block, under a wrapper the innermost dataset's,
+    goes through ``build_train_pipeline`` (the mosaic recipes, the YOLOv3 mstrain recipe, the plain ``Resize`` block).  Its
     ``LoadImageFromFile`` says how files are read, with the reference's meaning: ``color_type='color'`` (the default)
     applies the EXIF orientation, ``'color_ignore_orientation'`` does not."""
     dataset = build_dataset(cfg)
@@ -647,18 +677,23 @@ def build_train_loader(cfg, samples_per_gpu, seed=0, rank=0, world=1, device=Non
 def build_test_loader(cfg, samples_per_gpu=None, rank=0, world=1, device=None, entropy=None, prefetch=0, fallback=None,
                       batched=None):
     """``cfg``: ``cfg.data.val`` or ``cfg.data.test`` of a reference config, a dataset block with its test ``pipeline``
-    -> ``TestLoader``.  The dataset is built with ``test_mode=True`` whatever the block says (``apis/train.py:140``), so no
-    image is filtered.  ``samples_per_gpu``: ``None`` takes the block's own key (the YOLOv4 configs put
+    (or a wrapper or a list, as ``build_dataset`` takes them) -> ``TestLoader``.  A plain block is built with
+    ``test_mode=True`` whatever it says, and the blocks under a wrapper take it as their default (``apis/train.py:140``),
+    so no image is filtered.  ``samples_per_gpu``: ``None`` takes the block's own key (the YOLOv4 configs put
     ``samples_per_gpu=8`` into ``val``), else 1; the key never reaches the dataset.  The pipeline block goes through
     ``FusedTestPipeline.from_config`` (a transform it does not build is refused by name), its ``LoadImageFromFile`` decides
     the orientation as in ``build_train_loader``.  ``batched``: the pipeline's form, ``None`` for ``TEST_LOADER_BATCHED``."""
     from .preprocess import FusedTestPipeline
-    cfg = dict(cfg)
-    own = cfg.pop('samples_per_gpu', None)
+    own = None
+    if isinstance(cfg, dict):
+        cfg = dict(cfg)
+        own = cfg.pop('samples_per_gpu', None)
+        if 'ann_file' in cfg:
+            cfg['test_mode'] = True
+    # under a wrapper or in a list, test_mode reaches every plain block as a default argument (apis/train.py:140)
+    dataset = build_dataset(cfg, dict(test_mode=True))
     if samples_per_gpu is None:
         samples_per_gpu = 1 if own is None else own
-    cfg['test_mode'] = True
-    dataset = build_dataset(cfg)
     if dataset.pipeline is None:
         raise ValueError('build_test_loader: the dataset block has no pipeline')
     orientation = _reads_oriented(dataset.pipeline)

@@ -12,13 +12,13 @@ from ._lib import check
 from .ops import stream_ptr
 
 
-def _device(what, has=None, symbols=''):
-    """The current GPU; raises without one, or when ``has()`` says the loaded library lacks ``symbols``."""
+def _device(what, feature=None):
+    """The current GPU; raises without one, or when the loaded library lacks ``feature`` (``_lib.FEATURES``)."""
     if not torch.cuda.is_available():
         raise RuntimeError(f'{what} runs on the GPU through libyv4_hip.so; no GPU is visible '
                            '(there is no CPU fallback for this path)')
-    if has is not None and not has():
-        raise RuntimeError(f'the loaded libyv4_hip.so has no {symbols}; rebuild it')
+    if feature is not None:
+        _lib.require(feature)
     return torch.device('cuda', torch.cuda.current_device())
 
 

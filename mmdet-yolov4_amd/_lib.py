@@ -4,6 +4,7 @@ The library is the product: there is no CPU fallback.  ``lib()`` raises
 ``RuntimeError`` when the shared object has not been built, and every wrapper
 raises on a non-zero status with the library's own error message.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -37,17 +38,20 @@ TTA_MAX_AUGS = 16          # YV4_TTA_MAX_AUGS
 V3AUG_CONTRAST_NONE, V3AUG_CONTRAST_FIRST, V3AUG_CONTRAST_LAST = 0, 1, 2    # YV4_V3AUG_CONTRAST_*
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x64, TILE_64x128 = 0, 1, 2, 3, 4
 TILE_DMA_64x64, TILE_DMA_128x64, TILE_DMA_128x128, TILE_STEM, TILE_WS_1x1 = 5, 6, 7, 8, 9
-HTILE_NAMES = {1: 'h16_128x128', 2: 'h16_128x64', 3: 'h16_64x64', 4: 'h16_pp3x3', 5: 'h16_w3x3', 6: 'h16_ws_1x1', 7: 'h16_s3x3', 8: 'h16_wide'}
-# the pinned workgroup-tile shapes YV4_HTILE_W3x3_SHAPE(i) = 13, 21, .. 61 (i = 0 .. 6) and YV4_HTILE_WIDE_SHAPE(i) = 16, 24, .. 48 (tests,
-# tile sweeps): same kernels, same names
-HTILE_NAMES.update({5 + 8 * (i + 1): 'h16_w3x3' for i in range(7)})
-HTILE_NAMES.update({8 + 8 * (i + 1): 'h16_wide' for i in range(5)})
-TILE_NAMES = {0: 'auto', 1: '128x128', 2: '128x64', 3: '64x64', 4: '64x128', 5: 'dma64x64', 6: 'dma128x64',
-              7: 'dma128x128', 8: 'stem3x3', 9: 'ws_1x1', 10: 'w3x3', 26: 'w3x3', 42: 'w3x3', 58: 'w3x3', 74: 'w3x3', 90: 'w3x3',
-              11: 'wide', 27: 'wide', 43: 'wide', 59: 'wide', 75: 'wide', 91: 'wide'}
-TILE_W3x3 = 10
+TILE_W3x3, TILE_WIDE = 10, 11
 CONV_NT_OUT = 1            # yv4_conv_desc.flags (ABI 7): non-temporal output stores
-TILE_WIDE = 11
+HTILE_NAMES = {1: 'h16_128x128', 2: 'h16_128x64', 3: 'h16_64x64', 4: 'h16_pp3x3', 5: 'h16_w3x3', 6: 'h16_ws_1x1', 7: 'h16_s3x3', 8: 'h16_wide'}
+TILE_NAMES = {0: 'auto', 1: '128x128', 2: '128x64', 3: '64x64', 4: '64x128', 5: 'dma64x64', 6: 'dma128x64',
+              7: 'dma128x128', 8: 'stem3x3', 9: 'ws_1x1', 10: 'w3x3', 11: 'wide'}
+#: how many workgroup-tile shapes each ``YV4_*_SHAPE(i)`` macro pins (tests, tile sweeps): i = 0 .. count - 1
+SHAPE_COUNTS = {'TILE_W3x3': 5, 'TILE_WIDE': 5, 'HTILE_W3x3': 7, 'HTILE_WIDE': 5}
+# YV4_TILE_x_SHAPE(i) = x + 16 * (i + 1), YV4_HTILE_x_SHAPE(i) = x + 8 * (i + 1): same kernels, same names
+TILE_NAMES.update({TILE_W3x3 + 16 * (i + 1): 'w3x3' for i in range(SHAPE_COUNTS['TILE_W3x3'])})
+TILE_NAMES.update({TILE_WIDE + 16 * (i + 1): 'wide' for i in range(SHAPE_COUNTS['TILE_WIDE'])})
+HTILE_NAMES.update({5 + 8 * (i + 1): 'h16_w3x3' for i in range(SHAPE_COUNTS['HTILE_W3x3'])})
+HTILE_NAMES.update({8 + 8 * (i + 1): 'h16_wide' for i in range(SHAPE_COUNTS['HTILE_WIDE'])})
+E_INVALID, E_UNSUPPORTED = -1, -2                                           # YV4_E_*: the status of a refused call
+LOSS_MAX_LEVELS = V3_LOSS_MAX_LEVELS = 5
 
 
 class ConvDesc(C.Structure):
@@ -80,7 +84,7 @@ class LossLevel(C.Structure):
 
 class LossDesc(C.Structure):
     """``yv4_loss_desc``."""
-    _fields_ = [('levels', LossLevel * 5),
+    _fields_ = [('levels', LossLevel * LOSS_MAX_LEVELS),
                 ('num_levels', C.c_int32), ('N', C.c_int32), ('A', C.c_int32), ('num_classes', C.c_int32),
                 ('G', C.c_int32), ('dtype', C.c_int32),
                 ('gt', C.c_void_p), ('gt_label', C.c_void_p), ('gt_img', C.c_void_p),
@@ -110,7 +114,7 @@ class V3LossLevel(C.Structure):
 
 class V3LossDesc(C.Structure):
     """``yv4_v3_loss_desc`` (ABI 8)."""
-    _fields_ = [('levels', V3LossLevel * 5),
+    _fields_ = [('levels', V3LossLevel * V3_LOSS_MAX_LEVELS),
                 ('num_levels', C.c_int32), ('N', C.c_int32), ('A', C.c_int32), ('num_classes', C.c_int32),
                 ('G', C.c_int32), ('gt_max_assign_all', C.c_int32),
                 ('gt', C.c_void_p), ('gt_label', C.c_void_p), ('gt_img', C.c_void_p),
@@ -234,6 +238,16 @@ DRAW_NAME_BYTES = 32
 #: ``YV4_JPEG_ENC_WG_BLOCKS`` / ``YV4_JPEG_ENC_BLOCK_BITS`` / ``YV4_JPEG_ENC_HEADER_MAX`` (include/yv4.h): the blocks one
 #: workgroup of the encoder's bit-offset scan covers, the bound on a block's bits, the room the header writer asks for
 JPEG_ENC_WG_BLOCKS, JPEG_ENC_BLOCK_BITS, JPEG_ENC_HEADER_MAX = 256, 1660, 640
+
+#: every struct of include/yv4.h: C type name -> its ctypes mirror (tests/_abi_probe.py checks each field with a C compiler)
+STRUCTS = {
+    'yv4_conv_desc': ConvDesc, 'yv4_level_desc': LevelDesc, 'yv4_tta_aug': TtaAug, 'yv4_loss_level': LossLevel,
+    'yv4_loss_desc': LossDesc, 'yv4_loss_opts': LossOpts, 'yv4_v3_loss_level': V3LossLevel, 'yv4_v3_loss_desc': V3LossDesc,
+    'yv4_aug_image': AugImage, 'yv4_v3aug_image': V3AugImage, 'yv4_letterbox_slot': LetterboxSlot, 'yv4_pack_desc': PackDesc,
+    'yv4_jpeg_info': JpegInfo, 'yv4_jpeg_image': JpegImage, 'yv4_jpeg_huff': JpegHuff, 'yv4_jpeg_scan': JpegScan,
+    'yv4_jpeg_segment': JpegSegment, 'yv4_jpeg_wg': JpegWg, 'yv4_jpeg_chunk': JpegChunk, 'yv4_jpeg_entry': JpegEntry,
+    'yv4_jpeg_enc_image': JpegEncImage, 'yv4_draw_image': DrawImage, 'yv4_draw_style': DrawStyle,
+}
 
 _vp, _i, _i64, _f, _sz, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 
@@ -406,56 +420,56 @@ SIGNATURES = {
     'yv4_draw_boxes_host_ex': (C.c_int, [C.POINTER(DrawImage), _i, _vp, _i64, _vp, _vp, _i64, _vp, C.POINTER(DrawStyle), _i]),
 }
 
-#: symbols added by ABI 8: bound only when the library reports ABI >= 8, so that an ABI-7 build still loads for A/B
-#: runs (YV4_LIB_ABI_ANY=1); has_v3_loss() tells the YOLOv3 head whether its fused loss is there
-ABI8_SYMBOLS = frozenset(('yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'))
-#: the fp8 inference entry points (additive within ABI 8): bound when the library exports them, so that an ABI-8 build
-#: from before them still loads for A/B runs; has_fp8() tells the plan whether they are there
-FP8_SYMBOLS = frozenset(('yv4_conv_bn_act_fwd_f8', 'yv4_conv_f8_pick_tile', 'yv4_quantize_f8', 'yv4_spp_pool_fwd_f8'))
-#: the YOLOv3 test-time augmentation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_tta()
-TTA_SYMBOLS = frozenset(('yv4_letterbox_u8_flip', 'yv4_topk_slots_work', 'yv4_topk_slots', 'yv4_tta_merge'))
-#: a whole test batch's letterbox in one launch (additive within ABI 8, bound like FP8_SYMBOLS); has_letterbox_batch()
-LETTERBOX_BATCH_SYMBOLS = frozenset(('yv4_letterbox_u8_batch',))
-#: the soft-NMS entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_soft_nms()
-SOFT_NMS_SYMBOLS = frozenset(('yv4_soft_nms_images', 'yv4_soft_nms_split_work', 'yv4_soft_nms_split'))
-#: the YOLOv3 train-side input pipeline (additive within ABI 8, bound like FP8_SYMBOLS); has_v3_augment()
-V3_AUGMENT_SYMBOLS = frozenset(('yv4_v3_augment_u8',))
-#: the YOLOCSPHead loss with options: IoU / DIoU / CIoU box terms and SoftFocalLoss (additive within ABI 8, bound like
-#: FP8_SYMBOLS); has_loss_ex()
-LOSS_EX_SYMBOLS = frozenset(('yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'))
-#: the VOC-style mAP entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_map_eval()
-MAP_EVAL_SYMBOLS = frozenset(('yv4_bbox_overlaps_batched', 'yv4_tpfp_work', 'yv4_tpfp_batched'))
-#: the flat-table ends of the VOC-style mAP (additive within ABI 8, bound like FP8_SYMBOLS); has_map_flat()
-MAP_FLAT_SYMBOLS = frozenset(('yv4_map_rank_work', 'yv4_map_rank', 'yv4_map_accumulate_work', 'yv4_map_accumulate'))
-#: metric='fast-bbox' from the flat table (additive within ABI 8, bound like FP8_SYMBOLS); has_flex_flat()
-FLEX_FLAT_SYMBOLS = frozenset(('yv4_flex_tables', 'yv4_flex_accumulate_work', 'yv4_flex_accumulate'))
-#: the COCO bbox evaluation entry points (additive within ABI 8, bound like FP8_SYMBOLS); has_coco_eval()
-COCO_EVAL_SYMBOLS = frozenset(('yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_match', 'yv4_coco_accumulate_work',
-                               'yv4_coco_accumulate'))
-#: the flat result table of a test loop (additive within ABI 8, bound like FP8_SYMBOLS); has_results_append()
-RESULTS_SYMBOLS = frozenset(('yv4_results_append',))
-#: the baseline JPEG decoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg()
-JPEG_SYMBOLS = frozenset(('yv4_jpeg_parse', 'yv4_jpeg_entropy_decode', 'yv4_jpeg_layout', 'yv4_jpeg_reconstruct'))
-#: EXIF orientation in the JPEG decoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_orientation()
-JPEG_ORIENT_SYMBOLS = frozenset(('yv4_jpeg_layout_oriented',))
-#: the Huffman scan decode on the device (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_entropy()
-JPEG_ENTROPY_SYMBOLS = frozenset(('yv4_jpeg_scan_prepare', 'yv4_jpeg_entropy_workgroups', 'yv4_jpeg_entropy_decode_segments',
-                                  'yv4_jpeg_entropy_decode_device', 'yv4_jpeg_entropy_strerror'))
-#: the self-synchronising chunk decode of the Huffman scan (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_sync()
-JPEG_SYNC_SYMBOLS = frozenset(('yv4_jpeg_chunks_build', 'yv4_jpeg_entropy_decode_sync',
-                               'yv4_jpeg_entropy_decode_device_sync'))
-#: the baseline JPEG encoder (additive within ABI 8, bound like FP8_SYMBOLS); has_jpeg_encode()
-JPEG_ENCODE_SYMBOLS = frozenset(('yv4_jpeg_encode_layout', 'yv4_jpeg_encode_validate', 'yv4_jpeg_encode_header',
-                                 'yv4_jpeg_encode_host', 'yv4_jpeg_encode_coefficients', 'yv4_jpeg_encode_scan'))
-#: drawing detections onto images (additive within ABI 8, bound like FP8_SYMBOLS); has_draw()
-DRAW_SYMBOLS = frozenset(('yv4_draw_layout', 'yv4_draw_boxes', 'yv4_draw_boxes_host'))
-#: drawing with flags -- boxes without a score (additive within ABI 8, bound like FP8_SYMBOLS); has_draw_ex()
-DRAW_EX_SYMBOLS = frozenset(('yv4_draw_boxes_ex', 'yv4_draw_boxes_host_ex'))
+Feature = collections.namedtuple('Feature', 'symbols requires abi', defaults=((), 0))
+
+#: the entry points that came after the first ABI-8 build, by feature.  A symbol named here is bound when the library
+#: exports it and skipped when it does not, so that an older build still loads for A/B runs (``YV4_LIB_PATH``); every
+#: other symbol of ``SIGNATURES`` must exist.  ``has(name)`` says whether all of a feature's symbols, and those of the
+#: features it ``requires``, are there.  ``abi``: the feature came with that ABI number instead -- its symbols are bound
+#: when the library reports at least that ABI (``YV4_LIB_ABI_ANY=1`` admits the one before), and ``has`` is that test.
+FEATURES = {
+    # the fp8 (e4m3) inference plans
+    'fp8': Feature({'yv4_conv_bn_act_fwd_f8', 'yv4_conv_f8_pick_tile', 'yv4_quantize_f8', 'yv4_spp_pool_fwd_f8'}),
+    # the YOLOv3 test-time augmentation
+    'tta': Feature({'yv4_letterbox_u8_flip', 'yv4_topk_slots_work', 'yv4_topk_slots', 'yv4_tta_merge'}),
+    # a whole test batch's letterbox in one launch
+    'letterbox_batch': Feature({'yv4_letterbox_u8_batch'}),
+    'soft_nms': Feature({'yv4_soft_nms_images', 'yv4_soft_nms_split_work', 'yv4_soft_nms_split'}),
+    # the YOLOv3 train-side input pipeline
+    'v3_augment': Feature({'yv4_v3_augment_u8'}),
+    # the YOLOCSPHead loss with options: IoU / DIoU / CIoU box terms and SoftFocalLoss
+    'loss_ex': Feature({'yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'}),
+    # the VOC-style mAP, its flat-table ends, and metric='fast-bbox' from the flat table
+    'map_eval': Feature({'yv4_bbox_overlaps_batched', 'yv4_tpfp_work', 'yv4_tpfp_batched'}),
+    'map_flat': Feature({'yv4_map_rank_work', 'yv4_map_rank', 'yv4_map_accumulate_work', 'yv4_map_accumulate'}),
+    'flex_flat': Feature({'yv4_flex_tables', 'yv4_flex_accumulate_work', 'yv4_flex_accumulate'}, ('map_flat',)),
+    # the COCO bbox evaluation
+    'coco_eval': Feature({'yv4_coco_rank_work', 'yv4_coco_rank', 'yv4_coco_match', 'yv4_coco_accumulate_work',
+                          'yv4_coco_accumulate'}),
+    # the flat result table of a test loop
+    'results_append': Feature({'yv4_results_append'}),
+    # the baseline JPEG decoder, EXIF orientation in it, the Huffman scan decode on the device and its self-synchronising
+    # chunk form
+    'jpeg': Feature({'yv4_jpeg_parse', 'yv4_jpeg_entropy_decode', 'yv4_jpeg_layout', 'yv4_jpeg_reconstruct'}),
+    'jpeg_orientation': Feature({'yv4_jpeg_layout_oriented'}),
+    'jpeg_entropy': Feature({'yv4_jpeg_scan_prepare', 'yv4_jpeg_entropy_workgroups', 'yv4_jpeg_entropy_decode_segments',
+                             'yv4_jpeg_entropy_decode_device', 'yv4_jpeg_entropy_strerror'}),
+    'jpeg_sync': Feature({'yv4_jpeg_chunks_build', 'yv4_jpeg_entropy_decode_sync', 'yv4_jpeg_entropy_decode_device_sync'},
+                         ('jpeg_entropy',)),
+    # the baseline JPEG encoder
+    'jpeg_encode': Feature({'yv4_jpeg_encode_layout', 'yv4_jpeg_encode_validate', 'yv4_jpeg_encode_header',
+                            'yv4_jpeg_encode_host', 'yv4_jpeg_encode_coefficients', 'yv4_jpeg_encode_scan'}),
+    # drawing detections onto images; with flags (boxes without a score)
+    'draw': Feature({'yv4_draw_layout', 'yv4_draw_boxes', 'yv4_draw_boxes_host'}),
+    'draw_ex': Feature({'yv4_draw_boxes_ex', 'yv4_draw_boxes_host_ex'}, ('draw',)),
+    # the per-image mAP
+    'map_image': Feature({'yv4_map_image_ap_work', 'yv4_map_image_ap', 'yv4_map_image_mean'}),
+    # the proposal recall
+    'recall': Feature({'yv4_recall_work', 'yv4_recall_match'}),
+    # the fused YOLOv3 loss
+    'v3_loss': Feature({'yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'}, abi=8),
+}
 DRAW_NO_SCORE = 1          # YV4_DRAW_NO_SCORE
-#: the per-image mAP (additive within ABI 8, bound like FP8_SYMBOLS); has_map_image()
-MAP_IMAGE_SYMBOLS = frozenset(('yv4_map_image_ap_work', 'yv4_map_image_ap', 'yv4_map_image_mean'))
-#: the proposal recall (additive within ABI 8, bound like FP8_SYMBOLS); has_recall()
-RECALL_SYMBOLS = frozenset(('yv4_recall_work', 'yv4_recall_match'))
 RECALL_MAX_NUMS, RECALL_MAX_THRS, RECALL_LDS_BOXES = 16, 256, 1280      # csrc/recall.hip: kRcMaxNums, kRcMaxThrs, kRcLdsBoxes
 #: ``YV4_JPEG_MIN_CHUNK_BYTES`` / ``YV4_JPEG_MAX_CHUNK_BYTES`` / ``YV4_JPEG_MAX_ROUNDS`` (include/yv4.h)
 JPEG_MIN_CHUNK_BYTES, JPEG_MAX_CHUNK_BYTES, JPEG_MAX_ROUNDS = 4, 1 << 20, 4096
@@ -464,6 +478,7 @@ RESULTS_MAX_PER_IMG = 4096
 
 _lock = threading.Lock()
 _lib = None
+_has = None                # {feature: present in the bound library}, from _bind
 
 
 def build(verbose=False, measure=False):
@@ -482,7 +497,7 @@ def build(verbose=False, measure=False):
 
 def lib():
     """Load (once) and return the bound library.  No fallback: raises if absent."""
-    global _lib
+    global _lib, _has
     if _lib is not None:
         return _lib
     with _lock:
@@ -494,163 +509,54 @@ def lib():
                 'Run `python -c "import __graft_entry__ as g; g.build()"` (or '
                 f'`make -C {CSRC_DIR}`). There is no CPU fallback for this path.')
         handle = C.CDLL(LIB_PATH)
-        handle.yv4_abi_version.restype = C.c_int
-        handle.yv4_abi_version.argtypes = []
+        present = _bind(handle)
         got = handle.yv4_abi_version()
-        for name, (res, args) in SIGNATURES.items():
-            if name in ABI8_SYMBOLS and got < 8:
-                continue
-            if (name in FP8_SYMBOLS or name in TTA_SYMBOLS or name in SOFT_NMS_SYMBOLS
-                    or name in V3_AUGMENT_SYMBOLS or name in LOSS_EX_SYMBOLS or name in MAP_EVAL_SYMBOLS
-                    or name in COCO_EVAL_SYMBOLS or name in RESULTS_SYMBOLS or name in MAP_FLAT_SYMBOLS
-                    or name in FLEX_FLAT_SYMBOLS
-                    or name in JPEG_SYMBOLS or name in JPEG_ENTROPY_SYMBOLS or name in JPEG_SYNC_SYMBOLS
-                    or name in JPEG_ORIENT_SYMBOLS or name in LETTERBOX_BATCH_SYMBOLS or name in JPEG_ENCODE_SYMBOLS
-                    or name in DRAW_SYMBOLS or name in DRAW_EX_SYMBOLS or name in MAP_IMAGE_SYMBOLS
-                    or name in RECALL_SYMBOLS) \
-                    and not hasattr(handle, name):
-                continue
-            fn = getattr(handle, name)  # AttributeError if a symbol is missing
-            fn.restype = res
-            fn.argtypes = args
         if got != ABI_VERSION and not (os.environ.get('YV4_LIB_PATH') and os.environ.get('YV4_LIB_ABI_ANY') == '1'
                                        and got == ABI_VERSION - 1):
             # (YV4_LIB_ABI_ANY=1 with YV4_LIB_PATH: same-box A/B against the previous ABI's build -- ABI 8 only APPENDED
-            # the YOLOv3 loss entry points, which are left unbound for an ABI-7 library: see ABI8_SYMBOLS)
+            # the YOLOv3 loss entry points, which are left unbound for an ABI-7 library: FEATURES['v3_loss'])
             raise RuntimeError(f'libyv4_hip.so ABI {got} != binding ABI {ABI_VERSION}; rebuild')
         form = os.environ.get('YV4_NMS_IOU_FORM', '').lower()
         if form in ('mul', '1', 'product', 'cuda'):
             handle.yv4_nms_set_iou_form(NMS_IOU_MUL)      # mmcv's CUDA-kernel predicate instead of its CPU kernel's
-        _lib = handle
+        _has, _lib = present, handle
     return _lib
 
 
-def has_v3_loss():
-    """The loaded library exports ``yv4_yolov3_loss_fwd`` / ``_bwd`` (ABI >= 8)."""
-    return lib().yv4_abi_version() >= 8
+def _bind(handle):
+    """Give every entry point of ``handle`` its prototype from ``SIGNATURES`` by the rule of ``FEATURES`` (a symbol of
+    no feature that is missing: ``AttributeError``) -> ``{feature: present}``, what ``has`` answers from."""
+    handle.yv4_abi_version.restype, handle.yv4_abi_version.argtypes = SIGNATURES['yv4_abi_version']
+    abi = handle.yv4_abi_version()
+    owner = {s: ft for ft in FEATURES.values() for s in ft.symbols}
+    for name, (res, args) in SIGNATURES.items():
+        ft = owner.get(name)
+        if ft is not None and (abi < ft.abi if ft.abi else not hasattr(handle, name)):
+            continue                # an optional symbol that this library does not have
+        fn = getattr(handle, name)  # AttributeError if a symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    own = {f: abi >= ft.abi if ft.abi else all(hasattr(handle, s) for s in ft.symbols) for f, ft in FEATURES.items()}
+    return {f: own[f] and all(own[r] for r in ft.requires) for f, ft in FEATURES.items()}
 
 
-def has_fp8():
-    """The loaded library exports the fp8 (e4m3) inference entry points."""
-    h = lib()
-    return all(hasattr(h, n) for n in FP8_SYMBOLS)
+def has(feature):
+    """The loaded library exports every entry point of ``FEATURES[feature]`` and of the features it requires."""
+    lib()
+    return _has[feature]
 
 
-def has_tta():
-    """The loaded library exports the YOLOv3 test-time augmentation entry points."""
-    h = lib()
-    return all(hasattr(h, n) for n in TTA_SYMBOLS)
-
-
-def has_letterbox_batch():
-    """The loaded library exports ``yv4_letterbox_u8_batch`` (a whole test batch's letterbox in one launch)."""
-    h = lib()
-    return all(hasattr(h, n) for n in LETTERBOX_BATCH_SYMBOLS)
-
-
-def has_soft_nms():
-    """The loaded library exports the soft-NMS entry points."""
-    h = lib()
-    return all(hasattr(h, n) for n in SOFT_NMS_SYMBOLS)
-
-
-def has_v3_augment():
-    """The loaded library exports the YOLOv3 train-side input pipeline."""
-    h = lib()
-    return all(hasattr(h, n) for n in V3_AUGMENT_SYMBOLS)
-
-
-def has_loss_ex():
-    """The loaded library exports ``yv4_yolo_loss_fwd_ex`` / ``_bwd_ex`` (the box-loss family and SoftFocalLoss)."""
-    h = lib()
-    return all(hasattr(h, n) for n in LOSS_EX_SYMBOLS)
-
-
-def has_map_eval():
-    """The loaded library exports the VOC-style mAP entry points (``yv4_bbox_overlaps_batched`` / ``yv4_tpfp_batched``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in MAP_EVAL_SYMBOLS)
-
-
-def has_map_flat():
-    """The loaded library exports the flat-table mAP entry points (``yv4_map_rank`` / ``yv4_map_accumulate``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in MAP_FLAT_SYMBOLS)
-
-
-def has_flex_flat():
-    """The loaded library exports the flat-table fast-bbox entry points (``yv4_flex_tables`` / ``yv4_flex_accumulate``)."""
-    h = lib()
-    return has_map_flat() and all(hasattr(h, n) for n in FLEX_FLAT_SYMBOLS)
-
-
-def has_coco_eval():
-    """The loaded library exports the COCO bbox evaluation entry points (``yv4_coco_rank`` / ``_match`` / ``_accumulate``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in COCO_EVAL_SYMBOLS)
-
-
-def has_results_append():
-    """The loaded library exports ``yv4_results_append`` (the flat result table of a test loop)."""
-    h = lib()
-    return all(hasattr(h, n) for n in RESULTS_SYMBOLS)
-
-
-def has_jpeg():
-    """The loaded library exports the baseline JPEG decoder (``yv4_jpeg_parse`` .. ``yv4_jpeg_reconstruct``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in JPEG_SYMBOLS)
-
-
-def has_jpeg_orientation():
-    """The loaded library exports ``yv4_jpeg_layout_oriented``: its parse reads the EXIF orientation and its pixel stage
-    applies it."""
-    h = lib()
-    return all(hasattr(h, n) for n in JPEG_ORIENT_SYMBOLS)
-
-
-def has_jpeg_entropy():
-    """The loaded library exports the Huffman scan decode on the device (``yv4_jpeg_scan_prepare`` ..
-    ``yv4_jpeg_entropy_decode_device``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in JPEG_ENTROPY_SYMBOLS)
-
-
-def has_jpeg_sync():
-    """The loaded library exports the self-synchronising chunk decode (``yv4_jpeg_chunks_build`` ..
-    ``yv4_jpeg_entropy_decode_device_sync``)."""
-    h = lib()
-    return has_jpeg_entropy() and all(hasattr(h, n) for n in JPEG_SYNC_SYMBOLS)
-
-
-def has_jpeg_encode():
-    """The loaded library exports the baseline JPEG encoder (``yv4_jpeg_encode_layout`` .. ``yv4_jpeg_encode_scan``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in JPEG_ENCODE_SYMBOLS)
-
-
-def has_draw():
-    """The loaded library exports the drawing entry points (``yv4_draw_layout`` / ``yv4_draw_boxes``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in DRAW_SYMBOLS)
-
-
-def has_draw_ex():
-    """The loaded library exports ``yv4_draw_boxes_ex`` / ``yv4_draw_boxes_host_ex`` (boxes without a score)."""
-    h = lib()
-    return has_draw() and all(hasattr(h, n) for n in DRAW_EX_SYMBOLS)
-
-
-def has_map_image():
-    """The loaded library exports the per-image mAP entry points (``yv4_map_image_ap`` / ``yv4_map_image_mean``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in MAP_IMAGE_SYMBOLS)
-
-
-def has_recall():
-    """The loaded library exports the proposal-recall entry points (``yv4_recall_work`` / ``yv4_recall_match``)."""
-    h = lib()
-    return all(hasattr(h, n) for n in RECALL_SYMBOLS)
+def require(feature, what=None):
+    """``RuntimeError`` naming the missing entry points unless ``has(feature)``.  ``what``: the caller, or the argument as
+    the user wrote it, that asks for the feature."""
+    if has(feature):
+        return
+    names = [s for f in (feature,) + tuple(FEATURES[feature].requires) for s in sorted(FEATURES[f].symbols)]
+    missing = ' / '.join([s for s in names if not hasattr(_lib, s)] or names)      # (all: left unbound by the ABI rule)
+    if what is None:
+        raise RuntimeError(f'the loaded libyv4_hip.so has no {missing}: rebuild it')
+    raise RuntimeError(f'{what} needs {missing}, which the loaded libyv4_hip.so does not export (there is no fallback): '
+                       'rebuild it')
 
 
 class Yv4Error(RuntimeError):

@@ -55,8 +55,7 @@ def ceil32(thr):
 
 
 def _device():
-    _eval_common._device('image_maps', _lib.has_map_flat, 'yv4_map_rank')
-    return _eval_common._device('image_maps', _lib.has_map_image, 'yv4_map_image_ap / yv4_map_image_mean')
+    return _eval_common._device('image_maps', 'map_image')
 
 
 def _as_flat(results):

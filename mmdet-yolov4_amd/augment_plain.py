@@ -98,9 +98,7 @@ class PlainTrainPipeline:
         N = len(samples)
         if N == 0:
             raise ValueError('empty batch')
-        if not _lib.has_letterbox_batch():
-            raise RuntimeError('PlainTrainPipeline needs yv4_letterbox_u8_batch, which the loaded libyv4_hip.so does not '
-                               'export: rebuild it')
+        _lib.require('letterbox_batch', 'PlainTrainPipeline')
         for s in samples:
             img = s[0]
             if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 \

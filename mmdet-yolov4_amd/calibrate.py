@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvDesc, check
+from .ops import stream_ptr
 from .plan import bn_affine
 
 
@@ -46,7 +47,7 @@ def calibrate_bn(plan, *inputs):
     assert not any(op.info.get('fused') for op in plan.ops), \
         'calibrate_bn walks single-conv launches: calibrate through the fp32 plan (the statistics live in the modules) ' \
         'or compile the 16-bit plan with YV4_STEM_FUSE=0'
-    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    stream = stream_ptr()
     for slot, t in zip(plan.inputs, inputs):
         slot['src'] = t.contiguous()
     dev = plan.device

@@ -59,7 +59,7 @@ METRIC_NAMES = {'mAP': 0, 'mAP_50': 1, 'mAP_75': 2, 'mAP_s': 3, 'mAP_m': 4, 'mAP
 
 
 def _device():
-    return _eval_common._device('coco_eval', _lib.has_coco_eval, 'yv4_coco_rank / yv4_coco_match / yv4_coco_accumulate')
+    return _eval_common._device('coco_eval', 'coco_eval')
 
 
 class CocoGt:

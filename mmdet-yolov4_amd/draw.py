@@ -79,12 +79,6 @@ def _box_width(dets):
     return widths.pop() if widths else 5
 
 
-def _draw_call(name, has):
-    if not has():
-        raise RuntimeError(f'{name} is not exported by the loaded libyv4_hip.so: rebuild it')
-    return getattr(_lib.lib(), name)
-
-
 def draw_boxes_into(pixels, places, dets, labels, class_names, score_thr=0.3, bbox_color=(72, 101, 241),
                     text_color=(72, 101, 241), thickness=2, font_size=13):
     """Draws in place into the flat ``torch.uint8`` device buffer ``pixels``: image n lies at ``places[n]`` = ``(height,
@@ -94,7 +88,7 @@ def draw_boxes_into(pixels, places, dets, labels, class_names, score_thr=0.3, bb
     if not torch.cuda.is_available() or pixels.device.type != 'cuda':
         raise RuntimeError('draw_boxes runs on the GPU through libyv4_hip.so (there is no CPU fallback)')
     width = _box_width(dets)
-    call = _draw_call('yv4_draw_boxes_ex', _lib.has_draw_ex)
+    _lib.require('draw_ex')
     if pixels.dtype != torch.uint8 or not pixels.is_contiguous():
         raise ValueError('pixels must be a contiguous torch.uint8 tensor')
     dev = pixels.device
@@ -115,9 +109,10 @@ def draw_boxes_into(pixels, places, dets, labels, class_names, score_thr=0.3, bb
             lab = torch.cat([x.to(dev).reshape(-1) for x in labels]).to(torch.int32).contiguous()
         else:
             d = lab = None
-        check(call(table, up.data_ptr(), len(table), pixels.data_ptr(), pixels.numel(), d.data_ptr() if total else None,
-                   lab.data_ptr() if total else None, total, up.data_ptr() + noff, C.byref(st),
-                   _lib.DRAW_NO_SCORE if width == 4 else 0, stream_ptr()), 'yv4_draw_boxes_ex')
+        check(_lib.lib().yv4_draw_boxes_ex(
+            table, up.data_ptr(), len(table), pixels.data_ptr(), pixels.numel(), d.data_ptr() if total else None,
+            lab.data_ptr() if total else None, total, up.data_ptr() + noff, C.byref(st),
+            _lib.DRAW_NO_SCORE if width == 4 else 0, stream_ptr()), 'yv4_draw_boxes_ex')
     return pixels
 
 
@@ -146,7 +141,7 @@ def draw_boxes_host(img, dets, labels, class_names, score_thr=0.3, bbox_color=(7
     out = np.array(img, np.uint8, copy=True, order='C')
     dets = np.asarray(dets, np.float32)
     width = _box_width([dets])
-    call = _draw_call('yv4_draw_boxes_host_ex', _lib.has_draw_ex)
+    _lib.require('draw_ex')
     d = dets.reshape(-1, width)
     if width == 4:
         d = np.concatenate([d, np.zeros((d.shape[0], 1), np.float32)], 1)
@@ -155,8 +150,9 @@ def draw_boxes_host(img, dets, labels, class_names, score_thr=0.3, bbox_color=(7
     st = _style(len(class_names), score_thr, bbox_color, text_color, thickness, font_size)
     table, total = _tables([(out.shape[0], out.shape[1], 0, 3 * out.shape[1])], [d.shape[0]])
     names = name_table(class_names)
-    check(call(table, 1, out.ctypes.data, out.size, d.ctypes.data if total else None, lab.ctypes.data if total else None,
-               total, names.ctypes.data, C.byref(st), _lib.DRAW_NO_SCORE if width == 4 else 0), 'yv4_draw_boxes_host_ex')
+    check(_lib.lib().yv4_draw_boxes_host_ex(
+        table, 1, out.ctypes.data, out.size, d.ctypes.data if total else None, lab.ctypes.data if total else None,
+        total, names.ctypes.data, C.byref(st), _lib.DRAW_NO_SCORE if width == 4 else 0), 'yv4_draw_boxes_host_ex')
     return out
 
 

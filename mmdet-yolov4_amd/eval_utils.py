@@ -319,7 +319,7 @@ def flex_flat_device(flat, gt, iou_thrs, shared_tp=True, phases=None):
     ``yv4_flex_accumulate``, one download.  ``flat``: numpy arrays or GPU tensors (those never visit the host); ``gt``: a
     ``FlexGt``.  Returns host arrays shaped (C, B, T): ``num_det`` int64, ``recall`` float64, ``mAP`` float32.
     ``phases``: an optional dict that receives seconds per phase (each closed by a synchronise)."""
-    dev = _eval_common._device('eval_utils', _lib.has_flex_flat, 'yv4_flex_tables / yv4_flex_accumulate')
+    dev = _eval_common._device('eval_utils', 'flex_flat')
     timer = PhaseTimer(phases, dev)
     thrs = np.ascontiguousarray(iou_thrs, dtype=np.float32).reshape(-1)
     N, C, B, T = gt.num_imgs, gt.num_classes, gt.num_bkd, len(thrs)

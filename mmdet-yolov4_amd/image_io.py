@@ -62,9 +62,9 @@ def image_format(buf):
 
 def _raise(status, what):
     msg = _lib.lib().yv4_last_error().decode('utf-8', 'replace')      # thread-local: read on the thread that made the call
-    if status == -2:
+    if status == _lib.E_UNSUPPORTED:
         raise NotImplementedError(f'{what}: {msg}')
-    if status == -1:
+    if status == _lib.E_INVALID:
         raise ValueError(f'{what}: {msg}')
     raise _lib.Yv4Error(f'{what} failed with status {status}: {msg}')
 
@@ -172,14 +172,6 @@ def _host_decode_all(bufs, infos, base, coef_offs, what):
     else:
         with ThreadPoolExecutor(max_workers=min(MAX_DECODE_THREADS, len(bufs))) as pool:      # ctypes releases the GIL
             list(pool.map(one, range(len(bufs))))
-
-
-def _need(have, symbol, what=None):
-    """``RuntimeError`` unless the loaded library exports ``symbol``, which ``what`` (an argument as written) asks for."""
-    if not have:
-        why = f'{symbol} is not exported by the loaded libyv4_hip.so' if what is None else \
-            f'{what} needs {symbol}, which the loaded libyv4_hip.so does not export (there is no fallback)'
-        raise RuntimeError(why + ': rebuild it')
 
 
 class ScanTables:
@@ -343,7 +335,7 @@ def jpeg_entropy_decode_device_sync(bufs, chunk_bytes=None, max_rounds=None, dev
     coefficient tensor, int32 status tensor, int32 undecided tensor)`` on the GPU, nothing read back.  ``coef`` /
     ``status`` / ``undecided``: the caller's tensors to decode into, as in ``jpeg_entropy_decode_device``."""
     chunk_bytes, max_rounds = _sync_params(chunk_bytes, max_rounds)
-    _need(_lib.has_jpeg_sync(), 'yv4_jpeg_entropy_decode_device_sync')
+    _lib.require('jpeg_sync')
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     t = ScanTables(bufs) if tables is None else tables
     ch = ChunkTables(t, chunk_bytes)
@@ -467,9 +459,10 @@ def decode_into(bufs, channel_order='bgr', device=None, out=None, placement=None
     if own:
         host = HostHalf(bufs, entropy, chunk_bytes, max_rounds, run=False)
     mode = host.mode
-    _need(not orientation or _lib.has_jpeg_orientation(), 'yv4_jpeg_layout_oriented', 'orientation=True')
-    _need(mode == 'host' or _lib.has_jpeg_entropy(), 'yv4_jpeg_entropy_decode_device', "entropy='device'")
-    _need(mode != 'device_sync' or _lib.has_jpeg_sync(), 'yv4_jpeg_entropy_decode_device_sync', "entropy='device_sync'")
+    if orientation:
+        _lib.require('jpeg_orientation', 'orientation=True')
+    if mode != 'host':
+        _lib.require('jpeg_sync' if mode == 'device_sync' else 'jpeg_entropy', f'entropy={mode!r}')
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     L = _lib.lib()
     N = len(bufs)
@@ -736,7 +729,7 @@ def encode_stages(et, pixels, channel_order='bgr', coef=None, work=None, out=Non
     read back.  ``pixels``: the flat uint8 device buffer the table's ``src_off`` / ``src_pitch`` point into.  ``coef`` /
     ``work`` / ``out`` / ``sizes``: the caller's tensors (larger ones with the table's offsets moved, say); the library
     checks every region against their sizes before any launch."""
-    _need(_lib.has_jpeg_encode(), 'yv4_jpeg_encode_scan')
+    _lib.require('jpeg_encode')
     L, N, dev = _lib.lib(), len(et), pixels.device
     with torch.cuda.device(dev):
         stage = torch.empty(C.sizeof(et.table), dtype=torch.uint8, pin_memory=True)

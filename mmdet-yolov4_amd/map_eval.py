@@ -67,7 +67,7 @@ _F32_EPS = np.finfo(np.float32).eps
 
 
 def _device():
-    return _eval_common._device('map_eval', _lib.has_map_eval, 'yv4_bbox_overlaps_batched / yv4_tpfp_batched')
+    return _eval_common._device('map_eval', 'map_eval')
 
 
 def _boxes(a, cols=4):
@@ -365,7 +365,7 @@ class MapGt:
 
 def _device_flat():
     _device()
-    return _eval_common._device('map_eval', _lib.has_map_flat, 'yv4_map_rank / yv4_map_accumulate')
+    return _eval_common._device('map_eval', 'map_flat')
 
 
 def map_flat_device(flat, gt, mode, iou_thrs, area_ranges=None, ap_mode='area', curves=False, phases=None):

@@ -715,7 +715,7 @@ class Plan:
             cands = candidates or (1, 2, 3)            # YV4_HTILE_128x128 / 128x64 / 64x64
         else:
             cands = candidates or (_lib.TILE_DMA_64x64, _lib.TILE_DMA_128x64, _lib.TILE_DMA_128x128)
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = ops.stream_ptr()
         chosen = {}
         for idx, op in enumerate(self.ops):
             if op.kind != 'conv':
@@ -787,7 +787,7 @@ class Plan:
         if self.graph is not None:
             self.graph.replay()
         else:
-            self._launch_all(C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            self._launch_all(ops.stream_ptr())
         return [s['dst'] for s in getattr(self, 'outputs', [])]
 
     def capture(self):
@@ -808,6 +808,6 @@ class Plan:
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._launch_all(C.c_void_p(torch.cuda.current_stream().cuda_stream))
+            self._launch_all(ops.stream_ptr())
         self.graph = g
         return self

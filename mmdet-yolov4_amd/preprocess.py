@@ -203,9 +203,7 @@ class FusedTestPipeline:
 
     def _run_batched(self, images):
         """-> ``[(batch, img_metas) per augmentation]``: one slot per (augmentation, image), one launch."""
-        if not _lib.has_letterbox_batch():
-            raise RuntimeError('FusedTestPipeline(batched=True) needs yv4_letterbox_u8_batch, which the loaded libyv4_hip.so '
-                               'does not export: rebuild it')
+        _lib.require('letterbox_batch', 'FusedTestPipeline(batched=True)')
         dev = self._dev()
         images = list(images)
         if not images:

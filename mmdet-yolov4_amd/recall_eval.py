@@ -39,8 +39,7 @@ _EPS = float(np.float32(1e-6))
 
 
 def _device():
-    _eval_common._device('recall_eval', _lib.has_map_flat, 'yv4_map_rank')
-    return _eval_common._device('recall_eval', _lib.has_recall, 'yv4_recall_work / yv4_recall_match')
+    return _eval_common._device('recall_eval', 'recall')
 
 
 def set_recall_param(proposal_nums, iou_thrs):

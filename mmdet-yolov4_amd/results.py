@@ -42,8 +42,7 @@ class DeviceResults:
             raise ValueError('num_classes must be positive')
         if self.device.type != 'cuda':
             raise RuntimeError('DeviceResults lives on the GPU (yv4_results_append); there is no CPU fallback for this path')
-        if not _lib.has_results_append():
-            raise RuntimeError('the loaded libyv4_hip.so has no yv4_results_append; rebuild it')
+        _lib.require('results_append')
         self.D = 0
         self.num_images = 0
         self._alloc(max(int(capacity), 1))

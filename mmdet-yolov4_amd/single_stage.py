@@ -19,6 +19,7 @@ import torch.distributed as dist
 
 from .bricks import HipModule, plan_cache_get, plan_cache_put
 from .deferred import DeferredLogVars, read_back_later  # noqa: F401
+from .ops import stream_ptr
 from .plan import Plan
 from .registry import DETECTORS, build_backbone, build_head, build_neck
 from .yolocsp_head import collect_results, final_counts, set_scale_factors
@@ -85,7 +86,7 @@ class SingleStageDetector(HipModule):
             plan = self.build_plan(batch, height, width, device, rescale, dtype)
             if autotune and torch.device(device).type == 'cuda':
                 plan.inputs[0]['src'] = torch.zeros((batch, 3, height, width), dtype=torch.float32, device=device)
-                plan._launch_all(__import__('ctypes').c_void_p(torch.cuda.current_stream().cuda_stream))
+                plan._launch_all(stream_ptr())
                 plan.autotune()
             if graph:
                 plan.capture()

@@ -107,8 +107,7 @@ def emit_tta_post(plan, head, groups, flips, N, cfg=None):
     """Append the TTA post-processing to ``plan``.  ``groups``: list of (pred views of one batch, augmentation indices
     in batch order); augmentation a of group g is rows [r*N, (r+1)*N) of its batch, r its position in the group.
     ``flips``: the YV4_FLIP_* code per augmentation.  Sets and returns ``plan.post`` (collect_results' layout)."""
-    if not _lib.has_tta():
-        raise RuntimeError('libyv4_hip.so has no test-time augmentation entry points: rebuild it')
+    _lib.require('tta', 'test-time augmentation')
     cfg = head.test_cfg if cfg is None else cfg
     spec = ops.nms_spec(cfg['nms'])                  # "nms" or "soft_nms"; other types raise
     num_augs = len(flips)

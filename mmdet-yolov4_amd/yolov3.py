@@ -545,7 +545,7 @@ class YOLOV3Head(HipModule):
                 return False
         if type(self.loss_wh) is not _losses.MSELoss or self.loss_wh.reduction not in ('sum', 'mean'):
             return False
-        return _lib.has_v3_loss()
+        return _lib.has('v3_loss')
 
     def loss_single(self, pred_map, target_map, neg_map):
         num_imgs = len(pred_map)

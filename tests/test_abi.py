@@ -2,7 +2,11 @@
 import os
 import re
 
+import pytest
+
 import mmdet_yolov4_amd as pkg
+
+import _abi_probe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -31,6 +35,161 @@ def test_struct_layout_matches_header():
     assert ctypes.sizeof(pkg._lib.LossLevel) == 176 and ctypes.sizeof(pkg._lib.LossDesc) == 1016
     assert pkg._lib.LossDesc.slot_anchor.offset == 960 and pkg._lib.LossDesc.losses.offset == 1008
     assert ctypes.sizeof(pkg._lib.LevelDesc) == 8 + 3 * 4 + 4 + 8 * 4 * 4 or ctypes.sizeof(pkg._lib.LevelDesc) == 8 + 3 * 4 + 8 * 4 * 4 + 4
+
+
+def test_every_struct_and_field_matches_a_c_compiler():
+    """All of the ctypes mirror against the header: every struct the header declares is in ``STRUCTS``, with the
+    header's members in the header's order (a field missing at the end of a class would pass the offsets), and a C
+    compiler's ``sizeof`` of every struct and ``offsetof`` / ``sizeof`` of every field equal ctypes'."""
+    import ctypes
+    L = pkg._lib
+    declared = _abi_probe.header_structs()
+    assert set(declared) == set(L.STRUCTS), set(declared) ^ set(L.STRUCTS)
+    assert len(L.STRUCTS) == 23 and len(set(L.STRUCTS.values())) == 23
+    for cname, cls in L.STRUCTS.items():
+        assert issubclass(cls, ctypes.Structure) and [f[0] for f in cls._fields_] == declared[cname], cname
+    assert sum(len(cls._fields_) for cls in L.STRUCTS.values()) == 304
+    p = _abi_probe.probe()                                      # skips without a C compiler
+    assert len(p.sizeof) == 23 and len(p.fields) == 304
+    assert _abi_probe.mismatches() == []
+
+
+#: the header's constants that ``_lib`` deliberately does not mirror: nothing in the Python uses them
+NOT_MIRRORED = {'OK', 'E_LAUNCH', 'E_CAPACITY', 'HTILE_128x128', 'HTILE_128x64', 'HTILE_64x64', 'HTILE_PP3x3', 'HTILE_W3x3',
+                'HTILE_WIDE', 'HTILE_WS_1x1', 'HTILE_S3x3', 'JPEG_ERR_OVERRUN', 'JPEG_ERR_CODE', 'JPEG_ERR_DC_CATEGORY',
+                'JPEG_ERR_INDEX', 'JPEG_ERR_TRAILING', 'JPEG_WG_CHUNKS'}
+
+
+def test_constants_match_the_header():
+    """Every object-like numeric ``#define YV4_*`` equals ``_lib``'s value of the same name, or is in NOT_MIRRORED --
+    and is then really absent, so that the list cannot go stale in either direction."""
+    L = pkg._lib
+    defs = _abi_probe.header_constants()
+    assert len(defs) == 84 and NOT_MIRRORED <= set(defs), NOT_MIRRORED - set(defs)
+    for name, value in defs.items():
+        if name in NOT_MIRRORED:
+            assert not hasattr(L, name), f'{name} is mirrored: take it off NOT_MIRRORED'
+        else:
+            assert getattr(L, name) == value and type(getattr(L, name)) is int, name
+    assert set(L.HTILE_NAMES) >= {defs[k] for k in NOT_MIRRORED if k.startswith('HTILE_')}
+
+
+def test_pinned_tile_shapes_are_the_name_tables_keys():
+    """The four ``YV4_*_SHAPE(i)`` macros over their pinned ranges, from the C compiler: exactly the keys of TILE_NAMES /
+    HTILE_NAMES beyond the plain tile ids, under the name of the tile they pin."""
+    L = pkg._lib
+    shapes = _abi_probe.probe().shapes
+    assert set(shapes) == set(L.SHAPE_COUNTS) and all(len(shapes[m]) == n for m, n in L.SHAPE_COUNTS.items())
+    assert set(shapes['TILE_W3x3']) | set(shapes['TILE_WIDE']) == {t for t in L.TILE_NAMES if t > L.TILE_WIDE}
+    assert set(shapes['HTILE_W3x3']) | set(shapes['HTILE_WIDE']) == {t for t in L.HTILE_NAMES if t > 8}
+    for macro, names, base in (('TILE_W3x3', L.TILE_NAMES, L.TILE_W3x3), ('TILE_WIDE', L.TILE_NAMES, L.TILE_WIDE),
+                               ('HTILE_W3x3', L.HTILE_NAMES, 5), ('HTILE_WIDE', L.HTILE_NAMES, 8)):
+        assert all(names[t] == names[base] for t in shapes[macro]), macro
+
+
+# ---- the binding rule, on stand-in handles ---------------------------------------------------------------------------
+class _Fn:
+    """An entry point of a stand-in library: accepts ``restype`` / ``argtypes`` as a ctypes function does."""
+    restype = argtypes = None
+
+    def __init__(self, value=0):
+        self.value = value
+
+    def __call__(self):
+        return self.value
+
+
+def _handle(without=(), abi=8):
+    h = type('Handle', (), {})()
+    for name in pkg._lib.SIGNATURES:
+        if name not in without:
+            setattr(h, name, _Fn(abi))
+    return h
+
+
+def _load(monkeypatch, handle):
+    """``handle`` bound and in the place of the loaded library, for ``has`` / ``require``."""
+    present = pkg._lib._bind(handle)
+    monkeypatch.setattr(pkg._lib, '_lib', handle)
+    monkeypatch.setattr(pkg._lib, '_has', present)
+    return present
+
+
+def _bound(handle, name):
+    return getattr(handle, name).argtypes is pkg._lib.SIGNATURES[name][1]
+
+
+def test_feature_table_is_well_formed():
+    L = pkg._lib
+    assert list(L.FEATURES) == ['fp8', 'tta', 'letterbox_batch', 'soft_nms', 'v3_augment', 'loss_ex', 'map_eval', 'map_flat',
+                                'flex_flat', 'coco_eval', 'results_append', 'jpeg', 'jpeg_orientation', 'jpeg_entropy',
+                                'jpeg_sync', 'jpeg_encode', 'draw', 'draw_ex', 'map_image', 'recall', 'v3_loss']
+    owned = [s for ft in L.FEATURES.values() for s in ft.symbols]
+    assert len(owned) == len(set(owned)), 'a symbol belongs to two features'
+    assert all(ft.symbols and set(ft.symbols) <= set(L.SIGNATURES) for ft in L.FEATURES.values())
+    assert {f: ft.requires for f, ft in L.FEATURES.items() if ft.requires} == \
+        {'flex_flat': ('map_flat',), 'jpeg_sync': ('jpeg_entropy',), 'draw_ex': ('draw',)}
+    assert {f: ft.abi for f, ft in L.FEATURES.items() if ft.abi} == {'v3_loss': 8}
+    assert not [n for n in vars(L) if n.endswith('_SYMBOLS') or n.startswith('has_')]
+
+
+def test_bind_a_complete_library(monkeypatch):
+    L = pkg._lib
+    h = _handle()
+    assert _load(monkeypatch, h) == dict.fromkeys(L.FEATURES, True)
+    assert all(_bound(h, n) and getattr(h, n).restype is L.SIGNATURES[n][0] for n in L.SIGNATURES)
+    assert all(L.has(f) for f in L.FEATURES)
+    for f in L.FEATURES:
+        L.require(f)
+    with pytest.raises(KeyError):
+        L.has('jpeg_entropy_sync')
+
+
+def test_bind_a_library_without_one_feature(monkeypatch):
+    """Without jpeg_entropy's symbols: binding succeeds, the feature and the one that requires it are absent, nothing
+    else is, and ``require`` names a missing symbol."""
+    L = pkg._lib
+    gone = L.FEATURES['jpeg_entropy'].symbols
+    h = _handle(without=gone)
+    _load(monkeypatch, h)
+    assert {f for f in L.FEATURES if not L.has(f)} == {'jpeg_entropy', 'jpeg_sync'}
+    assert all(_bound(h, n) for n in L.SIGNATURES if n not in gone) and not any(hasattr(h, n) for n in gone)
+    with pytest.raises(RuntimeError, match='yv4_jpeg_entropy_decode_device.*rebuild'):
+        L.require('jpeg_sync')
+    with pytest.raises(RuntimeError, match="entropy='device' needs .*yv4_jpeg_scan_prepare"):
+        L.require('jpeg_entropy', "entropy='device'")
+    L.require('jpeg')
+
+
+def test_bind_refuses_a_library_without_a_core_symbol():
+    with pytest.raises(AttributeError, match='yv4_conv_bn_act_fwd'):
+        pkg._lib._bind(_handle(without={'yv4_conv_bn_act_fwd'}))
+
+
+def test_bind_half_a_feature(monkeypatch):
+    """One symbol of a two-symbol feature gone: the other is still bound, the feature is absent."""
+    L = pkg._lib
+    h = _handle(without={'yv4_recall_work'})
+    _load(monkeypatch, h)
+    assert _bound(h, 'yv4_recall_match') and not L.has('recall')
+    assert {f for f in L.FEATURES if not L.has(f)} == {'recall'}
+    with pytest.raises(RuntimeError, match='yv4_recall_work') as e:
+        L.require('recall')
+    assert 'yv4_recall_match' not in str(e.value)
+
+
+def test_bind_the_previous_abi(monkeypatch):
+    """A library that reports ABI 7: the v3_loss symbols are left unbound even where it has them, and ``has`` says so."""
+    L = pkg._lib
+    h = _handle(abi=7)
+    _load(monkeypatch, h)
+    assert not any(_bound(h, n) for n in L.FEATURES['v3_loss'].symbols)
+    assert all(_bound(h, n) for n in L.SIGNATURES if n not in L.FEATURES['v3_loss'].symbols)
+    assert {f for f in L.FEATURES if not L.has(f)} == {'v3_loss'}
+    with pytest.raises(RuntimeError, match='yv4_yolov3_loss_bwd / yv4_yolov3_loss_fwd'):
+        L.require('v3_loss')
+    with pytest.raises(AttributeError):          # ABI 8 without them is no ABI 8
+        L._bind(_handle(without={'yv4_yolov3_loss_fwd'}))
 
 
 def test_argument_validation_without_gpu():

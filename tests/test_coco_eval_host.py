@@ -212,7 +212,7 @@ def test_seeded_dataset_reaches_every_corner():
 def test_c_abi_argument_validation():
     L = pkg._lib
     lib = L.lib()
-    assert L.COCO_EVAL_SYMBOLS <= set(L.SIGNATURES) and L.has_coco_eval()
+    assert L.FEATURES['coco_eval'].symbols <= set(L.SIGNATURES) and L.has('coco_eval')
     one = ctypes.c_void_p(256)
     assert lib.yv4_coco_rank(None, None, 0, 0, 100, 40, one, one, one, one, one, one, None) == -1
     assert b'problem table' in lib.yv4_last_error()

@@ -327,7 +327,7 @@ def test_results_append_checks_its_arguments_without_a_gpu():
     import ctypes
     from mmdet_yolov4_amd import _lib
     L = _lib.lib()
-    assert _lib.has_results_append() and _lib.RESULTS_MAX_PER_IMG == 4096
+    assert _lib.has('results_append') and _lib.RESULTS_MAX_PER_IMG == 4096
     keep = [(ctypes.c_int64 * 8)() for _ in range(7)]
     ptr = [ctypes.addressof(b) for b in keep]
 

@@ -36,9 +36,9 @@ def test_fp8_symbols_declared_bound_exported():
     lib = pkg._lib.lib()
     for name in SYMS:
         assert re.search(r'\b' + name + r'\s*\(', text), name
-        assert name in pkg._lib.SIGNATURES and name in pkg._lib.FP8_SYMBOLS
+        assert name in pkg._lib.SIGNATURES and name in pkg._lib.FEATURES['fp8'].symbols
         assert getattr(lib, name).argtypes == pkg._lib.SIGNATURES[name][1]
-    assert pkg._lib.has_fp8()
+    assert pkg._lib.has('fp8')
     assert pkg._lib.ABI_VERSION == 8 and lib.yv4_abi_version() == 8
 
 

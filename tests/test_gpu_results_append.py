@@ -72,7 +72,7 @@ def _one(dev, dets, labels, count, img_index, C, slack=3, base=0):
 
 
 def test_has_the_entry_point():
-    assert _lib.has_results_append()
+    assert _lib.has('results_append')
 
 
 @pytest.mark.parametrize('M', [1, 300, 1000])

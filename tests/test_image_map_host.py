@@ -127,7 +127,7 @@ def test_headers_binding_and_library_hold_the_new_symbols():
     lib = pkg._lib.lib()
     for name in new:
         assert hasattr(lib, name), name
-    assert pkg._lib.has_map_image() and pkg._lib.has_draw_ex()
+    assert pkg._lib.has('map_image') and pkg._lib.has('draw_ex')
     assert lib.yv4_map_image_ap_work(0) == 4 and lib.yv4_map_image_ap_work(1000) == 4000     # sized by Dv alone
     # arguments are checked on the host before any device work
     assert lib.yv4_map_image_ap(None, None, 0, None, None, 0, None, 0, 0, 1, 1, 10, None, 0, None, 0, None, 0, None) == -1

@@ -50,8 +50,8 @@ def _segments(buf):
 def test_abi_exports_the_entropy_entries():
     names = ('yv4_jpeg_scan_prepare', 'yv4_jpeg_entropy_workgroups', 'yv4_jpeg_entropy_decode_segments',
              'yv4_jpeg_entropy_decode_device', 'yv4_jpeg_entropy_strerror')
-    assert set(names) == set(L.JPEG_ENTROPY_SYMBOLS) and set(names) <= set(L.SIGNATURES)
-    assert all(hasattr(L.lib(), n) for n in names) and L.has_jpeg_entropy()
+    assert set(names) == set(L.FEATURES['jpeg_entropy'].symbols) and set(names) <= set(L.SIGNATURES)
+    assert all(hasattr(L.lib(), n) for n in names) and L.has('jpeg_entropy')
     assert L.lib().yv4_abi_version() == 8
     assert (ctypes.sizeof(L.JpegHuff), ctypes.sizeof(L.JpegScan), ctypes.sizeof(L.JpegSegment), ctypes.sizeof(L.JpegWg)) == \
         (1344, 96, 40, 16)

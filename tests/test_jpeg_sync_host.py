@@ -104,8 +104,8 @@ def _check_entry_table(name, t, ch, entries, want, fin):
 
 def test_abi_exports_the_sync_entries():
     names = ('yv4_jpeg_chunks_build', 'yv4_jpeg_entropy_decode_sync', 'yv4_jpeg_entropy_decode_device_sync')
-    assert set(names) == set(L.JPEG_SYNC_SYMBOLS) and set(names) <= set(L.SIGNATURES)
-    assert all(hasattr(L.lib(), n) for n in names) and L.has_jpeg_sync()
+    assert set(names) == set(L.FEATURES['jpeg_sync'].symbols) and set(names) <= set(L.SIGNATURES)
+    assert all(hasattr(L.lib(), n) for n in names) and L.has('jpeg_sync')
     assert L.lib().yv4_abi_version() == 8
     assert (ctypes.sizeof(L.JpegChunk), ctypes.sizeof(L.JpegEntry), ctypes.sizeof(L.JpegSegment)) == (16, 48, 40)
     assert L.JpegEntry.nblk.offset == 24 and L.JpegEntry.dc.offset == 32 and L.JpegEntry.pred.offset == 40

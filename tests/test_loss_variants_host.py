@@ -11,9 +11,6 @@
 import ctypes
 import math
 import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -25,6 +22,7 @@ from mmdet_yolov4_amd import losses as Ls
 from mmdet_yolov4_amd.registry import build_loss
 from mmdet_yolov4_amd.yolocsp_head import RawPredMap, loss_options
 
+import _abi_probe
 import _loss_ref as R
 import _loss_variants_ref as V
 
@@ -117,9 +115,9 @@ def test_loss_ex_symbols_exported_and_bound():
     assert _lib.ABI_VERSION == 8 and lib.yv4_abi_version() == 8
     text = open(os.path.join(ROOT, 'include', 'yv4.h')).read()
     for name in ('yv4_yolo_loss_fwd_ex', 'yv4_yolo_loss_bwd_ex'):
-        assert name in _lib.SIGNATURES and name in _lib.LOSS_EX_SYMBOLS and f'int {name}(' in text
+        assert name in _lib.SIGNATURES and name in _lib.FEATURES['loss_ex'].symbols and f'int {name}(' in text
         assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
-    assert _lib.has_loss_ex()
+    assert _lib.has('loss_ex')
     assert ctypes.sizeof(_lib.LossDesc) == 1016
     for i, k in enumerate(('GIOU', 'IOU_LINEAR', 'IOU_LOG', 'DIOU', 'CIOU')):
         assert f'#define YV4_BOX_{k} {i}' in text and getattr(_lib, 'BOX_' + k) == i
@@ -131,17 +129,8 @@ def test_loss_opts_layout_matches_a_c_compiler():
     for k, v in OPTS_OFFSETS.items():
         assert getattr(O_, k).offset == v, k
     assert [f[0] for f in O_._fields_] == list(OPTS_OFFSETS)
-    cc = shutil.which('cc') or shutil.which('gcc')
-    if cc is None:
-        pytest.skip('no C compiler')
-    fields = ' '.join(f'printf("%zu ", offsetof(yv4_loss_opts, {k}));' for k in OPTS_OFFSETS)
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "yv4.h"\nint main(void) {'
-           'printf("%zu %zu ", sizeof(yv4_loss_opts), sizeof(yv4_loss_desc)); ' + fields + ' return 0; }\n')
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, 'probe.c'), os.path.join(d, 'probe')
-        open(c, 'w').write(src)
-        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), c, '-o', exe], check=True)
-        got = [int(x) for x in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    p = _abi_probe.probe()                                      # skips without a C compiler
+    got = [p.sizeof['yv4_loss_opts'], p.sizeof['yv4_loss_desc']] + [p.fields['yv4_loss_opts', k][0] for k in OPTS_OFFSETS]
     assert got == [OPTS_SIZE, 1016] + list(OPTS_OFFSETS.values())
 
 

@@ -119,8 +119,8 @@ def test_foreign_tpfp_fn_with_flat_input_raises_before_any_device_call(data, mon
 
 def test_flat_symbols_are_bound_and_validate_their_arguments():
     L = pkg._lib
-    assert L.MAP_FLAT_SYMBOLS == {'yv4_map_rank_work', 'yv4_map_rank', 'yv4_map_accumulate_work', 'yv4_map_accumulate'}
-    assert L.MAP_FLAT_SYMBOLS <= set(L.SIGNATURES) and L.has_map_flat()
+    assert L.FEATURES['map_flat'].symbols == {'yv4_map_rank_work', 'yv4_map_rank', 'yv4_map_accumulate_work', 'yv4_map_accumulate'}
+    assert L.FEATURES['map_flat'].symbols <= set(L.SIGNATURES) and L.has('map_flat')
     lib = L.lib()
     one = ctypes.c_void_p(256)                                   # non-null, aligned, never read
 

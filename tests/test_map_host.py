@@ -187,7 +187,7 @@ def test_more_than_2_24_detections_per_class_are_refused():
 # ---- the C-ABI calls reject bad arguments before touching the device --------------------------------------------------------
 def test_new_symbols_are_bound_and_validate_their_arguments():
     L = pkg._lib
-    assert L.MAP_EVAL_SYMBOLS <= set(L.SIGNATURES) and L.has_map_eval()
+    assert L.FEATURES['map_eval'].symbols <= set(L.SIGNATURES) and L.has('map_eval')
     lib = L.lib()
     one = ctypes.c_void_p(16)                                    # a non-null, 16-byte aligned placeholder: never read
     assert lib.yv4_bbox_overlaps_batched(None, None, None, None, None, 1, 0, 0, 1e-6, None, None) == -1

@@ -164,12 +164,12 @@ def test_headers_binding_and_library_hold_the_new_symbols():
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     declared = set(re.findall(r'\b(yv4_[a-z0-9_]+)\s*\(', text))
     new = {'yv4_recall_work', 'yv4_recall_match'}
-    assert new <= declared and new <= set(pkg._lib.SIGNATURES) and new == set(pkg._lib.RECALL_SYMBOLS)
+    assert new <= declared and new <= set(pkg._lib.SIGNATURES) and new == set(pkg._lib.FEATURES['recall'].symbols)
     assert re.search(r'#define\s+YV4_ABI_VERSION\s+8\b', text) and pkg._lib.ABI_VERSION == 8
     lib = pkg._lib.lib()
     for name in new:
         assert hasattr(lib, name), name
-    assert pkg._lib.has_recall()
+    assert pkg._lib.has('recall')
     src = open(os.path.join(ROOT, 'mmdet-yolov4_amd', 'csrc', 'recall.hip')).read()
     for const, value in (('kRcMaxNums', pkg._lib.RECALL_MAX_NUMS), ('kRcLdsBoxes', pkg._lib.RECALL_LDS_BOXES)):
         assert re.search(rf'constexpr int {const} = {value};', src)

@@ -87,8 +87,8 @@ def test_split_branch_resorts_by_the_decayed_scores():
 
 
 def test_symbols_and_constants():
-    assert L.SOFT_NMS_SYMBOLS <= set(L.SIGNATURES)
-    assert L.has_soft_nms()
+    assert L.FEATURES['soft_nms'].symbols <= set(L.SIGNATURES)
+    assert L.has('soft_nms')
     assert (L.SOFT_NMS_NAIVE, L.SOFT_NMS_LINEAR, L.SOFT_NMS_GAUSSIAN) == (0, 1, 2)
     assert L.SOFT_NMS_METHODS == R.METHODS
     assert callable(pkg.soft_nms)

@@ -108,7 +108,7 @@ def test_pipeline_form_and_bad_arguments():
     assert pkg.build_test_loader(_block(), batched=False).pipeline.batched is False
     assert pkg.build_test_loader(_block(), batched=True).pipeline.batched is True
     assert pkg.FusedTestPipeline().batched is False                                  # the default pipeline is per image
-    assert pkg._lib.has_letterbox_batch()
+    assert pkg._lib.has('letterbox_batch')
     # yv4_letterbox_slot (include/yv4.h): a pointer, two doubles, an int64, ten int32
     slot = pkg._lib.LetterboxSlot
     assert ctypes.sizeof(slot) == 72

@@ -74,9 +74,9 @@ def test_tta_symbols_declared_bound_exported():
     lib = pkg._lib.lib()
     for name in SYMS:
         assert re.search(r'\b' + name + r'\s*\(', text), name
-        assert name in pkg._lib.SIGNATURES and name in pkg._lib.TTA_SYMBOLS
+        assert name in pkg._lib.SIGNATURES and name in pkg._lib.FEATURES['tta'].symbols
         assert getattr(lib, name).argtypes == pkg._lib.SIGNATURES[name][1]
-    assert pkg._lib.has_tta()
+    assert pkg._lib.has('tta')
     assert pkg._lib.ABI_VERSION == 8 and lib.yv4_abi_version() == 8
     # yv4_tta_aug: 4 pointers, int64 total, int32 S, int32 flip
     assert ctypes.sizeof(pkg._lib.TtaAug) == 48 and pkg._lib.TtaAug.flip.offset == 44

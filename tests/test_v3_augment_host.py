@@ -161,7 +161,7 @@ def test_symbol_is_declared_bound_and_exported_within_abi_8():
     assert (pkg._lib.V3AUG_CONTRAST_NONE, pkg._lib.V3AUG_CONTRAST_FIRST, pkg._lib.V3AUG_CONTRAST_LAST) == (0, 1, 2)
     assert 'yv4_v3_augment_u8' in pkg._lib.SIGNATURES
     lib = pkg._lib.lib()
-    assert lib.yv4_abi_version() == 8 and hasattr(lib, 'yv4_v3_augment_u8') and pkg._lib.has_v3_augment()
+    assert lib.yv4_abi_version() == 8 and hasattr(lib, 'yv4_v3_augment_u8') and pkg._lib.has('v3_augment')
     # struct layout of the header: 8 + 8 * 4 + 4 * 4 + 3 * 4 + 4 * 4 + 3 * 4 + 10 * 4 bytes
     assert ctypes.sizeof(pkg._lib.V3AugImage) == 136
     assert pkg._lib.V3AugImage.perm.offset == 56 and pkg._lib.V3AugImage.fill.offset == 84

@@ -1,16 +1,12 @@
 """ABI 8: the YOLOv3 loss entry points (include/yv4.h yv4_yolov3_loss_fwd / _bwd) are exported, bound, and their
 descriptor has the header's layout.  No GPU needed."""
 import ctypes
-import os
-import shutil
-import subprocess
 
-import pytest
 import torch
 
 import mmdet_yolov4_amd as pkg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _abi_probe
 
 # gcc on include/yv4.h: sizeof(yv4_v3_loss_level), sizeof(yv4_v3_loss_desc), then offsetof of the fields below
 LEVEL_SIZE, DESC_SIZE = 192, 1128
@@ -22,9 +18,9 @@ def test_v3_loss_symbols_exported_and_bound():
     lib = pkg._lib.lib()
     assert pkg._lib.ABI_VERSION == 8 and lib.yv4_abi_version() == 8
     for name in ('yv4_yolov3_loss_fwd', 'yv4_yolov3_loss_bwd'):
-        assert name in pkg._lib.SIGNATURES and name in pkg._lib.ABI8_SYMBOLS
+        assert name in pkg._lib.SIGNATURES and name in pkg._lib.FEATURES['v3_loss'].symbols
         assert getattr(lib, name).argtypes == pkg._lib.SIGNATURES[name][1]
-    assert pkg._lib.has_v3_loss()
+    assert pkg._lib.has('v3_loss')
 
 
 def test_v3_loss_desc_layout_matches_header():
@@ -37,18 +33,8 @@ def test_v3_loss_desc_layout_matches_header():
 
 def test_v3_loss_desc_layout_matches_a_c_compiler():
     """The same numbers from a C compiler on the header itself, where one is installed."""
-    cc = shutil.which('cc') or shutil.which('gcc')
-    if cc is None:
-        pytest.skip('no C compiler')
-    import tempfile
-    fields = ' '.join(f'printf("%zu ", offsetof(yv4_v3_loss_desc, {k}));' for k in OFFSETS)
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "yv4.h"\nint main(void) {'
-           'printf("%zu %zu ", sizeof(yv4_v3_loss_level), sizeof(yv4_v3_loss_desc)); ' + fields + ' return 0; }\n')
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, 'probe.c'), os.path.join(d, 'probe')
-        open(c, 'w').write(src)
-        subprocess.run([cc, '-I', os.path.join(ROOT, 'include'), c, '-o', exe], check=True)
-        got = [int(x) for x in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    p = _abi_probe.probe()                                      # skips without a C compiler
+    got = [p.sizeof['yv4_v3_loss_level'], p.sizeof['yv4_v3_loss_desc']] + [p.fields['yv4_v3_loss_desc', k][0] for k in OFFSETS]
     assert got == [LEVEL_SIZE, DESC_SIZE] + list(OFFSETS.values())
 
 

@@ -189,11 +189,11 @@ def main():
     raws, biases = make_maps(a.batch, a.size, torch.bfloat16)
     call = AbiCall(make_head('giou', None), raws, biases, boxes, labels)
     out = dict(batch=a.batch, size=a.size, dtype='bf16', G=call.G, anchor_boxes=call.boxes, steps=a.steps, repeats=a.repeats,
-               lib=os.environ.get('YV4_LIB_PATH', 'in-tree'), has_loss_ex=_lib.has_loss_ex())
+               lib=os.environ.get('YV4_LIB_PATH', 'in-tree'), has_loss_ex=_lib.has('loss_ex'))
     for _ in range(a.warmup):
         call.step(None)
     torch.cuda.synchronize()
-    if a.plain_only or not _lib.has_loss_ex():
+    if a.plain_only or not _lib.has('loss_ex'):
         out['plain'] = stats([window(lambda: call.step(None), a.steps) for _ in range(a.repeats)])
         print(json.dumps(out['plain']), flush=True)
     else:

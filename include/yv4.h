@@ -931,6 +931,49 @@ int yv4_coco_accumulate(const float* det, const uint32_t* order, const int32_t* 
                         const int32_t* max_dets, int M, int T, int A, const double* rec_thrs, int R, void* work,
                         double* precision, double* recall, double* scores, void* stream);
 
+/* ---- COCO error analysis (csrc/coco_error.hip; additive within ABI 8) -------------------------------------------------
+ * The matching of tools/analysis_tools/coco_error_analysis.py's 1 + 2 K COCOeval runs in one pass (the definition is
+ * restated in mmdet-yolov4_amd/coco_error.py).  Its per-category runs relabel every annotation of c's supercategory
+ * ("Sim") or of any other category ("Oth") as category c with ignore = 1 and iscrowd = 1, and keep only c's detections:
+ * against the base run only the set of ground truths a detection of c may be matched to changes.  So the problems
+ * p = image * K + category, their rank order and det_off are yv4_coco_rank's (with num_at = A * (T + 2); its match_need
+ * is not used), and yv4_coco_accumulate follows unchanged with T + 2 in the place of T.  All pointers but `stream` are
+ * device pointers; float64 throughout, one IEEE operation per operation of the definition, integer sums.
+ *
+ * The ground truths are image-major, in annotation order inside an image: image i owns [gt_img_off[i], gt_img_off[i+1]).
+ *   gt_box (total_gt, 4) float64 x y w h; gt_area (total_gt) float64; gt_flag (total_gt) bytes: bit 0 = iscrowd,
+ *     bit 1 = ignore; gt_cat (total_gt) int32: the K-axis position of the annotation's category, or -1 for a category
+ *     outside the K axis (it takes part in the Oth walks only); gt_img_off (P / K + 1) int64.
+ *   cat_group (K) int32: the supercategory group of each K-axis position; equal values = same supercategory.
+ *
+ * yv4_coco_error_need: *need (1) int64 = the doubles of workspace yv4_coco_error_match needs for num_walks =
+ *   A * (T + 2) walks with this max_det: the problems whose IoU block (min(num_det, max_det) x the image's gts) exceeds
+ *   YV4_COCO_ERROR_LDS_PAIRS doubles, or whose image has more than YV4_COCO_ERROR_LDS_GTS gts.  The caller reads it back.
+ *
+ * yv4_coco_error_match: one wave per problem that has detections (groups of 64 walks when A * (T + 2) > 64).
+ *   The IoU block of the problem's first min(num_det, max_det) detections in rank order against ALL gts of the image is
+ *     computed once: the ordinary union by the gt's own crowd bit for a gt with gt_cat == k, union = detection area
+ *     (the crowd form) for every other gt.  It sits in LDS up to the two capacities above, else in `work`.
+ *   Walks, one per lane, w = a * (T + 2) + t: t < T the base walk at iou_thrs[t] over the gts with gt_cat == k;
+ *     t == T the Sim walk at conf_thr over those and the gts with gt_cat >= 0 and cat_group[gt_cat] == cat_group[k];
+ *     t == T + 1 the Oth walk at conf_thr over all gts of the image.  A gt of k keeps its own flags and area test; every
+ *     other gt is ignored and crowd in every area range.  The walk is yv4_coco_match's: not-ignored gts first, stable in
+ *     annotation order (a foreign gt sits among k's own ignored ones in that order), no second pass after a match, a
+ *     taken gt is skipped unless crowd, iou < best is skipped, equality passes (the later gt wins).
+ *   flags (total_det, A * (T + 2)) bytes, zeroed first: flags[s * A*(T+2) + w], bits as yv4_coco_match's.
+ *   counts (K, A) int32, zeroed first: as yv4_coco_match's (only gts with gt_cat == k count; the same in all runs).
+ *   work / work_len: at least *need doubles (may be null / 0 when that is 0).  state (2) int64: [1] != 0 afterwards
+ *     means the workspace was too small and problems were skipped.
+ *   YV4_E_INVALID before anything is launched: a null pointer, A > 64, non-positive sizes, K * A * (T + 2) >= 2^31. */
+enum { YV4_COCO_ERROR_LDS_PAIRS = 9216, YV4_COCO_ERROR_LDS_GTS = 512 };   /* the LDS capacities above */
+int yv4_coco_error_need(const int64_t* det_off, const int64_t* gt_img_off, int P, int K, int max_det, int num_walks,
+                        int64_t* need, void* stream);
+int yv4_coco_error_match(const float* det, const uint32_t* order, const int64_t* det_off, const double* gt_box,
+                         const double* gt_area, const uint8_t* gt_flag, const int32_t* gt_cat, const int64_t* gt_img_off,
+                         const int32_t* cat_group, int P, int K, int64_t total_det, int64_t total_gt, int max_det,
+                         const double* iou_thrs, int T, double conf_thr, const double* area_rng, int A, double* work,
+                         int64_t work_len, int64_t* state, uint8_t* flags, int32_t* counts, void* stream);
+
 /* ---- VOC-style mAP from the flat result table (csrc/map_flat.hip; additive within ABI 8) ------------------------------
  * The two ends the list path of eval_map leaves to the host: ordering the detections and accumulating tp / fp into
  * recall, precision and AP.  Between them run yv4_bbox_overlaps_batched and yv4_tpfp_batched, unchanged.  N images x C

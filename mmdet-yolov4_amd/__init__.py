@@ -35,6 +35,7 @@ from .map_eval import (MapGt, bbox_overlaps, eval_map, evaluate_map, print_map_s
                        tpfp_imagenet)
 from .recall_eval import RecallGt, eval_recalls, print_recall_summary, recall_device, set_recall_param  # noqa: F401
 from .coco_eval import COCOeval, CocoGt, evaluate_bbox, flatten_results  # noqa: F401
+from .coco_error import ErrorAnalysis, error_analysis  # noqa: F401
 from .results import CocoBBoxDataset, CustomBBoxDataset, DeviceResults  # noqa: F401
 from .analysis import ResultVisualizer, bbox_map_eval, image_maps  # noqa: F401
 from .datasets import (CocoDataset, DistributedGroupSampler, GroupSampler, TestLoader, TrainLoader,  # noqa: F401

@@ -387,6 +387,9 @@ SIGNATURES = {
     'yv4_coco_accumulate_work': (_sz, [_i64, _i, _i]),
     'yv4_coco_accumulate': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp,
                                       _vp, _vp]),
+    'yv4_coco_error_need': (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'yv4_coco_error_match': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i64, _i64, _i, _vp, _i, _d, _vp,
+                                       _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     'yv4_results_append': (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp]),
     'yv4_jpeg_parse': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo)]),
     'yv4_jpeg_entropy_decode': (C.c_int, [_vp, _sz, C.POINTER(JpegInfo), _vp, _i64]),
@@ -475,6 +478,9 @@ RECALL_MAX_NUMS, RECALL_MAX_THRS, RECALL_LDS_BOXES = 16, 256, 1280      # csrc/r
 JPEG_MIN_CHUNK_BYTES, JPEG_MAX_CHUNK_BYTES, JPEG_MAX_ROUNDS = 4, 1 << 20, 4096
 #: ``YV4_RESULTS_MAX_PER_IMG`` (include/yv4.h): the labels of one image that yv4_results_append holds in LDS
 RESULTS_MAX_PER_IMG = 4096
+#: ``YV4_COCO_ERROR_LDS_PAIRS`` / ``YV4_COCO_ERROR_LDS_GTS`` (an enum of include/yv4.h): the IoU block (doubles) and the ground truths
+#: of an image up to which a problem of yv4_coco_error_match stays in LDS; beyond either it takes the workspace
+COCO_ERROR_LDS_PAIRS, COCO_ERROR_LDS_GTS = 9216, 512
 
 _lock = threading.Lock()
 _lib = None

@@ -94,6 +94,16 @@ class CocoGt:
         ids = list(ids) if isinstance(ids, (list, tuple, np.ndarray)) else [ids]
         return [self.cats[int(i)] for i in ids]
 
+    def cat_group(self):
+        """``{category id: supercategory group}``, the groups numbered in the order ``categories`` first names them.  A
+        category without a ``supercategory`` key forms a group of its own (``getCatIds(supNms=...)`` of the reference
+        raises ``KeyError`` there)."""
+        groups, out = {}, {}
+        for cid, c in self.cats.items():
+            key = ('name', c['supercategory']) if 'supercategory' in c else ('alone', cid)
+            out[cid] = groups.setdefault(key, len(groups))
+        return out
+
 
 class Params:
     """``pycocotools.cocoeval.Params`` for ``iouType='bbox'``."""

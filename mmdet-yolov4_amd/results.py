@@ -258,6 +258,13 @@ class CocoBBoxDataset:
             _log(''.join(log_msg), logger)
         return eval_results
 
+    def error_analysis(self, results, **kw):
+        """``coco_error.error_analysis`` of ``results`` (any form it takes) against the annotation file held here, with
+        this dataset's label -> category and index -> image maps: the C75 / C50 / Loc / Sim / Oth / BG / FN breakdown of
+        the reference's ``tools/analysis_tools/coco_error_analysis.py``."""
+        from .coco_error import error_analysis
+        return error_analysis(self.coco, results, cat_ids=self.cat_ids, img_ids=self.img_ids, **kw)
+
 
 class CustomBBoxDataset:
     """The ``.dataset`` of a validation loader that scores ``metric='mAP'``, as ``CustomDataset.evaluate`` and
